@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: CycleGAN train steps/sec on 132^3 x 1 volumes (BASELINE.json config[1]).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--no-cpu-baseline] [--dump-outputs DIR]
 
 With --gpus N > 1 outside torch.distributed.run the script starts `python -m torch.distributed.run --nproc-per-node N
 bench.py ...` itself as a CHILD process (before touching the GPU), relays rank 0's JSON line and exits with the child's
@@ -20,9 +20,6 @@ import sys
 import time
 
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")   # dmabuf IPC for RCCL; must be set before HIP initialises
-# The step runs on three streams and RCCL adds its own: with HIP's default of 4 hardware queues per process two of them
-# share a queue and serialize (measured: 9.49 instead of 8.51 ms/step with the exchange on).  Read when HIP initialises.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 import numpy as np
 import torch
@@ -81,6 +78,20 @@ def per_kernel_profile(model, st, steps, streams=True):
             if by == d["big_bytes"] and by > 0:
                 d["big_ms"] += t; d["big_n"] += 1
     return agg
+
+
+def dump_outputs(path, model, losses):
+    """--dump-outputs DIR: what the last timed step handed its caller -- the 7 losses it returned and the four networks'
+    kernels it updated in place (flat fp32 vectors in parameter order) -- as DIR/<name>.npy.  The inputs and the
+    initial weights are seeded, so two builds run with the same arguments can be compared file by file."""
+    arrays = {"losses": np.asarray(losses, np.float32)}
+    for name in ("generator_g", "generator_f", "discriminator_x", "discriminator_y"):
+        arrays[name] = getattr(model, name).params.theta.detach().cpu().numpy().astype(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, f"--dump-outputs: {total} bytes"       # ~1.2 MB: the weights do not depend on --dimsize
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def self_launch(argv, nproc):
@@ -148,8 +159,12 @@ def main():
     ap.add_argument("--single-stream", action="store_true",
                     help="run the step on one stream (kernel durations free of overlap: use under rocprofv3 to "
                          "check roofline.avg_launch_us)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write the last step's losses and updated kernels to DIR/<name>.npy (rank 0)")
     ap.add_argument("--dry-dist", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(sys.argv[1:], args.gpus))
@@ -216,6 +231,8 @@ def main():
         dt = float(t.item())
     losses = losses.cpu().numpy()
     assert np.isfinite(losses).all(), losses
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, losses)     # before the sustain / profiling steps move the weights on
     sustained = None
     if args.sustain > 0 and not args.no_kernel_profile:
         # the timed region above is a short burst; this window is long enough for the clock to settle under load

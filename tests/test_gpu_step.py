@@ -167,8 +167,9 @@ def test_train_step_132_matches_oracle(tmp_path):
 
 
 def test_graph_replay_equals_eager(tmp_path):
-    """use_graph=True replays the captured three-stream step: same kernels, same order constraints,
-    bit-identical losses and parameters (every kernel is deterministic)."""
+    """use_graph=True replays the captured step (the three-stream schedule with 4+ hardware queues, the flat
+    single-stream order below that): same kernels, same order constraints, bit-identical losses and parameters
+    (every kernel is deterministic)."""
     from transfer_em_amd.cgan import EM2EM
     shape = (1, 74, 74, 74, 1)
     rx, ry = torch.from_numpy(_inputs(shape, 3)), torch.from_numpy(_inputs(shape, 4))
