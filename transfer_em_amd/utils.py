@@ -6,9 +6,14 @@ is already in memory.  Per tile: uint8 -> float (fused scale+standardize kernel)
 forward (dropout off) -> (unstandardize+1)*127.5 -> round -> uint8 (fused kernel, wraps like
 astype(uint8)) -> written into the output block.  Tiles are independent: `rank`/`world_size`
 shard them over processes (one per GPU) without any collective.
+
+`predict_volume` is the out-of-core form for volumes that do not fit in memory (np.memmap, h5py, zarr): the same
+tiles, grouped into chunks of whole tiles (`chunk_plan`), each read from the volume by its footprint only and
+streamed through the same kernels with the I/O of neighbouring chunks overlapped with the GPU work.
 """
 import json
 import os
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -103,6 +108,215 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
     return out
 
 
+class VolumeChunk(NamedTuple):
+    """One box of whole tiles of a streamed prediction (chunk_plan).  Boxes are (z, y, x) (lo, hi) pairs."""
+    tiles: tuple         # indices into tile_plan's rois / index
+    origins: tuple       # per tile: (z, y, x) haloed-tile origin relative to read[*][0] (may be negative)
+    offsets: tuple       # per tile: (z, y, x) of its interior in the chunk's output block
+    read: tuple          # footprint in volume coordinates: union of the tiles' haloed boxes, clipped to the volume
+    block: tuple         # footprint shape (a side is 0 when the chunk lies wholly outside the volume)
+    base: tuple          # (z, y, x) of the output block's origin in `out` (before clipping)
+    dims: tuple          # output block shape on the device: whole tiles
+    out_box: tuple       # the part of the output block that lands in `out`: dims clipped to size
+
+
+def _default_chunk_tiles(grid, cap):
+    """(kz, ky, kx) with kz*ky*kx <= cap and fewest chunks over `grid`; ties go to the most cube-like box (least halo
+    read per tile), then to more tiles per chunk."""
+    best, key = (1, 1, 1), None
+    for kz in range(1, min(grid[0], cap) + 1):
+        for ky in range(1, min(grid[1], cap // kz) + 1):
+            for kx in range(1, min(grid[2], cap // (kz * ky)) + 1):
+                n = -(-grid[0] // kz) * -(-grid[1] // ky) * -(-grid[2] // kx)
+                k = (n, max(kz, ky, kx), -kz * ky * kx)
+                if key is None or k < key:
+                    best, key = (kz, ky, kx), k
+    return best
+
+
+def _chunk_plan(start, size, outdimsize, buffer, vol_shape, chunk_tiles, rank=0, world_size=1):
+    outdimsize, buffer, tpad, rois, index = tile_plan(start, size, outdimsize, buffer)
+    od, edge = outdimsize, outdimsize + 2 * buffer
+    size_zyx = (size[2], size[1], size[0])
+    grid = tuple(len(range(0, n, od)) for n in size_zyx)
+    if chunk_tiles is None:
+        chunk_tiles = _default_chunk_tiles(grid, TILE_BATCH)
+    kz, ky, kx = (int(v) for v in chunk_tiles)
+    if min(kz, ky, kx) < 1:
+        raise ValueError(f"chunk_tiles must be positive, got {chunk_tiles}")
+    at = {(iz // od, iy // od, ix // od): i for i, (ix, iy, iz) in enumerate(index)}   # tile grid cell -> tile
+    chunks = []
+    for gz in range(0, grid[0], kz):            # z-major: consecutive chunks read neighbouring slabs of the volume
+        for gy in range(0, grid[1], ky):
+            for gx in range(0, grid[2], kx):
+                cells = [(a, b, c) for c in range(gx, min(gx + kx, grid[2])) for b in range(gy, min(gy + ky, grid[1]))
+                         for a in range(gz, min(gz + kz, grid[0]))]
+                tiles = tuple(sorted(at[c] for c in cells))            # tile_plan order
+                org = [(rois[i][2], rois[i][1], rois[i][0]) for i in tiles]
+                read = tuple((min(max(min(o[d] for o in org), 0), vol_shape[d]),
+                              max(min(max(o[d] for o in org) + edge, vol_shape[d]), 0)) for d in range(3))
+                read = tuple((lo, max(lo, hi)) for lo, hi in read)
+                base = (gz * od, gy * od, gx * od)
+                dims = tuple(k * od for k in (min(kz, grid[0] - gz), min(ky, grid[1] - gy), min(kx, grid[2] - gx)))
+                chunks.append(VolumeChunk(
+                    tiles=tiles,
+                    origins=tuple(tuple(o[d] - read[d][0] for d in range(3)) for o in org),
+                    offsets=tuple((index[i][2] - base[0], index[i][1] - base[1], index[i][0] - base[2]) for i in tiles),
+                    read=read, block=tuple(hi - lo for lo, hi in read), base=base, dims=dims,
+                    out_box=tuple((base[d], min(base[d] + dims[d], size_zyx[d])) for d in range(3))))
+    # same tile count => same generator batch: grouping them keeps the plan cache (MAX_PLANS) from rebuilding a plan
+    # per chunk when the faces of the ROI leave tails along several axes
+    chunks.sort(key=lambda c: -len(c.tiles))
+    return outdimsize, buffer, tpad, chunks[rank::world_size]
+
+
+def chunk_plan(start, size, outdimsize, buffer, vol_shape, chunk_tiles, rank=0, world_size=1):
+    """Group the tiles of tile_plan(start, size, outdimsize, buffer) into boxes of chunk_tiles = (kz, ky, kx) whole
+    tiles (fewer at the ROI's far faces) over a volume of shape vol_shape = (Z, Y, X).  Chunks go round-robin to the
+    ranks.  Returns this rank's list of VolumeChunk; chunk_tiles=None picks the box predict_volume uses by default
+    (at most TILE_BATCH tiles, fewest chunks).
+
+    The staging block of a chunk is exactly footprint = (union of its tiles' haloed boxes) n volume, and every tile
+    voxel lies in that union.  So a tile voxel falls outside the block if and only if it falls outside the volume,
+    and the resident-volume gather (tem_u8_tiles_to_f32_std) given the block, its dims and block-relative origins
+    reads the same bytes as on the whole volume, zeros outside included."""
+    return _chunk_plan(start, size, outdimsize, buffer, tuple(int(v) for v in vol_shape), chunk_tiles, rank,
+                       world_size)[3]
+
+
+def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, chunk_tiles=None, tile_batch=None,
+                   outdimsize=None, buffer=None, rank=0, world_size=1, stats=None):
+    """Out-of-core predict_cube: the subvolume [start, start+size) (x,y,z order) of a uint8 array-like `volume`
+    indexed [z, y, x] (ndarray, np.memmap, h5py / zarr dataset: `.shape` and basic slicing are all it needs) is
+    predicted chunk by chunk (chunk_plan) into `out`, a writable uint8 array-like of shape (size[2], size[1], size[0])
+    (allocated when None) that is returned.  Only the chunks' footprints are ever read from `volume`; device memory
+    is bounded by the chunk, not by the ROI.  The result equals predict_cube's bit for bit.
+
+    Pipeline per chunk: one host thread reads the footprint into a pinned staging buffer -> H2D on a copy stream ->
+    gather + generator plan + scatter on the compute stream (the plan's buffers are reused run to run, so these stay
+    in order on one stream) -> D2H on a second copy stream into a pinned output buffer -> the host thread writes the
+    chunk's interior into `out`.  Staging is double-buffered (pinned and device, input and output), so the reads,
+    copies and writes of neighbouring chunks run while the GPU computes.  Ranks (rank / world_size) take chunks
+    round-robin and write disjoint boxes of a shared `out`; no collective is used.  `stats` (a dict) receives the
+    host thread's read and write seconds and the number of chunks."""
+    import time
+    from concurrent.futures import ThreadPoolExecutor
+    from . import _lib
+    lib = H.require_gpu()
+    gen = model.generator_g
+    if not hasattr(gen, "plan"):
+        raise TypeError("predict_volume needs a generator with launch plans (EM2EM or a saved model)")
+    vol_shape = tuple(int(v) for v in volume.shape)
+    if len(vol_shape) != 3:
+        raise ValueError(f"volume must be 3-D [z, y, x], got shape {vol_shape}")
+    od, buf, tpad, chunks = _chunk_plan(start, size, model.outdimsize if outdimsize is None else outdimsize,
+                                        model.buffer if buffer is None else buffer, vol_shape, chunk_tiles, rank,
+                                        world_size)
+    edge = od + 2 * buf
+    if out is None:
+        out = np.zeros((size[2], size[1], size[0]), np.uint8)
+    elif tuple(out.shape) != (size[2], size[1], size[0]):
+        raise ValueError(f"out has shape {tuple(out.shape)}, expected {(size[2], size[1], size[0])}")
+    st = {"read_s": 0.0, "write_s": 0.0, "chunks": len(chunks)}
+    if stats is not None:
+        stats.update(st)
+    if not chunks:
+        return out
+    K = len(chunks)
+    # a chunk wholly outside the volume has an empty footprint: it gathers from one zero byte (all voxels read 0)
+    gdims = [c.block if min(c.block) > 0 else (1, 1, 1) for c in chunks]
+    in_bytes = [int(np.prod(g)) for g in gdims]
+    out_bytes = [int(np.prod(c.dims)) for c in chunks]
+    nb = max(1, min(int(tile_batch or TILE_BATCH), max(len(c.tiles) for c in chunks)))
+    dev = model.device
+    compute = torch.cuda.current_stream(dev)
+    h2d, d2h = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
+    pin_in = [torch.empty(max(in_bytes), dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+    pin_out = [torch.empty(max(out_bytes), dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+    dev_in = [torch.empty(max(in_bytes), dtype=torch.uint8, device=dev) for _ in range(2)]
+    dev_out = [torch.empty(max(out_bytes), dtype=torch.uint8, device=dev) for _ in range(2)]
+    first = np.cumsum([0] + [len(c.tiles) for c in chunks])
+    org = torch.tensor([o for c in chunks for o in c.origins], dtype=torch.int32).to(dev)     # every chunk's, once
+    idx = torch.tensor([o for c in chunks for o in c.offsets], dtype=torch.int32).to(dev)
+    h2d_done, gathered, d2h_done, d2h_evt = {}, {}, {}, [None, None]
+
+    def read(k):                        # host thread: footprint of chunk k -> pin_in[k % 2]
+        if k >= 2:
+            h2d_done.pop(k - 2).synchronize()           # the buffer's previous H2D has finished
+        t0 = time.perf_counter()
+        c, dst = chunks[k], pin_in[k % 2][:in_bytes[k]].numpy().reshape(gdims[k])
+        if min(c.block) > 0:
+            (z0, z1), (y0, y1), (x0, x1) = c.read
+            dst[...] = volume[z0:z1, y0:y1, x0:x1]
+        else:
+            dst[...] = 0
+        st["read_s"] += time.perf_counter() - t0
+
+    def write(k):                       # host thread: pin_out[k % 2] -> the chunk's box of `out`
+        d2h_done.pop(k).synchronize()
+        t0 = time.perf_counter()
+        c, src = chunks[k], pin_out[k % 2][:out_bytes[k]].numpy().reshape(chunks[k].dims)
+        (z0, z1), (y0, y1), (x0, x1) = c.out_box
+        out[z0:z1, y0:y1, x0:x1] = src[:z1 - z0, :y1 - y0, :x1 - x0]
+        st["write_s"] += time.perf_counter() - t0
+
+    pool = ThreadPoolExecutor(max_workers=1)
+    reads, writes = {k: pool.submit(read, k) for k in range(min(2, K))}, {}
+    try:
+        plan = None
+        for k, c in enumerate(chunks):
+            s = k % 2
+            reads.pop(k).result()
+            if k >= 2:
+                h2d.wait_event(gathered.pop(k - 2))          # dev_in[s]: chunk k-2 has been gathered from it
+            with torch.cuda.stream(h2d):
+                dev_in[s][:in_bytes[k]].copy_(pin_in[s][:in_bytes[k]], non_blocking=True)
+            h2d_done[k] = h2d.record_event()
+            compute.wait_event(h2d_done[k])
+            if k >= 2:
+                compute.wait_event(d2h_evt[s])               # dev_out[s]: chunk k-2's D2H has read it
+            Z, Y, X = gdims[k]
+            OZ, OY, OX = c.dims
+            n = len(c.tiles)
+            for b0 in range(0, n, nb):
+                m = min(nb, n - b0)
+                if plan is None or plan.x.shape[0] != m:
+                    plan = None                              # let the plan cache release an evicted plan's buffers
+                    plan = gen.plan((m, edge, edge, edge, 1))
+                t = int(first[k]) + b0
+                _lib.check(lib.tem_u8_tiles_to_f32_std(dev_in[s].data_ptr(), Z, Y, X, org.data_ptr() + 12 * t, m, edge,
+                                                       plan.x.data_ptr(), float(meanstd_x[0]), float(meanstd_x[1]),
+                                                       compute.cuda_stream), "tem_u8_tiles_to_f32_std")
+                if b0 + m == n:
+                    gathered[k] = compute.record_event()
+                data_y = plan.run(compute.cuda_stream)
+                assert data_y.shape[1] - 2 * tpad == od, (data_y.shape, tpad, od)
+                _lib.check(lib.tem_f32_tiles_unstd_to_u8(data_y.data_ptr(), m, data_y.shape[1], tpad,
+                                                         idx.data_ptr() + 12 * t, dev_out[s].data_ptr(), OZ, OY, OX,
+                                                         float(meanstd_y[0]), float(meanstd_y[1]), compute.cuda_stream),
+                           "tem_f32_tiles_unstd_to_u8")
+            scattered = compute.record_event()
+            if k >= 2:
+                writes.pop(k - 2).result()                   # pin_out[s]: chunk k-2 is in `out`
+            d2h.wait_event(scattered)
+            with torch.cuda.stream(d2h):
+                pin_out[s][:out_bytes[k]].copy_(dev_out[s][:out_bytes[k]], non_blocking=True)
+            d2h_done[k] = d2h_evt[s] = d2h.record_event()
+            writes[k] = pool.submit(write, k)
+            if k + 2 < K:
+                reads[k + 2] = pool.submit(read, k + 2)
+        for k in sorted(writes):
+            writes.pop(k).result()
+    except BaseException:
+        pool.shutdown(wait=True, cancel_futures=True)
+        torch.cuda.synchronize(dev)                          # nothing in flight on the buffers about to be freed
+        raise
+    pool.shutdown(wait=True)
+    if stats is not None:
+        stats.update(st)
+    return out
+
+
 def save_model(name, ckpt_dir, meanstd_x, meanstd_y, size=132, is3d=True):
     """Export generator_g for inference (utils.py:133-167): weights + meta.json with the
     reference's keys (buffer, outdimsize, meanstd_x, meanstd_y)."""
@@ -124,6 +338,7 @@ def save_model(name, ckpt_dir, meanstd_x, meanstd_y, size=132, is3d=True):
 class _SavedGenerator:
     def __init__(self, gen, meta):
         self.generator_g, self.outdimsize, self.buffer, self.device = gen, meta["outdimsize"], meta["buffer"], gen.device
+        self.meta = meta
 
     def predict(self, data):
         return self.generator_g(data)
@@ -147,11 +362,24 @@ def predict_ng_cube(location, start, size, model, meanstd_x, meanstd_y, cloudrun
 def predict_cube_from_saved_model(location, start, size, cloudrun, model_dir, fetch_input=False):
     """Reference signature (utils.py:12-38) over a local array: `location` is the uint8 volume,
     `cloudrun` is accepted and ignored, `model_dir` is a directory written by save_model."""
-    from .models.generator import unet_generator
     volume = _local_volume(location)
+    model = _load_saved(model_dir)
+    return predict_cube(volume, start, size, model, model.meta["meanstd_x"], model.meta["meanstd_y"],
+                        fetch_input=fetch_input, outdimsize=model.outdimsize, buffer=model.buffer)
+
+
+def predict_volume_from_saved_model(volume, start, size, model_dir, out=None, **kw):
+    """predict_volume with the generator and statistics exported by save_model to `model_dir` (the out-of-core
+    sibling of predict_cube_from_saved_model); `kw` are predict_volume's chunk_tiles, tile_batch, rank, world_size."""
+    model = _load_saved(model_dir)
+    return predict_volume(_local_volume(volume), start, size, model, model.meta["meanstd_x"], model.meta["meanstd_y"],
+                          out=out, outdimsize=model.outdimsize, buffer=model.buffer, **kw)
+
+
+def _load_saved(model_dir):
+    from .models.generator import unet_generator
     meta = json.load(open(os.path.join(model_dir, 'meta.json')))
     blob = torch.load(os.path.join(model_dir, "generator_g.pt"), map_location="cpu", weights_only=True)
     gen, _ = unet_generator(blob["dimsize"], blob["is3d"])
     gen.params.theta.copy_(blob["theta"])
-    return predict_cube(volume, start, size, _SavedGenerator(gen, meta), meta["meanstd_x"], meta["meanstd_y"],
-                        fetch_input=fetch_input, outdimsize=meta["outdimsize"], buffer=meta["buffer"])
+    return _SavedGenerator(gen, meta)
