@@ -278,6 +278,19 @@ int tem_f32_tiles_unstd_to_u8(const float *y, int32_t ntile, int32_t yedge, int3
                               uint8_t *out, int32_t OZ, int32_t OY, int32_t OX, float mean, float std,
                               tem_stream_t stream);
 
+/* Tiled inference of the 2-D networks, input side: tile t of out[ntile][edge][edge] = the edge x edge window of
+ * section z of the uint8 volume vol[Z][Y][X] at origin (z,y,x) = origins_dev[3t..3t+2] -- pixels outside the volume
+ * (sections outside [0, Z) included) read as 0 -- converted as tem_u8_to_f32_std.  Any ntile; no z halo. */
+int tem_u8_tiles2d_to_f32_std(const uint8_t *vol, int32_t Z, int32_t Y, int32_t X, const int32_t *origins_dev,
+                              int32_t ntile, int32_t edge, float *out, float mean, float std, tem_stream_t stream);
+
+/* Tiled inference of the 2-D networks, output side: the interior of tile t of y[ntile][yedge][yedge] (`tpad` pixels
+ * stripped per side) is converted as tem_f32_unstd_to_u8 and written into section z of the uint8 volume
+ * out[OZ][OY][OX] at (z,y,x) = index_dev[3t..3t+2].  Pixels that fall outside `out` are dropped.  Any ntile. */
+int tem_f32_tiles2d_unstd_to_u8(const float *y, int32_t ntile, int32_t yedge, int32_t tpad, const int32_t *index_dev,
+                                uint8_t *out, int32_t OZ, int32_t OY, int32_t OX, float mean, float std,
+                                tem_stream_t stream);
+
 /* Random augmentation of one cached sample (datasets.py:123-155) with host-drawn parameters:
  *   dst = reverse(transpose(src, perm = (p0,p1,p2)), dims with f_k != 0) * scale + shift
  * src is a dense single-channel (D,H,W) volume (2-D: D == 1, p0 must be 0); dst has extents

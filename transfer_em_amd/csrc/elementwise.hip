@@ -121,14 +121,26 @@ __global__ __launch_bounds__(256) void adam_keras_k(float *theta, const float *g
 
 __global__ void step_tick_k(uint32_t *s) { *s += 1u; }
 
+// The per-voxel arithmetic of every uint8 <-> float boundary (whole-array, 3-D tiles, 2-D tiles): one definition, so
+// the kernel pairs cannot drift apart.  Correctly rounded float32 ops as in the reference (datasets.py, utils.py:109),
+// with one exception: y * std + mean is ONE fused multiply-add (hipcc contracts the __fmul_rn / __fadd_rn pair into
+// v_fma_f32, and every release of these kernels has computed it so; it is spelled out here so that it no longer
+// depends on the compiler).  Next to a rounding boundary the reference's two roundings can land one step away: the
+// oracle comparisons allow 1 LSB on under 1 % of the voxels.
+__device__ __forceinline__ float u8_std(float x, float mean, float std) {
+  x = __fsub_rn(__fdiv_rn(x, 127.5f), 1.f);          // datasets.py:200
+  return __fdiv_rn(__fsub_rn(x, mean), std);         // datasets.py:161-162
+}
+
+__device__ __forceinline__ uint8_t unstd_u8(float v, float mean, float std) {
+  v = __fmul_rn(__fadd_rn(__fmaf_rn(v, std, mean), 1.f), 127.5f);             // utils.py:109
+  const int q = (int)rintf(v);                                                  // np.around: half to even
+  return (uint8_t)(q & 0xFF);                                                   // astype(uint8) wraps
+}
+
 __global__ __launch_bounds__(256) void u8_to_f32_std_k(const uint8_t *in, float *out, int64_t n, float mean, float std) {
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    // explicit _rn ops: no FMA contraction, so the result is bit-identical to the
-    // reference's op-by-op float32 arithmetic
-    float x = (float)in[i];
-    x = __fsub_rn(__fdiv_rn(x, 127.5f), 1.f);          // datasets.py:200
-    out[i] = __fdiv_rn(__fsub_rn(x, mean), std);       // datasets.py:161-162
-  }
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+    out[i] = u8_std((float)in[i], mean, std);
 }
 
 __global__ __launch_bounds__(256) void f32_unstd_to_u8_k(V5 y, uint8_t *out, int64_t oD, int64_t oH, int64_t oW,
@@ -136,10 +148,7 @@ __global__ __launch_bounds__(256) void f32_unstd_to_u8_k(V5 y, uint8_t *out, int
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
     int x = (int)(i % y.W); int64_t r = i / y.W;
     int yy = (int)(r % y.H); int z = (int)(r / y.H);
-    float v = y.ptr[z * y.sD + yy * y.sH + x * y.sW];
-    v = __fmul_rn(__fadd_rn(__fadd_rn(__fmul_rn(v, std), mean), 1.f), 127.5f);   // utils.py:109, op by op
-    int q = (int)rintf(v);                               // np.around: half to even
-    out[z * oD + yy * oH + x * oW] = (uint8_t)(q & 0xFF);  // astype(uint8) wraps
+    out[z * oD + yy * oH + x * oW] = unstd_u8(y.ptr[z * y.sD + yy * y.sH + x * y.sW], mean, std);
   }
 }
 
@@ -265,9 +274,7 @@ __global__ __launch_bounds__(256) void u8_tiles_to_f32_std_k(const uint8_t *vol,
     const int y = (int)(r % edge), z = (int)(r / edge);
     const int gz = oz + z, gy = oy + y, gx = ox + x;
     const bool in = (unsigned)gz < (unsigned)Z && (unsigned)gy < (unsigned)Y && (unsigned)gx < (unsigned)X;
-    float v = in ? (float)vol[((int64_t)gz * Y + gy) * X + gx] : 0.f;
-    v = __fsub_rn(__fdiv_rn(v, 127.5f), 1.f);          // datasets.py:200
-    o[i] = __fdiv_rn(__fsub_rn(v, mean), std);         // datasets.py:161-162
+    o[i] = u8_std(in ? (float)vol[((int64_t)gz * Y + gy) * X + gx] : 0.f, mean, std);
   }
 }
 
@@ -281,10 +288,71 @@ __global__ __launch_bounds__(256) void f32_tiles_unstd_to_u8_k(const float *y, i
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < per_tile; i += (int64_t)gridDim.x * 256) {
     const int x = (int)(i % od); const int64_t r = i / od;
     const int yy = (int)(r % od), z = (int)(r / od);
-    float v = src[((int64_t)(z + tpad) * yedge + (yy + tpad)) * yedge + (x + tpad)];
-    v = __fmul_rn(__fadd_rn(__fadd_rn(__fmul_rn(v, std), mean), 1.f), 127.5f);   // utils.py:109, op by op
-    const int q = (int)rintf(v);                                                  // np.around: half to even
-    out[((int64_t)(iz + z) * OY + (iy + yy)) * OX + (ix + x)] = (uint8_t)(q & 0xFF);   // astype(uint8) wraps
+    out[((int64_t)(iz + z) * OY + (iy + yy)) * OX + (ix + x)] =
+        unstd_u8(src[((int64_t)(z + tpad) * yedge + (yy + tpad)) * yedge + (x + tpad)], mean, std);
+  }
+}
+
+// 2-D tiles (one section each).  Thousands of small tiles per batch: the grid is flat over all tiles' element groups
+// (no blockIdx.y tile, so no 65,535-tile limit), and xcd_contiguous_block keeps neighbouring groups -- one tile's rows,
+// then the next tile's -- in one XCD's L2.
+// gather: thread g fills V consecutive floats of the flat ntile x edge x edge output (one dwordx4 store when V == 4:
+// edge even => every tile starts on 16 bytes); the V pixels may wrap onto the next row of the tile
+template <int V>
+__global__ __launch_bounds__(256) void u8_tiles2d_to_f32_std_k(const uint8_t *vol, int Z, int Y, int X,
+                                                               const int32_t *origins, int edge, float *out, float mean,
+                                                               float std, int64_t ngroup) {
+  const int64_t g = (int64_t)xcd_contiguous_block(blockIdx.x, gridDim.x) * 256 + threadIdx.x;
+  if (g >= ngroup) return;
+  const int per_tile = edge * edge / V;                        // groups per tile (edge * edge % V == 0)
+  const int t = (int)(g / per_tile), e = (int)(g - (int64_t)t * per_tile) * V;
+  const int oz = origins[3 * t], oy = origins[3 * t + 1], ox = origins[3 * t + 2];
+  int yy = e / edge, xx = e - yy * edge;
+  const bool zin = (unsigned)oz < (unsigned)Z;
+  const uint8_t *plane = vol + (int64_t)(zin ? oz : 0) * Y * X;
+  float v[V];
+#pragma unroll
+  for (int j = 0; j < V; ++j) {
+    if (xx == edge) { xx = 0; ++yy; }
+    const int gy = oy + yy, gx = ox + xx;
+    const bool in = zin && (unsigned)gy < (unsigned)Y && (unsigned)gx < (unsigned)X;
+    v[j] = u8_std(in ? (float)plane[(int64_t)gy * X + gx] : 0.f, mean, std);
+    ++xx;
+  }
+  float *o = out + g * V;
+  if constexpr (V == 4)
+    *reinterpret_cast<float4 *>(o) = make_float4(v[0], v[1], v[2], v[3]);
+  else
+    o[0] = v[0];
+}
+
+// scatter: thread g converts 4 consecutive interior pixels of one row of one tile (tpad stripped per side) and writes
+// them to out[iz][iy + row][ix + col ...]: one packed dword when the 4 land in the row on a 4-byte boundary, bytes
+// otherwise (the tail of a row whose interior is not a multiple of 4, unaligned offsets).  Pixels outside `out` are
+// dropped.
+__global__ __launch_bounds__(256) void f32_tiles2d_unstd_to_u8_k(const float *y, int yedge, int tpad,
+                                                                 const int32_t *index, uint8_t *out, int OZ, int OY,
+                                                                 int OX, float mean, float std, int64_t ngroup) {
+  const int64_t g = (int64_t)xcd_contiguous_block(blockIdx.x, gridDim.x) * 256 + threadIdx.x;
+  if (g >= ngroup) return;
+  const int od = yedge - 2 * tpad, gpr = (od + 3) >> 2, per_tile = od * gpr;
+  const int t = (int)(g / per_tile), r = (int)(g - (int64_t)t * per_tile);
+  const int row = r / gpr, col = (r - row * gpr) * 4;
+  const int iz = index[3 * t], oy = index[3 * t + 1] + row, ox = index[3 * t + 2] + col;
+  if ((unsigned)iz >= (unsigned)OZ || (unsigned)oy >= (unsigned)OY) return;
+  const float *src = y + (int64_t)t * yedge * yedge + (int64_t)(row + tpad) * yedge + (col + tpad);
+  const int n = min(4, od - col);
+  uint8_t q[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) q[j] = j < n ? unstd_u8(src[j], mean, std) : 0;
+  uint8_t *dst = out + ((int64_t)iz * OY + oy) * OX;
+  if (n == 4 && ox >= 0 && ox + 4 <= OX && (((uintptr_t)(dst + ox)) & 3) == 0) {
+    *reinterpret_cast<uint32_t *>(dst + ox) = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) |
+                                              ((uint32_t)q[3] << 24);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (j < n && (unsigned)(ox + j) < (unsigned)OX) dst[ox + j] = q[j];
   }
 }
 
@@ -398,6 +466,45 @@ extern "C" int tem_f32_tiles_unstd_to_u8(const float *y, int32_t ntile, int32_t 
   unsigned gx = grid_for((int64_t)od * od * od); if (gx > 512) gx = 512;
   hipLaunchKernelGGL(f32_tiles_unstd_to_u8_k, dim3(gx, (unsigned)ntile), dim3(256), 0, (hipStream_t)stream, y, yedge, tpad,
                      index_dev, out, OY, OX, mean, std);
+  TEM_CHECK_LAUNCH();
+  return TEM_OK;
+}
+
+extern "C" int tem_u8_tiles2d_to_f32_std(const uint8_t *vol, int32_t Z, int32_t Y, int32_t X, const int32_t *origins_dev,
+                                         int32_t ntile, int32_t edge, float *out, float mean, float std,
+                                         tem_stream_t stream) {
+  TEM_CLEAR_ERR();
+  if (!vol || !origins_dev || !out || Z < 1 || Y < 1 || X < 1 || ntile < 0 || edge < 1 || edge > 46340)
+    return TEM_EINVAL;
+  if (ntile == 0) return TEM_OK;
+  const int V = (edge % 2 == 0 && ((uintptr_t)out & 15) == 0) ? 4 : 1;
+  const int64_t ngroup = (int64_t)ntile * edge * edge / V;
+  const int64_t nblk = (ngroup + 255) / 256;
+  if (nblk > 0x7fffffff) return TEM_EUNSUPPORTED;
+  if (V == 4)
+    hipLaunchKernelGGL(u8_tiles2d_to_f32_std_k<4>, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, vol, Z, Y,
+                       X, origins_dev, edge, out, mean, std, ngroup);
+  else
+    hipLaunchKernelGGL(u8_tiles2d_to_f32_std_k<1>, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, vol, Z, Y,
+                       X, origins_dev, edge, out, mean, std, ngroup);
+  TEM_CHECK_LAUNCH();
+  return TEM_OK;
+}
+
+extern "C" int tem_f32_tiles2d_unstd_to_u8(const float *y, int32_t ntile, int32_t yedge, int32_t tpad,
+                                           const int32_t *index_dev, uint8_t *out, int32_t OZ, int32_t OY, int32_t OX,
+                                           float mean, float std, tem_stream_t stream) {
+  TEM_CLEAR_ERR();
+  if (!y || !index_dev || !out || ntile < 0 || yedge < 1 || yedge > 46340 || tpad < 0 || 2 * tpad >= yedge || OZ < 1 ||
+      OY < 1 || OX < 1)
+    return TEM_EINVAL;
+  if (ntile == 0) return TEM_OK;
+  const int od = yedge - 2 * tpad;
+  const int64_t ngroup = (int64_t)ntile * od * ((od + 3) / 4);
+  const int64_t nblk = (ngroup + 255) / 256;
+  if (nblk > 0x7fffffff) return TEM_EUNSUPPORTED;
+  hipLaunchKernelGGL(f32_tiles2d_unstd_to_u8_k, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, y, yedge, tpad,
+                     index_dev, out, OZ, OY, OX, mean, std, ngroup);
   TEM_CHECK_LAUNCH();
   return TEM_OK;
 }

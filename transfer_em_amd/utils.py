@@ -10,6 +10,10 @@ shard them over processes (one per GPU) without any collective.
 `predict_volume` is the out-of-core form for volumes that do not fit in memory (np.memmap, h5py, zarr): the same
 tiles, grouped into chunks of whole tiles (`chunk_plan`), each read from the volume by its footprint only and
 streamed through the same kernels with the I/O of neighbouring chunks overlapped with the GPU work.
+
+Every entry point dispatches on `model.generator_g.is3d`.  A 2-D model predicts a stack of sections [z, y, x] section
+by section (`tile_plan_2d`: tile_plan's in-plane tiling in every section, no halo and no rounding along z) through the
+2-D tile kernels, or one image [y, x] given 2-element start / size.
 """
 import json
 import os
@@ -41,6 +45,91 @@ def tile_plan(start, size, outdimsize, buffer):
 TILE_BATCH = 27      # tiles per generator launch sequence (27 x 132^3: ~10 GB of activations; 288 GB HBM)
 
 
+def tile_plan_2d(start, size, outdimsize, buffer):
+    """The 2-D counterpart of tile_plan: every section z in [start[2], start[2] + size[2]) is tiled on its own with
+    tile_plan's in-plane rules (same "multiple of 6" quirk, tpad, halo, rounding up to whole tiles in y and x); no
+    halo and no rounding along z.  Returns (outdimsize, buffer, tpad, rois, index) with (x, y, z) rois / index whose z
+    is the section itself (absolute in rois, relative to start[2] in index)."""
+    tpad = 0
+    if (outdimsize // 6) != 0:
+        diff = outdimsize % 6
+        outdimsize -= diff
+        tpad = diff // 2
+        buffer += tpad
+    rois, index = [], []
+    for xiter in range(start[0], start[0] + size[0], outdimsize):
+        for yiter in range(start[1], start[1] + size[1], outdimsize):
+            for ziter in range(start[2], start[2] + size[2]):
+                rois.append((xiter - buffer, yiter - buffer, ziter))
+                index.append((xiter - start[0], yiter - start[1], ziter - start[2]))
+    return outdimsize, buffer, tpad, rois, index
+
+
+def plan_bytes_per_tile(edge, is3d=True, wf=8):
+    """Bytes one input tile of edge `edge` pins in a generator inference plan (GenForward): the fp32 input and every
+    layer's activation."""
+    from .models.generator import generator_edges, generator_param_shapes
+    shapes = generator_param_shapes(is3d, wf)
+    ch = {k: v[-1] for k, v in shapes.items()}
+    ch["u2b"], ch["u1b"] = shapes["u2b"][3], shapes["u1b"][3]
+    e, d = generator_edges(edge), 3 if is3d else 2
+    return 4 * (edge ** d + sum(e[k] ** d * c for k, c in ch.items()))
+
+
+TILE_BATCH_MAX_2D = 4096     # cap of the 2-D batch (see default_tile_batch)
+
+
+def default_tile_batch(edge, is3d=True):
+    """Tiles per generator launch sequence when the caller gives none.  3-D: TILE_BATCH.  2-D tiles are ~100x smaller,
+    so the batch is sized by bytes instead: as many tiles as fit the activations TILE_BATCH tiles of the 132^3 model
+    pin (~8 GB; 2-D 132: ~2,500 tiles), capped at TILE_BATCH_MAX_2D.  A prediction runs full batches and one remainder,
+    and the generator caches MAX_PLANS = 2 plan shapes; the cap keeps the small models' batch below the size of most
+    requests, so that their full-batch plan is reused from request to request instead of every request's size
+    becoming a plan of its own."""
+    if is3d:
+        return TILE_BATCH
+    budget = TILE_BATCH * plan_bytes_per_tile(132, True)
+    return max(1, min(TILE_BATCH_MAX_2D, budget // plan_bytes_per_tile(edge, False)))
+
+
+def _tile_kernels(lib, is3d):
+    """(gather, scatter) C entry points and their names: the cube tiles or the 2-D (one section) tiles."""
+    names = (("tem_u8_tiles_to_f32_std", "tem_f32_tiles_unstd_to_u8") if is3d else
+             ("tem_u8_tiles2d_to_f32_std", "tem_f32_tiles2d_unstd_to_u8"))
+    return tuple((getattr(lib, n), n) for n in names)
+
+
+class _OneSection:
+    """A [y, x] array-like seen as a one-section stack [1, y, x] (basic slicing only, for predict_volume)."""
+
+    def __init__(self, a):
+        self.a, self.shape = a, (1,) + tuple(int(v) for v in a.shape)
+
+    def _key(self, key):
+        z, y, x = key
+        if range(1)[z] != range(1):                    # the whole (only) section
+            raise IndexError(f"section {z} of a single image")
+        return y, x
+
+    def __getitem__(self, key):
+        return np.asarray(self.a[self._key(key)])[None]
+
+    def __setitem__(self, key, value):
+        self.a[self._key(key)] = value[0]
+
+
+def _single_image(model, start, size):
+    """True for the [y, x] single-image form (2-element start and size), which only 2-D models accept."""
+    if len(start) == 2 and len(size) == 2:
+        if getattr(getattr(model, "generator_g", None), "is3d", True):
+            raise ValueError("a single [y, x] image (2-element start / size) needs a 2-D model")
+        return True
+    if len(start) != 3 or len(size) != 3:
+        raise ValueError(f"start and size must both have 3 elements (x, y, z) or, for one image, 2 (x, y): "
+                         f"got {start}, {size}")
+    return False
+
+
 def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=False, outdimsize=None, buffer=None,
                  rank=0, world_size=1, tile_batch=None):
     """Predict the subvolume [start, start+size) (x,y,z order as in the reference) of a uint8
@@ -52,14 +141,24 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
     standardized, tem_u8_tiles_to_f32_std); the generator runs the batch as ONE launch sequence (batch = tile
     count: the small inner layers then fill the chip); one scatter kernel un-standardizes, rounds and writes
     every tile's interior into the uint8 output volume (tem_f32_tiles_unstd_to_u8).  Tile geometry, halo and
-    the "multiple of 6" quirk are the reference's (tile_plan)."""
+    the "multiple of 6" quirk are the reference's (tile_plan).
+
+    A 2-D model (generator_g.is3d False) predicts every section of [start[2], start[2] + size[2]) on its own
+    (tile_plan_2d) through the 2-D tile kernels; it also takes one image `volume` [y, x] with 2-element (x, y) `start`
+    and `size`, and then returns [y, x] arrays."""
     from . import _lib
     lib = H.require_gpu()
+    gen = getattr(model, "generator_g", None)
+    is3d = getattr(gen, "is3d", True)
+    if _single_image(model, start, size):
+        res = predict_cube(np.asarray(volume)[None], tuple(start) + (0,), tuple(size) + (1,), model, meanstd_x,
+                           meanstd_y, fetch_input, outdimsize, buffer, rank, world_size, tile_batch)
+        return tuple(r[0] for r in res) if fetch_input else res[0]
     if outdimsize is None:
         outdimsize = model.outdimsize
     if buffer is None:
         buffer = model.buffer
-    outdimsize, buffer, tpad, rois, index = tile_plan(start, size, outdimsize, buffer)
+    outdimsize, buffer, tpad, rois, index = (tile_plan if is3d else tile_plan_2d)(start, size, outdimsize, buffer)
     edge = outdimsize + buffer * 2
     z, y, x = size[2], size[1], size[0]
     rnd = lambda v: v + ((outdimsize - (v % outdimsize)) if (v % outdimsize) != 0 else 0)
@@ -67,11 +166,12 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
     vol_host = np.ascontiguousarray(volume, dtype=np.uint8)
     vol = torch.from_numpy(vol_host).to(dev, non_blocking=True)          # ONE upload of the whole volume
     Z, Y, X = vol_host.shape
-    out_buffer = torch.zeros((rnd(z), rnd(y), rnd(x)), dtype=torch.uint8, device=dev)
+    out_buffer = torch.zeros((rnd(z) if is3d else z, rnd(y), rnd(x)), dtype=torch.uint8, device=dev)
     OZ, OY, OX = out_buffer.shape
     mine = list(range(rank, len(rois), world_size))
-    nb = max(1, min(int(tile_batch or TILE_BATCH), len(mine) or 1))
-    gen = getattr(model, "generator_g", None)
+    nb = max(1, min(int(tile_batch or default_tile_batch(edge, is3d)), len(mine) or 1))
+    tile = (edge, edge, edge) if is3d else (1, edge, edge)               # (D, H, W) of one generator input
+    (gather, gname), (scatter, sname) = _tile_kernels(lib, is3d)
     stream = H.current_stream()
     for c0 in range(0, len(mine), nb):
         chunk = mine[c0:c0 + nb]
@@ -79,19 +179,17 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
         org = torch.tensor([[rois[i][2], rois[i][1], rois[i][0]] for i in chunk], dtype=torch.int32).to(dev)   # (z,y,x)
         idx = torch.tensor([[index[i][2], index[i][1], index[i][0]] for i in chunk], dtype=torch.int32).to(dev)
         if hasattr(gen, "plan"):
-            plan = gen.plan((n, edge, edge, edge, 1))                      # static launch plan, buffers reused
+            plan = gen.plan((n,) + tile + (1,))                            # static launch plan, buffers reused
             tiles = plan.x
         else:
-            plan, tiles = None, torch.empty((n, edge, edge, edge, 1), dtype=torch.float32, device=dev)
-        _lib.check(lib.tem_u8_tiles_to_f32_std(vol.data_ptr(), Z, Y, X, org.data_ptr(), n, edge, tiles.data_ptr(),
-                                               float(meanstd_x[0]), float(meanstd_x[1]), stream),
-                   "tem_u8_tiles_to_f32_std")
+            plan, tiles = None, torch.empty((n,) + tile + (1,), dtype=torch.float32, device=dev)
+        _lib.check(gather(vol.data_ptr(), Z, Y, X, org.data_ptr(), n, edge, tiles.data_ptr(), float(meanstd_x[0]),
+                          float(meanstd_x[1]), stream), gname)
         data_y = plan.run() if plan is not None else model.predict(tiles).contiguous()
-        yedge = data_y.shape[1]
+        yedge = data_y.shape[2]
         assert yedge - 2 * tpad == outdimsize, (yedge, tpad, outdimsize)
-        _lib.check(lib.tem_f32_tiles_unstd_to_u8(data_y.data_ptr(), n, yedge, tpad, idx.data_ptr(), out_buffer.data_ptr(),
-                                                 OZ, OY, OX, float(meanstd_y[0]), float(meanstd_y[1]), stream),
-                   "tem_f32_tiles_unstd_to_u8")
+        _lib.check(scatter(data_y.data_ptr(), n, yedge, tpad, idx.data_ptr(), out_buffer.data_ptr(), OZ, OY, OX,
+                           float(meanstd_y[0]), float(meanstd_y[1]), stream), sname)
     if world_size > 1 and torch.distributed.is_initialized():
         torch.distributed.all_reduce(out_buffer, op=torch.distributed.ReduceOp.MAX)   # disjoint tiles, zeros elsewhere
     out = out_buffer[0:size[2], 0:size[1], 0:size[0]].cpu().numpy()
@@ -134,17 +232,46 @@ def _default_chunk_tiles(grid, cap):
     return best
 
 
-def _chunk_plan(start, size, outdimsize, buffer, vol_shape, chunk_tiles, rank=0, world_size=1):
-    outdimsize, buffer, tpad, rois, index = tile_plan(start, size, outdimsize, buffer)
+def _default_chunk_tiles_2d(grid, cap, od, halo):
+    """(kz, ky, kx) sections x tiles with kz*ky*kx <= cap over `grid`.  Every distinct chunk tile count is a generator
+    plan of its own (built per call once there are more than MAX_PLANS), so among the boxes within 1.5x of the fewest
+    chunks the one with the fewest distinct tile counts wins; ties go to fewer chunks, then to the least footprint read
+    per tile (the in-plane halo; there is none along z), then to more tiles per chunk."""
+    ext = lambda g, k: {k} | ({g % k} if g % k else set())       # chunk extents along an axis: full, tail
+    cands = []
+    for kz in range(1, min(grid[0], cap) + 1):
+        for ky in range(1, min(grid[1], cap // kz) + 1):
+            for kx in range(1, min(grid[2], cap // (kz * ky)) + 1):
+                n = -(-grid[0] // kz) * -(-grid[1] // ky) * -(-grid[2] // kx)
+                cands.append((n, kz, ky, kx))
+    if not cands:
+        return 1, 1, 1
+    n_min = min(c[0] for c in cands)
+    best, key = (1, 1, 1), None
+    for n, kz, ky, kx in cands:
+        if n > 1.5 * n_min:
+            continue
+        shapes = len({a * b * c for a in ext(grid[0], kz) for b in ext(grid[1], ky) for c in ext(grid[2], kx)})
+        k = (shapes, n, (ky * od + 2 * halo) * (kx * od + 2 * halo) / (ky * kx), -kz * ky * kx)
+        if key is None or k < key:
+            best, key = (kz, ky, kx), k
+    return best
+
+
+def _chunk_plan(start, size, outdimsize, buffer, vol_shape, chunk_tiles, rank=0, world_size=1, is3d=True):
+    outdimsize, buffer, tpad, rois, index = (tile_plan if is3d else tile_plan_2d)(start, size, outdimsize, buffer)
     od, edge = outdimsize, outdimsize + 2 * buffer
+    # (z, y, x) extent of one tile's output (`step`) and haloed input (`ext`): a 2-D tile is one section thick
+    step, ext = ((od, od, od), (edge, edge, edge)) if is3d else ((1, od, od), (1, edge, edge))
     size_zyx = (size[2], size[1], size[0])
-    grid = tuple(len(range(0, n, od)) for n in size_zyx)
+    grid = tuple(len(range(0, n, s)) for n, s in zip(size_zyx, step))
     if chunk_tiles is None:
-        chunk_tiles = _default_chunk_tiles(grid, TILE_BATCH)
+        chunk_tiles = (_default_chunk_tiles(grid, TILE_BATCH) if is3d else
+                       _default_chunk_tiles_2d(grid, default_tile_batch(edge, False), od, buffer))
     kz, ky, kx = (int(v) for v in chunk_tiles)
     if min(kz, ky, kx) < 1:
         raise ValueError(f"chunk_tiles must be positive, got {chunk_tiles}")
-    at = {(iz // od, iy // od, ix // od): i for i, (ix, iy, iz) in enumerate(index)}   # tile grid cell -> tile
+    at = {(iz // step[0], iy // step[1], ix // step[2]): i for i, (ix, iy, iz) in enumerate(index)}   # grid cell -> tile
     chunks = []
     for gz in range(0, grid[0], kz):            # z-major: consecutive chunks read neighbouring slabs of the volume
         for gy in range(0, grid[1], ky):
@@ -154,10 +281,11 @@ def _chunk_plan(start, size, outdimsize, buffer, vol_shape, chunk_tiles, rank=0,
                 tiles = tuple(sorted(at[c] for c in cells))            # tile_plan order
                 org = [(rois[i][2], rois[i][1], rois[i][0]) for i in tiles]
                 read = tuple((min(max(min(o[d] for o in org), 0), vol_shape[d]),
-                              max(min(max(o[d] for o in org) + edge, vol_shape[d]), 0)) for d in range(3))
+                              max(min(max(o[d] for o in org) + ext[d], vol_shape[d]), 0)) for d in range(3))
                 read = tuple((lo, max(lo, hi)) for lo, hi in read)
-                base = (gz * od, gy * od, gx * od)
-                dims = tuple(k * od for k in (min(kz, grid[0] - gz), min(ky, grid[1] - gy), min(kx, grid[2] - gx)))
+                base = (gz * step[0], gy * step[1], gx * step[2])
+                dims = tuple(k * s for k, s in zip((min(kz, grid[0] - gz), min(ky, grid[1] - gy), min(kx, grid[2] - gx)),
+                                                   step))
                 chunks.append(VolumeChunk(
                     tiles=tiles,
                     origins=tuple(tuple(o[d] - read[d][0] for d in range(3)) for o in org),
@@ -170,7 +298,7 @@ def _chunk_plan(start, size, outdimsize, buffer, vol_shape, chunk_tiles, rank=0,
     return outdimsize, buffer, tpad, chunks[rank::world_size]
 
 
-def chunk_plan(start, size, outdimsize, buffer, vol_shape, chunk_tiles, rank=0, world_size=1):
+def chunk_plan(start, size, outdimsize, buffer, vol_shape, chunk_tiles, rank=0, world_size=1, is3d=True):
     """Group the tiles of tile_plan(start, size, outdimsize, buffer) into boxes of chunk_tiles = (kz, ky, kx) whole
     tiles (fewer at the ROI's far faces) over a volume of shape vol_shape = (Z, Y, X).  Chunks go round-robin to the
     ranks.  Returns this rank's list of VolumeChunk; chunk_tiles=None picks the box predict_volume uses by default
@@ -179,9 +307,13 @@ def chunk_plan(start, size, outdimsize, buffer, vol_shape, chunk_tiles, rank=0, 
     The staging block of a chunk is exactly footprint = (union of its tiles' haloed boxes) n volume, and every tile
     voxel lies in that union.  So a tile voxel falls outside the block if and only if it falls outside the volume,
     and the resident-volume gather (tem_u8_tiles_to_f32_std) given the block, its dims and block-relative origins
-    reads the same bytes as on the whole volume, zeros outside included."""
+    reads the same bytes as on the whole volume, zeros outside included.
+
+    is3d=False groups tile_plan_2d's tiles instead: a chunk is a run of kz sections x (ky x kx) in-plane tiles, its
+    footprint is haloed in y and x only (its z extent is exactly its sections, clipped to the volume), and
+    chunk_tiles=None picks at most default_tile_batch(edge, False) tiles, fewest chunks, least halo read per tile."""
     return _chunk_plan(start, size, outdimsize, buffer, tuple(int(v) for v in vol_shape), chunk_tiles, rank,
-                       world_size)[3]
+                       world_size, is3d)[3]
 
 
 def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, chunk_tiles=None, tile_batch=None,
@@ -198,7 +330,10 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
     chunk's interior into `out`.  Staging is double-buffered (pinned and device, input and output), so the reads,
     copies and writes of neighbouring chunks run while the GPU computes.  Ranks (rank / world_size) take chunks
     round-robin and write disjoint boxes of a shared `out`; no collective is used.  `stats` (a dict) receives the
-    host thread's read and write seconds and the number of chunks."""
+    host thread's read and write seconds and the number of chunks.
+
+    A 2-D model streams chunks of chunk_plan(..., is3d=False) through the same pipeline with the 2-D tile kernels;
+    it also takes one image `volume` [y, x] with 2-element (x, y) `start` / `size` (`out` is then [y, x])."""
     import time
     from concurrent.futures import ThreadPoolExecutor
     from . import _lib
@@ -206,13 +341,24 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
     gen = model.generator_g
     if not hasattr(gen, "plan"):
         raise TypeError("predict_volume needs a generator with launch plans (EM2EM or a saved model)")
+    if _single_image(model, start, size):
+        if len(volume.shape) != 2:
+            raise ValueError(f"a 2-element start / size needs one image [y, x], got shape {tuple(volume.shape)}")
+        if out is None:
+            out = np.zeros((size[1], size[0]), np.uint8)
+        predict_volume(_OneSection(volume), tuple(start) + (0,), tuple(size) + (1,), model, meanstd_x, meanstd_y,
+                       _OneSection(out), chunk_tiles, tile_batch, outdimsize, buffer, rank, world_size, stats)
+        return out
+    is3d = gen.is3d
     vol_shape = tuple(int(v) for v in volume.shape)
     if len(vol_shape) != 3:
         raise ValueError(f"volume must be 3-D [z, y, x], got shape {vol_shape}")
     od, buf, tpad, chunks = _chunk_plan(start, size, model.outdimsize if outdimsize is None else outdimsize,
                                         model.buffer if buffer is None else buffer, vol_shape, chunk_tiles, rank,
-                                        world_size)
+                                        world_size, is3d)
     edge = od + 2 * buf
+    tile = (edge, edge, edge) if is3d else (1, edge, edge)               # (D, H, W) of one generator input
+    (gather, gname), (scatter, sname) = _tile_kernels(lib, is3d)
     if out is None:
         out = np.zeros((size[2], size[1], size[0]), np.uint8)
     elif tuple(out.shape) != (size[2], size[1], size[0]):
@@ -227,7 +373,7 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
     gdims = [c.block if min(c.block) > 0 else (1, 1, 1) for c in chunks]
     in_bytes = [int(np.prod(g)) for g in gdims]
     out_bytes = [int(np.prod(c.dims)) for c in chunks]
-    nb = max(1, min(int(tile_batch or TILE_BATCH), max(len(c.tiles) for c in chunks)))
+    nb = max(1, min(int(tile_batch or default_tile_batch(edge, is3d)), max(len(c.tiles) for c in chunks)))
     dev = model.device
     compute = torch.cuda.current_stream(dev)
     h2d, d2h = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
@@ -282,19 +428,17 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
                 m = min(nb, n - b0)
                 if plan is None or plan.x.shape[0] != m:
                     plan = None                              # let the plan cache release an evicted plan's buffers
-                    plan = gen.plan((m, edge, edge, edge, 1))
+                    plan = gen.plan((m,) + tile + (1,))
                 t = int(first[k]) + b0
-                _lib.check(lib.tem_u8_tiles_to_f32_std(dev_in[s].data_ptr(), Z, Y, X, org.data_ptr() + 12 * t, m, edge,
-                                                       plan.x.data_ptr(), float(meanstd_x[0]), float(meanstd_x[1]),
-                                                       compute.cuda_stream), "tem_u8_tiles_to_f32_std")
+                _lib.check(gather(dev_in[s].data_ptr(), Z, Y, X, org.data_ptr() + 12 * t, m, edge, plan.x.data_ptr(),
+                                  float(meanstd_x[0]), float(meanstd_x[1]), compute.cuda_stream), gname)
                 if b0 + m == n:
                     gathered[k] = compute.record_event()
                 data_y = plan.run(compute.cuda_stream)
-                assert data_y.shape[1] - 2 * tpad == od, (data_y.shape, tpad, od)
-                _lib.check(lib.tem_f32_tiles_unstd_to_u8(data_y.data_ptr(), m, data_y.shape[1], tpad,
-                                                         idx.data_ptr() + 12 * t, dev_out[s].data_ptr(), OZ, OY, OX,
-                                                         float(meanstd_y[0]), float(meanstd_y[1]), compute.cuda_stream),
-                           "tem_f32_tiles_unstd_to_u8")
+                assert data_y.shape[2] - 2 * tpad == od, (data_y.shape, tpad, od)
+                _lib.check(scatter(data_y.data_ptr(), m, data_y.shape[2], tpad, idx.data_ptr() + 12 * t,
+                                   dev_out[s].data_ptr(), OZ, OY, OX, float(meanstd_y[0]), float(meanstd_y[1]),
+                                   compute.cuda_stream), sname)
             scattered = compute.record_event()
             if k >= 2:
                 writes.pop(k - 2).result()                   # pin_out[s]: chunk k-2 is in `out`
