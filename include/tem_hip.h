@@ -305,6 +305,35 @@ int tem_augment_f32(const float *src, int32_t D, int32_t H, int32_t W, int32_t p
 int tem_warp_f32(const float *src, int32_t D, int32_t H, int32_t W, float rate, uint64_t seed, float *dst,
                  uint8_t *seeds, double *sum, tem_stream_t stream);
 
+/* One batch of the generator dataset's crops (datasets.py:69-155 over generators.py:59-118), cut in one launch.
+ * Source: `src` is uint8 (src_f32 == 0: converted x / 127.5 - 1) or float32 (src_f32 == 1: taken as is); sample b
+ * reads src + b * sB with element strides sZ, sY, sX and extents vol[3] (z, y, x).  Crop b is the n[3] box at origin
+ * params[12b + 0..2] (z, y, x), REFLECT-padded by pad_lo / pad_hi voxels per axis as np.pad(..., "reflect") (the
+ * padding is an index map inside the crop; a crop not inside vol reads NaN).  Then, when enabled:
+ * (v - mean) / std (standardize), and dst = reverse(transpose(v, perm), flagged dims) * var_adj + mean_adj
+ * (augment; perm = params[12b + 3..5], flips = params[12b + 6..8], var_adj / mean_adj = the float bits of
+ * params[12b + 9..10], params[12b + 11] unused).  Every step is one correctly rounded float32 operation, in that order.
+ * dst: B dense samples of the padded extents permuted (sample stride = their product), 16-byte aligned.  params is a
+ * device pointer. */
+typedef struct tem_crop_args {
+  const void *src;
+  int32_t src_f32;
+  int32_t B;
+  int64_t sB, sZ, sY, sX;
+  int64_t vol[3];
+  int32_t n[3], pad_lo[3], pad_hi[3];
+  int32_t standardize, augment;
+  float mean, std;
+  const int32_t *params;
+  float *dst;
+} tem_crop_args;
+
+int tem_crop_batch(const tem_crop_args *args, tem_stream_t stream);
+
+/* Statistics pass of the dataset (datasets.py:173-190): B dense float32 samples of n elements; block k of sample b
+ * writes partials[(b * nblk + k) * 2 + {0, 1}] = float64 {sum, sum of squares} of its grid-strided share. */
+int tem_sample_sums_f32(const float *src, int32_t B, int64_t n, int32_t nblk, double *partials, tem_stream_t stream);
+
 /* dst[i] = value */
 int tem_fill_f32(float *dst, int64_t n, float value, tem_stream_t stream);
 

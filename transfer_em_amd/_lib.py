@@ -72,6 +72,14 @@ class tem_head_bwd_args(C.Structure):
                 ("slab_w1", C.c_void_p), ("slab_w2", C.c_void_p), ("slab_b", C.c_void_p), ("nslab", C.c_int32), ("nvox", C.c_int64)]
 
 
+
+class tem_crop_args(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("src_f32", C.c_int32), ("B", C.c_int32),
+                ("sB", C.c_int64), ("sZ", C.c_int64), ("sY", C.c_int64), ("sX", C.c_int64), ("vol", C.c_int64 * 3),
+                ("n", C.c_int32 * 3), ("pad_lo", C.c_int32 * 3), ("pad_hi", C.c_int32 * 3),
+                ("standardize", C.c_int32), ("augment", C.c_int32), ("mean", C.c_float), ("std", C.c_float),
+                ("params", C.c_void_p), ("dst", C.c_void_p)]
+
 _VP = C.POINTER(tem_view)
 _SIGS = {
     "tem_disc_head_nslab": [C.c_int64],
@@ -123,6 +131,8 @@ _SIGS = {
     "tem_warp_f32": [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                      C.c_void_p],
     "tem_fill_f32": [C.c_void_p, C.c_int64, C.c_float, C.c_void_p],
+    "tem_crop_batch": [C.POINTER(tem_crop_args), C.c_void_p],
+    "tem_sample_sums_f32": [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p],
     "tem_copy_view": [_VP, _VP, C.c_void_p],
     "tem_add_view": [_VP, _VP, C.c_void_p],
     "tem_leaky_gate_view": [_VP, _VP, C.c_float, C.c_void_p],

@@ -52,6 +52,11 @@ def get_meanstd(dataset, replicas=False):
         t = np.asarray(tensor, np.float32)
         mean += float(t.mean(dtype=np.float32))
         var += float(t.var(dtype=np.float32))
+    return _combine_meanstd(mean, var, count, replicas)
+
+
+def _combine_meanstd(mean, var, count, replicas):
+    """get_meanstd's last step: the sums of per-tensor means and variances over `count` tensors -> (mean, std)."""
     if replicas:
         import torch
         import torch.distributed as dist
@@ -244,7 +249,7 @@ def meanstd_samples(sample_voxels, epoch_size):
 
 def create_dataset_from_generator(dataset, shape=None, custom_map=None, batch_size=BATCH_SIZE, epoch_size=EPOCH_SIZE,
                                   global_adjust=True, meanstd=None, padding=None, enable_augmentation=False, seed=0,
-                                  device=None, rank=0, world_size=1):
+                                  device=None, rank=0, world_size=1, resident_bytes=None):
     """Takes an (infinite) python generator of 2D/3D uint8 arrays; every epoch draws `epoch_size` fresh samples
     (datasets.py:69-119; `shape` is deprecated and ignored there too).
 
@@ -253,7 +258,28 @@ def create_dataset_from_generator(dataset, shape=None, custom_map=None, batch_si
     pass (meanstd_samples: the whole epoch for 2-D tiles, the first 64 volumes of a 3-D stream), whose samples are
     then used as the head of epoch 1 instead of being thrown away.  Under data parallelism (torch.distributed
     initialised, every rank drawing its own crops) the ranks' statistics are combined before anything is
-    standardized, so all replicas -- and the checkpoint / meta.json rank 0 writes -- share one (mean, std)."""
+    standardized, so all replicas -- and the checkpoint / meta.json rank 0 writes -- share one (mean, std).
+
+    `dataset` may be a sampler of generators.volume3d_ng / image2d_ng.  With world_size > 1 each rank then draws from
+    the sampler's per-rank stream.  With `device=` and custom_map None or debug.warp_tensor, the crops are cut, warped,
+    standardized and augmented on the GPU (device_volume.DeviceVolumeDataset: the same numbers as this host path, no
+    float work on the host); the region every crop can touch is uploaded once if it fits in `resident_bytes`
+    (default 4 GiB), else each batch's crops are streamed."""
+    from .generators import VolumeSampler
+    if isinstance(dataset, VolumeSampler):
+        if world_size > 1:
+            dataset = dataset.for_rank(rank)
+        from .. import debug
+        if device is not None and (custom_map is None or custom_map is debug.warp_tensor):
+            from . import device_volume as V
+            ds = V.DeviceVolumeDataset(dataset, batch_size, epoch_size, padding=padding,
+                                       warp=custom_map is not None, meanstd=meanstd, global_adjust=global_adjust,
+                                       enable_augmentation=enable_augmentation, seed=seed, device=device, rank=rank,
+                                       world_size=world_size,
+                                       resident_bytes=V.RESIDENT_BYTES if resident_bytes is None else resident_bytes)
+            if global_adjust and meanstd is None:
+                meanstd = ds.compute_meanstd(meanstd_samples(ds.voxels, epoch_size))
+            return ds, meanstd
     source = iter(dataset)
     first = []
     if global_adjust and meanstd is None:
