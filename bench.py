@@ -1,7 +1,14 @@
 #!/usr/bin/env python
 """Headline benchmark: CycleGAN train steps/sec on 132^3 x 1 volumes (BASELINE.json config[1]).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--no-cpu-baseline] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--sustain S] [--kernel-table]]
+
+A plain run sets up, runs W warm-up and K timed steps, writes --dump-outputs and prints the JSON line: `value`,
+`ms_per_step` and the `config` fields (algorithmic GFLOP / GB per step are summed from the launches' metadata, no run).
+--full adds what takes runs of its own: the sustained window (S = 400 further steps), the per-kernel HIP-event profile
+behind `roofline` (and the --kernel-table on stderr) and `cpu_baseline` (timed PyTorch-CPU steps at the full size).
+Without --full those fields are null.
 
 With --gpus N > 1 outside torch.distributed.run the script starts `python -m torch.distributed.run --nproc-per-node N
 bench.py ...` itself as a CHILD process (before touching the GPU), relays rank 0's JSON line and exits with the child's
@@ -138,6 +145,136 @@ def dry_dist(args, world, rank):
     dist.destroy_process_group()
 
 
+def algorithmic_per_step(st):
+    """Algorithmic FLOP and HBM bytes of one step: the sum of Launch.meta over the step's launches,
+    no run needed."""
+    launches = st.compute + st.update
+    return sum(l.meta.get("flops", 0.0) for l in launches), sum(l.meta.get("bytes", 0.0) for l in launches)
+
+
+def roofline_report(model, st, args, dt):
+    """--full: `roofline` of the line from per-launch HIP-event timing of extra steps (dominant kernel, whole step,
+    kernel families, HBM-bound layers, counter tables); prints the per-kernel table with --kernel-table."""
+    nprof = max(2, min(5, args.steps))
+    # roofline of the dominant kernel: launches timed one at a time on the launch stream (no other kernel on
+    # the GPU); the same launches under the real 3-stream schedule are reported beside it
+    agg = per_kernel_profile(model, st, nprof, streams=False)
+    conc = per_kernel_profile(model, st, 2, streams=True) if model.two_streams else {}
+    dom_k, dom = max(((k, v) for k, v in agg.items() if v["flops"] > 0), key=lambda kv: kv[1]["ms"])
+    secs = dom["ms"] * 1e-3
+    ai = dom["flops"] / dom["bytes"]
+    if ai > (RIDGE if args.dtype == "f32" else BF16_PEAK_TFLOPS * 1e12 / (HBM_PEAK_GBS * 1e9)):
+        roof = dict(bound="mfma", achieved=dom["flops"] / secs / 1e12,
+                    peak=FP32_PEAK_TFLOPS if args.dtype == "f32" else BF16_PEAK_TFLOPS, unit="TFLOP/s")
+    else:
+        roof = dict(bound="hbm", achieved=dom["bytes"] / secs / 1e9, peak=HBM_PEAK_GBS, unit="GB/s")
+    roof["frac"] = roof["achieved"] / roof["peak"]
+    # `achieved` counts ALGORITHMIC work (SURVEY 8(d): direct-form flops of the operator).  The Winograd-form kernels
+    # execute 2.25x fewer multiply-adds on the matrix cores for it: their hardware utilisation is reported beside it.
+    roof["flop_count"] = "algorithmic (direct-form convolution flops / launch duration)"
+    if roof["bound"] == "mfma" and dom_k.startswith("wino_"):
+        roof["executed_mfma_tflops"] = roof["achieved"] / 2.25
+        roof["executed_mfma_frac"] = roof["achieved"] / 2.25 / roof["peak"]
+    # HBM bytes per launch of this kernel from the PMC passes of profiles/collect_round.sh (the counters cannot
+    # be read inside this process): average over the same launches of the train step that `achieved` averages
+    # over.  The tables are stamped with a digest of the kernel sources they were collected on: null when the
+    # sources of this run differ (a stale table is worse than none) or the kernel has not been profiled.
+    sys.path.insert(0, os.path.join(ROOT, "profiles"))
+    from collect_traffic import csrc_digest
+    digest = csrc_digest()
+
+    def table(name):
+        try:
+            t = json.load(open(os.path.join(ROOT, "profiles", name)))
+        except (OSError, ValueError):
+            return {}
+        return t if t.get("_meta", {}).get("csrc_digest") == digest else {}
+    traffic, mfma = table("hbm_traffic.json"), table("mfma_busy.json")
+    roof["counters_match_sources"] = bool(traffic)
+    roof["traffic"] = None
+    key = dom_k.split("(")[0]
+    if key in traffic:
+        roof["traffic"] = traffic[key]["hbm_bytes_per_launch"]
+        roof["algorithmic_bytes_per_launch"] = dom["bytes"] / dom["launches"]
+    # share of the launch with the matrix pipes busy (SQ_VALU_MFMA_BUSY_CYCLES pass, profiles/collect_mfma.py)
+    roof["mfma_busy"] = mfma[key]["mfma_busy"] if key in mfma else None
+    roof["kernel"] = dom_k
+    roof["avg_launch_us"] = dom["ms"] * 1e3 / dom["launches"]
+    roof["share_of_step"] = dom["ms"] / sum(v["ms"] for v in agg.values())
+    if dom_k in conc and conc[dom_k]["ms"] > 0:       # same launches while the other two streams are busy
+        roof["concurrent_avg_launch_us"] = conc[dom_k]["ms"] * 1e3 / conc[dom_k]["launches"]
+    alone = agg
+    tot_flops, tot_bytes = algorithmic_per_step(st)
+    # whole step against the fp32 matrix peak, and the per-family table behind it (stand-alone kernel times)
+    roof["whole_step"] = {"achieved_tflops": tot_flops / (dt / args.steps) / 1e12,
+                          "frac": tot_flops / (dt / args.steps) / 1e12 / (FP32_PEAK_TFLOPS if args.dtype == "f32" else BF16_PEAK_TFLOPS),
+                          "achieved_gbs": tot_bytes / (dt / args.steps) / 1e9,
+                          "hbm_frac": tot_bytes / (dt / args.steps) / 1e9 / HBM_PEAK_GBS,
+                          "standalone_kernel_ms_per_step": sum(v["ms"] for v in agg.values()) / nprof}
+    fam = {}
+    for k, v in agg.items():
+        f = fam.setdefault(k.split("<")[0], dict(ms=0.0, flops=0.0, bytes=0.0, counter=0.0, counter_alg=0.0, busy=0.0, busy_ms=0.0))
+        f["ms"] += v["ms"]; f["flops"] += v["flops"]; f["bytes"] += v["bytes"]
+        if k in traffic and v["bytes"] > 0:            # PMC passes of profiles/collect_round.sh, same launches
+            f["counter"] += traffic[k]["hbm_bytes_per_launch"] * v["launches"]
+            f["counter_alg"] += v["bytes"]
+        if k in mfma and mfma[k]["mfma_busy"] is not None:
+            f["busy"] += mfma[k]["mfma_busy"] * v["ms"]; f["busy_ms"] += v["ms"]
+    roof["classes"] = {
+        name: {"ms_per_step": f["ms"] / nprof, "tflops": f["flops"] / (f["ms"] * 1e-3) / 1e12 if f["ms"] else 0.0,
+               "gbs": f["bytes"] / (f["ms"] * 1e-3) / 1e9 if f["ms"] else 0.0,
+               "traffic_ratio": (f["counter"] / f["counter_alg"]) if f["counter_alg"] else None,
+               "mfma_busy": (f["busy"] / f["busy_ms"]) if f["busy_ms"] else None}
+        for name, f in sorted(fam.items(), key=lambda kv: -kv[1]["ms"]) if f["flops"] > 0}
+    # the HBM-bound layers (C_in = 1 / C_out = 1: arithmetic intensity below the ridge) -- the only fp32 layers
+    # where an HBM-roofline fraction is meaningful (SURVEY F6); worst and best of them
+    hb = {k: v["bytes"] / (v["ms"] * 1e-3) / 1e9 for k, v in agg.items()
+          if v["flops"] > 0 and v["ms"] > 0 and v["flops"] / v["bytes"] < RIDGE and v["bytes"] / v["launches"] > 4e6}
+    if hb:
+        kmin, kmax = min(hb, key=hb.get), max(hb, key=hb.get)
+        # fractions of the 8.0 TB/s spec AND of the guide's measured copy rate (6.29 TB/s: what a pure stream reaches)
+        roof["hbm_bound_kernels"] = {"worst": {"kernel": kmin, "gbs": hb[kmin], "frac": hb[kmin] / HBM_PEAK_GBS,
+                                               "frac_of_measured_copy": hb[kmin] / HBM_COPY_GBS},
+                                     "best": {"kernel": kmax, "gbs": hb[kmax], "frac": hb[kmax] / HBM_PEAK_GBS,
+                                              "frac_of_measured_copy": hb[kmax] / HBM_COPY_GBS},
+                                     "all": {k: round(g, 1) for k, g in sorted(hb.items(), key=lambda kv: kv[1])},
+                                     # the same for each symbol's largest launches only (the averages above include the
+                                     # cycle path's cone windows, whose small grids cannot fill the chip)
+                                     "full_size": {k: round(agg[k]["big_bytes"] * agg[k]["big_n"] / (agg[k]["big_ms"] * 1e-3) / 1e9, 1)
+                                                   for k in sorted(hb, key=hb.get) if agg[k]["big_ms"] > 0},
+                                     "traffic_ratio": {k: round(traffic[k]["hbm_bytes_per_launch"] * agg[k]["launches"] / agg[k]["bytes"], 3)
+                                                       for k in hb if k in traffic}}
+    if args.kernel_table:
+        for k, v in sorted(alone.items(), key=lambda kv: -kv[1]["ms"]):
+            s_ = v["ms"] * 1e-3
+            print(f"{k:48s} {v['launches']:5d} launches {v['ms']:9.3f} ms  "
+                  f"{v['flops'] / s_ / 1e12 if s_ else 0:7.2f} TFLOP/s {v['bytes'] / s_ / 1e9 if s_ else 0:8.1f} GB/s",
+                  file=sys.stderr)
+    return roof
+
+
+def cpu_baseline(args, rx, ry):
+    """--full: `cpu_baseline` of the line, timed train steps of oracle/torch_ref.py at the benchmark's size."""
+    n, B = args.dimsize, args.batch
+    from oracle.torch_ref import TimedBaseline
+    cores = min(len(os.sched_getaffinity(0)), 16)       # a GPU's share of the host: 16 cores
+    TimedBaseline(74, batch=1, is3d=False, threads=cores).step(          # library warm-up, tiny 2-D case
+        torch.zeros(1, 1, 1, 74, 74), torch.zeros(1, 1, 1, 74, 74))
+    base = TimedBaseline(n, batch=B, is3d=True, threads=cores)
+    cx, cy = rx.cpu().permute(0, 4, 1, 2, 3).contiguous(), ry.cpu().permute(0, 4, 1, 2, 3).contiguous()
+    base.step(cx, cy)                                   # 1 warm-up step at the full size (SURVEY 8(d))
+    ncpu = 3
+    c0 = time.perf_counter()
+    for _ in range(ncpu):
+        base.step(cx, cy)
+    cdt = (time.perf_counter() - c0) / ncpu
+    print(f"cpu baseline: {cdt:.1f} s/step on {cores} threads", file=sys.stderr, flush=True)
+    return dict(value=1.0 / cdt, unit="steps/s", cores=cores, kind="port",
+                sample=f"mean of {ncpu} timed train steps after 1 warm-up step, 3D {n}^3 batch {B} fp32, "
+                       "oracle/torch_ref.py: PyTorch-CPU/oneDNN restatement of cgan.py:144-230 "
+                       "(TF2 itself is not installable here)")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -145,26 +282,32 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--batch", type=int, default=1, help="volumes per GPU per step")
     ap.add_argument("--dimsize", type=int, default=132)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--kernel-table", action="store_true", help="also print the per-kernel table to stderr")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the sustained window, the per-kernel profile / roofline and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--kernel-table", action="store_true", help="with --full: also print the per-kernel table to stderr")
     ap.add_argument("--no-kernel-profile", action="store_true",
                     help="only the timed steps (counter-collection runs of profiles/collect_round.sh); no JSON line")
     ap.add_argument("--graph", action="store_true", help="replay the step as captured HIP graphs instead of eager launches")
-    ap.add_argument("--sustain", type=int, default=400,
-                    help="extra steps run after the timed region and reported as sustained_ms_per_step (clock/thermal "
-                         "steady state; 0 = skip)")
+    ap.add_argument("--sustain", type=int, default=None,
+                    help="with --full: extra steps run after the timed region and reported as sustained_ms_per_step "
+                         "(clock/thermal steady state; default 400, 0 = skip)")
     ap.add_argument("--dtype", choices=("f32", "bf16"), default="f32",
                     help="f32: the headline (BASELINE configs[1], the reference's arithmetic); bf16: mixed precision "
                          "(BASELINE configs[4]: bf16 activations / kernel copies, fp32 accumulation, master weights and Adam)")
     ap.add_argument("--single-stream", action="store_true",
-                    help="run the step on one stream (kernel durations free of overlap: use under rocprofv3 to "
-                         "check roofline.avg_launch_us)")
+                    help="run the step on one stream (kernel durations free of overlap: use with --full under "
+                         "rocprofv3 to check roofline.avg_launch_us)")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="after the timed steps write the last step's losses and updated kernels to DIR/<name>.npy (rank 0)")
     ap.add_argument("--dry-dist", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full and (args.kernel_table or (args.sustain or 0) > 0):
+        ap.error("--kernel-table and --sustain > 0 are part of --full")
+    if args.sustain is None:
+        args.sustain = 400 if args.full else 0
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(sys.argv[1:], args.gpus))
@@ -252,121 +395,9 @@ def main():
         return
     if rank == 0:
         st = model._steps[B]
-        nprof = max(2, min(5, args.steps))
-        # roofline of the dominant kernel: launches timed one at a time on the launch stream (no other kernel on
-        # the GPU); the same launches under the real 3-stream schedule are reported beside it
-        agg = per_kernel_profile(model, st, nprof, streams=False)
-        conc = per_kernel_profile(model, st, 2, streams=True) if model.two_streams else {}
-        dom_k, dom = max(((k, v) for k, v in agg.items() if v["flops"] > 0), key=lambda kv: kv[1]["ms"])
-        secs = dom["ms"] * 1e-3
-        ai = dom["flops"] / dom["bytes"]
-        if ai > (RIDGE if args.dtype == "f32" else BF16_PEAK_TFLOPS * 1e12 / (HBM_PEAK_GBS * 1e9)):
-            roof = dict(bound="mfma", achieved=dom["flops"] / secs / 1e12,
-                        peak=FP32_PEAK_TFLOPS if args.dtype == "f32" else BF16_PEAK_TFLOPS, unit="TFLOP/s")
-        else:
-            roof = dict(bound="hbm", achieved=dom["bytes"] / secs / 1e9, peak=HBM_PEAK_GBS, unit="GB/s")
-        roof["frac"] = roof["achieved"] / roof["peak"]
-        # `achieved` counts ALGORITHMIC work (direct-form flops of the operator).  The Winograd-form kernels
-        # execute 2.25x fewer multiply-adds on the matrix cores for it: their hardware utilisation is reported beside it.
-        roof["flop_count"] = "algorithmic (direct-form convolution flops / launch duration)"
-        if roof["bound"] == "mfma" and dom_k.startswith("wino_"):
-            roof["executed_mfma_tflops"] = roof["achieved"] / 2.25
-            roof["executed_mfma_frac"] = roof["achieved"] / 2.25 / roof["peak"]
-        # HBM bytes per launch of this kernel from the PMC passes of profiles/collect_round.sh (the counters cannot
-        # be read inside this process): average over the same launches of the train step that `achieved` averages
-        # over.  The tables are stamped with a digest of the kernel sources they were collected on: null when the
-        # sources of this run differ (a stale table is worse than none) or the kernel has not been profiled.
-        sys.path.insert(0, os.path.join(ROOT, "profiles"))
-        from collect_traffic import csrc_digest
-        digest = csrc_digest()
-
-        def table(name):
-            try:
-                t = json.load(open(os.path.join(ROOT, "profiles", name)))
-            except (OSError, ValueError):
-                return {}
-            return t if t.get("_meta", {}).get("csrc_digest") == digest else {}
-        traffic, mfma = table("hbm_traffic.json"), table("mfma_busy.json")
-        roof["counters_match_sources"] = bool(traffic)
-        roof["traffic"] = None
-        key = dom_k.split("(")[0]
-        if key in traffic:
-            roof["traffic"] = traffic[key]["hbm_bytes_per_launch"]
-            roof["algorithmic_bytes_per_launch"] = dom["bytes"] / dom["launches"]
-        # share of the launch with the matrix pipes busy (SQ_VALU_MFMA_BUSY_CYCLES pass, profiles/collect_mfma.py)
-        roof["mfma_busy"] = mfma[key]["mfma_busy"] if key in mfma else None
-        roof["kernel"] = dom_k
-        roof["avg_launch_us"] = dom["ms"] * 1e3 / dom["launches"]
-        roof["share_of_step"] = dom["ms"] / sum(v["ms"] for v in agg.values())
-        if dom_k in conc and conc[dom_k]["ms"] > 0:       # same launches while the other two streams are busy
-            roof["concurrent_avg_launch_us"] = conc[dom_k]["ms"] * 1e3 / conc[dom_k]["launches"]
-        alone = agg
-        tot_flops = sum(v["flops"] for v in agg.values()) / nprof
-        tot_bytes = sum(v["bytes"] for v in agg.values()) / nprof
-        # whole step against the fp32 matrix peak, and the per-family table behind it (stand-alone kernel times)
-        roof["whole_step"] = {"achieved_tflops": tot_flops / (dt / args.steps) / 1e12,
-                              "frac": tot_flops / (dt / args.steps) / 1e12 / (FP32_PEAK_TFLOPS if args.dtype == "f32" else BF16_PEAK_TFLOPS),
-                              "achieved_gbs": tot_bytes / (dt / args.steps) / 1e9,
-                              "hbm_frac": tot_bytes / (dt / args.steps) / 1e9 / HBM_PEAK_GBS,
-                              "standalone_kernel_ms_per_step": sum(v["ms"] for v in agg.values()) / nprof}
-        fam = {}
-        for k, v in agg.items():
-            f = fam.setdefault(k.split("<")[0], dict(ms=0.0, flops=0.0, bytes=0.0, counter=0.0, counter_alg=0.0, busy=0.0, busy_ms=0.0))
-            f["ms"] += v["ms"]; f["flops"] += v["flops"]; f["bytes"] += v["bytes"]
-            if k in traffic and v["bytes"] > 0:            # PMC passes of profiles/collect_round.sh, same launches
-                f["counter"] += traffic[k]["hbm_bytes_per_launch"] * v["launches"]
-                f["counter_alg"] += v["bytes"]
-            if k in mfma and mfma[k]["mfma_busy"] is not None:
-                f["busy"] += mfma[k]["mfma_busy"] * v["ms"]; f["busy_ms"] += v["ms"]
-        roof["classes"] = {
-            name: {"ms_per_step": f["ms"] / nprof, "tflops": f["flops"] / (f["ms"] * 1e-3) / 1e12 if f["ms"] else 0.0,
-                   "gbs": f["bytes"] / (f["ms"] * 1e-3) / 1e9 if f["ms"] else 0.0,
-                   "traffic_ratio": (f["counter"] / f["counter_alg"]) if f["counter_alg"] else None,
-                   "mfma_busy": (f["busy"] / f["busy_ms"]) if f["busy_ms"] else None}
-            for name, f in sorted(fam.items(), key=lambda kv: -kv[1]["ms"]) if f["flops"] > 0}
-        # the HBM-bound layers (C_in = 1 / C_out = 1: arithmetic intensity below the ridge) -- the only fp32 layers
-        # where an HBM-roofline fraction is meaningful; worst and best of them
-        hb = {k: v["bytes"] / (v["ms"] * 1e-3) / 1e9 for k, v in agg.items()
-              if v["flops"] > 0 and v["ms"] > 0 and v["flops"] / v["bytes"] < RIDGE and v["bytes"] / v["launches"] > 4e6}
-        if hb:
-            kmin, kmax = min(hb, key=hb.get), max(hb, key=hb.get)
-            # fractions of the 8.0 TB/s spec AND of the guide's measured copy rate (6.29 TB/s: what a pure stream reaches)
-            roof["hbm_bound_kernels"] = {"worst": {"kernel": kmin, "gbs": hb[kmin], "frac": hb[kmin] / HBM_PEAK_GBS,
-                                                   "frac_of_measured_copy": hb[kmin] / HBM_COPY_GBS},
-                                         "best": {"kernel": kmax, "gbs": hb[kmax], "frac": hb[kmax] / HBM_PEAK_GBS,
-                                                  "frac_of_measured_copy": hb[kmax] / HBM_COPY_GBS},
-                                         "all": {k: round(g, 1) for k, g in sorted(hb.items(), key=lambda kv: kv[1])},
-                                         # the same for each symbol's largest launches only (the averages above include the
-                                         # cycle path's cone windows, whose small grids cannot fill the chip)
-                                         "full_size": {k: round(agg[k]["big_bytes"] * agg[k]["big_n"] / (agg[k]["big_ms"] * 1e-3) / 1e9, 1)
-                                                       for k in sorted(hb, key=hb.get) if agg[k]["big_ms"] > 0},
-                                         "traffic_ratio": {k: round(traffic[k]["hbm_bytes_per_launch"] * agg[k]["launches"] / agg[k]["bytes"], 3)
-                                                           for k in hb if k in traffic}}
-        if args.kernel_table:
-            for k, v in sorted(alone.items(), key=lambda kv: -kv[1]["ms"]):
-                s_ = v["ms"] * 1e-3
-                print(f"{k:48s} {v['launches']:5d} launches {v['ms']:9.3f} ms  "
-                      f"{v['flops'] / s_ / 1e12 if s_ else 0:7.2f} TFLOP/s {v['bytes'] / s_ / 1e9 if s_ else 0:8.1f} GB/s",
-                      file=sys.stderr)
-        cpu = None
-        if not args.no_cpu_baseline and world == 1:
-            from oracle.torch_ref import TimedBaseline
-            cores = min(len(os.sched_getaffinity(0)), 16)       # the GPU box grants 16 host cores per GPU
-            TimedBaseline(74, batch=1, is3d=False, threads=cores).step(          # library warm-up, tiny 2-D case
-                torch.zeros(1, 1, 1, 74, 74), torch.zeros(1, 1, 1, 74, 74))
-            base = TimedBaseline(n, batch=B, is3d=True, threads=cores)
-            cx, cy = rx.cpu().permute(0, 4, 1, 2, 3).contiguous(), ry.cpu().permute(0, 4, 1, 2, 3).contiguous()
-            base.step(cx, cy)                                   # 1 warm-up step at the full size
-            ncpu = 3
-            c0 = time.perf_counter()
-            for _ in range(ncpu):
-                base.step(cx, cy)
-            cdt = (time.perf_counter() - c0) / ncpu
-            print(f"cpu baseline: {cdt:.1f} s/step on {cores} threads", file=sys.stderr, flush=True)
-            cpu = dict(value=1.0 / cdt, unit="steps/s", cores=cores, kind="port",
-                       sample=f"mean of {ncpu} timed train steps after 1 warm-up step, 3D {n}^3 batch {B} fp32, "
-                              "oracle/torch_ref.py: PyTorch-CPU/oneDNN restatement of cgan.py:144-230 "
-                              "(TF2 itself is not installable here)")
+        tot_flops, tot_bytes = algorithmic_per_step(st)
+        roof = roofline_report(model, st, args, dt) if args.full else None
+        cpu = cpu_baseline(args, rx, ry) if args.full and not args.no_cpu_baseline and world == 1 else None
         steps_per_s = args.steps * world / dt
         out = {
             "metric": "CycleGAN train steps/sec on 132^3 x1 uint8 volumes (per-GPU batch of 1 volume; aggregate over GPUs)",
@@ -374,7 +405,7 @@ def main():
             "ms_per_step": dt / args.steps * 1e3, "sustained_ms_per_step": sustained,
             "sustained_steps": args.sustain if sustained is not None else 0,
             "sustained_value": (world * 1e3 / sustained) if sustained else None, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": args.dtype, "data": "synthetic",
+            "dtype": args.dtype, "data": "synthetic", "full": args.full,
             "config": {"workload": (f"3D {n}^3 single-channel synthetic volumes, batch={B} per GPU, fp32, "
                                     f"EM2EM.train_step (BASELINE.json configs[1])") if args.dtype == "f32" else
                                    (f"3D {n}^3 single-channel synthetic volumes, batch={B} per GPU, bf16 mixed precision "

@@ -186,3 +186,16 @@ def test_blocks_are_specs_and_callables():
     if not torch.cuda.is_available():
         with pytest.raises(_lib.TemError, match="no CPU fallback"):
             down(torch.zeros(1, 8, 8, 8, 8))
+
+
+def test_bench_extras_need_full():
+    """The kernel table and the sustained window take runs of their own and belong to `bench.py --full`: asked for
+    without it, the benchmark refuses before it touches the GPU rather than ignoring the option."""
+    import os
+    import subprocess
+    import sys
+    bench = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py")
+    for extra in (["--kernel-table"], ["--sustain", "5"]):
+        p = subprocess.run([sys.executable, bench, "--steps", "1", "--warmup", "0"] + extra,
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120)
+        assert p.returncode == 2 and "part of --full" in p.stderr, p.stderr[-2000:]
