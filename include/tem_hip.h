@@ -393,13 +393,16 @@ int tem_leaky_gate_view(const tem_view *g, const tem_view *saved, float slope, t
  * carry bf16 pointers, strides stay in ELEMENTS.  `w` is the layer's kernel packed [tap][co][ci] in bf16
  * (tem_pack_weights_bf16); w_layout == TEM_W_FLIP_CO_CI reverses the taps (input-gradient of a stride-1 layer over
  * the un-transposed copy).  Accumulation, bias, LeakyReLU / gate / dropout run in fp32; outputs are rounded to
- * bf16 (nearest even) on store.  Same operator definition and epilogue order as tem_conv. */
+ * bf16 (nearest even) on store.  Same operator definition and epilogue order as tem_conv.
+ * 2-D geometry -- depth-1 views, kd = sd = 1, pd = 0, kh = kw in {3, 4}, sh = sw, ph = pw (is3d=False) -- is accepted by
+ * tem_conv_bf16 (k3 s1 and k4 s2), tem_conv_transpose_bf16 (k4 s2) and tem_conv_bwd_weight_bf16 (k3 s1, k4 s2, also
+ * the swapped C_out = 1 form with ph = pw = 2) for the channel pairs of the 2-D networks; 1x1 layers arrive as 1x1x1. */
 int tem_conv_bf16(const tem_conv_args *a, tem_stream_t stream);
 
 /* TEM_OK and the kernel's name (as rocprofv3 prints it) if tem_conv_bf16 accepts these arguments. */
 int tem_conv_bf16_describe(const tem_conv_args *a, char *name, int32_t name_len);
 
-/* bf16 form of tem_conv_transpose (k4 s2 only): `w` = bf16 kernel [tap][co][ci]. */
+/* bf16 form of tem_conv_transpose (k4 s2 only, 3-D or 2-D geometry): `w` = bf16 kernel [tap][co][ci]. */
 int tem_conv_transpose_bf16(const tem_conv_args *a, tem_stream_t stream);
 int tem_conv_transpose_bf16_describe(const tem_conv_args *a, char *name, int32_t name_len);
 

@@ -294,8 +294,8 @@ class EM2EM(object):
         if precision not in ("fp32", "bf16"):
             raise ValueError("precision must be 'fp32' (the reference's arithmetic, cgan.py:13-14) or 'bf16' (mixed precision: "
                              "bf16 activations and kernel copies, fp32 accumulation / master weights / Adam)")
-        if precision == "bf16" and (not is3d or disc_prior is not None):
-            raise RuntimeError("bf16 mixed precision is built for the 3-D networks without a prior")
+        if precision == "bf16" and disc_prior is not None:
+            raise RuntimeError("bf16 mixed precision is not built for a disc_prior (2-D or 3-D): train with precision='fp32'")
         self.precision, self.dtype = precision, (torch.bfloat16 if precision == "bf16" else torch.float32)
         self.device = torch.device(device or f"cuda:{torch.cuda.current_device()}")
         self.dimsize, self.exp_name, self.is3d = dimsize, exp_name, is3d

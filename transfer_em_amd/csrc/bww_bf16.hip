@@ -18,6 +18,7 @@
 #include <type_traits>
 
 int tem_bww_c1_bf16_try(const tem_bww_args *a, hipStream_t st, bool dry, int *nslab_out, char *name, int name_len);
+int tem_bww2d_bf16_try(const tem_bww_args *a, hipStream_t st, bool dry, int *nslab_out, char *name, int name_len);   // bww2d_bf16.hip
 
 namespace bww_bf16 {
 
@@ -333,6 +334,10 @@ int run(Dev p, int N, int max_slabs, hipStream_t st, bool dry, int *nslab_out) {
 
 int dispatch(const tem_bww_args *a, hipStream_t st, bool dry, int *nslab_out) {
   const tem_view &i0 = a->in0, &g = a->dout;
+  {                                                          // 2-D geometry, 3x3 / 4x4: bww2d_bf16.hip
+    const int rc = tem_bww2d_bf16_try(a, st, dry, nslab_out, g_name, g_name_len);
+    if (rc != TEM_EUNSUPPORTED) return rc;
+  }
   {                                                          // one input channel, 3x3x3: the matrix-core march of bww_c1.hip
     const int rc = tem_bww_c1_bf16_try(a, st, dry, nslab_out, g_name, g_name_len);
     if (rc != TEM_EUNSUPPORTED) return rc;

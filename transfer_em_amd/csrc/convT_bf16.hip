@@ -399,15 +399,21 @@ int dispatch(const tem_conv_args *a, hipStream_t st, bool dry) {
 
 }  // namespace convt_bf16
 
+int tem_conv_transpose2d_bf16_try(const tem_conv_args *a, hipStream_t st, bool dry, char *name, int name_len);  // convT2d_bf16.hip
+
 // bf16 mode of tem_conv_transpose (see tem_conv_bf16): `w` is the bf16 kernel [tap][co][ci].
 extern "C" int tem_conv_transpose_bf16(const tem_conv_args *a, tem_stream_t stream) {
   TEM_CLEAR_ERR();
   if (!a || !tem_view_ok(a->in0) || !tem_view_ok(a->out0) || !a->w) return TEM_EINVAL;
+  const int rc0 = tem_conv_transpose2d_bf16_try(a, (hipStream_t)stream, false, nullptr, 0);   // 2-D geometry
+  if (rc0 != TEM_EUNSUPPORTED) return rc0;
   return convt_bf16::dispatch(a, (hipStream_t)stream, false);
 }
 
 extern "C" int tem_conv_transpose_bf16_describe(const tem_conv_args *a, char *buf, int32_t len) {
   if (!a || !tem_view_ok(a->in0) || !tem_view_ok(a->out0) || !a->w) return TEM_EINVAL;
+  const int rc0 = tem_conv_transpose2d_bf16_try(a, nullptr, true, buf, len);
+  if (rc0 != TEM_EUNSUPPORTED) return rc0;
   convt_bf16::g_name = buf; convt_bf16::g_name_len = len;
   int rc = convt_bf16::dispatch(a, nullptr, true);
   convt_bf16::g_name = nullptr;

@@ -76,8 +76,8 @@ class DiscForward:
         self.dtype = x.dtype
         bf = self.bf16 = x.dtype == torch.bfloat16           # bf16 mixed precision: see models/generator.GenForward
         if bf:
-            if not is3d or net.prior is not None:
-                raise RuntimeError("bf16 mixed precision is built for the 3-D networks without a prior")
+            if net.prior is not None:
+                raise RuntimeError("bf16 mixed precision is not built for a disc_prior (2-D or 3-D)")
             P.enable_bf16()
         N = x.shape[0]
         e = self.edges = discriminator_edges(x.shape[3], is3d)

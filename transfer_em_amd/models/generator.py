@@ -140,8 +140,6 @@ class GenForward:
         self.dtype = dtype = x.dtype
         bf = self.bf16 = dtype == torch.bfloat16
         if bf:
-            if not is3d:
-                raise RuntimeError("bf16 mixed precision is built for the 3-D networks")
             P.enable_bf16()
         wf = P.wht if bf else P.w                 # forward Conv
         wT = P.wh if bf else P.w                  # forward ConvTranspose
@@ -177,7 +175,8 @@ class GenForward:
                 self.keep[blk] = torch.zeros(nbytes, dtype=torch.uint8, device=x.device)
         # fp32 3-D: ONE small launch per call draws both layers' keep bits ahead of the transposed convolutions, which
         # then read them like the input-gradient kernels do (the Philox rounds cost g.u1b 10 of its 50 us)
-        premask = bool(self.keep) and is3d and not direct        # (bf16 too: convT_bf16_k reads the keep bits as convT_mfma_k does)
+        # (bf16 too: convT_bf16_k reads the keep bits as convT_mfma_k does; 2-D, fp32 and bf16: drawn in the epilogue)
+        premask = bool(self.keep) and is3d and not direct
         km = lambda blk, mode: (self.keep[blk], 2 if (premask and mode == 1) else mode) if blk in self.keep else None
         kw = dict(is3d=is3d, direct=direct)
         pc = lambda p, s, i, o: p + lo(i) - s * lo(o) if i else p - s * lo(o)      # conv-like pad ('' = full input x)
