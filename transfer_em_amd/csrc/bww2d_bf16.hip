@@ -11,20 +11,15 @@
 // run.  Per unit it loads the band's input rows and gradient rows into LDS; the next unit's loads fly in registers under
 // the current unit's matrix work.  C_in == 1 (first layers, and the swapped form of the C_out == 1 layer) takes its A
 // fragments with plain 2-byte reads: 4 consecutive pixels of one tap are contiguous.
-#include "tem_common.h"
+#include "bf16_common.h"
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
 
 namespace bww2d_bf16 {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned short u16;
+using namespace tem_bf16;
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
-// x / d for 0 <= x < 2^31 with magic = ceil(2^32 / d) (d == 1: the magic does not fit 32 bits)
-__device__ __forceinline__ int fdiv(int x, int d, uint32_t magic) { return d == 1 ? x : (int)__umulhi((uint32_t)x, magic); }
 
 struct Dev {
   const u16 *in0, *in1;
@@ -232,8 +227,6 @@ __global__ __launch_bounds__(256) void bww2d_bf16_k(Dev p) {
 }
 
 // ------------------------------------------------------------------------------------------ host
-static uint32_t magic_for(int d) { return d <= 1 ? 0u : (uint32_t)((0x100000000ull + (uint64_t)d - 1) / (uint64_t)d); }
-
 template <int CI, int CO, int K, int S, int PFX, int PFG>
 int run(Dev p, int N, int max_slabs, hipStream_t st, bool dry, int *nslab_out, char *name, int name_len) {
   constexpr int NTAP = K * K;
@@ -270,9 +263,7 @@ int run(Dev p, int N, int max_slabs, hipStream_t st, bool dry, int *nslab_out, c
     if (name) snprintf(name, name_len, "bww2d_bf16_k<%d, %d, %d, %d, %d, %d>", CI, CO, K, S, PFX, PFG);
     return TEM_OK;
   }
-  static int dbg = -1;
-  if (dbg < 0) dbg = tem_env_int("TEM_DEBUG_FLAGS", 0);
-  if (dbg & 8)
+  if (tem_debug_flags() & 8)
     fprintf(stderr, "bww2d_bf16<%d,%d,%d,%d> O=%dx%d P=%d: TY=%d units=%d per=%d blocks=%d lds=%zu\n", CI, CO, K, S, p.OH,
             p.OW, p.P, p.TY, p.units, p.per, nblocks, lds_bytes);
   auto kern = bww2d_bf16_k<CI, CO, K, S, PFX, PFG>;
@@ -298,15 +289,9 @@ int tem_bww2d_bf16_try(const tem_bww_args *a, hipStream_t st, bool dry, int *nsl
     return TEM_EUNSUPPORTED;
   if (i0.D != 1 || g.D != 1) return TEM_EUNSUPPORTED;
   if (g.N != i0.N) return TEM_ESHAPE;
-  auto U = [](const float *q) { return reinterpret_cast<const u16 *>(q); };
-  auto span_ok = [](const tem_view &v) {
-    int64_t span = (int64_t)(v.N - 1) * v.sN + (int64_t)(v.D - 1) * v.sD + (int64_t)(v.H - 1) * v.sH + (int64_t)(v.W - 1) * v.sW + v.C;
-    return span < ((int64_t)1 << 31);
-  };
-  auto al16 = [](const tem_view &v) {
-    return v.C % 8 != 0 || (((uintptr_t)v.ptr & 15) == 0 && v.sW % 8 == 0 && v.sH % 8 == 0 && v.sN % 8 == 0);
-  };
-  if (!span_ok(i0) || !span_ok(g) || !al16(i0) || !al16(g) || g.C % 8) return TEM_EUNSUPPORTED;
+  auto U = as_u16;
+  auto al16 = [](const tem_view &v) { return v.C % 8 != 0 || aligned(v, 8, false); };     // 16-byte channel chunks: 8 bf16
+  if (!fits32(i0) || !fits32(g) || !al16(i0) || !al16(g) || g.C % 8) return TEM_EUNSUPPORTED;
   Dev p{};
   p.in0 = U(i0.ptr); p.i0N = (int)i0.sN; p.i0H = (int)i0.sH; p.i0W = (int)i0.sW; p.C0 = i0.C;
   p.in1 = p.in0; p.i1N = p.i0N; p.i1H = p.i0H; p.i1W = p.i0W;
@@ -314,7 +299,7 @@ int tem_bww2d_bf16_try(const tem_bww_args *a, hipStream_t st, bool dry, int *nsl
   if (a->in1.ptr) {
     const tem_view &i1 = a->in1;
     if (i1.N != i0.N || i1.D != i0.D || i1.H != i0.H || i1.W != i0.W) return TEM_ESHAPE;
-    if (!span_ok(i1) || !al16(i1) || i0.C % 8 || i1.C % 8) return TEM_EUNSUPPORTED;
+    if (!fits32(i1) || !al16(i1) || i0.C % 8 || i1.C % 8) return TEM_EUNSUPPORTED;
     p.in1 = U(i1.ptr); p.i1N = (int)i1.sN; p.i1H = (int)i1.sH; p.i1W = (int)i1.sW;
     CI += i1.C;
   }

@@ -12,7 +12,7 @@
 // group; they live in registers for the whole run, so each workgroup writes one deterministic fp32 slab
 // (tem_reduce_slabs_multi finishes the sum, as in fp32 mode).  C_in == 1 (first layers, and the swapped form of the
 // C_out == 1 layer) takes its A fragments with plain 2-byte reads: 4 consecutive voxels of one tap are contiguous.
-#include "tem_common.h"
+#include "bf16_common.h"
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
@@ -22,13 +22,8 @@ int tem_bww2d_bf16_try(const tem_bww_args *a, hipStream_t st, bool dry, int *nsl
 
 namespace bww_bf16 {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned short u16;
+using namespace tem_bf16;
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
-// x / d for 0 <= x < 2^31 with magic = ceil(2^32 / d) (d == 1: the magic does not fit 32 bits)
-__device__ __forceinline__ int fdiv(int x, int d, uint32_t magic) { return d == 1 ? x : (int)__umulhi((uint32_t)x, magic); }
 
 struct Dev {
   const u16 *in0, *in1;
@@ -269,12 +264,8 @@ __global__ __launch_bounds__(256) void bww_bf16_k(Dev p) {
 }
 
 // ------------------------------------------------------------------------------------------ host
-static uint32_t magic_for(int d) { return d <= 1 ? 0u : (uint32_t)((0x100000000ull + (uint64_t)d - 1) / (uint64_t)d); }
-static thread_local char *g_name = nullptr;
-static thread_local int g_name_len = 0;
-
 template <int CI, int CO, int K, int S, int PFX, int PFG, int MTG>
-int run(Dev p, int N, int max_slabs, hipStream_t st, bool dry, int *nslab_out) {
+int run(Dev p, int N, int max_slabs, hipStream_t st, bool dry, int *nslab_out, char *name, int name_len) {
   constexpr int NTAP = K * K * K, MT = (NTAP * CI + 15) / 16;
   constexpr int PITCH = CI >= 8 ? (CI <= 16 ? CI : CI + 4) : 1, GP = CO <= 16 ? CO : CO + 4, CPX = CI >= 8 ? CI / 8 : 1, CPG = CO / 8;
   p.OWp = (p.OW + 15) & ~15;
@@ -317,7 +308,7 @@ int run(Dev p, int N, int max_slabs, hipStream_t st, bool dry, int *nslab_out) {
   p.magicPlaneR = magic_for(p.rows * p.colsR);
   p.magicOW = magic_for(p.OW);
   if (dry) {
-    if (g_name) snprintf(g_name, g_name_len, "bww_bf16_k<%d, %d, %d, %d, %d, %d, %d>", CI, CO, K, S, PFX, PFG, MTG);
+    if (name) snprintf(name, name_len, "bww_bf16_k<%d, %d, %d, %d, %d, %d, %d>", CI, CO, K, S, PFX, PFG, MTG);
     return TEM_OK;
   }
   auto kern = bww_bf16_k<CI, CO, K, S, PFX, PFG, MTG>;
@@ -332,28 +323,14 @@ int run(Dev p, int N, int max_slabs, hipStream_t st, bool dry, int *nslab_out) {
   return TEM_OK;
 }
 
-int dispatch(const tem_bww_args *a, hipStream_t st, bool dry, int *nslab_out) {
+int dispatch(const tem_bww_args *a, hipStream_t st, bool dry, int *nslab_out, char *name, int name_len) {
   const tem_view &i0 = a->in0, &g = a->dout;
-  {                                                          // 2-D geometry, 3x3 / 4x4: bww2d_bf16.hip
-    const int rc = tem_bww2d_bf16_try(a, st, dry, nslab_out, g_name, g_name_len);
-    if (rc != TEM_EUNSUPPORTED) return rc;
-  }
-  {                                                          // one input channel, 3x3x3: the matrix-core march of bww_c1.hip
-    const int rc = tem_bww_c1_bf16_try(a, st, dry, nslab_out, g_name, g_name_len);
-    if (rc != TEM_EUNSUPPORTED) return rc;
-  }
   if (!(a->kd == a->kh && a->kh == a->kw && a->sd == a->sh && a->sh == a->sw && a->pd == a->ph && a->ph == a->pw))
     return TEM_EUNSUPPORTED;
   if (g.N != i0.N) return TEM_ESHAPE;
-  auto U = [](const float *q) { return reinterpret_cast<const u16 *>(q); };
-  auto span_ok = [](const tem_view &v) {
-    int64_t span = (int64_t)(v.N - 1) * v.sN + (int64_t)(v.D - 1) * v.sD + (int64_t)(v.H - 1) * v.sH + (int64_t)(v.W - 1) * v.sW + v.C;
-    return span < ((int64_t)1 << 31);
-  };
-  auto al16 = [](const tem_view &v) {
-    return v.C % 8 != 0 || (((uintptr_t)v.ptr & 15) == 0 && v.sW % 8 == 0 && v.sH % 8 == 0 && v.sD % 8 == 0 && v.sN % 8 == 0);
-  };
-  if (!span_ok(i0) || !span_ok(g) || !al16(i0) || !al16(g) || g.C % 8) return TEM_EUNSUPPORTED;
+  auto U = as_u16;
+  auto al16 = [](const tem_view &v) { return v.C % 8 != 0 || aligned(v, 8, true); };      // 16-byte channel chunks: 8 bf16
+  if (!fits32(i0) || !fits32(g) || !al16(i0) || !al16(g) || g.C % 8) return TEM_EUNSUPPORTED;
   Dev p{};
   p.in0 = U(i0.ptr); p.i0N = (int)i0.sN; p.i0D = (int)i0.sD; p.i0H = (int)i0.sH; p.i0W = (int)i0.sW; p.C0 = i0.C;
   p.in1 = p.in0; p.i1N = p.i0N; p.i1D = p.i0D; p.i1H = p.i0H; p.i1W = p.i0W;
@@ -361,7 +338,7 @@ int dispatch(const tem_bww_args *a, hipStream_t st, bool dry, int *nslab_out) {
   if (a->in1.ptr) {
     const tem_view &i1 = a->in1;
     if (i1.N != i0.N || i1.D != i0.D || i1.H != i0.H || i1.W != i0.W) return TEM_ESHAPE;
-    if (!span_ok(i1) || !al16(i1) || i0.C % 8 || i1.C % 8) return TEM_EUNSUPPORTED;
+    if (!fits32(i1) || !al16(i1) || i0.C % 8 || i1.C % 8) return TEM_EUNSUPPORTED;
     p.in1 = U(i1.ptr); p.i1N = (int)i1.sN; p.i1D = (int)i1.sD; p.i1H = (int)i1.sH; p.i1W = (int)i1.sW;
     CI += i1.C;
   }
@@ -373,7 +350,7 @@ int dispatch(const tem_bww_args *a, hipStream_t st, bool dry, int *nslab_out) {
   p.slab_stride = a->slab_stride ? a->slab_stride : (int64_t)K * K * K * CI * CO;
   const int max_slabs = a->nslab;
 #define BW(ci, co, k, s, pfx, pfg, mtg) \
-  if (CI == ci && CO == co && K == k && S == s) return run<ci, co, k, s, pfx, pfg, mtg>(p, N, max_slabs, st, dry, nslab_out);
+  if (CI == ci && CO == co && K == k && S == s) return run<ci, co, k, s, pfx, pfg, mtg>(p, N, max_slabs, st, dry, nslab_out, name, name_len);
   //  CI  CO  K  S  X-chunks  G-chunks  m-tiles per row group (all of them unless the accumulators would not fit)
   BW(1, 8, 3, 1, 12, 4, 2)  BW(1, 16, 3, 1, 12, 4, 2)
   BW(8, 8, 3, 1, 12, 4, 14) BW(8, 16, 3, 1, 12, 4, 14) BW(16, 8, 3, 1, 12, 4, 27) BW(16, 16, 3, 1, 12, 4, 27)
@@ -387,23 +364,29 @@ int dispatch(const tem_bww_args *a, hipStream_t st, bool dry, int *nslab_out) {
 
 }  // namespace bww_bf16
 
+// One route for the launch, the slab count and the kernel name; a new kernel-gradient kernel is one line here.
+static int route(const tem_bww_args *a, hipStream_t st, bool dry, int *nslab_out, char *name, int name_len) {
+  int rc = tem_bww2d_bf16_try(a, st, dry, nslab_out, name, name_len);                         // 2-D geometry, 3x3 / 4x4
+  if (rc == TEM_EUNSUPPORTED) rc = tem_bww_c1_bf16_try(a, st, dry, nslab_out, name, name_len);   // one input channel, 3x3x3: the matrix-core march
+  if (rc == TEM_EUNSUPPORTED) rc = bww_bf16::dispatch(a, st, dry, nslab_out, name, name_len);
+  return rc;
+}
+
 // bf16 mode of tem_conv_bwd_weight: in0 / in1 / dout are bf16 views, the partial slabs stay float32.
 // The launch writes exactly tem_conv_bwd_weight_bf16_nslab(a) slabs.
 extern "C" int tem_conv_bwd_weight_bf16(const tem_bww_args *a, tem_stream_t stream) {
   TEM_CLEAR_ERR();
   if (!a || !tem_view_ok(a->in0) || !tem_view_ok(a->dout) || !a->slabs || a->nslab < 1 || a->accumulate) return TEM_EINVAL;
   int n = 0;
-  int rc = bww_bf16::dispatch(a, nullptr, true, &n);
+  int rc = route(a, nullptr, true, &n, nullptr, 0);
   if (rc != TEM_OK) return rc;
   if (n != a->nslab) return TEM_EINVAL;                    // size the workspace with tem_conv_bwd_weight_bf16_nslab
-  return bww_bf16::dispatch(a, (hipStream_t)stream, false, nullptr);
+  return route(a, (hipStream_t)stream, false, nullptr, nullptr, 0);
 }
 
 extern "C" int tem_conv_bwd_weight_bf16_nslab(const tem_bww_args *a, char *name, int32_t name_len) {
   if (!a || !tem_view_ok(a->in0) || !tem_view_ok(a->dout) || a->nslab < 1) return TEM_EINVAL;
   int n = 0;
-  bww_bf16::g_name = name; bww_bf16::g_name_len = name_len;
-  int rc = bww_bf16::dispatch(a, nullptr, true, &n);
-  bww_bf16::g_name = nullptr;
+  int rc = route(a, nullptr, true, &n, name, name_len);
   return rc == TEM_OK ? n : rc;
 }

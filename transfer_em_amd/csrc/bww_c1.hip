@@ -351,10 +351,7 @@ static int run(const tem_bww_args *a, hipStream_t st, bool dry, int *nslab_out, 
   if (x.sW != 1 || x.W % 4) return TEM_EUNSUPPORTED;          // X rows are fetched as 16-byte chunks of 4 voxels, none across a row end
   // (dout may be any window of the layer's output: voxel o reads x[o + tap - p], zeros outside x -- the region-restricted
   // cycle path passes such windows)
-  auto span = [](const tem_view &v) {
-    return (int64_t)(v.N - 1) * v.sN + (int64_t)(v.D - 1) * v.sD + (int64_t)(v.H - 1) * v.sH + (int64_t)(v.W - 1) * v.sW + v.C;
-  };
-  if (span(x) >= ((int64_t)1 << 31) || span(g) >= ((int64_t)1 << 31)) return TEM_EUNSUPPORTED;
+  if (view_span(x) >= ((int64_t)1 << 31) || view_span(g) >= ((int64_t)1 << 31)) return TEM_EUNSUPPORTED;
   if (((uintptr_t)g.ptr & 15) || g.sW % 4 || g.sH % 4 || g.sD % 4 || g.sN % 4) return TEM_EUNSUPPORTED;
   const int CO = g.C, PY = 8;
   C1Dev p{};
@@ -543,10 +540,7 @@ static int run_h(const tem_bww_args *a, hipStream_t st, bool dry, int *nslab_out
   if (!cube || x.C != 1 || a->in1.ptr || (g.C != 8 && g.C != 16) || x.D < 2 || x.N != g.N) return TEM_EUNSUPPORTED;
   // X rows arrive as 4-byte chunks of 2 voxels: even W, even strides and a 4-byte aligned origin
   if (x.sW != 1 || x.W % 2 || x.sH % 2 || x.sD % 2 || x.sN % 2 || ((uintptr_t)x.ptr & 3)) return TEM_EUNSUPPORTED;
-  auto span = [](const tem_view &v) {
-    return (int64_t)(v.N - 1) * v.sN + (int64_t)(v.D - 1) * v.sD + (int64_t)(v.H - 1) * v.sH + (int64_t)(v.W - 1) * v.sW + v.C;
-  };
-  if (span(x) >= ((int64_t)1 << 30) || span(g) >= ((int64_t)1 << 30)) return TEM_EUNSUPPORTED;
+  if (view_span(x) >= ((int64_t)1 << 30) || view_span(g) >= ((int64_t)1 << 30)) return TEM_EUNSUPPORTED;
   if (((uintptr_t)g.ptr & 15) || g.sW % 8 || g.sH % 8 || g.sD % 8 || g.sN % 8) return TEM_EUNSUPPORTED;
   const int CO = g.C, PY = 8;
   C1Dev p{};

@@ -375,11 +375,7 @@ __global__ __launch_bounds__(NW * 64) void bww_lds_k(Dev p) {
 
 // ------------------------------------------------------------------------------------------ host
 constexpr int LDS_BUDGET = 150 * 1024;
-static thread_local char *g_name = nullptr;
-static thread_local int g_name_len = 0;
 constexpr int TARGET_BLOCKS = 256;   // one workgroup per CU: swept 128..1024 on the 132^3 step (TEM_BWW_BLOCKS), 256 is fastest
-
-static uint32_t magic_for(int d) { return (uint32_t)((0x100000000ull + (uint64_t)d - 1) / (uint64_t)d); }
 
 // Fills the plan fields of `p`; returns false when the geometry does not fit this kernel.
 template <int CI, int CO, int K, int S, int NW, int MAXPFX, int MAXPFG, bool XSH>
@@ -422,14 +418,14 @@ bool plan(Dev &p, int max_slabs, size_t &lds_bytes, int &nblocks) {
 }
 
 template <int CI, int CO, int K, int S, int NW, int MAXPFX, int MAXPFG, bool XSH = false>
-int run(Dev &p, int max_slabs, hipStream_t st, bool dry, int *nslab_out) {
+int run(Dev &p, int max_slabs, hipStream_t st, bool dry, int *nslab_out, char *name, int name_len) {
   size_t lds_bytes = 0;
   int nblocks = 0;
   if (!plan<CI, CO, K, S, NW, MAXPFX, MAXPFG, XSH>(p, max_slabs, lds_bytes, nblocks)) return TEM_EUNSUPPORTED;
   if (nslab_out) *nslab_out = nblocks;
   if (dry) {
-    if (g_name)
-      snprintf(g_name, g_name_len, "bww_lds_k<%d, %d, %d, %d, %d, %d, %d, %s>", CI, CO, K, S, NW, MAXPFX, MAXPFG,
+    if (name)
+      snprintf(name, name_len, "bww_lds_k<%d, %d, %d, %d, %d, %d, %d, %s>", CI, CO, K, S, NW, MAXPFX, MAXPFG,
                XSH ? "true" : "false");
     return TEM_OK;
   }
@@ -446,12 +442,12 @@ int run(Dev &p, int max_slabs, hipStream_t st, bool dry, int *nslab_out) {
 }
 
 #define BWW_CASE(ci, co, k, s, nw, pfx, pfg) \
-  if (CI == ci && CO == co && K == k && S == s) return run<ci, co, k, s, nw, pfx, pfg>(p, max_slabs, st, dry, nslab_out);
+  if (CI == ci && CO == co && K == k && S == s) return run<ci, co, k, s, nw, pfx, pfg>(p, max_slabs, st, dry, nslab_out, name, name_len);
 #define BWW_CASE_XSH(ci, co, k, s, nw, pfx, pfg) \
-  if (CI == ci && CO == co && K == k && S == s && xsh) return run<ci, co, k, s, nw, pfx, pfg, true>(p, max_slabs, st, dry, nslab_out);
+  if (CI == ci && CO == co && K == k && S == s && xsh) return run<ci, co, k, s, nw, pfx, pfg, true>(p, max_slabs, st, dry, nslab_out, name, name_len);
 
 // Dispatch; `dry` only computes the number of slabs the launch would write.
-int dispatch(const tem_bww_args *a, hipStream_t st, bool dry, int *nslab_out) {
+int dispatch(const tem_bww_args *a, hipStream_t st, bool dry, int *nslab_out, char *name, int name_len) {
   const tem_view &i0 = a->in0, &g = a->dout;
   const bool cube_k = a->kd == a->kh && a->kh == a->kw, cube_s = a->sd == a->sh && a->sh == a->sw;
   const bool cube_p = a->pd == a->ph && a->ph == a->pw;
@@ -507,13 +503,11 @@ int dispatch(const tem_bww_args *a, hipStream_t st, bool dry, int *nslab_out) {
 
 // Called by tem_conv_bwd_weight (conv_bww.hip) before it falls back to the global-load kernel.
 int tem_bww_lds_try(const tem_bww_args *a, hipStream_t st, bool dry, int *nslab_out) {
-  return bwwlds::dispatch(a, st, dry, nslab_out);
+  return bwwlds::dispatch(a, st, dry, nslab_out, nullptr, 0);
 }
 
 int tem_bww_lds_describe(const tem_bww_args *a, char *buf, int len) {
-  bwwlds::g_name = buf; bwwlds::g_name_len = len;
   int n = 0;
-  int rc = bwwlds::dispatch(a, nullptr, true, &n);
-  bwwlds::g_name = nullptr;
+  int rc = bwwlds::dispatch(a, nullptr, true, &n, buf, len);
   return rc == TEM_OK && n == a->nslab ? TEM_OK : TEM_EUNSUPPORTED;
 }

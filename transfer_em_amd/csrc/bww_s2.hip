@@ -385,17 +385,9 @@ __global__ __launch_bounds__(256) void bww_s2tb_k(Dev p) {
 }
 
 // ------------------------------------------------------------------------------------------ host
-static uint32_t magic_for(int d) { return (uint32_t)((0x100000000ull + (uint64_t)d - 1) / (uint64_t)d); }
-
-static int64_t span_of(const tem_view &v) {
-  return (int64_t)(v.N - 1) * v.sN + (int64_t)(v.D - 1) * v.sD + (int64_t)(v.H - 1) * v.sH + (int64_t)(v.W - 1) * v.sW + v.C;
-}
-
-static thread_local char *g_name = nullptr;
-static thread_local int g_name_len = 0;
 
 template <int CI, int CO, int KS = 4, int S = 2>
-static int run(Dev p, int max_slabs, hipStream_t st, bool dry, int *nslab_out) {
+static int run(Dev p, int max_slabs, hipStream_t st, bool dry, int *nslab_out, char *name, int name_len) {
   constexpr int MT = (CO + 15) / 16, J = CI / 4, NACC = KS * J * MT;
   const size_t lds_bytes = CI == 32 ? 0 : (size_t)4 * NACC * 64 * 16;
   // row ranges: 128 (two workgroups per CU with the four kz) where the LDS sum leaves room for two, else 64; at least ~4
@@ -410,7 +402,7 @@ static int run(Dev p, int max_slabs, hipStream_t st, bool dry, int *nslab_out) {
   if (R < 1) return TEM_EUNSUPPORTED;
   p.R = R;
   if (nslab_out) *nslab_out = R;
-  if (g_name) snprintf(g_name, g_name_len, "bww_s2_k<%d, %d, %d, %d>", CI, CO, KS, S);
+  if (name) snprintf(name, name_len, "bww_s2_k<%d, %d, %d, %d>", CI, CO, KS, S);
   if (dry) return TEM_OK;
   static bool attr = false;
   if (!attr && lds_bytes > 64 * 1024) {
@@ -423,7 +415,7 @@ static int run(Dev p, int max_slabs, hipStream_t st, bool dry, int *nslab_out) {
   return TEM_OK;
 }
 
-static int run_tb(Dev p, int max_slabs, hipStream_t st, bool dry, int *nslab_out) {
+static int run_tb(Dev p, int max_slabs, hipStream_t st, bool dry, int *nslab_out, char *name, int name_len) {
   const size_t lds_bytes = (size_t)4 * 16 * 64 * 16;            // 64 KB: two workgroups per CU
   int R = 512;
   static int rr = -1;
@@ -436,7 +428,7 @@ static int run_tb(Dev p, int max_slabs, hipStream_t st, bool dry, int *nslab_out
   if (R < 1) return TEM_EUNSUPPORTED;
   p.R = R;
   if (nslab_out) *nslab_out = R;
-  if (g_name) snprintf(g_name, g_name_len, "bww_s2tb_k<%d>", nb == 6 ? 6 : 8);
+  if (name) snprintf(name, name_len, "bww_s2tb_k<%d>", nb == 6 ? 6 : 8);
   if (dry) return TEM_OK;
   static bool attr = false;
   if (!attr) {
@@ -451,7 +443,7 @@ static int run_tb(Dev p, int max_slabs, hipStream_t st, bool dry, int *nslab_out
   return TEM_OK;
 }
 
-static int dispatch(const tem_bww_args *a, hipStream_t st, bool dry, int *nslab_out) {
+static int dispatch(const tem_bww_args *a, hipStream_t st, bool dry, int *nslab_out, char *name, int name_len) {
   const tem_view &i0 = a->in0, &g = a->dout;
   if (a->in1.ptr) return TEM_EUNSUPPORTED;
   const bool k4s2 = a->kd == 4 && a->kh == 4 && a->kw == 4 && a->sd == 2 && a->sh == 2 && a->sw == 2;
@@ -462,7 +454,7 @@ static int dispatch(const tem_bww_args *a, hipStream_t st, bool dry, int *nslab_
   if (enabled < 0) enabled = tem_env_int("TEM_BWW_S2", 1);
   if (!enabled) return TEM_EUNSUPPORTED;
   if (g.N != i0.N) return TEM_ESHAPE;
-  const int64_t ispan = span_of(i0), gspan = span_of(g);
+  const int64_t ispan = view_span(i0), gspan = view_span(g);
   if (ispan >= ((int64_t)1 << 29) || gspan >= ((int64_t)1 << 29)) return TEM_EUNSUPPORTED;   // byte offsets below 2^31
   if (((uintptr_t)i0.ptr & 15) || i0.sW % 4 || i0.sH % 4 || i0.sD % 4 || i0.sN % 4) return TEM_EUNSUPPORTED;
   const int64_t rows = (int64_t)g.N * g.D * g.H;
@@ -483,33 +475,31 @@ static int dispatch(const tem_bww_args *a, hipStream_t st, bool dry, int *nslab_
     static int tb = -1;
     if (tb < 0) tb = tem_env_int("TEM_BWW_S2_TB", 1);
     if (!tb) return TEM_EUNSUPPORTED;
-    return run_tb(p, a->nslab, st, dry, nslab_out);
+    return run_tb(p, a->nslab, st, dry, nslab_out, name, name_len);
   }
   if (k3s1) {
     // the 3x3x3 layers the Winograd-domain kernel leaves alone (hip_ops.WINO_MIN_VOXELS): g.u2a, d.d3a
     static int k3 = -1;
     if (k3 < 0) k3 = tem_env_int("TEM_BWW_S2_K3", 1);
     if (!k3 || (int64_t)g.D * g.H * g.W > 40000) return TEM_EUNSUPPORTED;
-    if (CI == 16 && CO == 32) return run<16, 32, 3, 1>(p, a->nslab, st, dry, nslab_out);
-    if (CI == 32 && CO == 32) return run<32, 32, 3, 1>(p, a->nslab, st, dry, nslab_out);
+    if (CI == 16 && CO == 32) return run<16, 32, 3, 1>(p, a->nslab, st, dry, nslab_out, name, name_len);
+    if (CI == 32 && CO == 32) return run<32, 32, 3, 1>(p, a->nslab, st, dry, nslab_out, name, name_len);
     return TEM_EUNSUPPORTED;
   }
-  if (CI == 8 && CO == 16) return run<8, 16>(p, a->nslab, st, dry, nslab_out);     // g.u1b (transposed conv: input and gradient swapped)
-  if (CI == 16 && CO == 16) return run<16, 16>(p, a->nslab, st, dry, nslab_out);   // g.d2b
-  if (CI == 16 && CO == 32) return run<16, 32>(p, a->nslab, st, dry, nslab_out);   // g.u2b
-  if (CI == 32 && CO == 32) return run<32, 32>(p, a->nslab, st, dry, nslab_out);   // d.d2b, d.d3b
+  if (CI == 8 && CO == 16) return run<8, 16>(p, a->nslab, st, dry, nslab_out, name, name_len);     // g.u1b (transposed conv: input and gradient swapped)
+  if (CI == 16 && CO == 16) return run<16, 16>(p, a->nslab, st, dry, nslab_out, name, name_len);   // g.d2b
+  if (CI == 16 && CO == 32) return run<16, 32>(p, a->nslab, st, dry, nslab_out, name, name_len);   // g.u2b
+  if (CI == 32 && CO == 32) return run<32, 32>(p, a->nslab, st, dry, nslab_out, name, name_len);   // d.d2b, d.d3b
   return TEM_EUNSUPPORTED;
 }
 
 }  // namespace bwws2
 
 // Called by tem_conv_bwd_weight (conv_bww.hip) ahead of the LDS-ring kernel.
-int tem_bww_s2_try(const tem_bww_args *a, hipStream_t st, bool dry, int *nslab_out) { return bwws2::dispatch(a, st, dry, nslab_out); }
+int tem_bww_s2_try(const tem_bww_args *a, hipStream_t st, bool dry, int *nslab_out) { return bwws2::dispatch(a, st, dry, nslab_out, nullptr, 0); }
 
 int tem_bww_s2_describe(const tem_bww_args *a, char *buf, int len) {
-  bwws2::g_name = buf; bwws2::g_name_len = len;
   int n = 0;
-  int rc = bwws2::dispatch(a, nullptr, true, &n);
-  bwws2::g_name = nullptr;
+  int rc = bwws2::dispatch(a, nullptr, true, &n, buf, len);
   return rc == TEM_OK && n == a->nslab ? TEM_OK : TEM_EUNSUPPORTED;
 }

@@ -337,19 +337,13 @@ __global__ __launch_bounds__(256, 2) void c1out_h_k(DevH p) {
 }
 
 // ------------------------------------------------------------------------------------------ host
-static bool fits32(const tem_view &v) {
-  int64_t span = (int64_t)(v.N - 1) * v.sN + (int64_t)(v.D - 1) * v.sD + (int64_t)(v.H - 1) * v.sH +
-                 (int64_t)(v.W - 1) * v.sW + v.C;
-  return span < ((int64_t)1 << 29);                  // (byte offsets of the buffer loads stay below 2^31)
-}
+static bool fits29(const tem_view &v) { return view_span(v) < ((int64_t)1 << 29); }    // (byte offsets of the buffer loads stay below 2^31)
 
-static thread_local char *g_name = nullptr;
-static thread_local int g_name_len = 0;
 
 template <int CI, bool FLIP, bool GATE>
-static int run1(Dev p, int N, hipStream_t st, bool dry) {
+static int run1(Dev p, int N, hipStream_t st, bool dry, char *name, int name_len) {
   if (dry) {
-    if (g_name) snprintf(g_name, g_name_len, "c1out_mfma_k<%d, %s, %s>", CI, FLIP ? "true" : "false", GATE ? "true" : "false");
+    if (name) snprintf(name, name_len, "c1out_mfma_k<%d, %s, %s>", CI, FLIP ? "true" : "false", GATE ? "true" : "false");
     return TEM_OK;
   }
   p.ntx = (p.OW + TX - 1) / TX; p.nty = (p.OH + TY - 1) / TY;
@@ -379,11 +373,11 @@ static int run1(Dev p, int N, hipStream_t st, bool dry) {
 }
 
 template <int CI, bool FLIP>
-static int run(Dev p, int N, hipStream_t st, bool dry) {
-  return p.gate ? run1<CI, FLIP, true>(p, N, st, dry) : run1<CI, FLIP, false>(p, N, st, dry);
+static int run(Dev p, int N, hipStream_t st, bool dry, char *name, int name_len) {
+  return p.gate ? run1<CI, FLIP, true>(p, N, st, dry, name, name_len) : run1<CI, FLIP, false>(p, N, st, dry, name, name_len);
 }
 
-static int dispatch(const tem_conv_args *a, hipStream_t st, bool dry) {
+static int dispatch(const tem_conv_args *a, hipStream_t st, bool dry, char *name, int name_len) {
   const tem_view &i0 = a->in0, &o0 = a->out0;
   if (a->in1.ptr || a->out1.ptr || o0.C != 1) return TEM_EUNSUPPORTED;
   if (a->kd != 3 || a->kh != 3 || a->kw != 3 || a->sd != 1 || a->sh != 1 || a->sw != 1) return TEM_EUNSUPPORTED;
@@ -396,18 +390,17 @@ static int dispatch(const tem_conv_args *a, hipStream_t st, bool dry) {
   if (enabled < 0) enabled = tem_env_int("TEM_C1OUT_MFMA", 1);
   if (!enabled) return TEM_EUNSUPPORTED;
   if (o0.N != i0.N) return TEM_ESHAPE;
-  if (!fits32(i0) || !fits32(o0)) return TEM_EUNSUPPORTED;
+  if (!fits29(i0) || !fits29(o0)) return TEM_EUNSUPPORTED;
   if (((uintptr_t)i0.ptr & 15) || i0.sW % 4 || i0.sH % 4 || i0.sD % 4 || i0.sN % 4) return TEM_EUNSUPPORTED;
   Dev p{};
   p.in = i0.ptr; p.iN = (int)i0.sN; p.iD = (int)i0.sD; p.iH = (int)i0.sH; p.iW = (int)i0.sW;
   p.D = i0.D; p.H = i0.H; p.W = i0.W;
-  p.in_bytes = (int)(((int64_t)(i0.N - 1) * i0.sN + (int64_t)(i0.D - 1) * i0.sD + (int64_t)(i0.H - 1) * i0.sH +
-                      (int64_t)(i0.W - 1) * i0.sW + i0.C) * 4);
+  p.in_bytes = (int)(view_span(i0) * 4);
   p.w = a->w;
   p.out = o0.ptr; p.oN = (int)o0.sN; p.oD = (int)o0.sD; p.oH = (int)o0.sH; p.oW = (int)o0.sW;
   p.OD = o0.D; p.OH = o0.H; p.OW = o0.W;
   auto bytes_of = [](const tem_view &v) {
-    return (int)(((int64_t)(v.N - 1) * v.sN + (int64_t)(v.D - 1) * v.sD + (int64_t)(v.H - 1) * v.sH + (int64_t)(v.W - 1) * v.sW + v.C) * 4);
+    return (int)(view_span(v) * 4);
   };
   p.out_bytes = bytes_of(o0);
   p.P = a->pd;
@@ -415,15 +408,15 @@ static int dispatch(const tem_conv_args *a, hipStream_t st, bool dry) {
   if (a->ep.gate.ptr) {
     const tem_view &g = a->ep.gate;
     if (g.N != o0.N || g.D != o0.D || g.H != o0.H || g.W != o0.W || g.C < o0.C) return TEM_ESHAPE;
-    if (!fits32(g)) return TEM_EUNSUPPORTED;
+    if (!fits29(g)) return TEM_EUNSUPPORTED;
     p.gate = g.ptr; p.gN = (int)g.sN; p.gD = (int)g.sD; p.gH = (int)g.sH; p.gW = (int)g.sW;
     p.gate_bytes = bytes_of(g);
   }
   const bool flip = a->w_layout == TEM_W_FLIP_CO_CI;
   if (a->w_layout != TEM_W_TAP_CI_CO && !flip) return TEM_EUNSUPPORTED;
   const int N = i0.N;
-  if (i0.C == 8) return flip ? run<8, true>(p, N, st, dry) : run<8, false>(p, N, st, dry);   // input-gradients of the first convolutions
-  return flip ? run<16, true>(p, N, st, dry) : run<16, false>(p, N, st, dry);     // g.f2 forward
+  if (i0.C == 8) return flip ? run<8, true>(p, N, st, dry, name, name_len) : run<8, false>(p, N, st, dry, name, name_len);   // input-gradients of the first convolutions
+  return flip ? run<16, true>(p, N, st, dry, name, name_len) : run<16, false>(p, N, st, dry, name, name_len);     // g.f2 forward
 }
 
 
@@ -465,19 +458,18 @@ static int dispatch_h(const tem_conv_args *a, hipStream_t st, bool dry, char *na
   if (a->pd != a->ph || a->ph != a->pw) return TEM_EUNSUPPORTED;
   if (a->ep.dropout || a->ep.add.ptr) return TEM_EUNSUPPORTED;
   if (o0.N != i0.N) return TEM_ESHAPE;
-  if (!fits32(i0) || !fits32(o0)) return TEM_EUNSUPPORTED;
+  if (!fits29(i0) || !fits29(o0)) return TEM_EUNSUPPORTED;
   if (((uintptr_t)i0.ptr & 7) || i0.sW % 4 || i0.sH % 4 || i0.sD % 4 || i0.sN % 4) return TEM_EUNSUPPORTED;
   auto U = [](const float *q) { return reinterpret_cast<const u16 *>(q); };
   DevH p{};
   p.in = U(i0.ptr); p.iN = (int)i0.sN; p.iD = (int)i0.sD; p.iH = (int)i0.sH; p.iW = (int)i0.sW;
   p.D = i0.D; p.H = i0.H; p.W = i0.W;
-  p.in_bytes = (int)(((int64_t)(i0.N - 1) * i0.sN + (int64_t)(i0.D - 1) * i0.sD + (int64_t)(i0.H - 1) * i0.sH +
-                      (int64_t)(i0.W - 1) * i0.sW + i0.C) * 2);
+  p.in_bytes = (int)(view_span(i0) * 2);
   p.w = U(a->w);
   p.out = const_cast<u16 *>(U(o0.ptr)); p.oN = (int)o0.sN; p.oD = (int)o0.sD; p.oH = (int)o0.sH; p.oW = (int)o0.sW;
   p.OD = o0.D; p.OH = o0.H; p.OW = o0.W;
   auto bytes_of = [](const tem_view &v) {
-    return (int)(((int64_t)(v.N - 1) * v.sN + (int64_t)(v.D - 1) * v.sD + (int64_t)(v.H - 1) * v.sH + (int64_t)(v.W - 1) * v.sW + v.C) * 2);
+    return (int)(view_span(v) * 2);
   };
   p.out_bytes = bytes_of(o0);
   p.P = a->pd;
@@ -485,7 +477,7 @@ static int dispatch_h(const tem_conv_args *a, hipStream_t st, bool dry, char *na
   if (a->ep.gate.ptr) {
     const tem_view &g = a->ep.gate;
     if (g.N != o0.N || g.D != o0.D || g.H != o0.H || g.W != o0.W || g.C < o0.C) return TEM_ESHAPE;
-    if (!fits32(g)) return TEM_EUNSUPPORTED;
+    if (!fits29(g)) return TEM_EUNSUPPORTED;
     p.gate = U(g.ptr); p.gN = (int)g.sN; p.gD = (int)g.sD; p.gH = (int)g.sH; p.gW = (int)g.sW;
     p.gate_bytes = bytes_of(g);
   }
@@ -499,12 +491,10 @@ static int dispatch_h(const tem_conv_args *a, hipStream_t st, bool dry, char *na
 }  // namespace c1out
 
 // Called by tem_conv (dispatch.hip) ahead of the VALU stencil.
-int tem_conv_c1out_try(const tem_conv_args *a, hipStream_t st, bool dry) { return c1out::dispatch(a, st, dry); }
+int tem_conv_c1out_try(const tem_conv_args *a, hipStream_t st, bool dry) { return c1out::dispatch(a, st, dry, nullptr, 0); }
 
 int tem_conv_c1out_describe(const tem_conv_args *a, char *buf, int len) {
-  c1out::g_name = buf; c1out::g_name_len = len;
-  int rc = c1out::dispatch(a, nullptr, true);
-  c1out::g_name = nullptr;
+  int rc = c1out::dispatch(a, nullptr, true, buf, len);
   return rc;
 }
 

@@ -12,21 +12,13 @@
 //   * MFMA k index = (tap, ci): 9 C_in (k3) or 16 C_in (k4) rows; C_in == 1 uses the taps as K (one k-step);
 //   * the epilogue of conv_bf16_k: bias, skip-gradient add, LeakyReLU' gate, Philox dropout with keep-mask
 //     write / read, LeakyReLU, split outputs, 8-byte bf16 stores of 4 channels per lane.
-#include "tem_common.h"
+#include "bf16_common.h"
 #include <cstdio>
 #include <cstdlib>
 
 namespace conv2d_bf16 {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned short u16;
-
-__device__ __forceinline__ float bf2f(u16 h) { return __uint_as_float((uint32_t)h << 16); }
-__device__ __forceinline__ u16 f2bf(float f) { return __builtin_bit_cast(u16, (__bf16)f); }   // round to nearest even
-
-// x / d for 0 <= x < 2^31 with magic = ceil(2^32 / d) (d == 1: the magic does not fit 32 bits)
-__device__ __forceinline__ int fdiv(int x, int d, uint32_t magic) { return d == 1 ? x : (int)__umulhi((uint32_t)x, magic); }
+using namespace tem_bf16;
 
 struct Ep {
   const float *bias;
@@ -321,14 +313,6 @@ __global__ __launch_bounds__(256) void conv2d_bf16_k(Dev p) {
 }
 
 // ------------------------------------------------------------------------------------------ host
-static uint32_t magic_for(int d) { return d <= 1 ? 0u : (uint32_t)((0x100000000ull + (uint64_t)d - 1) / (uint64_t)d); }
-
-static bool fits32(const tem_view &v) {
-  int64_t span = (int64_t)(v.N - 1) * v.sN + (int64_t)(v.D - 1) * v.sD + (int64_t)(v.H - 1) * v.sH +
-                 (int64_t)(v.W - 1) * v.sW + v.C;
-  return span < ((int64_t)1 << 31);
-}
-
 constexpr int LDS_MAX = 64 * 1024;
 
 template <int CI, int CO, int K, int S, int PF>
@@ -386,10 +370,8 @@ int launch(Dev p, int N, size_t best_bytes, hipStream_t st, bool dry, char *name
     if (name) snprintf(name, name_len, "conv2d_bf16_k<%d, %d, %d, %d, %d>", CI, CO, K, S, PF);
     return TEM_OK;
   }
-  static int dbg = -1;
-  if (dbg < 0) dbg = tem_env_int("TEM_DEBUG_FLAGS", 0);
   const int nblocks = N * p.nby * p.nbx;
-  if (dbg & 8)
+  if (tem_debug_flags() & 8)
     fprintf(stderr, "conv2d_bf16<%d,%d,%d,%d> O=%dx%d P=%d: TX=%d TY=%d patch=%dx%d blocks=%d lds=%zu\n", CI, CO, K, S,
             p.OH, p.OW, p.P, p.TX, p.TY, p.rows, p.cols, nblocks, best_bytes);
   auto kern = conv2d_bf16_k<CI, CO, K, S, PF>;
@@ -417,13 +399,9 @@ int tem_conv2d_bf16_try(const tem_conv_args *a, hipStream_t st, bool dry, char *
   if (o0.N != i0.N) return TEM_ESHAPE;
   if (!fits32(i0) || !fits32(o0)) return TEM_EUNSUPPORTED;
   Dev p{};
-  auto U = [](const float *q) { return reinterpret_cast<const u16 *>(q); };
-  auto al16 = [](const tem_view &v) {       // 16-byte channel chunks: 8 bf16
-    return v.C % 8 != 0 || (((uintptr_t)v.ptr & 15) == 0 && v.sW % 8 == 0 && v.sH % 8 == 0 && v.sN % 8 == 0);
-  };
-  auto al8 = [](const tem_view &v) {        // 8-byte accesses of 4 bf16 (stores, gate, add)
-    return v.C % 4 != 0 || (((uintptr_t)v.ptr & 7) == 0 && v.sW % 4 == 0 && v.sH % 4 == 0 && v.sN % 4 == 0);
-  };
+  auto U = as_u16;
+  auto al16 = [](const tem_view &v) { return v.C % 8 != 0 || aligned(v, 8, false); };     // 16-byte channel chunks: 8 bf16
+  auto al8 = [](const tem_view &v) { return v.C % 4 != 0 || aligned(v, 4, false); };      // 8-byte stores of 4 bf16
   p.in0 = U(i0.ptr); p.i0N = (int)i0.sN; p.i0H = (int)i0.sH; p.i0W = (int)i0.sW; p.C0 = i0.C;
   p.in1 = p.in0; p.i1N = p.i0N; p.i1H = p.i0H; p.i1W = p.i0W;
   int CI = i0.C;
@@ -449,44 +427,8 @@ int tem_conv2d_bf16_try(const tem_conv_args *a, hipStream_t st, bool dry, char *
     CO += o1.C;
   }
   p.OH = o0.H; p.OW = o0.W; p.P = a->ph;
-  const tem_epilogue &e = a->ep;
-  Ep &q = p.ep;
-  q.bias = e.bias; q.slope = e.slope; q.gate_slope = e.gate_slope;
-  if (e.gate.ptr) {
-    const tem_view &g = e.gate;
-    if (g.N != o0.N || g.D != 1 || g.H != o0.H || g.W != o0.W || g.C < o0.C) return TEM_ESHAPE;
-    if (!fits32(g) || !al8(g) || o0.C % 4) return TEM_EUNSUPPORTED;
-    q.gate = U(g.ptr); q.gN = (int)g.sN; q.gH = (int)g.sH; q.gW = (int)g.sW;
-  }
-  if (e.add.ptr) {
-    const tem_view &ad = e.add;
-    if (ad.C < o0.C || ad.N != o0.N || ad.D != 1 || e.add_off[0] != 0) return TEM_ESHAPE;
-    if (!fits32(ad) || !al8(ad) || o0.C % 4) return TEM_EUNSUPPORTED;
-    q.add = U(ad.ptr); q.aN = (int)ad.sN; q.aH = (int)ad.sH; q.aW = (int)ad.sW;
-    q.aoy = e.add_off[1]; q.aox = e.add_off[2];
-    q.aHh = ad.H; q.aWw = ad.W;
-  }
-  q.dropout = e.dropout;
-  if (e.dropout && o0.C % 8) return TEM_EUNSUPPORTED;
-  q.ds.k0 = (uint32_t)e.seed; q.ds.k1 = (uint32_t)(e.seed >> 32); q.ds.site = e.site; q.ds.step = e.step;
-  q.step_dev = e.step_dev;
-  q.keep_mask = (e.dropout && e.keep_mask) ? e.keep_mask : nullptr;
-  q.keep_mode = q.keep_mask ? e.keep_mode : 0;
-  q.doz = e.drop_org[0]; q.doy = e.drop_org[1]; q.dox = e.drop_org[2];
-  q.dD = e.drop_dims[0] ? e.drop_dims[0] : o0.D; q.dH = e.drop_dims[0] ? e.drop_dims[1] : o0.H;
-  q.dW = e.drop_dims[0] ? e.drop_dims[2] : o0.W;
-  {
-    auto span = [](const tem_view &v) {
-      return (int64_t)(v.N - 1) * v.sN + (int64_t)(v.D - 1) * v.sD + (int64_t)(v.H - 1) * v.sH + (int64_t)(v.W - 1) * v.sW + v.C;
-    };
-    const int64_t melems = (int64_t)o0.N * q.dD * q.dH * q.dW * o0.C;
-    if (melems >= ((int64_t)1 << 33)) return TEM_EUNSUPPORTED;
-    q.mbytes = (int)((melems + 7) / 8);
-    if ((e.gate.ptr && span(e.gate) >= ((int64_t)1 << 30)) || (e.add.ptr && span(e.add) >= ((int64_t)1 << 30)))
-      return TEM_EUNSUPPORTED;                     // byte offsets of the epilogue's buffer loads stay below 2^31
-    q.gbytes = e.gate.ptr ? (int)(span(e.gate) * 2) : 0;
-    q.abytes = e.add.ptr ? (int)(span(e.add) * 2) : 0;
-  }
+  p.ep.bias = a->ep.bias;
+  if (const int rc = fill_epilogue<false, true>(p.ep, a->ep, o0)) return rc;
   const int K = a->kh, S = a->sh, N = i0.N;
 #define C2(ci, co, k, s, pf) if (CI == ci && CO == co && K == k && S == s) return run<ci, co, k, s, pf>(p, N, st, dry, name, name_len);
   // k3 s1: forward layers and (flip) their input-gradients of both 2-D networks

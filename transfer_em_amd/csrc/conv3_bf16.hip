@@ -22,19 +22,13 @@
 //     dropout by the keep mask the forward pass wrote (a launch that has to DRAW the mask stays in conv_bf16_k),
 //     LeakyReLU, split outputs.
 // MFMA k index = (tap, ci) as in conv_bf16_k, so the packed kernel [tap][co][ci] is read as it is.
-#include "tem_common.h"
+#include "bf16_common.h"
 #include <cstdio>
 #include <cstdlib>
 
 namespace conv3_bf16 {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned short u16;
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+using namespace tem_bf16;
 
 constexpr int OOB = (int)0x80000000;
 constexpr int LDS_MAX = 160 * 1024;
@@ -383,9 +377,6 @@ __global__ __launch_bounds__((NW + 1) * 64) void conv3_bf16_k(Dev p) {
 
 // ------------------------------------------------------------------------------------------ host
 static bool fits31(int64_t v) { return v >= 0 && v < ((int64_t)1 << 30); }
-static int64_t span(const tem_view &v) {
-  return (int64_t)(v.N - 1) * v.sN + (int64_t)(v.D - 1) * v.sD + (int64_t)(v.H - 1) * v.sH + (int64_t)(v.W - 1) * v.sW + v.C;
-}
 
 template <int CI, int CO, int K, int S, int NW, bool SPLIT, int EPI>
 static int run(Dev p, int N, hipStream_t st, bool dry, char *name, int name_len) {
@@ -459,11 +450,9 @@ static int run(Dev p, int N, hipStream_t st, bool dry, char *name, int name_len)
     if (name) snprintf(name, name_len, "conv3_bf16_k<%d, %d, %d, %d, %d, %s, %d>", CI, CO, K, S, NW, SPLIT ? "true" : "false", EPI);
     return TEM_OK;
   }
-  static int dbg = -1;
-  if (dbg < 0) dbg = tem_env_int("TEM_DEBUG_FLAGS", 0);
   const int nblocks = N * p.nby * p.nbx * p.zsegs;
   const size_t lds = (size_t)p.RD * p.slot_bytes;
-  if (dbg & 8)
+  if (tem_debug_flags() & 8)
     fprintf(stderr, "conv3_bf16<%d,%d> O=%dx%dx%d P=%d: TX=%d TY=%d RW=%d zsegs=%d zper=%d blocks=%d lds=%zu ndma=%d RD=%d\n", CI, CO, p.OD,
             p.OH, p.OW, p.P, p.TX, p.TY, p.RW, p.zsegs, p.zper, nblocks, lds, p.ndma, p.RD);
   auto kern = conv3_bf16_k<CI, CO, K, S, NW, SPLIT, EPI>;
@@ -486,42 +475,38 @@ int dispatch(const tem_conv_args *a, hipStream_t st, bool dry, char *name, int n
   if (!((k3s1 || k4s2) && a->pd == a->ph && a->ph == a->pw)) return TEM_EUNSUPPORTED;
   if (a->ep.dropout && !(a->ep.keep_mask && a->ep.keep_mode == 2)) return TEM_EUNSUPPORTED;     // reads a keep mask, draws none
   if (o0.N != i0.N) return TEM_ESHAPE;
-  auto U = [](const float *q) { return reinterpret_cast<const u16 *>(q); };
-  auto al16 = [](const tem_view &v) {
-    return ((uintptr_t)v.ptr & 15) == 0 && v.C % 8 == 0 && v.sW % 8 == 0 && v.sH % 8 == 0 && v.sD % 8 == 0 && v.sN % 8 == 0;
-  };
-  auto al8 = [](const tem_view &v) {
-    return ((uintptr_t)v.ptr & 7) == 0 && v.C % 4 == 0 && v.sW % 4 == 0 && v.sH % 4 == 0 && v.sD % 4 == 0 && v.sN % 4 == 0;
-  };
+  auto U = as_u16;
+  auto al16 = [](const tem_view &v) { return v.C % 8 == 0 && aligned(v, 8, true); };
+  auto al8 = [](const tem_view &v) { return v.C % 4 == 0 && aligned(v, 4, true); };
   Dev p{};
-  if (!al16(i0) || !fits31(span(i0))) return TEM_EUNSUPPORTED;
+  if (!al16(i0) || !fits31(view_span(i0))) return TEM_EUNSUPPORTED;
   int CI = i0.C;
   p.in0 = U(i0.ptr); p.in1 = p.in0;
-  p.in0_bytes = (uint32_t)(span(i0) * 2); p.in1_bytes = p.in0_bytes;
+  p.in0_bytes = (uint32_t)(view_span(i0) * 2); p.in1_bytes = p.in0_bytes;
   p.i0N = (int)i0.sN; p.i0D = (int)i0.sD; p.i0H = (int)i0.sH; p.i0W = (int)i0.sW; p.C0 = i0.C;
   p.i1N = p.i0N; p.i1D = p.i0D; p.i1H = p.i0H; p.i1W = p.i0W;
   if (a->in1.ptr) {
     const tem_view &i1 = a->in1;
     if (i1.N != i0.N || i1.D != i0.D || i1.H != i0.H || i1.W != i0.W) return TEM_ESHAPE;
-    if (!al16(i1) || !fits31(span(i1))) return TEM_EUNSUPPORTED;
-    p.in1 = U(i1.ptr); p.in1_bytes = (uint32_t)(span(i1) * 2);
+    if (!al16(i1) || !fits31(view_span(i1))) return TEM_EUNSUPPORTED;
+    p.in1 = U(i1.ptr); p.in1_bytes = (uint32_t)(view_span(i1) * 2);
     p.i1N = (int)i1.sN; p.i1D = (int)i1.sD; p.i1H = (int)i1.sH; p.i1W = (int)i1.sW;
     CI += i1.C;
   }
   p.D = i0.D; p.H = i0.H; p.W = i0.W; p.P = a->pd;
   p.w = U(a->w); p.flip = a->w_layout == TEM_W_FLIP_CO_CI;
-  if (!al8(o0) || !fits31(span(o0))) return TEM_EUNSUPPORTED;
+  if (!al8(o0) || !fits31(view_span(o0))) return TEM_EUNSUPPORTED;
   p.oN = (int)o0.sN; p.oD = (int)o0.sD; p.oH = (int)o0.sH; p.oW = (int)o0.sW;
   p.CO0 = o0.C;
   int CO = o0.C;
   p.out0 = const_cast<u16 *>(U(o0.ptr)); p.out1 = p.out0;
-  p.out0_bytes = (uint32_t)(span(o0) * 2); p.out1_bytes = p.out0_bytes;
+  p.out0_bytes = (uint32_t)(view_span(o0) * 2); p.out1_bytes = p.out0_bytes;
   if (a->out1.ptr) {
     const tem_view &o1 = a->out1;
     if (o1.N != o0.N || o1.D != o0.D || o1.H != o0.H || o1.W != o0.W) return TEM_ESHAPE;
-    if (!al8(o1) || !fits31(span(o1))) return TEM_EUNSUPPORTED;
+    if (!al8(o1) || !fits31(view_span(o1))) return TEM_EUNSUPPORTED;
     if (o1.sN != o0.sN || o1.sD != o0.sD || o1.sH != o0.sH || o1.sW != o0.sW) return TEM_EUNSUPPORTED;    // one scalar offset for both
-    p.out1 = const_cast<u16 *>(U(o1.ptr)); p.out1_bytes = (uint32_t)(span(o1) * 2);
+    p.out1 = const_cast<u16 *>(U(o1.ptr)); p.out1_bytes = (uint32_t)(view_span(o1) * 2);
     CO += o1.C;
   }
   p.OD = o0.D; p.OH = o0.H; p.OW = o0.W;
@@ -535,16 +520,16 @@ int dispatch(const tem_conv_args *a, hipStream_t st, bool dry, char *name, int n
   if (e.gate.ptr) {
     const tem_view &g = e.gate;
     if (g.N != o0.N || g.D != o0.D || g.H != o0.H || g.W != o0.W || g.C < o0.C) return TEM_ESHAPE;
-    if (!al8(g) || !fits31(span(g))) return TEM_EUNSUPPORTED;
-    p.gate = U(g.ptr); p.gN = (int)g.sN; p.gD = (int)g.sD; p.gH = (int)g.sH; p.gW = (int)g.sW; p.gbytes = (int)(span(g) * 2);
+    if (!al8(g) || !fits31(view_span(g))) return TEM_EUNSUPPORTED;
+    p.gate = U(g.ptr); p.gN = (int)g.sN; p.gD = (int)g.sD; p.gH = (int)g.sH; p.gW = (int)g.sW; p.gbytes = (int)(view_span(g) * 2);
   }
   if (e.add.ptr) {
     const tem_view &ad = e.add;
     if (ad.C < o0.C || ad.N != o0.N) return TEM_ESHAPE;
-    if (!al8(ad) || !fits31(span(ad))) return TEM_EUNSUPPORTED;
+    if (!al8(ad) || !fits31(view_span(ad))) return TEM_EUNSUPPORTED;
     p.add = U(ad.ptr); p.aN = (int)ad.sN; p.aD = (int)ad.sD; p.aH = (int)ad.sH; p.aW = (int)ad.sW;
     p.aoz = e.add_off[0]; p.aoy = e.add_off[1]; p.aox = e.add_off[2];
-    p.aDd = ad.D; p.aHh = ad.H; p.aWw = ad.W; p.abytes = (int)(span(ad) * 2);
+    p.aDd = ad.D; p.aHh = ad.H; p.aWw = ad.W; p.abytes = (int)(view_span(ad) * 2);
   }
   if (e.dropout) {
     if (o0.C % 8) return TEM_EUNSUPPORTED;

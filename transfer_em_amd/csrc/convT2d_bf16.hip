@@ -14,17 +14,13 @@
 // exactly one k-step.  A workgroup owns (n, a band of Q_y rows) and runs BOTH r_y classes over one LDS patch (their B
 // fragments stay in registers); tiles of 16 Q voxels run across row ends.  Dropout keep bits follow the fp32 2-D path:
 // drawn in the epilogue (keep_mode 1 writes the mask), read back by the backward (keep_mode 2).
-#include "tem_common.h"
+#include "bf16_common.h"
 #include <cstdio>
 #include <cstdlib>
 
 namespace convt2d_bf16 {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned short u16;
-__device__ __forceinline__ float bf2f(u16 h) { return __uint_as_float((uint32_t)h << 16); }
-__device__ __forceinline__ u16 f2bf(float f) { return __builtin_bit_cast(u16, (__bf16)f); }   // round to nearest even
+using namespace tem_bf16;
 
 struct Ep {
   float slope;
@@ -242,16 +238,6 @@ __global__ __launch_bounds__(256) void convT2d_bf16_k(Dev p, const u16 *__restri
 }
 
 // ------------------------------------------------------------------------------------------ host
-static uint32_t magic_for(int d) { return (uint32_t)((0x100000000ull + (uint64_t)d - 1) / (uint64_t)d); }
-
-static bool fits32(const tem_view &v) {
-  int64_t span = (int64_t)(v.N - 1) * v.sN + (int64_t)(v.D - 1) * v.sD + (int64_t)(v.H - 1) * v.sH +
-                 (int64_t)(v.W - 1) * v.sW + v.C;
-  return span < ((int64_t)1 << 31);
-}
-
-static int floordiv2(int v) { return v >= 0 ? v / 2 : -((-v + 1) / 2); }
-
 constexpr int LDS_MAX = 64 * 1024;
 
 template <int CI, int CO, int PF>
@@ -283,11 +269,9 @@ int run(Dev p, int N, const u16 *w, hipStream_t st, bool dry, int epm, char *nam
     if (name) snprintf(name, name_len, "convT2d_bf16_k<%d, %d, %d, %d>", CI, CO, PF, epm);
     return TEM_OK;
   }
-  static int dbg = -1;
-  if (dbg < 0) dbg = tem_env_int("TEM_DEBUG_FLAGS", 0);
   const size_t lds_bytes = (((size_t)p.rows * p.cols * CI + 7) & ~(size_t)7) * 2 + TP_BYTES;
   const int nblocks = N * p.nband;
-  if (dbg & 8)
+  if (tem_debug_flags() & 8)
     fprintf(stderr, "convT2d_bf16<%d,%d> O=%dx%d P=%d: nQ=%dx%d TY=%d bands=%d blocks=%d lds=%zu\n", CI, CO, p.OH, p.OW,
             p.P, p.nQy, p.nQx, p.TY, p.nband, nblocks, lds_bytes);
   if (epm == 2) hipLaunchKernelGGL((convT2d_bf16_k<CI, CO, PF, 2>), dim3((unsigned)nblocks), dim3(256), lds_bytes, st, p, w);
@@ -309,60 +293,17 @@ int tem_conv_transpose2d_bf16_try(const tem_conv_args *a, hipStream_t st, bool d
   if (a->in1.ptr || a->out1.ptr || a->ep.bias) return TEM_EUNSUPPORTED;
   if (o0.N != i0.N) return TEM_ESHAPE;
   if (!fits32(i0) || !fits32(o0)) return TEM_EUNSUPPORTED;
-  auto U = [](const float *q) { return reinterpret_cast<const u16 *>(q); };
-  auto al16 = [](const tem_view &v) {       // 16-byte chunks of 8 bf16
-    return ((uintptr_t)v.ptr & 15) == 0 && v.sW % 8 == 0 && v.sH % 8 == 0 && v.sN % 8 == 0;
-  };
-  auto aligned = [](const tem_view &v) {    // 8-byte accesses of 4 bf16
-    return ((uintptr_t)v.ptr & 7) == 0 && v.sW % 4 == 0 && v.sH % 4 == 0 && v.sN % 4 == 0;
-  };
-  if (!al16(i0) || !aligned(o0)) return TEM_EUNSUPPORTED;
+  auto U = as_u16;
+  if (!aligned(i0, 8, false) || !aligned(o0, 4, false)) return TEM_EUNSUPPORTED;     // 16-byte input chunks, 8-byte stores
   Dev p{};
   p.in = U(i0.ptr); p.iN = (int)i0.sN; p.iH = (int)i0.sH; p.iW = (int)i0.sW;
   p.H = i0.H; p.W = i0.W;
   p.out = const_cast<u16 *>(U(o0.ptr)); p.oN = (int)o0.sN; p.oH = (int)o0.sH; p.oW = (int)o0.sW;
   p.OH = o0.H; p.OW = o0.W;
   p.P = a->ph;
-  const tem_epilogue &e = a->ep;
-  Ep &q = p.ep;
-  q.slope = e.slope; q.gate_slope = e.gate_slope;
-  if (e.gate.ptr) {
-    const tem_view &g = e.gate;
-    if (g.N != o0.N || g.D != 1 || g.H != o0.H || g.W != o0.W || g.C < o0.C) return TEM_ESHAPE;
-    if (!fits32(g) || !aligned(g)) return TEM_EUNSUPPORTED;
-    q.gate = U(g.ptr); q.gN = (int)g.sN; q.gH = (int)g.sH; q.gW = (int)g.sW;
-  }
-  if (e.add.ptr) {
-    const tem_view &ad = e.add;
-    if (ad.C < o0.C || ad.N != o0.N || ad.D != 1 || e.add_off[0] != 0) return TEM_ESHAPE;
-    if (!fits32(ad) || !aligned(ad)) return TEM_EUNSUPPORTED;
-    q.add = U(ad.ptr); q.aN = (int)ad.sN; q.aH = (int)ad.sH; q.aW = (int)ad.sW;
-    q.aoy = e.add_off[1]; q.aox = e.add_off[2];
-    q.aHh = ad.H; q.aWw = ad.W;
-  }
-  q.dropout = e.dropout;
-  q.ds.k0 = (uint32_t)e.seed; q.ds.k1 = (uint32_t)(e.seed >> 32); q.ds.site = e.site; q.ds.step = e.step;
-  q.step_dev = e.step_dev;
-  q.keep_mask = (e.dropout && e.keep_mask) ? e.keep_mask : nullptr;
-  q.keep_mode = q.keep_mask ? e.keep_mode : 0;
-  if (q.keep_mode && o0.C % 8 != 0) return TEM_EUNSUPPORTED;
-  q.doz = e.drop_org[0]; q.doy = e.drop_org[1]; q.dox = e.drop_org[2];
-  q.dD = e.drop_dims[0] ? e.drop_dims[0] : o0.D; q.dH = e.drop_dims[0] ? e.drop_dims[1] : o0.H;
-  q.dW = e.drop_dims[0] ? e.drop_dims[2] : o0.W;
-  {
-    auto span = [](const tem_view &v) {
-      return (int64_t)(v.N - 1) * v.sN + (int64_t)(v.D - 1) * v.sD + (int64_t)(v.H - 1) * v.sH + (int64_t)(v.W - 1) * v.sW + v.C;
-    };
-    const int64_t melems = (int64_t)o0.N * q.dD * q.dH * q.dW * o0.C;
-    if (melems >= ((int64_t)1 << 33)) return TEM_EUNSUPPORTED;
-    q.mbytes = (int)((melems + 7) / 8);
-    if ((e.gate.ptr && span(e.gate) >= ((int64_t)1 << 30)) || (e.add.ptr && span(e.add) >= ((int64_t)1 << 30)))
-      return TEM_EUNSUPPORTED;                     // byte offsets of the epilogue's buffer loads stay below 2^31
-    q.gbytes = e.gate.ptr ? (int)(span(e.gate) * 2) : 0;
-    q.abytes = e.add.ptr ? (int)(span(e.add) * 2) : 0;
-  }
+  if (const int rc = fill_epilogue<false, false>(p.ep, a->ep, o0)) return rc;
   const int CI = i0.C, CO = o0.C, N = i0.N;
-  const int epm = (!q.dropout && q.gate) ? 2 : 0;
+  const int epm = (!p.ep.dropout && p.ep.gate) ? 2 : 0;
 #define CT_CASE(ci, co, pf) if (CI == ci && CO == co) return run<ci, co, pf>(p, N, U(a->w), st, dry, epm, name, name_len);
   CT_CASE(16, 8, 12)     // g.u1b forward (Conv2DTranspose 16 -> 8, Dropout)
   CT_CASE(32, 16, 12)    // g.u2b forward

@@ -19,19 +19,13 @@
 // fragments of its n-tile in registers for the whole run (2 C_in VGPRs), gathers A per 16-voxel tile (tiles run
 // across row ends: v = q_y * nQx + q_x), and leaves through the fused epilogue (skip-gradient add, LeakyReLU
 // gradient gate, Philox dropout incl. writing / reading the keep mask, LeakyReLU) as 16-byte channel runs.
-#include "tem_common.h"
+#include "bf16_common.h"
 #include <cstdio>
 #include <cstdlib>
 
 namespace convt_bf16 {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef unsigned short u16;
-__device__ __forceinline__ float bf2f(u16 h) { return __uint_as_float((uint32_t)h << 16); }
-__device__ __forceinline__ u16 f2bf(float f) { return __builtin_bit_cast(u16, (__bf16)f); }   // round to nearest even
-
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace tem_bf16;
 
 struct Ep {
   float slope;
@@ -271,21 +265,8 @@ __global__ __launch_bounds__(256) void convT_bf16_k(Dev p, const u16 *__restrict
 }
 
 // ------------------------------------------------------------------------------------------ host
-static uint32_t magic_for(int d) { return (uint32_t)((0x100000000ull + (uint64_t)d - 1) / (uint64_t)d); }
-
-static bool fits32(const tem_view &v) {
-  int64_t span = (int64_t)(v.N - 1) * v.sN + (int64_t)(v.D - 1) * v.sD + (int64_t)(v.H - 1) * v.sH +
-                 (int64_t)(v.W - 1) * v.sW + v.C;
-  return span < ((int64_t)1 << 31);
-}
-
-static thread_local char *g_name = nullptr;
-static thread_local int g_name_len = 0;
-
-static int floordiv2(int v) { return v >= 0 ? v / 2 : -((-v + 1) / 2); }
-
 template <int CI, int CO, int PF, int NCLS>
-int run(Dev p, int N, const u16 *w, hipStream_t st, bool dry, int epm) {
+int run(Dev p, int N, const u16 *w, hipStream_t st, bool dry, int epm, char *name, int name_len) {
   constexpr int CIP = CI, CPV = CI / 8;
   // o + P = 2Q + r  =>  Q in [floor(P/2), floor((O-1+P)/2)]
   p.Qlo_x = floordiv2(p.P); p.nQx = floordiv2(p.OW - 1 + p.P) - p.Qlo_x + 1;
@@ -307,14 +288,12 @@ int run(Dev p, int N, const u16 *w, hipStream_t st, bool dry, int epm) {
   p.magicQx = magic_for(p.nQx);
   p.magicCols = magic_for(p.cols);
   if (dry) {
-    if (g_name) snprintf(g_name, g_name_len, "convT_bf16_k<%d, %d, %d, %d, %d>", CI, CO, PF, NCLS, epm);
+    if (name) snprintf(name, name_len, "convT_bf16_k<%d, %d, %d, %d, %d>", CI, CO, PF, NCLS, epm);
     return TEM_OK;
   }
-  static int dbg = -1;
-  if (dbg < 0) dbg = tem_env_int("TEM_DEBUG_FLAGS", 0);
   const size_t lds_bytes = (((size_t)2 * p.rows * p.cols * CIP + 7) & ~(size_t)7) * 2 + 4 * 16 * 20 * 4;
   const int nblocks = N * p.nband * p.nQz * (4 / NCLS);
-  if (dbg & 8)
+  if (tem_debug_flags() & 8)
     fprintf(stderr, "convT_bf16<%d,%d> O=%dx%dx%d P=%d: nQ=%dx%dx%d TY=%d bands=%d blocks=%d lds=%zu\n", CI, CO, p.OD, p.OH,
             p.OW, p.P, p.nQz, p.nQy, p.nQx, p.TY, p.nband, nblocks, lds_bytes);
   if (epm == 1) hipLaunchKernelGGL((convT_bf16_k<CI, CO, PF, NCLS, 1>), dim3((unsigned)nblocks), dim3(256), lds_bytes, st, p, w);
@@ -324,70 +303,27 @@ int run(Dev p, int N, const u16 *w, hipStream_t st, bool dry, int epm) {
   return TEM_OK;
 }
 
-int dispatch(const tem_conv_args *a, hipStream_t st, bool dry) {
+int dispatch(const tem_conv_args *a, hipStream_t st, bool dry, char *name, int name_len) {
   const tem_view &i0 = a->in0, &o0 = a->out0;
   if (a->in1.ptr || a->out1.ptr || a->ep.bias) return TEM_EUNSUPPORTED;
   if (a->kd != 4 || a->kh != 4 || a->kw != 4 || a->sd != 2 || a->sh != 2 || a->sw != 2) return TEM_EUNSUPPORTED;
   if (a->pd != a->ph || a->ph != a->pw) return TEM_EUNSUPPORTED;
   if (o0.N != i0.N) return TEM_ESHAPE;
   if (!fits32(i0) || !fits32(o0)) return TEM_EUNSUPPORTED;
-  auto U = [](const float *q) { return reinterpret_cast<const u16 *>(q); };
-  auto al16 = [](const tem_view &v) {       // 16-byte chunks of 8 bf16
-    return ((uintptr_t)v.ptr & 15) == 0 && v.sW % 8 == 0 && v.sH % 8 == 0 && v.sD % 8 == 0 && v.sN % 8 == 0;
-  };
-  auto aligned = [](const tem_view &v) {    // 8-byte accesses of 4 bf16
-    return ((uintptr_t)v.ptr & 7) == 0 && v.sW % 4 == 0 && v.sH % 4 == 0 && v.sD % 4 == 0 && v.sN % 4 == 0;
-  };
-  if (!al16(i0) || !aligned(o0)) return TEM_EUNSUPPORTED;
+  auto U = as_u16;
+  if (!aligned(i0, 8, true) || !aligned(o0, 4, true)) return TEM_EUNSUPPORTED;       // 16-byte input chunks, 8-byte stores
   Dev p{};
   p.in = U(i0.ptr); p.iN = (int)i0.sN; p.iD = (int)i0.sD; p.iH = (int)i0.sH; p.iW = (int)i0.sW;
   p.D = i0.D; p.H = i0.H; p.W = i0.W;
   p.out = const_cast<u16 *>(U(o0.ptr)); p.oN = (int)o0.sN; p.oD = (int)o0.sD; p.oH = (int)o0.sH; p.oW = (int)o0.sW;
   p.OD = o0.D; p.OH = o0.H; p.OW = o0.W;
   p.P = a->pd;
-  const tem_epilogue &e = a->ep;
-  Ep &q = p.ep;
-  q.slope = e.slope; q.gate_slope = e.gate_slope;
-  if (e.gate.ptr) {
-    const tem_view &g = e.gate;
-    if (g.N != o0.N || g.D != o0.D || g.H != o0.H || g.W != o0.W || g.C < o0.C) return TEM_ESHAPE;
-    if (!fits32(g) || !aligned(g)) return TEM_EUNSUPPORTED;
-    q.gate = U(g.ptr); q.gN = (int)g.sN; q.gD = (int)g.sD; q.gH = (int)g.sH; q.gW = (int)g.sW;
-  }
-  if (e.add.ptr) {
-    const tem_view &ad = e.add;
-    if (ad.C < o0.C || ad.N != o0.N) return TEM_ESHAPE;
-    if (!fits32(ad) || !aligned(ad)) return TEM_EUNSUPPORTED;
-    q.add = U(ad.ptr); q.aN = (int)ad.sN; q.aD = (int)ad.sD; q.aH = (int)ad.sH; q.aW = (int)ad.sW;
-    q.aoz = e.add_off[0]; q.aoy = e.add_off[1]; q.aox = e.add_off[2];
-    q.aDd = ad.D; q.aHh = ad.H; q.aWw = ad.W;
-  }
-  q.dropout = e.dropout;
-  q.ds.k0 = (uint32_t)e.seed; q.ds.k1 = (uint32_t)(e.seed >> 32); q.ds.site = e.site; q.ds.step = e.step;
-  q.step_dev = e.step_dev;
-  q.keep_mask = (e.dropout && e.keep_mask) ? e.keep_mask : nullptr;
-  q.keep_mode = q.keep_mask ? e.keep_mode : 0;
-  if (q.keep_mode && o0.C % 8 != 0) return TEM_EUNSUPPORTED;
-  q.doz = e.drop_org[0]; q.doy = e.drop_org[1]; q.dox = e.drop_org[2];
-  q.dD = e.drop_dims[0] ? e.drop_dims[0] : o0.D; q.dH = e.drop_dims[0] ? e.drop_dims[1] : o0.H;
-  q.dW = e.drop_dims[0] ? e.drop_dims[2] : o0.W;
-  {
-    auto span = [](const tem_view &v) {
-      return (int64_t)(v.N - 1) * v.sN + (int64_t)(v.D - 1) * v.sD + (int64_t)(v.H - 1) * v.sH + (int64_t)(v.W - 1) * v.sW + v.C;
-    };
-    const int64_t melems = (int64_t)o0.N * q.dD * q.dH * q.dW * o0.C;
-    if (melems >= ((int64_t)1 << 33)) return TEM_EUNSUPPORTED;
-    q.mbytes = (int)((melems + 7) / 8);
-    if ((e.gate.ptr && span(e.gate) >= ((int64_t)1 << 30)) || (e.add.ptr && span(e.add) >= ((int64_t)1 << 30)))
-      return TEM_EUNSUPPORTED;                     // byte offsets of the epilogue's buffer loads stay below 2^31
-    q.gbytes = e.gate.ptr ? (int)(span(e.gate) * 2) : 0;
-    q.abytes = e.add.ptr ? (int)(span(e.add) * 2) : 0;
-  }
+  if (const int rc = fill_epilogue<true, false>(p.ep, a->ep, o0)) return rc;
   const int CI = i0.C, CO = o0.C, N = i0.N;
   int epm = 0;
   if (p.ep.dropout && p.ep.keep_mode == 2 && !p.ep.gate && !p.ep.add) epm = 1;
   else if (!p.ep.dropout && p.ep.gate) epm = 2;
-#define CT_CASE(ci, co, pf, ncls) if (CI == ci && CO == co) return run<ci, co, pf, ncls>(p, N, U(a->w), st, dry, epm);
+#define CT_CASE(ci, co, pf, ncls) if (CI == ci && CO == co) return run<ci, co, pf, ncls>(p, N, U(a->w), st, dry, epm, name, name_len);
   CT_CASE(16, 8, 12, 1)     // g.u1b forward (Conv3DTranspose 16 -> 8)
   CT_CASE(32, 16, 12, 1)    // g.u2b forward
   CT_CASE(8, 8, 12, 1)      // input-gradient of g.d1b / d.d1b    (more classes per patch measured no faster)
@@ -402,20 +338,19 @@ int dispatch(const tem_conv_args *a, hipStream_t st, bool dry) {
 int tem_conv_transpose2d_bf16_try(const tem_conv_args *a, hipStream_t st, bool dry, char *name, int name_len);  // convT2d_bf16.hip
 
 // bf16 mode of tem_conv_transpose (see tem_conv_bf16): `w` is the bf16 kernel [tap][co][ci].
+// One route for the launch and its dry query; a new transposed kernel is one line here.
+static int route(const tem_conv_args *a, hipStream_t st, bool dry, char *name, int name_len) {
+  if (!a || !tem_view_ok(a->in0) || !tem_view_ok(a->out0) || !a->w) return TEM_EINVAL;
+  int rc = tem_conv_transpose2d_bf16_try(a, st, dry, name, name_len);                         // 2-D geometry
+  if (rc == TEM_EUNSUPPORTED) rc = convt_bf16::dispatch(a, st, dry, name, name_len);
+  return rc;
+}
+
 extern "C" int tem_conv_transpose_bf16(const tem_conv_args *a, tem_stream_t stream) {
   TEM_CLEAR_ERR();
-  if (!a || !tem_view_ok(a->in0) || !tem_view_ok(a->out0) || !a->w) return TEM_EINVAL;
-  const int rc0 = tem_conv_transpose2d_bf16_try(a, (hipStream_t)stream, false, nullptr, 0);   // 2-D geometry
-  if (rc0 != TEM_EUNSUPPORTED) return rc0;
-  return convt_bf16::dispatch(a, (hipStream_t)stream, false);
+  return route(a, (hipStream_t)stream, false, nullptr, 0);
 }
 
 extern "C" int tem_conv_transpose_bf16_describe(const tem_conv_args *a, char *buf, int32_t len) {
-  if (!a || !tem_view_ok(a->in0) || !tem_view_ok(a->out0) || !a->w) return TEM_EINVAL;
-  const int rc0 = tem_conv_transpose2d_bf16_try(a, nullptr, true, buf, len);
-  if (rc0 != TEM_EUNSUPPORTED) return rc0;
-  convt_bf16::g_name = buf; convt_bf16::g_name_len = len;
-  int rc = convt_bf16::dispatch(a, nullptr, true);
-  convt_bf16::g_name = nullptr;
-  return rc;
+  return route(a, nullptr, true, buf, len);
 }

@@ -278,21 +278,9 @@ __global__ __launch_bounds__(256) void convT_mfma_k(Dev p, const float *__restri
 }
 
 // ------------------------------------------------------------------------------------------ host
-static uint32_t magic_for(int d) { return (uint32_t)((0x100000000ull + (uint64_t)d - 1) / (uint64_t)d); }
-
-static bool fits32(const tem_view &v) {
-  int64_t span = (int64_t)(v.N - 1) * v.sN + (int64_t)(v.D - 1) * v.sD + (int64_t)(v.H - 1) * v.sH +
-                 (int64_t)(v.W - 1) * v.sW + v.C;
-  return span < ((int64_t)1 << 31);
-}
-
-static thread_local char *g_name = nullptr;
-static thread_local int g_name_len = 0;
-
-static int floordiv2(int v) { return v >= 0 ? v / 2 : -((-v + 1) / 2); }
 
 template <int CI, int CO, int PF, int NCLS>
-int run(Dev p, int N, const float *w, hipStream_t st, bool dry, int epm) {
+int run(Dev p, int N, const float *w, hipStream_t st, bool dry, int epm, char *name, int name_len) {
   constexpr int CIP = CI + 2, CPV = CI / 4;
   // o + P = 2Q + r  =>  Q in [floor(P/2), floor((O-1+P)/2)]
   p.Qlo_x = floordiv2(p.P); p.nQx = floordiv2(p.OW - 1 + p.P) - p.Qlo_x + 1;
@@ -314,7 +302,7 @@ int run(Dev p, int N, const float *w, hipStream_t st, bool dry, int epm) {
   p.magicQx = magic_for(p.nQx);
   p.magicCols = magic_for(p.cols);
   if (dry) {
-    if (g_name) snprintf(g_name, g_name_len, "convT_mfma_k<%d, %d, %d, %d, %d>", CI, CO, PF, NCLS, epm);
+    if (name) snprintf(name, name_len, "convT_mfma_k<%d, %d, %d, %d, %d>", CI, CO, PF, NCLS, epm);
     return TEM_OK;
   }
   static int dbg = -1;
@@ -331,7 +319,7 @@ int run(Dev p, int N, const float *w, hipStream_t st, bool dry, int epm) {
   return TEM_OK;
 }
 
-int dispatch(const tem_conv_args *a, hipStream_t st, bool dry) {
+int dispatch(const tem_conv_args *a, hipStream_t st, bool dry, char *name, int name_len) {
   const tem_view &i0 = a->in0, &o0 = a->out0;
   if (a->in1.ptr || a->out1.ptr || a->ep.bias) return TEM_EUNSUPPORTED;
   if (a->kd != 4 || a->kh != 4 || a->kw != 4 || a->sd != 2 || a->sh != 2 || a->sw != 2) return TEM_EUNSUPPORTED;
@@ -359,14 +347,14 @@ int dispatch(const tem_conv_args *a, hipStream_t st, bool dry) {
     if (g.N != o0.N || g.D != o0.D || g.H != o0.H || g.W != o0.W || g.C < o0.C) return TEM_ESHAPE;
     if (!fits32(g) || !aligned(g)) return TEM_EUNSUPPORTED;
     q.gate = g.ptr; q.gN = (int)g.sN; q.gD = (int)g.sD; q.gH = (int)g.sH; q.gW = (int)g.sW;
-    q.gbytes = (int)(((int64_t)(g.N - 1) * g.sN + (int64_t)(g.D - 1) * g.sD + (int64_t)(g.H - 1) * g.sH + (int64_t)(g.W - 1) * g.sW + g.C) * 4);
+    q.gbytes = (int)(view_span(g) * 4);
   }
   if (e.add.ptr) {
     const tem_view &ad = e.add;
     if (ad.C < o0.C || ad.N != o0.N) return TEM_ESHAPE;
     if (!fits32(ad) || !aligned(ad)) return TEM_EUNSUPPORTED;
     q.add = ad.ptr; q.aN = (int)ad.sN; q.aD = (int)ad.sD; q.aH = (int)ad.sH; q.aW = (int)ad.sW;
-    q.abytes = (int)(((int64_t)(ad.N - 1) * ad.sN + (int64_t)(ad.D - 1) * ad.sD + (int64_t)(ad.H - 1) * ad.sH + (int64_t)(ad.W - 1) * ad.sW + ad.C) * 4);
+    q.abytes = (int)(view_span(ad) * 4);
     q.aoz = e.add_off[0]; q.aoy = e.add_off[1]; q.aox = e.add_off[2];
     q.aDd = ad.D; q.aHh = ad.H; q.aWw = ad.W;
   }
@@ -383,10 +371,7 @@ int dispatch(const tem_conv_args *a, hipStream_t st, bool dry) {
     const int64_t melems = (int64_t)o0.N * q.dD * q.dH * q.dW * o0.C;
     if (melems >= ((int64_t)1 << 32)) return TEM_EUNSUPPORTED;
     q.mbytes = (int)((melems + 7) / 8);
-    auto span = [](const tem_view &v) {
-      return (int64_t)(v.N - 1) * v.sN + (int64_t)(v.D - 1) * v.sD + (int64_t)(v.H - 1) * v.sH + (int64_t)(v.W - 1) * v.sW + v.C;
-    };
-    if ((e.gate.ptr && span(e.gate) >= ((int64_t)1 << 29)) || (e.add.ptr && span(e.add) >= ((int64_t)1 << 29)))
+    if ((e.gate.ptr && view_span(e.gate) >= ((int64_t)1 << 29)) || (e.add.ptr && view_span(e.add) >= ((int64_t)1 << 29)))
       return TEM_EUNSUPPORTED;                     // byte offsets of the epilogue's buffer loads stay below 2^31
   }
   const int CI = i0.C, CO = o0.C, N = i0.N;
@@ -397,7 +382,7 @@ int dispatch(const tem_conv_args *a, hipStream_t st, bool dry) {
     if (q.dropout && q.keep_mode == 2 && !q.gate && !q.add) epm = 1;
     else if (!q.dropout && q.gate) epm = 2;
   }
-#define CT_CASE(ci, co, pf, ncls) if (CI == ci && CO == co) return run<ci, co, pf, ncls>(p, N, a->w, st, dry, epm);
+#define CT_CASE(ci, co, pf, ncls) if (CI == ci && CO == co) return run<ci, co, pf, ncls>(p, N, a->w, st, dry, epm, name, name_len);
   CT_CASE(16, 8, 12, 1)     // g.u1b forward (Conv3DTranspose 16 -> 8)
   CT_CASE(32, 16, 12, 1)    // g.u2b forward
   CT_CASE(8, 8, 12, 1)      // input-gradient of g.d1b / d.d1b    (more classes per patch measured no faster)
@@ -410,11 +395,9 @@ int dispatch(const tem_conv_args *a, hipStream_t st, bool dry) {
 }  // namespace convt_mfma
 
 // Called by tem_conv_transpose (dispatch.hip) before it falls back to the direct kernel.
-int tem_convT_mfma_try(const tem_conv_args *a, hipStream_t st, bool dry) { return convt_mfma::dispatch(a, st, dry); }
+int tem_convT_mfma_try(const tem_conv_args *a, hipStream_t st, bool dry) { return convt_mfma::dispatch(a, st, dry, nullptr, 0); }
 
 int tem_convT_mfma_describe(const tem_conv_args *a, char *buf, int len) {
-  convt_mfma::g_name = buf; convt_mfma::g_name_len = len;
-  int rc = convt_mfma::dispatch(a, nullptr, true);
-  convt_mfma::g_name = nullptr;
+  int rc = convt_mfma::dispatch(a, nullptr, true, buf, len);
   return rc;
 }

@@ -16,21 +16,13 @@
 //   * narrow outputs (C_out 1 or 8) simply leave MFMA columns empty -- irrelevant at this arithmetic intensity;
 //   * fused epilogue as in the fp32 kernels (bias, skip-gradient add, LeakyReLU' gate, Philox dropout with keep-mask
 //     write / read, LeakyReLU, split outputs), 8-byte bf16 stores of 4 channels per lane.
-#include "tem_common.h"
+#include "bf16_common.h"
 #include <cstdio>
 #include <cstdlib>
 
 namespace conv_bf16 {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned short u16;
-
-__device__ __forceinline__ float bf2f(u16 h) { return __uint_as_float((uint32_t)h << 16); }
-__device__ __forceinline__ u16 f2bf(float f) { return __builtin_bit_cast(u16, (__bf16)f); }   // round to nearest even
-
-// x / d for 0 <= x < 2^31 with magic = ceil(2^32 / d) (d == 1: the magic does not fit 32 bits)
-__device__ __forceinline__ int fdiv(int x, int d, uint32_t magic) { return d == 1 ? x : (int)__umulhi((uint32_t)x, magic); }
+using namespace tem_bf16;
 
 struct Ep {
   const float *bias;
@@ -378,19 +370,8 @@ __global__ __launch_bounds__(256) void conv_bf16_k(Dev p) {
 }
 
 // ------------------------------------------------------------------------------------------ host
-static uint32_t magic_for(int d) { return d <= 1 ? 0u : (uint32_t)((0x100000000ull + (uint64_t)d - 1) / (uint64_t)d); }
-
-static bool fits32(const tem_view &v) {
-  int64_t span = (int64_t)(v.N - 1) * v.sN + (int64_t)(v.D - 1) * v.sD + (int64_t)(v.H - 1) * v.sH +
-                 (int64_t)(v.W - 1) * v.sW + v.C;
-  return span < ((int64_t)1 << 31);
-}
-
-static thread_local char *g_name = nullptr;
-static thread_local int g_name_len = 0;
-
 template <int CI, int CO, int K, int S, int PF, bool BLDS>
-int run(Dev p, int N, hipStream_t st, bool dry) {
+int run(Dev p, int N, hipStream_t st, bool dry, char *name, int name_len) {
   constexpr int NTAP = K * K * K, NSTEP = (NTAP * CI + 31) / 32, NT = (CO + 15) / 16;
   constexpr int PITCH = CI >= 8 ? CI : 1, CPV = CI >= 8 ? CI / 8 : 1;
   constexpr size_t B_BYTES = BLDS ? (size_t)NSTEP * NT * 64 * 16 : 0;
@@ -421,13 +402,11 @@ int run(Dev p, int N, hipStream_t st, bool dry) {
   p.magicPlane = magic_for(p.rows * p.cols);
   p.magicTX = magic_for(p.TX);
   if (dry) {
-    if (g_name) snprintf(g_name, g_name_len, "conv_bf16_k<%d, %d, %d, %d, %d, %s>", CI, CO, K, S, PF, BLDS ? "true" : "false");
+    if (name) snprintf(name, name_len, "conv_bf16_k<%d, %d, %d, %d, %d, %s>", CI, CO, K, S, PF, BLDS ? "true" : "false");
     return TEM_OK;
   }
-  static int dbg = -1;
-  if (dbg < 0) dbg = tem_env_int("TEM_DEBUG_FLAGS", 0);
   const int nblocks = N * p.nby * p.nbx * p.OD;
-  if (dbg & 8)
+  if (tem_debug_flags() & 8)
     fprintf(stderr, "conv_bf16<%d,%d,%d,%d> O=%dx%dx%d P=%d: TX=%d TY=%d patch=%dx%d blocks=%d lds=%zu\n", CI, CO, K, S, p.OD,
             p.OH, p.OW, p.P, p.TX, p.TY, p.rows, p.cols, nblocks, best_bytes);
   auto kern = conv_bf16_k<CI, CO, K, S, PF, BLDS>;
@@ -442,20 +421,16 @@ int run(Dev p, int N, hipStream_t st, bool dry) {
   return TEM_OK;
 }
 
-int dispatch(const tem_conv_args *a, hipStream_t st, bool dry) {
+int dispatch(const tem_conv_args *a, hipStream_t st, bool dry, char *name, int name_len) {
   const tem_view &i0 = a->in0, &o0 = a->out0;
   if (!(a->kd == a->kh && a->kh == a->kw && a->sd == a->sh && a->sh == a->sw && a->pd == a->ph && a->ph == a->pw))
     return TEM_EUNSUPPORTED;
   if (o0.N != i0.N) return TEM_ESHAPE;
   if (!fits32(i0) || !fits32(o0)) return TEM_EUNSUPPORTED;
   Dev p{};
-  auto U = [](const float *q) { return reinterpret_cast<const u16 *>(q); };
-  auto al16 = [](const tem_view &v) {       // 16-byte channel chunks: 8 bf16
-    return v.C % 8 != 0 || (((uintptr_t)v.ptr & 15) == 0 && v.sW % 8 == 0 && v.sH % 8 == 0 && v.sD % 8 == 0 && v.sN % 8 == 0);
-  };
-  auto al8 = [](const tem_view &v) {        // 8-byte accesses of 4 bf16 (stores, gate, add)
-    return v.C % 4 != 0 || (((uintptr_t)v.ptr & 7) == 0 && v.sW % 4 == 0 && v.sH % 4 == 0 && v.sD % 4 == 0 && v.sN % 4 == 0);
-  };
+  auto U = as_u16;
+  auto al16 = [](const tem_view &v) { return v.C % 8 != 0 || aligned(v, 8, true); };      // 16-byte channel chunks: 8 bf16
+  auto al8 = [](const tem_view &v) { return v.C % 4 != 0 || aligned(v, 4, true); };       // 8-byte stores of 4 bf16
   p.in0 = U(i0.ptr); p.i0N = (int)i0.sN; p.i0D = (int)i0.sD; p.i0H = (int)i0.sH; p.i0W = (int)i0.sW; p.C0 = i0.C;
   p.in1 = p.in0; p.i1N = p.i0N; p.i1D = p.i0D; p.i1H = p.i0H; p.i1W = p.i0W;
   int CI = i0.C;
@@ -481,47 +456,11 @@ int dispatch(const tem_conv_args *a, hipStream_t st, bool dry) {
     CO += o1.C;
   }
   p.OD = o0.D; p.OH = o0.H; p.OW = o0.W; p.P = a->pd;
-  const tem_epilogue &e = a->ep;
-  Ep &q = p.ep;
-  q.bias = e.bias; q.slope = e.slope; q.gate_slope = e.gate_slope;
-  if (e.gate.ptr) {
-    const tem_view &g = e.gate;
-    if (g.N != o0.N || g.D != o0.D || g.H != o0.H || g.W != o0.W || g.C < o0.C) return TEM_ESHAPE;
-    if (!fits32(g) || !al8(g) || o0.C % 4) return TEM_EUNSUPPORTED;
-    q.gate = U(g.ptr); q.gN = (int)g.sN; q.gD = (int)g.sD; q.gH = (int)g.sH; q.gW = (int)g.sW;
-  }
-  if (e.add.ptr) {
-    const tem_view &ad = e.add;
-    if (ad.C < o0.C || ad.N != o0.N) return TEM_ESHAPE;
-    if (!fits32(ad) || !al8(ad) || o0.C % 4) return TEM_EUNSUPPORTED;
-    q.add = U(ad.ptr); q.aN = (int)ad.sN; q.aD = (int)ad.sD; q.aH = (int)ad.sH; q.aW = (int)ad.sW;
-    q.aoz = e.add_off[0]; q.aoy = e.add_off[1]; q.aox = e.add_off[2];
-    q.aDd = ad.D; q.aHh = ad.H; q.aWw = ad.W;
-  }
-  q.dropout = e.dropout;
-  if (e.dropout && o0.C % 8) return TEM_EUNSUPPORTED;
-  q.ds.k0 = (uint32_t)e.seed; q.ds.k1 = (uint32_t)(e.seed >> 32); q.ds.site = e.site; q.ds.step = e.step;
-  q.step_dev = e.step_dev;
-  q.keep_mask = (e.dropout && e.keep_mask) ? e.keep_mask : nullptr;
-  q.keep_mode = q.keep_mask ? e.keep_mode : 0;
-  q.doz = e.drop_org[0]; q.doy = e.drop_org[1]; q.dox = e.drop_org[2];
-  q.dD = e.drop_dims[0] ? e.drop_dims[0] : o0.D; q.dH = e.drop_dims[0] ? e.drop_dims[1] : o0.H;
-  q.dW = e.drop_dims[0] ? e.drop_dims[2] : o0.W;
-  {
-    auto span = [](const tem_view &v) {
-      return (int64_t)(v.N - 1) * v.sN + (int64_t)(v.D - 1) * v.sD + (int64_t)(v.H - 1) * v.sH + (int64_t)(v.W - 1) * v.sW + v.C;
-    };
-    const int64_t melems = (int64_t)o0.N * q.dD * q.dH * q.dW * o0.C;
-    if (melems >= ((int64_t)1 << 33)) return TEM_EUNSUPPORTED;
-    q.mbytes = (int)((melems + 7) / 8);
-    if ((e.gate.ptr && span(e.gate) >= ((int64_t)1 << 30)) || (e.add.ptr && span(e.add) >= ((int64_t)1 << 30)))
-      return TEM_EUNSUPPORTED;                     // byte offsets of the epilogue's buffer loads stay below 2^31
-    q.gbytes = e.gate.ptr ? (int)(span(e.gate) * 2) : 0;
-    q.abytes = e.add.ptr ? (int)(span(e.add) * 2) : 0;
-  }
+  p.ep.bias = a->ep.bias;
+  if (const int rc = fill_epilogue<true, true>(p.ep, a->ep, o0)) return rc;
   const int K = a->kd, S = a->sd, N = i0.N;
-#define CB(ci, co, k, s, pf) if (CI == ci && CO == co && K == k && S == s) return run<ci, co, k, s, pf, true>(p, N, st, dry);
-#define CBG(ci, co, k, s, pf) if (CI == ci && CO == co && K == k && S == s) return run<ci, co, k, s, pf, false>(p, N, st, dry);
+#define CB(ci, co, k, s, pf) if (CI == ci && CO == co && K == k && S == s) return run<ci, co, k, s, pf, true>(p, N, st, dry, name, name_len);
+#define CBG(ci, co, k, s, pf) if (CI == ci && CO == co && K == k && S == s) return run<ci, co, k, s, pf, false>(p, N, st, dry, name, name_len);
   // k3 s1: forward layers and (flip) their input-gradients
   CB(1, 8, 3, 1, 12) CB(8, 1, 3, 1, 12) CB(1, 16, 3, 1, 12) CB(16, 1, 3, 1, 12)
   CB(8, 8, 3, 1, 12) CB(8, 16, 3, 1, 12) CB(16, 8, 3, 1, 12) CB(16, 16, 3, 1, 12)
@@ -544,32 +483,23 @@ int tem_conv2d_bf16_try(const tem_conv_args *a, hipStream_t st, bool dry, char *
 
 // bf16 mode: activations, gate / add views and the packed kernel are bf16 (the float* fields of tem_conv_args carry
 // bf16 pointers, strides in elements); slope / bias / dropout as in tem_conv.
+// The route of a launch and of its dry query (`name` receives the kernel that takes the layer): the first kernel that does
+// not answer TEM_EUNSUPPORTED.  A new forward kernel is one line here.
+static int route(const tem_conv_args *a, hipStream_t st, bool dry, char *name, int name_len) {
+  if (!a || !tem_view_ok(a->in0) || !tem_view_ok(a->out0) || !a->w) return TEM_EINVAL;
+  int rc = tem_conv2d_bf16_try(a, st, dry, name, name_len);                                   // 2-D geometry, 3x3 / 4x4
+  if (rc == TEM_EUNSUPPORTED) rc = tem_conv_c1_bf16_try(a, st, dry, name, name_len);          // one input channel, 3x3x3
+  if (rc == TEM_EUNSUPPORTED) rc = tem_conv_c1out_bf16_try(a, st, dry, name, name_len);       // one output channel, 3x3x3
+  if (rc == TEM_EUNSUPPORTED) rc = conv3_bf16::dispatch(a, st, dry, name, name_len);          // 3x3x3 s1 / 4x4x4 s2, 8..32 channels
+  if (rc == TEM_EUNSUPPORTED) rc = conv_bf16::dispatch(a, st, dry, name, name_len);           // every other layer of the tables
+  return rc;
+}
+
 extern "C" int tem_conv_bf16(const tem_conv_args *a, tem_stream_t stream) {
   TEM_CLEAR_ERR();
-  if (!a || !tem_view_ok(a->in0) || !tem_view_ok(a->out0) || !a->w) return TEM_EINVAL;
-  const int rc0 = tem_conv2d_bf16_try(a, (hipStream_t)stream, false, nullptr, 0);     // 2-D geometry, 3x3 / 4x4
-  if (rc0 != TEM_EUNSUPPORTED) return rc0;
-  const int rc1 = tem_conv_c1_bf16_try(a, (hipStream_t)stream, false, nullptr, 0);    // one input channel, 3x3x3
-  if (rc1 != TEM_EUNSUPPORTED) return rc1;
-  const int rc2 = tem_conv_c1out_bf16_try(a, (hipStream_t)stream, false, nullptr, 0); // one output channel, 3x3x3
-  if (rc2 != TEM_EUNSUPPORTED) return rc2;
-  const int rc = conv3_bf16::dispatch(a, (hipStream_t)stream, false, nullptr, 0);     // 3x3x3 stride 1, 8..32 channels
-  if (rc != TEM_EUNSUPPORTED) return rc;
-  return conv_bf16::dispatch(a, (hipStream_t)stream, false);
+  return route(a, (hipStream_t)stream, false, nullptr, 0);
 }
 
 extern "C" int tem_conv_bf16_describe(const tem_conv_args *a, char *buf, int32_t len) {
-  if (!a || !tem_view_ok(a->in0) || !tem_view_ok(a->out0) || !a->w) return TEM_EINVAL;
-  const int rc0 = tem_conv2d_bf16_try(a, nullptr, true, buf, len);
-  if (rc0 != TEM_EUNSUPPORTED) return rc0;
-  const int rc1 = tem_conv_c1_bf16_try(a, nullptr, true, buf, len);
-  if (rc1 != TEM_EUNSUPPORTED) return rc1;
-  const int rc2 = tem_conv_c1out_bf16_try(a, nullptr, true, buf, len);
-  if (rc2 != TEM_EUNSUPPORTED) return rc2;
-  const int rc3 = conv3_bf16::dispatch(a, nullptr, true, buf, len);
-  if (rc3 != TEM_EUNSUPPORTED) return rc3;
-  conv_bf16::g_name = buf; conv_bf16::g_name_len = len;
-  int rc = conv_bf16::dispatch(a, nullptr, true);
-  conv_bf16::g_name = nullptr;
-  return rc;
+  return route(a, nullptr, true, buf, len);
 }

@@ -446,21 +446,11 @@ __global__ __launch_bounds__(NW * 64) void conv_lds_k(Dev p) {
 
 // ------------------------------------------------------------------------------------------ host
 constexpr int LDS_MAX = 160 * 1024;                     // gfx950: 160 KiB per workgroup
-static thread_local char *g_name = nullptr;   // set by tem_conv_describe around a dry run
-static thread_local int g_name_len = 0;
 constexpr int TARGET_BLOCKS = 512;
-
-static uint32_t magic_for(int d) { return (uint32_t)((0x100000000ull + (uint64_t)d - 1) / (uint64_t)d); }
-
-static bool fits32(const tem_view &v) {
-  int64_t span = (int64_t)(v.N - 1) * v.sN + (int64_t)(v.D - 1) * v.sD + (int64_t)(v.H - 1) * v.sH +
-                 (int64_t)(v.W - 1) * v.sW + v.C;
-  return span < (int64_t)1 << 31 && v.sN < ((int64_t)1 << 31);
-}
 
 // mode 0: launch; 1: dry run; 2: only predict (*cost receives the model's cycles)
 template <int CI, int CO, int K, int S, int NW, int MAXPFX, int MTW, bool DROP>
-int run(Dev p, hipStream_t st, int mode, double *cost) {
+int run(Dev p, hipStream_t st, int mode, double *cost, char *name, int name_len) {
   constexpr int CIP = CI + 2, NT = (CO + 15) / 16;
   const int NTHR = NW * 64;
   p.WX = (p.OW - 1) * S + K;
@@ -512,8 +502,8 @@ int run(Dev p, hipStream_t st, int mode, double *cost) {
   const bool dry = mode == 1;
   int nblocks = p.N * p.nych * p.zsegs;
   if (dry) {
-    if (g_name)
-      snprintf(g_name, g_name_len, "conv_lds_k<%d, %d, %d, %d, %d, %d, %d, %s>", CI, CO, K, S, NW, MAXPFX, MTW,
+    if (name)
+      snprintf(name, name_len, "conv_lds_k<%d, %d, %d, %d, %d, %d, %d, %s>", CI, CO, K, S, NW, MAXPFX, MTW,
                DROP ? "true" : "false");
     return TEM_OK;
   }
@@ -534,36 +524,36 @@ int run(Dev p, hipStream_t st, int mode, double *cost) {
 
 // each geometry is built with 4 and with 2 (and 1) accumulator tiles per wave; the cost model picks
 template <int CI, int CO, int K, int S, int NW, int MAXPFX, bool DROP>
-int run_best(const Dev &p, hipStream_t st, bool dry) {
+int run_best(const Dev &p, hipStream_t st, bool dry, char *name, int name_len) {
   double c4 = 1e300, c2 = 1e300, c1 = 1e300;
-  run<CI, CO, K, S, NW, MAXPFX, 4, DROP>(p, st, 2, &c4);
-  run<CI, CO, K, S, NW, MAXPFX, 2, DROP>(p, st, 2, &c2);
-  run<CI, CO, K, S, NW, MAXPFX, 1, DROP>(p, st, 2, &c1);
+  run<CI, CO, K, S, NW, MAXPFX, 4, DROP>(p, st, 2, &c4, nullptr, 0);
+  run<CI, CO, K, S, NW, MAXPFX, 2, DROP>(p, st, 2, &c2, nullptr, 0);
+  run<CI, CO, K, S, NW, MAXPFX, 1, DROP>(p, st, 2, &c1, nullptr, 0);
   if (c4 >= 1e300 && c2 >= 1e300 && c1 >= 1e300) return TEM_EUNSUPPORTED;
-  if (c4 <= c2 && c4 <= c1) return run<CI, CO, K, S, NW, MAXPFX, 4, DROP>(p, st, dry ? 1 : 0, nullptr);
-  if (c2 <= c1) return run<CI, CO, K, S, NW, MAXPFX, 2, DROP>(p, st, dry ? 1 : 0, nullptr);
-  return run<CI, CO, K, S, NW, MAXPFX, 1, DROP>(p, st, dry ? 1 : 0, nullptr);
+  if (c4 <= c2 && c4 <= c1) return run<CI, CO, K, S, NW, MAXPFX, 4, DROP>(p, st, dry ? 1 : 0, nullptr, name, name_len);
+  if (c2 <= c1) return run<CI, CO, K, S, NW, MAXPFX, 2, DROP>(p, st, dry ? 1 : 0, nullptr, name, name_len);
+  return run<CI, CO, K, S, NW, MAXPFX, 1, DROP>(p, st, dry ? 1 : 0, nullptr, name, name_len);
 }
 
 #define CONV_CASE(ci, co, k, s, nw, pfx, mtw) \
-  if (CI == ci && CO == co && K == k && S == s && !a->ep.dropout) return run_best<ci, co, k, s, nw, pfx_of(pfx), false>(p, st, dry);
+  if (CI == ci && CO == co && K == k && S == s && !a->ep.dropout) return run_best<ci, co, k, s, nw, pfx_of(pfx), false>(p, st, dry, name, name_len);
 #define CONV_CASE_DROP(ci, co, k, s, nw, pfx, mtw) \
-  if (CI == ci && CO == co && K == k && S == s && a->ep.dropout) return run_best<ci, co, k, s, nw, pfx_of(pfx), true>(p, st, dry);
+  if (CI == ci && CO == co && K == k && S == s && a->ep.dropout) return run_best<ci, co, k, s, nw, pfx_of(pfx), true>(p, st, dry, name, name_len);
 
-int dispatch(const tem_conv_args *a, hipStream_t st, bool dry) {
+int dispatch(const tem_conv_args *a, hipStream_t st, bool dry, char *name, int name_len) {
   const tem_view &i0 = a->in0, &o0 = a->out0;
   const bool cube = a->kd == a->kh && a->kh == a->kw && a->sd == a->sh && a->sh == a->sw && a->pd == a->ph &&
                     a->ph == a->pw;
   if (!cube || a->kd < 3) return TEM_EUNSUPPORTED;
   Dev p{};
-  if (!fits32(i0) || !fits32(o0)) return TEM_EUNSUPPORTED;
+  if (!fits32_sN(i0) || !fits32_sN(o0)) return TEM_EUNSUPPORTED;
   p.in0 = i0.ptr; p.i0N = (int)i0.sN; p.i0D = (int)i0.sD; p.i0H = (int)i0.sH; p.i0W = (int)i0.sW; p.C0 = i0.C;
   p.in1 = i0.ptr; p.i1N = p.i0N; p.i1D = p.i0D; p.i1H = p.i0H; p.i1W = p.i0W;
   int CI = i0.C;
   if (a->in1.ptr) {
     const tem_view &i1 = a->in1;
     if (i1.N != i0.N || i1.D != i0.D || i1.H != i0.H || i1.W != i0.W) return TEM_ESHAPE;
-    if (!fits32(i1)) return TEM_EUNSUPPORTED;
+    if (!fits32_sN(i1)) return TEM_EUNSUPPORTED;
     p.in1 = i1.ptr; p.i1N = (int)i1.sN; p.i1D = (int)i1.sD; p.i1H = (int)i1.sH; p.i1W = (int)i1.sW;
     CI += i1.C;
     if (i0.C % 4 || i1.C % 4) return TEM_EUNSUPPORTED;
@@ -575,7 +565,7 @@ int dispatch(const tem_conv_args *a, hipStream_t st, bool dry) {
   if (a->out1.ptr) {
     const tem_view &o1 = a->out1;
     if (o1.N != o0.N || o1.D != o0.D || o1.H != o0.H || o1.W != o0.W) return TEM_ESHAPE;
-    if (!fits32(o1)) return TEM_EUNSUPPORTED;
+    if (!fits32_sN(o1)) return TEM_EUNSUPPORTED;
     p.out1 = o1.ptr; p.o1N = (int)o1.sN; p.o1D = (int)o1.sD; p.o1H = (int)o1.sH; p.o1W = (int)o1.sW;
     CO += o1.C;
   }
@@ -596,13 +586,13 @@ int dispatch(const tem_conv_args *a, hipStream_t st, bool dry) {
   if (e.gate.ptr) {
     const tem_view &g = e.gate;
     if (g.N != o0.N || g.D != o0.D || g.H != o0.H || g.W != o0.W || g.C < o0.C) return TEM_ESHAPE;
-    if (!fits32(g)) return TEM_EUNSUPPORTED;
+    if (!fits32_sN(g)) return TEM_EUNSUPPORTED;
     q.gate = g.ptr; q.gN = (int)g.sN; q.gD = (int)g.sD; q.gH = (int)g.sH; q.gW = (int)g.sW;
   }
   if (e.add.ptr) {
     const tem_view &ad = e.add;
     if (ad.C < o0.C || ad.N != o0.N) return TEM_ESHAPE;
-    if (!fits32(ad)) return TEM_EUNSUPPORTED;
+    if (!fits32_sN(ad)) return TEM_EUNSUPPORTED;
     q.add = ad.ptr; q.aN = (int)ad.sN; q.aD = (int)ad.sD; q.aH = (int)ad.sH; q.aW = (int)ad.sW;
     q.aoz = e.add_off[0]; q.aoy = e.add_off[1]; q.aox = e.add_off[2];
     q.aDd = ad.D; q.aHh = ad.H; q.aWw = ad.W;
@@ -645,11 +635,9 @@ int dispatch(const tem_conv_args *a, hipStream_t st, bool dry) {
 }  // namespace convlds
 
 // Called by tem_conv (dispatch.hip) before it falls back to the direct kernel.
-int tem_conv_lds_try(const tem_conv_args *a, hipStream_t st, bool dry) { return convlds::dispatch(a, st, dry); }
+int tem_conv_lds_try(const tem_conv_args *a, hipStream_t st, bool dry) { return convlds::dispatch(a, st, dry, nullptr, 0); }
 
 int tem_conv_lds_describe(const tem_conv_args *a, char *buf, int len) {
-  convlds::g_name = buf; convlds::g_name_len = len;
-  int rc = convlds::dispatch(a, nullptr, true);
-  convlds::g_name = nullptr;
+  int rc = convlds::dispatch(a, nullptr, true, buf, len);
   return rc;
 }

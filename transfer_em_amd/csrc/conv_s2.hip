@@ -290,19 +290,9 @@ __global__ __launch_bounds__(CI / 2 * 64) void conv_s2_k(Dev p) {
 }
 
 // ------------------------------------------------------------------------------------------ host
-static uint32_t magic_for(int d) { return (uint32_t)((0x100000000ull + (uint64_t)d - 1) / (uint64_t)d); }
-
-static bool fits32(const tem_view &v) {
-  int64_t span = (int64_t)(v.N - 1) * v.sN + (int64_t)(v.D - 1) * v.sD + (int64_t)(v.H - 1) * v.sH +
-                 (int64_t)(v.W - 1) * v.sW + v.C;
-  return span < ((int64_t)1 << 31);
-}
-
-static thread_local char *g_name = nullptr;
-static thread_local int g_name_len = 0;
 
 template <int CI, int NT, int T, bool TB = false>
-static int run(Dev p, hipStream_t st, bool dry) {
+static int run(Dev p, hipStream_t st, bool dry, char *name, int name_len) {
   constexpr int NWAVE = CI / 2, VPT = TB ? 15 : 16;
   // every geometry check comes BEFORE the dry-run answer: tem_conv_is_tiled / Launch.meta must name the kernel the launch
   // really runs (a 260^3 model's g.d1b has tiles_pp = 1084 and falls through to the generic kernel)
@@ -312,7 +302,7 @@ static int run(Dev p, hipStream_t st, bool dry) {
   const int64_t total = (int64_t)p.oN_count * p.OD * p.tiles_pp;
   if (total > (1 << 22) || p.tiles_pp > 1024 || p.OW > 1024) return TEM_EUNSUPPORTED;    // range of the magic divisions
   if (dry) {
-    if (g_name) snprintf(g_name, g_name_len, "conv_s2_k<%d, %d, %d, %s>", CI, NT, T, TB ? "true" : "false");
+    if (name) snprintf(name, name_len, "conv_s2_k<%d, %d, %d, %s>", CI, NT, T, TB ? "true" : "false");
     return TEM_OK;
   }
   p.total = (int)total;
@@ -337,11 +327,7 @@ static int run(Dev p, hipStream_t st, bool dry) {
   return TEM_OK;
 }
 
-static int64_t span_of(const tem_view &v) {
-  return (int64_t)(v.N - 1) * v.sN + (int64_t)(v.D - 1) * v.sD + (int64_t)(v.H - 1) * v.sH + (int64_t)(v.W - 1) * v.sW + v.C;
-}
-
-static int dispatch(const tem_conv_args *a, hipStream_t st, bool dry) {
+static int dispatch(const tem_conv_args *a, hipStream_t st, bool dry, char *name, int name_len) {
   const tem_view &i0 = a->in0, &o0 = a->out0;
   if (a->in1.ptr || a->out1.ptr || a->w_layout != TEM_W_TAP_CI_CO) return TEM_EUNSUPPORTED;
   if (a->kd != 4 || a->kh != 4 || a->kw != 4 || a->sd != 2 || a->sh != 2 || a->sw != 2) return TEM_EUNSUPPORTED;
@@ -351,7 +337,7 @@ static int dispatch(const tem_conv_args *a, hipStream_t st, bool dry) {
   if (!enabled) return TEM_EUNSUPPORTED;
   if (o0.N != i0.N) return TEM_ESHAPE;
   if (!fits32(i0) || !fits32(o0)) return TEM_EUNSUPPORTED;
-  const int64_t in_span = span_of(i0);
+  const int64_t in_span = view_span(i0);
   if (in_span >= ((int64_t)1 << 29)) return TEM_EUNSUPPORTED;            // byte offsets of the buffer loads stay below 2^31
   auto aligned = [](const tem_view &v) {
     return ((uintptr_t)v.ptr & 15) == 0 && v.sW % 4 == 0 && v.sH % 4 == 0 && v.sD % 4 == 0 && v.sN % 4 == 0;
@@ -365,14 +351,14 @@ static int dispatch(const tem_conv_args *a, hipStream_t st, bool dry) {
   if (e.gate.ptr) {
     const tem_view &g = e.gate;
     if (g.N != o0.N || g.D != o0.D || g.H != o0.H || g.W != o0.W || g.C < o0.C) return TEM_ESHAPE;
-    if (!aligned(g) || span_of(g) >= ((int64_t)1 << 29)) return TEM_EUNSUPPORTED;
-    q.gate = g.ptr; q.gN = (int)g.sN; q.gD = (int)g.sD; q.gH = (int)g.sH; q.gW = (int)g.sW; q.gbytes = (int)(span_of(g) * 4);
+    if (!aligned(g) || view_span(g) >= ((int64_t)1 << 29)) return TEM_EUNSUPPORTED;
+    q.gate = g.ptr; q.gN = (int)g.sN; q.gD = (int)g.sD; q.gH = (int)g.sH; q.gW = (int)g.sW; q.gbytes = (int)(view_span(g) * 4);
   }
   if (e.add.ptr) {
     const tem_view &ad = e.add;
     if (ad.C < o0.C || ad.N != o0.N) return TEM_ESHAPE;
-    if (!aligned(ad) || span_of(ad) >= ((int64_t)1 << 29)) return TEM_EUNSUPPORTED;
-    q.add = ad.ptr; q.aN = (int)ad.sN; q.aD = (int)ad.sD; q.aH = (int)ad.sH; q.aW = (int)ad.sW; q.abytes = (int)(span_of(ad) * 4);
+    if (!aligned(ad) || view_span(ad) >= ((int64_t)1 << 29)) return TEM_EUNSUPPORTED;
+    q.add = ad.ptr; q.aN = (int)ad.sN; q.aD = (int)ad.sD; q.aH = (int)ad.sH; q.aW = (int)ad.sW; q.abytes = (int)(view_span(ad) * 4);
     q.aoz = e.add_off[0]; q.aoy = e.add_off[1]; q.aox = e.add_off[2];
     q.aDd = ad.D; q.aHh = ad.H; q.aWw = ad.W;
   }
@@ -387,22 +373,20 @@ static int dispatch(const tem_conv_args *a, hipStream_t st, bool dry) {
   const int CI = i0.C, CO = o0.C;
   static int tb = -1;
   if (tb < 0) tb = tem_env_int("TEM_S2_TB", 1);
-  if (tb && CI == 8 && CO == 8) return run<8, 1, 4, true>(p, st, dry);           // g.d1b, d.d1b: two-block form
-  if (CI == 8 && (CO == 8 || CO == 16)) return run<8, 1, 2>(p, st, dry);     // 8 -> 8 without the two-block form (fallback); input-gradient of g.u1b
-  if (CI == 16 && CO == 16) return run<16, 1, 2>(p, st, dry);                // g.d2b
-  if (CI == 16 && CO == 32) return run<16, 2, 2>(p, st, dry);                // input-gradient of g.u2b
-  if (CI == 32 && CO == 32) return run<32, 1, 1>(p, st, dry);                // d.d2b, d.d3b (two workgroups per tile: one per 16 output channels)
+  if (tb && CI == 8 && CO == 8) return run<8, 1, 4, true>(p, st, dry, name, name_len);           // g.d1b, d.d1b: two-block form
+  if (CI == 8 && (CO == 8 || CO == 16)) return run<8, 1, 2>(p, st, dry, name, name_len);     // 8 -> 8 without the two-block form (fallback); input-gradient of g.u1b
+  if (CI == 16 && CO == 16) return run<16, 1, 2>(p, st, dry, name, name_len);                // g.d2b
+  if (CI == 16 && CO == 32) return run<16, 2, 2>(p, st, dry, name, name_len);                // input-gradient of g.u2b
+  if (CI == 32 && CO == 32) return run<32, 1, 1>(p, st, dry, name, name_len);                // d.d2b, d.d3b (two workgroups per tile: one per 16 output channels)
   return TEM_EUNSUPPORTED;
 }
 
 }  // namespace convs2
 
 // Called by tem_conv (dispatch.hip) ahead of the LDS-ring kernel.
-int tem_conv_s2_try(const tem_conv_args *a, hipStream_t st, bool dry) { return convs2::dispatch(a, st, dry); }
+int tem_conv_s2_try(const tem_conv_args *a, hipStream_t st, bool dry) { return convs2::dispatch(a, st, dry, nullptr, 0); }
 
 int tem_conv_s2_describe(const tem_conv_args *a, char *buf, int len) {
-  convs2::g_name = buf; convs2::g_name_len = len;
-  int rc = convs2::dispatch(a, nullptr, true);
-  convs2::g_name = nullptr;
+  int rc = convs2::dispatch(a, nullptr, true, buf, len);
   return rc;
 }

@@ -1,13 +1,11 @@
 // elementwise_bf16.hip -- the non-convolution kernels of the bf16 mixed-precision mode (BASELINE config 5): casts,
 // the per-step bf16 kernel copies, losses on bf16 activations (fp32 arithmetic, double loss sums, bf16 gradients),
 // view copies / adds and the bias gradient.  All HBM-streaming or tiny.
-#include "tem_common.h"
+#include "bf16_common.h"
 
 namespace {
 
-typedef unsigned short u16;
-__device__ __forceinline__ float bf2f(u16 h) { return __uint_as_float((uint32_t)h << 16); }
-__device__ __forceinline__ u16 f2bf(float f) { return __builtin_bit_cast(u16, (__bf16)f); }   // round to nearest even
+using namespace tem_bf16;
 
 struct V5h {  // device copy of a tem_view over bf16 elements
   u16 *ptr; int32_t N, D, H, W, C; int64_t sN, sD, sH, sW;

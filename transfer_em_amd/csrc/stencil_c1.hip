@@ -389,19 +389,9 @@ __global__ __launch_bounds__(256) void c1_mfma_k(DevM p, const float *__restrict
 }
 
 // ------------------------------------------------------------------------------------------ host
-static uint32_t magic_for(int d) { return (uint32_t)((0x100000000ull + (uint64_t)d - 1) / (uint64_t)d); }
-
-static bool fits32(const tem_view &v) {
-  int64_t span = (int64_t)(v.N - 1) * v.sN + (int64_t)(v.D - 1) * v.sD + (int64_t)(v.H - 1) * v.sH +
-                 (int64_t)(v.W - 1) * v.sW + v.C;
-  return span < ((int64_t)1 << 31);
-}
-
-static thread_local char *g_name = nullptr;
-static thread_local int g_name_len = 0;
 
 template <int CI, int CO, bool FLIP, int PF>
-int run(Dev p, int N, hipStream_t st, bool dry) {
+int run(Dev p, int N, hipStream_t st, bool dry, char *name, int name_len) {
   constexpr int CIP = CI == 1 ? 1 : CI + 4, CPV = CI == 1 ? 1 : CI / 4;
   // patch shape: maximise useful lanes x (1 / halo over-fetch), subject to the loader's register budget
   double best = -1.0;
@@ -428,7 +418,7 @@ int run(Dev p, int N, hipStream_t st, bool dry) {
   p.magicTX = magic_for(p.TX);
   p.magicCols = magic_for(p.TX + 2);
   if (dry) {
-    if (g_name) snprintf(g_name, g_name_len, "c1_stencil_k<%d, %d, %s, %d>", CI, CO, FLIP ? "true" : "false", PF);
+    if (name) snprintf(name, name_len, "c1_stencil_k<%d, %d, %s, %d>", CI, CO, FLIP ? "true" : "false", PF);
     return TEM_OK;
   }
   static int dbg = -1;
@@ -445,7 +435,7 @@ int run(Dev p, int N, hipStream_t st, bool dry) {
 }
 
 template <int CO, bool FLIP>
-int run_mfma(const Dev &q, int N, hipStream_t st, bool dry) {
+int run_mfma(const Dev &q, int N, hipStream_t st, bool dry, char *name, int name_len) {
   constexpr int NZ = CO == 8 ? 2 : 1, NP = NZ + 2;
   DevM p{};
   if (q.iW != 1 || q.W % 4) return TEM_EUNSUPPORTED;      // 16-byte loads of 4 x-consecutive voxels, never across a row end
@@ -487,7 +477,7 @@ int run_mfma(const Dev &q, int N, hipStream_t st, bool dry) {
   const size_t lds_bytes = (size_t)NP * (p.TY + 2) * p.colsP * 4;
   if (lds_bytes > 64 * 1024) return TEM_EUNSUPPORTED;
   if (dry) {
-    if (g_name) snprintf(g_name, g_name_len, "c1_mfma_k<%d, %s, %d>", CO, FLIP ? "true" : "false", q.gate ? 1 : 0);
+    if (name) snprintf(name, name_len, "c1_mfma_k<%d, %s, %d>", CO, FLIP ? "true" : "false", q.gate ? 1 : 0);
     return TEM_OK;
   }
   const int nblocks = N * p.nty * p.nzg;
@@ -497,7 +487,7 @@ int run_mfma(const Dev &q, int N, hipStream_t st, bool dry) {
   return TEM_OK;
 }
 
-int dispatch(const tem_conv_args *a, hipStream_t st, bool dry) {
+int dispatch(const tem_conv_args *a, hipStream_t st, bool dry, char *name, int name_len) {
   const tem_view &i0 = a->in0, &o0 = a->out0;
   if (a->in1.ptr || a->out1.ptr) return TEM_EUNSUPPORTED;
   if (a->kd != 3 || a->kh != 3 || a->kw != 3 || a->sd != 1 || a->sh != 1 || a->sw != 1) return TEM_EUNSUPPORTED;
@@ -531,15 +521,15 @@ int dispatch(const tem_conv_args *a, hipStream_t st, bool dry) {
   const int N = i0.N;
   { static int dbg = -1; if (dbg < 0) dbg = tem_env_int("TEM_DEBUG_FLAGS", 0); p.dbg = dbg; }
 #define C1_CASE(ci, co, pf) \
-  if (CI == ci && CO == co) return flip ? run<ci, co, true, pf>(p, N, st, dry) : run<ci, co, false, pf>(p, N, st, dry);
+  if (CI == ci && CO == co) return flip ? run<ci, co, true, pf>(p, N, st, dry, name, name_len) : run<ci, co, false, pf>(p, N, st, dry, name, name_len);
   static int use_mfma = -1;
   if (use_mfma < 0) use_mfma = tem_env_int("TEM_C1_MFMA", 1);
   if (use_mfma && CI == 1 && CO == 8) {    // g.c0, d.d1a forward
-    const int rc = flip ? run_mfma<8, true>(p, N, st, dry) : run_mfma<8, false>(p, N, st, dry);
+    const int rc = flip ? run_mfma<8, true>(p, N, st, dry, name, name_len) : run_mfma<8, false>(p, N, st, dry, name, name_len);
     if (rc != TEM_EUNSUPPORTED) return rc;  // (odd row lengths / strided x: the VALU form below)
   }
   if (use_mfma && CI == 1 && CO == 16) {   // input-gradient of g.f2 (gated by f1)
-    const int rc = flip ? run_mfma<16, true>(p, N, st, dry) : run_mfma<16, false>(p, N, st, dry);
+    const int rc = flip ? run_mfma<16, true>(p, N, st, dry, name, name_len) : run_mfma<16, false>(p, N, st, dry, name, name_len);
     if (rc != TEM_EUNSUPPORTED) return rc;
   }
   C1_CASE(1, 8, 3)
@@ -781,12 +771,10 @@ int dispatch_h(const tem_conv_args *a, hipStream_t st, bool dry, char *name, int
 }  // namespace stencil_c1
 
 // Called by tem_conv (dispatch.hip) after the LDS/MFMA-tiled kernel declined.
-int tem_conv_c1_try(const tem_conv_args *a, hipStream_t st, bool dry) { return stencil_c1::dispatch(a, st, dry); }
+int tem_conv_c1_try(const tem_conv_args *a, hipStream_t st, bool dry) { return stencil_c1::dispatch(a, st, dry, nullptr, 0); }
 
 int tem_conv_c1_describe(const tem_conv_args *a, char *buf, int len) {
-  stencil_c1::g_name = buf; stencil_c1::g_name_len = len;
-  int rc = stencil_c1::dispatch(a, nullptr, true);
-  stencil_c1::g_name = nullptr;
+  int rc = stencil_c1::dispatch(a, nullptr, true, buf, len);
   return rc;
 }
 

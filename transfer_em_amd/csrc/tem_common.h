@@ -31,6 +31,30 @@ static inline bool tem_view_ok(const tem_view &v) {
   return v.ptr != nullptr && v.N > 0 && v.D > 0 && v.H > 0 && v.W > 0 && v.C > 0;
 }
 
+// ---------------------------------------------------------------- host helpers of the dispatch functions
+// ceil(2^32 / d): x / d == __umulhi(x, magic) for 0 <= x < 2^31.  d == 1 has no 32-bit magic (2^32 truncates to 0,
+// which is what the plain formula returns as well); the kernels test d == 1 before they use one.
+static inline uint32_t magic_for(int d) { return d <= 1 ? 0u : (uint32_t)((0x100000000ull + (uint64_t)d - 1) / (uint64_t)d); }
+
+static inline int floordiv2(int v) { return v >= 0 ? v / 2 : -((-v + 1) / 2); }
+
+// elements from the first of a view to one past its last
+static inline int64_t view_span(const tem_view &v) {
+  return (int64_t)(v.N - 1) * v.sN + (int64_t)(v.D - 1) * v.sD + (int64_t)(v.H - 1) * v.sH + (int64_t)(v.W - 1) * v.sW + v.C;
+}
+
+// every element offset of the view fits a signed 32-bit index
+static inline bool fits32(const tem_view &v) { return view_span(v) < ((int64_t)1 << 31); }
+// ... and so does the image stride, which a kernel may hold as an int even where N == 1
+static inline bool fits32_sN(const tem_view &v) { return fits32(v) && v.sN < ((int64_t)1 << 31); }
+
+// TEM_DEBUG_FLAGS (knob builds; 0 in the shipped library): 8 prints the launch plan of a tiled kernel, the other bits are
+// per-kernel ablation switches
+static inline int tem_debug_flags() {
+  static const int flags = tem_env_int("TEM_DEBUG_FLAGS", 0);
+  return flags;
+}
+
 // ---------------------------------------------------------------- Philox4x32-10
 // Same stream definition as oracle/tem_oracle.c:orc_dropout_mask.
 struct Philox128 { uint32_t r[4]; };

@@ -467,8 +467,6 @@ __global__ __launch_bounds__(256) void wino_weights_k(const float *theta, float 
 
 // ------------------------------------------------------------------------------------------ host
 constexpr int LDS_MAX = 160 * 1024;
-static thread_local char *g_name = nullptr;
-static thread_local int g_name_len = 0;
 
 template <int CI, int CO, int NI>
 int plan(Dev &p, double *cost, size_t *lds_bytes, int EE) {
@@ -553,7 +551,7 @@ static int launch(const Dev &p, size_t lds_bytes, hipStream_t st) {
 }
 
 template <int CI, int CO, int NI, int EP>
-int run_best(Dev p, hipStream_t st, bool dry) {
+int run_best(Dev p, hipStream_t st, bool dry, char *name, int name_len) {
   // the compiled row pitches: the cheapest plan wins (ties: the narrower pitch)
   static int force = -1;
   if (force < 0) force = tem_env_int("TEM_WINO_EE", 0);
@@ -572,7 +570,7 @@ int run_best(Dev p, hipStream_t st, bool dry) {
   p = best;
   p.magicBX = magic_for(p.BX); p.magicE = magic_for(p.E);
   if (dry) {
-    if (g_name) snprintf(g_name, g_name_len, "wino_conv_k<%d, %d, %d, %d, %d>", CI, CO, NI, EP, p.E);
+    if (name) snprintf(name, name_len, "wino_conv_k<%d, %d, %d, %d, %d>", CI, CO, NI, EP, p.E);
     return TEM_OK;
   }
   const int nblocks = p.N * p.nby * p.nbx * p.zsegs;
@@ -582,12 +580,12 @@ int run_best(Dev p, hipStream_t st, bool dry) {
   return p.E == 9 ? launch<CI, CO, NI, EP, 9>(p, lds_bytes, st) : launch<CI, CO, NI, EP, 17>(p, lds_bytes, st);
 }
 
-int dispatch(const tem_conv_args *a, hipStream_t st, bool dry) {
+int dispatch(const tem_conv_args *a, hipStream_t st, bool dry, char *name, int name_len) {
   const tem_view &i0 = a->in0, &o0 = a->out0;
   const bool cube = a->kd == 3 && a->kh == 3 && a->kw == 3 && a->sd == 1 && a->sh == 1 && a->sw == 1 && a->pd == a->ph &&
                     a->ph == a->pw;
   if (!cube || a->w_layout != TEM_W_WINOGRAD || a->pd < 0) return TEM_EUNSUPPORTED;
-  if (!fits32(i0) || !fits32(o0)) return TEM_EUNSUPPORTED;
+  if (!fits32_sN(i0) || !fits32_sN(o0)) return TEM_EUNSUPPORTED;
   Dev p{};
   p.in0 = i0.ptr; p.i0N = (int)i0.sN; p.i0D = (int)i0.sD; p.i0H = (int)i0.sH; p.i0W = (int)i0.sW; p.C0 = i0.C;
   p.in1 = i0.ptr; p.i1N = p.i0N; p.i1D = p.i0D; p.i1H = p.i0H; p.i1W = p.i0W;
@@ -599,7 +597,7 @@ int dispatch(const tem_conv_args *a, hipStream_t st, bool dry) {
   if (a->in1.ptr) {
     const tem_view &i1 = a->in1;
     if (i1.N != i0.N || i1.D != i0.D || i1.H != i0.H || i1.W != i0.W) return TEM_ESHAPE;
-    if (!fits32(i1) || !aligned(i1)) return TEM_EUNSUPPORTED;
+    if (!fits32_sN(i1) || !aligned(i1)) return TEM_EUNSUPPORTED;
     p.in1 = i1.ptr; p.i1N = (int)i1.sN; p.i1D = (int)i1.sD; p.i1H = (int)i1.sH; p.i1W = (int)i1.sW;
     CI += i1.C;
     if (i0.C % 8) return TEM_EUNSUPPORTED;                 // a sub-image (8 channels) has one source
@@ -618,7 +616,7 @@ int dispatch(const tem_conv_args *a, hipStream_t st, bool dry) {
   if (a->out1.ptr) {
     const tem_view &o1 = a->out1;
     if (o1.N != o0.N || o1.D != o0.D || o1.H != o0.H || o1.W != o0.W) return TEM_ESHAPE;
-    if (!fits32(o1)) return TEM_EUNSUPPORTED;
+    if (!fits32_sN(o1)) return TEM_EUNSUPPORTED;
     p.out1 = o1.ptr; p.o1N = (int)o1.sN; p.o1D = (int)o1.sD; p.o1H = (int)o1.sH; p.o1W = (int)o1.sW;
     CO += o1.C;
   }
@@ -644,7 +642,7 @@ int dispatch(const tem_conv_args *a, hipStream_t st, bool dry) {
   if (e.gate.ptr) {
     const tem_view &g = e.gate;
     if (g.N != o0.N || g.D != o0.D || g.H != o0.H || g.W != o0.W || g.C < o0.C) return TEM_ESHAPE;
-    if (!fits32(g) || e.slope != 1.f) return TEM_EUNSUPPORTED;
+    if (!fits32_sN(g) || e.slope != 1.f) return TEM_EUNSUPPORTED;
     q.gate = g.ptr; q.gN = (int)g.sN; q.gD = (int)g.sD; q.gH = (int)g.sH; q.gW = (int)g.sW;
     const int64_t gspan = (int64_t)(g.D - 1) * g.sD + (int64_t)(g.H - 1) * g.sH + (int64_t)(g.W - 1) * g.sW + g.C;
     if (gspan >= ((int64_t)1 << 29)) return TEM_EUNSUPPORTED;            // byte offsets below 2^31
@@ -664,7 +662,7 @@ int dispatch(const tem_conv_args *a, hipStream_t st, bool dry) {
     q.mbytes = (int)(((int64_t)o0.N * q.dD * q.dH * q.dW * o0.C + 7) / 8);
     EP = 2;
   }
-#define WINO_CASE(ci, co, ni, epi) if (CI == ci && CO == co && EP == epi) return run_best<ci, co, ni, epi>(p, st, dry);
+#define WINO_CASE(ci, co, ni, epi) if (CI == ci && CO == co && EP == epi) return run_best<ci, co, ni, epi>(p, st, dry, name, name_len);
   WINO_CASE(16, 16, 2, 0) WINO_CASE(16, 16, 2, 1) WINO_CASE(16, 16, 2, 2)
   WINO_CASE(8, 8, 3, 0) WINO_CASE(8, 8, 3, 1)
   WINO_CASE(8, 16, 2, 0) WINO_CASE(8, 16, 2, 1)
@@ -678,12 +676,10 @@ int dispatch(const tem_conv_args *a, hipStream_t st, bool dry) {
 
 }  // namespace wino
 
-int tem_conv_wino_try(const tem_conv_args *a, hipStream_t st, bool dry) { return wino::dispatch(a, st, dry); }
+int tem_conv_wino_try(const tem_conv_args *a, hipStream_t st, bool dry) { return wino::dispatch(a, st, dry, nullptr, 0); }
 
 int tem_conv_wino_describe(const tem_conv_args *a, char *buf, int len) {
-  wino::g_name = buf; wino::g_name_len = len;
-  int rc = wino::dispatch(a, nullptr, true);
-  wino::g_name = nullptr;
+  int rc = wino::dispatch(a, nullptr, true, buf, len);
   return rc;
 }
 

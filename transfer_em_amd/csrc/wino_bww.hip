@@ -458,7 +458,7 @@ static int run_bww(const tem_bww_args *a, hipStream_t st, int mode, int *nslab, 
   const bool cube = a->kd == 3 && a->kh == 3 && a->kw == 3 && a->sd == 1 && a->sh == 1 && a->sw == 1 && a->pd == a->ph &&
                     a->ph == a->pw && a->pd >= 0;
   if (!cube || i0.D < 2) return TEM_EUNSUPPORTED;
-  if (!fits32(i0) || !fits32(dy)) return TEM_EUNSUPPORTED;
+  if (!fits32_sN(i0) || !fits32_sN(dy)) return TEM_EUNSUPPORTED;
   BDev p{};
   p.in0 = i0.ptr; p.i0N = (int)i0.sN; p.i0D = (int)i0.sD; p.i0H = (int)i0.sH; p.i0W = (int)i0.sW; p.C0 = i0.C;
   p.in1 = i0.ptr; p.i1N = p.i0N; p.i1D = p.i0D; p.i1H = p.i0H; p.i1W = p.i0W;
@@ -470,7 +470,7 @@ static int run_bww(const tem_bww_args *a, hipStream_t st, int mode, int *nslab, 
   if (a->in1.ptr) {
     const tem_view &i1 = a->in1;
     if (i1.N != i0.N || i1.D != i0.D || i1.H != i0.H || i1.W != i0.W) return TEM_ESHAPE;
-    if (!fits32(i1) || !aligned(i1) || i0.C % 8) return TEM_EUNSUPPORTED;
+    if (!fits32_sN(i1) || !aligned(i1) || i0.C % 8) return TEM_EUNSUPPORTED;
     p.in1 = i1.ptr; p.i1N = (int)i1.sN; p.i1D = (int)i1.sD; p.i1H = (int)i1.sH; p.i1W = (int)i1.sW;
     CI += i1.C;
   }

@@ -74,12 +74,4 @@ __device__ __forceinline__ void dma_subimage(const float *base, int span, const 
   }
 }
 
-static uint32_t magic_for(int d) { return d <= 1 ? 0u : (uint32_t)((0x100000000ull + (uint64_t)d - 1) / (uint64_t)d); }
-
-static bool fits32(const tem_view &v) {
-  int64_t span = (int64_t)(v.N - 1) * v.sN + (int64_t)(v.D - 1) * v.sD + (int64_t)(v.H - 1) * v.sH +
-                 (int64_t)(v.W - 1) * v.sW + v.C;
-  return span < (int64_t)1 << 31 && v.sN < ((int64_t)1 << 31);
-}
-
 }  // namespace wino
