@@ -48,10 +48,19 @@ def conv_bwd_weight(x, dout, kshape, stride=1, pad=0):
     return np.ascontiguousarray(gw.numpy().transpose(2, 3, 4, 1, 0))
 
 
-def convT_fwd(x, w, stride=2, pad=1):
-    """Keras Conv3DTranspose(k, strides=2, padding='same') for k = 4: o = 2 j + t - 1; w is (kd,kh,kw,CO,CI)."""
+def convT_fwd(x, w, stride=2, pad=1, out_dims=None):
+    """Keras Conv3DTranspose(k, strides=2, padding='same') for k = 4: o = 2 j + t - 1; w is (kd,kh,kw,CO,CI).
+    out_dims (ops.convT_fwd): the output is the window [pad, pad + out_dims) of the un-padded (n - 1) s + k rows, zero
+    past their end; the default is the natural extent (n - 1) s + k - 2 pad."""
     wt = torch.from_numpy(np.ascontiguousarray(np.asarray(w).transpose(4, 3, 0, 1, 2))).double()    # (CI,CO,k,k,k)
-    return _out(F.conv_transpose3d(_in(x), wt, stride=_3(stride), padding=_3(pad)))
+    if out_dims is None:
+        return _out(F.conv_transpose3d(_in(x), wt, stride=_3(stride), padding=_3(pad)))
+    y = F.conv_transpose3d(_in(x), wt, stride=_3(stride))
+    p, od = _3(pad), tuple(int(d) for d in out_dims)
+    win = y[:, :, p[0]:p[0] + od[0], p[1]:p[1] + od[1], p[2]:p[2] + od[2]]
+    full = torch.zeros(tuple(y.shape[:2]) + od, dtype=y.dtype)
+    full[:, :, :win.shape[2], :win.shape[3], :win.shape[4]] = win
+    return _out(full)
 
 
 def convT_bwd_data(dout, w, in_shape, stride=2, pad=1):
@@ -60,6 +69,20 @@ def convT_bwd_data(dout, w, in_shape, stride=2, pad=1):
     y = F.conv3d(_in(dout), wt, stride=_3(stride), padding=_3(pad))
     assert tuple(y.shape[2:]) == tuple(in_shape[1:4]), (y.shape, in_shape)
     return _out(y)
+
+
+def convT_bwd_weight(x, dout, kshape, stride=2, pad=1):
+    """Kernel gradient of convT_fwd -> (kd,kh,kw,CO,CI) float64: the strided convolution dout -> x that is convT_fwd's
+    adjoint has the kernel (out = CI, in = CO), so its Conv3DBackpropFilter with the roles of x and dout swapped."""
+    xi, g = _in(x), _in(dout)
+    wshape = (xi.shape[1], g.shape[1]) + tuple(int(k) for k in kshape)
+    gw = torch.nn.grad.conv3d_weight(g, wshape, xi, stride=_3(stride), padding=_3(pad))
+    return np.ascontiguousarray(gw.numpy().transpose(2, 3, 4, 1, 0))
+
+
+def channel_sum(g):
+    """Bias gradient: sum over batch and voxels per channel, float64 (C,)."""
+    return np.asarray(g, np.float64).reshape(-1, np.asarray(g).shape[-1]).sum(0)
 
 
 def leaky_relu(x, alpha=0.3):

@@ -288,20 +288,20 @@ def test_generator_inference_bf16_2d(oracle_lib):
     assert 1e-4 < _l2(y, y32) < 3e-2
 
 
-def test_train_step_bf16_2d_matches_oracle(tmp_path, oracle_lib):
-    """EM2EM(74, is3d=False, precision='bf16').train_step at batch 2 against the oracle's bf16 storage mode with the HIP
+def _step_bf16_2d_matches_oracle(tmp_path, n, batch):
+    """EM2EM(n, is3d=False, precision='bf16').train_step at `batch` against the oracle's bf16 storage mode with the HIP
     forward's LeakyReLU branches (util.hip_gates): the thresholds of test_train_step_bf16_matches_oracle."""
     from oracle import graph
     from transfer_em_amd.cgan import EM2EM
     from test_gpu_step import _load, _state
     from util import activation_stats, hip_gates
-    n, shape = 74, (2, 1, 74, 74, 1)
+    shape = (batch, 1, n, n, 1)
     rx, ry = _inputs(shape, 1234), _inputs(shape, 5678)
     st = _state(graph, False, True)
     model = EM2EM(n, "bf16_2d", is3d=False, seed=42, checkpoint_root=str(tmp_path), precision="bf16")
     _load(model, st)
     got = model.train_step(torch.from_numpy(rx), torch.from_numpy(ry)).cpu().numpy()
-    cs = model._steps[2]
+    cs = model._steps[batch]
     grads_hip = {k: net.params.to_dict("grad") for k, net in zip(("g", "f", "dx", "dy"), model._nets)}
     with graph.precision("bf16"):
         losses, grads, aux = graph.train_step(st, rx, ry, False, 2.0, 42, gates=hip_gates(cs, False))
@@ -335,6 +335,16 @@ def test_train_step_bf16_2d_matches_oracle(tmp_path, oracle_lib):
             if l.meta.get("kernel", "").startswith(("conv", "bww"))}
     assert all(k.startswith(("conv2d_bf16_k", "convT2d_bf16_k", "bww2d_bf16_k")) or
                re.match(r"(conv|bww)_bf16_k<\d+, \d+, 1, 1,", k) for k in kern), kern
+
+
+def test_train_step_bf16_2d_matches_oracle(tmp_path, oracle_lib):
+    _step_bf16_2d_matches_oracle(tmp_path, 74, 2)
+
+
+def test_train_step_bf16_2d_notebook_config_matches_oracle(tmp_path, oracle_lib):
+    """The reference's training example at its own size, 132^2 batch 64, with every assertion and bar of the 74^2
+    instance: the only check of the bf16 step's gradients, moments and activations at the configuration users run."""
+    _step_bf16_2d_matches_oracle(tmp_path, 132, 64)
 
 
 def test_train_step_bf16_2d_notebook_config(tmp_path):

@@ -36,17 +36,29 @@ def _state(graph, is3d, scaled):
     return st
 
 
-@pytest.mark.parametrize("is3d,batch,scaled", [(False, 2, True), (False, 1, False), (True, 1, True)])
-def test_train_step_matches_oracle(tmp_path, oracle_lib, is3d, batch, scaled):
+def _pole_margin(aux, rx, ry, b, crop_by):
+    """Smallest 1 - |a - b| / 2 over the pixels of the four cycle / identity terms, from the oracle's own outputs: the
+    loss -log(1 - |a - b| / 2) has a pole there, and its gradient moves by delta / (2 margin) of itself when an output
+    moves by delta (conditioning note)."""
+    worst = np.inf
+    for key, real in (("same_x", rx), ("same_y", ry), ("cyc_x", rx), ("cyc_y", ry)):
+        a, o = (crop_by(real, 2 * b), crop_by(aux[key], b)) if key.startswith("cyc") else (crop_by(real, b), aux[key])
+        worst = min(worst, float((1.0 - np.abs(a.astype(np.float64) - o) / 2).min()))
+    return worst
+
+
+def _step_matches_oracle(tmp_path, n, batch, is3d, scaled, amplitude=1.0, gtol_net=None):
+    """Two fp32 train steps of EM2EM(n) at `batch` against the oracle: losses, generator outputs, saved activations,
+    every gradient, the Adam moments and the parameters.  amplitude scales the two input images; gtol_net = {network:
+    (bar of step 0, bar of step 1)} replaces the gradient / moment bar of single networks (never below the common one)."""
     from oracle import graph
     from transfer_em_amd.cgan import EM2EM
-    n = 74
     shape = (batch, n if is3d else 1, n, n, 1)
-    rx, ry = _inputs(shape, 1234), _inputs(shape, 5678)
+    rx, ry = np.float32(amplitude) * _inputs(shape, 1234), np.float32(amplitude) * _inputs(shape, 5678)
     st = _state(graph, is3d, scaled)
     model = EM2EM(n, "parity", is3d=is3d, seed=42, checkpoint_root=str(tmp_path))
     _load(model, st)
-    assert model.outdimsize == 40 and model.buffer == 17            # generator.py:20, cgan.py:65
+    assert (model.outdimsize, model.buffer) == {74: (40, 17), 132: (96, 18)}[n]     # generator.py:20, cgan.py:65
 
     for step in range(2):                                           # 2 steps: Adam t=1,2 and dropout step 0,1
         _load(model, st)          # every step starts from the oracle's exact state (no drift amplification)
@@ -60,6 +72,11 @@ def test_train_step_matches_oracle(tmp_path, oracle_lib, is3d, batch, scaled):
         assert rel_err(got, losses) < 1e-5, (got, losses)
         b = model.buffer
         crop = (lambda t: t[:, b:-b, b:-b, b:-b, :]) if is3d else (lambda t: t[:, :, b:-b, b:-b, :])
+        crop_by = (lambda t, c: t[:, c:-c, c:-c, c:-c, :]) if is3d else (lambda t, c: t[:, :, c:-c, c:-c, :])
+        margin = _pole_margin(aux, rx, ry, b, crop_by)
+        print(f"step {step}: smallest 1 - |a - b| / 2 of the cycle / identity terms (oracle): {margin:.3g}")
+        if amplitude != 1.0:
+            assert margin >= 0.05, margin             # the instance claims to be well conditioned: hold it to that
         for key, plan in (("fake_y", "g1"), ("cyc_x", "f2"), ("fake_x", "f1"), ("cyc_y", "g2"), ("same_x", "f3"),
                           ("same_y", "g3")):
             ref = crop(aux[key]) if key.startswith("cyc") else aux[key]      # cycled_*: only the cropped window exists
@@ -71,18 +88,21 @@ def test_train_step_matches_oracle(tmp_path, oracle_lib, is3d, batch, scaled):
         print(f"step {step}: {flips} gate flips of {total} activations (aligned), worst activation error {worst:.1e} at "
               f"{where}, gradient tolerance {gtol:g}")
         assert rel_err(cs.bwd["f2"].dx.cpu().numpy(), aux["d_fake_y"]) < gtol
+        tol_of = {net: max(gtol, (gtol_net or {}).get(net, (0.0, 0.0))[step]) for net in ("g", "f", "dx", "dy")}
         for net in ("g", "f", "dx", "dy"):
+            worst_g = max(np.abs(grads_hip[net][name] - ref).max() / np.abs(ref).max() for name, ref in grads[net].items())
+            print(f"step {step}: network {net}: worst gradient error {worst_g:.2e} of a layer's largest entry, bar {tol_of[net]:g}")
             for name, ref in grads[net].items():
                 scale = max(np.abs(v).max() for v in grads[net].values())
                 err = np.abs(grads_hip[net][name] - ref).max()
                 # the bias gradient is a sum of logit gradients of both signs: absolute floor from fp32 dz
                 floor = 1e-7 * scale + (3e-8 if name.endswith("_bias") else 0.0)
-                assert err <= gtol * np.abs(ref).max() + floor, (step, net, name, err, np.abs(ref).max())
+                assert err <= tol_of[net] * np.abs(ref).max() + floor, (step, net, name, err, np.abs(ref).max())
         for net, obj in zip(("g", "f", "dx", "dy"), model._nets):
             # Adam moments are linear / quadratic in g: tight relative check.  theta moves by ~lr per
             # step whatever |g| is (m/sqrt(v)), which amplifies relative gradient error where |g| ~ eps:
             # compare the parameters in units of lr.
-            for which, tol in (("m", gtol), ("v", 2 * gtol)):
+            for which, tol in (("m", tol_of[net]), ("v", 2 * tol_of[net])):
                 got_s = obj.params.to_dict(which)
                 for name, ref in st[which][net].items():
                     scale = max(np.abs(v).max() for v in st[which][net].values())
@@ -98,6 +118,43 @@ def test_train_step_matches_oracle(tmp_path, oracle_lib, is3d, batch, scaled):
                 big = gref >= 1e-2 * gref.max()
                 assert np.abs(th[name] - st[net][name])[big].max() < 0.15 * 2e-4, (step, net, name)
                 assert np.abs(th[name] - st[net][name]).max() <= 2.05 * 2e-4, (step, net, name)
+
+
+@pytest.mark.parametrize("is3d,batch,scaled", [(False, 2, True), (False, 1, False), (True, 1, True)])
+def test_train_step_matches_oracle(tmp_path, oracle_lib, is3d, batch, scaled):
+    _step_matches_oracle(tmp_path, 74, batch, is3d, scaled)
+
+
+# Gradient / moment bar of generator_f at 2-D 132^2, batch 64, steps 0 and 1: 4 x the error of the SAME step computed in
+# float32 by PyTorch on the CPU (oracle/torch_ref.py, dtype=float32, LeakyReLU branches taken from its float64 run)
+# against its float64 run -- the reference alone, no HIP code involved.  Measured, as the largest error of a layer over
+# the layer's largest entry: generator_f 1.01e-3 at step 0 and 9.4e-5 at step 1 (each of its twelve layers 3.3e-4 ..
+# 1.0e-3 at step 0), generator_g 4.5e-6 / 3.5e-6, the discriminators <= 2.8e-6, the four generator outputs <= 9.1e-7.
+# Reason: the identity term -log(1 - |x - F(x)| / 2) has a pole at |x - F(x)| = 2.  With the test weights F(x) reaches
+# 1.2 at this size and the oracle's own 1 - |a - b| / 2 runs through zero (where Keras clips) over the 590 k pixels of
+# the term; a pixel with margin t carries ~ 1 / t of the typical gradient and moves by delta / (2 t) of itself when
+# F(x) moves by delta, so float32's 1e-6 on the outputs becomes 1e-4 .. 1e-3 on the few pixels that dominate every
+# kernel gradient of the network, in any float32 implementation (conditioning note).  The 74^2 instances,
+# 3200 pixels per term, stay clear of it.  The HIP step measures 4.6e-4 at step 0 (2.1e-4 .. 4.6e-4 over the layers,
+# one common factor: the gradient entering the network, not a kernel of it).  Every other bar of the instance, and
+# generator_g's and the discriminators' gradient bar -- the same kernels and tile plans -- stay those of 74^2.
+GTOL_F_NOTEBOOK = (4 * 1.01e-3, 4 * 9.4e-5)
+
+
+def test_train_step_2d_notebook_config_matches_oracle(tmp_path, oracle_lib):
+    """The reference's training example at its own size -- 2-D 132^2, batch 64, fp32 -- with every assertion of the 74^2
+    instances: the fp32 step that test_train_step_bf16_2d_notebook_config measures the bf16 step against.  Bars as at
+    74^2 except generator_f's gradients and moments (GTOL_F_NOTEBOOK: the float32 CPU reference itself is 1e-3 from the
+    float64 one there); test_train_step_2d_notebook_config_matches_oracle_away_from_the_pole holds generator_f to the
+    74^2 bar on the same configuration."""
+    _step_matches_oracle(tmp_path, 132, 64, False, True, gtol_net={"f": GTOL_F_NOTEBOOK})
+
+
+def test_train_step_2d_notebook_config_matches_oracle_away_from_the_pole(tmp_path, oracle_lib):
+    """132^2, batch 64, fp32 with the two images at half amplitude: the oracle's own outputs keep every pixel of the
+    cycle / identity terms at 1 - |a - b| / 2 >= 0.05 (asserted), so an output error delta moves no gradient entry by
+    more than 10 delta of itself and the 74^2 bars apply to every network."""
+    _step_matches_oracle(tmp_path, 132, 64, False, True, amplitude=0.5)
 
 
 def test_train_step_3d_batch2_one_step(tmp_path, oracle_lib):

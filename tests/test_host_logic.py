@@ -199,3 +199,19 @@ def test_bench_extras_need_full():
         p = subprocess.run([sys.executable, bench, "--steps", "1", "--warmup", "0"] + extra,
                            stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120)
         assert p.returncode == 2 and "part of --full" in p.stderr, p.stderr[-2000:]
+
+
+def test_xcd_contiguous_block_is_a_permutation():
+    """tem_common.h's xcd_contiguous_block(b, nb) -- workgroup b runs on XCD b % 8; give each XCD a contiguous range of
+    the logical blocks: q = nb / 8, r = nb % 8, k = b % 8 -> k q + min(k, r) + b / 8 -- restated here: for every grid
+    size it must hit every logical block exactly once (a repeated block would compute one patch twice and leave another
+    unwritten), and XCD k's blocks must be consecutive."""
+    def xcd(b, nb):
+        q, r, k = nb >> 3, nb & 7, b & 7
+        return k * q + min(k, r) + (b >> 3)
+    for nb in range(1, 4097):
+        got = [xcd(b, nb) for b in range(nb)]
+        assert sorted(got) == list(range(nb)), nb
+        for k in range(min(8, nb)):
+            mine = got[k::8]
+            assert mine == list(range(mine[0], mine[0] + len(mine))), (nb, k)

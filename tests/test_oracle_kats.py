@@ -245,3 +245,48 @@ def test_torch_ops_agree_with_c_oracle(oracle_lib):
     assert y.shape == (1, 10, 12, 14, 3) and close(oracle_lib.convT_fwd(x, w), y)
     g = r(*y.shape)
     assert close(oracle_lib.convT_bwd_data(g, w, x.shape), T.convT_bwd_data(g, w, x.shape))
+
+
+def test_torch_ops_2d_and_transposed_extensions_agree_with_c_oracle(oracle_lib):
+    """The forms the full-size bf16 / 2-D tests add to oracle/torch_ops.py, against oracle/ops.py: per-axis stride and
+    padding tuples on depth-1 (2-D) tensors with batch > 1, convT_fwd's out_dims (natural, larger, smaller),
+    convT_bwd_weight in 3-D and 2-D, bias, and channel_sum against a plain float64 loop."""
+    from oracle import torch_ops as T
+    rng = np.random.default_rng(1)
+    r = lambda *s: rng.standard_normal(s).astype(np.float32)
+    close = lambda a, b: np.shape(a) == np.shape(b) and np.abs(np.asarray(a, np.float64) - b).max() <= 2e-6 * np.abs(b).max()
+    x, w, b = r(3, 1, 11, 13, 5), r(1, 3, 3, 5, 7), r(7)
+    for pad in ((0, 0, 0), (0, 2, 2)):
+        y = T.conv_fwd(x, w, (1, 1, 1), pad, b)
+        assert close(oracle_lib.conv_fwd(x, w, (1, 1, 1), pad, b), y)
+        g = r(*y.shape)
+        assert close(oracle_lib.conv_bwd_data(g, w, x.shape, (1, 1, 1), pad), T.conv_bwd_data(g, w, x.shape, (1, 1, 1), pad))
+        assert close(oracle_lib.conv_bwd_weight(x, g, (1, 3, 3), (1, 1, 1), pad), T.conv_bwd_weight(x, g, (1, 3, 3), (1, 1, 1), pad))
+    x, w = r(2, 1, 13, 12, 4), r(1, 4, 4, 4, 6)              # k4 s2: VALID with an odd edge, and pad 1
+    for pad in ((0, 0, 0), (0, 1, 1)):
+        y = T.conv_fwd(x, w, (1, 2, 2), pad)
+        g = r(*y.shape)
+        assert close(oracle_lib.conv_fwd(x, w, (1, 2, 2), pad), y)
+        assert close(oracle_lib.conv_bwd_data(g, w, x.shape, (1, 2, 2), pad), T.conv_bwd_data(g, w, x.shape, (1, 2, 2), pad))
+        assert close(oracle_lib.conv_bwd_weight(x, g, (1, 4, 4), (1, 2, 2), pad), T.conv_bwd_weight(x, g, (1, 4, 4), (1, 2, 2), pad))
+    x, w = r(2, 1, 6, 7, 6), r(1, 4, 4, 3, 6)                # 2-D transposed convolution, kernel (1,k,k,CO,CI)
+    for pad in (0, 1):
+        nat = (1, 2 * 6 + 2 - 2 * pad, 2 * 7 + 2 - 2 * pad)
+        for od in (None, nat, (1, nat[1] + 1, nat[2] + 2), (1, nat[1] - 1, nat[2] - 3)):
+            y = T.convT_fwd(x, w, (1, 2, 2), (0, pad, pad), out_dims=od)
+            assert y.shape[1:4] == (od or nat)
+            assert close(oracle_lib.convT_fwd(x, w, (1, 2, 2), (0, pad, pad), out_dims=od), y)
+        g = r(2, *nat, 3)
+        assert close(oracle_lib.convT_bwd_data(g, w, x.shape, (1, 2, 2), (0, pad, pad)), T.convT_bwd_data(g, w, x.shape, (1, 2, 2), (0, pad, pad)))
+        assert close(oracle_lib.convT_bwd_weight(x, g, (1, 4, 4), (1, 2, 2), (0, pad, pad)),
+                     T.convT_bwd_weight(x, g, (1, 4, 4), (1, 2, 2), (0, pad, pad)))
+    x, w = r(2, 4, 5, 6, 6), r(4, 4, 4, 3, 6)                # 3-D Conv3DTranspose kernel gradient and out_dims
+    y = T.convT_fwd(x, w, 2, 1, out_dims=(8, 10, 12))
+    assert close(oracle_lib.convT_fwd(x, w, 2, 1, out_dims=(8, 10, 12)), y)
+    g = r(*y.shape)
+    assert close(oracle_lib.convT_bwd_weight(x, g, (4, 4, 4), 2, 1), T.convT_bwd_weight(x, g, (4, 4, 4), 2, 1))
+    g = r(2, 3, 4, 5, 8)
+    ref = np.zeros(8)
+    for v in g.reshape(-1, 8):
+        ref += v.astype(np.float64)
+    assert np.allclose(T.channel_sum(g), ref, rtol=1e-13, atol=0) and T.channel_sum(g).dtype == np.float64
