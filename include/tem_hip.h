@@ -284,6 +284,26 @@ int tem_f32_tiles_unstd_to_u8(const float *y, int32_t ntile, int32_t yedge, int3
 int tem_u8_tiles2d_to_f32_std(const uint8_t *vol, int32_t Z, int32_t Y, int32_t X, const int32_t *origins_dev,
                               int32_t ntile, int32_t edge, float *out, float mean, float std, tem_stream_t stream);
 
+/* Tiled inference with a boundary mode at the volume's faces.  tem_u8_tiles_to_f32_std / tem_u8_tiles2d_to_f32_std
+ * read a voxel outside the volume as 0; these read, on every axis, index fold(i, n) of an axis of extent n:
+ *   TEM_BOUNDARY_EDGE      clamp(i, 0, n-1)
+ *   TEM_BOUNDARY_REFLECT   n == 1: 0; else m = 2(n-1), r = i mod m (non-negative), r < n ? r : m - r
+ * (numpy.pad's "edge" and "reflect" for any pad width).  The volume has extents (Z, Y, X); `blk`[BZ][BY][BX] holds
+ * its box at (lz, ly, lx), which must lie inside it (the resident form: blk = the volume, l = 0).  Tile t is the
+ * window at block-relative origin (z,y,x) = origins_dev[3t..3t+2]: its voxel p has volume coordinate l + origin + p
+ * (|l + origin| + edge must stay below 2^31), is folded against (Z, Y, X) and reads blk[folded - l], converted as
+ * tem_u8_to_f32_std.  A folded coordinate outside the block reads 0 and touches no memory.  A tile wholly inside the
+ * volume takes the path of the zero-mode kernels.  The 2-D form folds its section too.  edge <= 46340.
+ * TEM_EINVAL, without a launch: another mode, a zero extent, a block outside the volume. */
+#define TEM_BOUNDARY_REFLECT 1
+#define TEM_BOUNDARY_EDGE 2
+int tem_u8_tiles_to_f32_std_bc(const uint8_t *blk, int32_t BZ, int32_t BY, int32_t BX, int32_t lz, int32_t ly,
+                               int32_t lx, int32_t Z, int32_t Y, int32_t X, int32_t mode, const int32_t *origins_dev,
+                               int32_t ntile, int32_t edge, float *out, float mean, float std, tem_stream_t stream);
+int tem_u8_tiles2d_to_f32_std_bc(const uint8_t *blk, int32_t BZ, int32_t BY, int32_t BX, int32_t lz, int32_t ly,
+                                 int32_t lx, int32_t Z, int32_t Y, int32_t X, int32_t mode, const int32_t *origins_dev,
+                                 int32_t ntile, int32_t edge, float *out, float mean, float std, tem_stream_t stream);
+
 /* Tiled inference of the 2-D networks, output side: the interior of tile t of y[ntile][yedge][yedge] (`tpad` pixels
  * stripped per side) is converted as tem_f32_unstd_to_u8 and written into section z of the uint8 volume
  * out[OZ][OY][OX] at (z,y,x) = index_dev[3t..3t+2].  Pixels that fall outside `out` are dropped.  Any ntile. */

@@ -16,6 +16,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libtem_hip.so")
 
 TEM_OK, TEM_EINVAL, TEM_EUNSUPPORTED, TEM_ESHAPE = 0, -1, -2, -3
 TEM_W_TAP_CI_CO, TEM_W_FLIP_CO_CI, TEM_W_WINOGRAD = 0, 1, 2
+TEM_BOUNDARY_REFLECT, TEM_BOUNDARY_EDGE = 1, 2
 _ERR = {TEM_EINVAL: "TEM_EINVAL (malformed descriptor)",
         TEM_EUNSUPPORTED: "TEM_EUNSUPPORTED (geometry outside the compiled set)",
         TEM_ESHAPE: "TEM_ESHAPE (inconsistent tensor extents)"}
@@ -124,6 +125,10 @@ _SIGS = {
                                   C.c_int32, C.c_float, C.c_float, C.c_void_p],
     "tem_u8_tiles2d_to_f32_std": [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
                                   C.c_void_p, C.c_float, C.c_float, C.c_void_p],
+    "tem_u8_tiles_to_f32_std_bc": [C.c_void_p] + [C.c_int32] * 10 + [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                                                      C.c_float, C.c_float, C.c_void_p],
+    "tem_u8_tiles2d_to_f32_std_bc": [C.c_void_p] + [C.c_int32] * 10 + [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                                                        C.c_float, C.c_float, C.c_void_p],
     "tem_f32_tiles2d_unstd_to_u8": [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                                     C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p],
     "tem_augment_f32": [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,

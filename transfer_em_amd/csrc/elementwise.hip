@@ -278,6 +278,62 @@ __global__ __launch_bounds__(256) void u8_tiles_to_f32_std_k(const uint8_t *vol,
   }
 }
 
+// Index that coordinate i of an axis of extent n >= 1 reads under a boundary mode: clamp (edge) or mirror without
+// repeating the face voxel (reflect, period 2(n-1): numpy.pad's modes for any pad width, extent 1 included).  reflect is
+// even in i, so one bounce costs no division; only a coordinate further than n-1 past a face pays the modulo.
+template <int MODE>
+__device__ __forceinline__ int bc_fold(int i, int n) {
+  if constexpr (MODE == TEM_BOUNDARY_EDGE) {
+    return min(max(i, 0), n - 1);
+  } else {
+    if (n == 1) return 0;
+    const int m = 2 * (n - 1);
+    i = i < 0 ? -i : i;
+    if (i >= m) i %= m;
+    return i < n ? i : m - i;
+  }
+}
+
+// gather with a boundary mode: as u8_tiles_to_f32_std_k on the staging block blk[BZ][BY][BX] that holds the volume's
+// box at (lz, ly, lx); a voxel outside the volume [0,Z)x[0,Y)x[0,X) reads the volume voxel bc_fold names.  A folded
+// coordinate outside the block reads 0 (the planner's footprint hull holds them all; the predicate keeps a wrong plan
+// from reading outside blk).  A tile inside the volume (uniform per workgroup) runs the plain loop; a face tile goes
+// row by row, one wave per row, so that z and y are folded once per row (in scalar registers) and only x per voxel.
+template <int MODE>
+__global__ __launch_bounds__(256) void u8_tiles_to_f32_std_bc_k(const uint8_t *blk, int BZ, int BY, int BX, int lz, int ly,
+                                                                int lx, int Z, int Y, int X, const int32_t *origins,
+                                                                int edge, float *out, float mean, float std,
+                                                                int64_t per_tile) {
+  const int t = blockIdx.y;
+  const int oz = origins[3 * t], oy = origins[3 * t + 1], ox = origins[3 * t + 2];
+  const int vz = lz + oz, vy = ly + oy, vx = lx + ox;                  // the tile's origin in volume coordinates
+  float *o = out + (int64_t)t * per_tile;
+  if (vz >= 0 && vz + edge <= Z && vy >= 0 && vy + edge <= Y && vx >= 0 && vx + edge <= X) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < per_tile; i += (int64_t)gridDim.x * 256) {
+      const int x = (int)(i % edge); const int64_t r = i / edge;
+      const int y = (int)(r % edge), z = (int)(r / edge);
+      const int gz = oz + z, gy = oy + y, gx = ox + x;
+      const bool in = (unsigned)gz < (unsigned)BZ && (unsigned)gy < (unsigned)BY && (unsigned)gx < (unsigned)BX;
+      o[i] = u8_std(in ? (float)blk[((int64_t)gz * BY + gy) * BX + gx] : 0.f, mean, std);
+    }
+    return;
+  }
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+  const int rows = edge * edge;                                        // edge <= 46340 (entry point)
+  for (int r = (int)blockIdx.x * 4 + wave; r < rows; r += (int)gridDim.x * 4) {
+    const int z = r / edge, y = r - z * edge;
+    const int bz = bc_fold<MODE>(vz + z, Z) - lz, by = bc_fold<MODE>(vy + y, Y) - ly;
+    const bool rin = (unsigned)bz < (unsigned)BZ && (unsigned)by < (unsigned)BY;
+    const uint8_t *row = blk + (rin ? ((int64_t)bz * BY + by) * BX : 0);
+    float *orow = o + (int64_t)r * edge;
+    for (int x = lane; x < edge; x += 64) {
+      const int bx = bc_fold<MODE>(vx + x, X) - lx;
+      const bool in = rin && (unsigned)bx < (unsigned)BX;
+      orow[x] = u8_std(in ? (float)row[bx] : 0.f, mean, std);
+    }
+  }
+}
+
 // scatter: the interior (tpad stripped, utils.py:113-116) of tile t of y -> uint8 block of the output volume at index[t]
 __global__ __launch_bounds__(256) void f32_tiles_unstd_to_u8_k(const float *y, int yedge, int tpad, const int32_t *index,
                                                                uint8_t *out, int OY, int OX, float mean, float std) {
@@ -318,6 +374,54 @@ __global__ __launch_bounds__(256) void u8_tiles2d_to_f32_std_k(const uint8_t *vo
     const bool in = zin && (unsigned)gy < (unsigned)Y && (unsigned)gx < (unsigned)X;
     v[j] = u8_std(in ? (float)plane[(int64_t)gy * X + gx] : 0.f, mean, std);
     ++xx;
+  }
+  float *o = out + g * V;
+  if constexpr (V == 4)
+    *reinterpret_cast<float4 *>(o) = make_float4(v[0], v[1], v[2], v[3]);
+  else
+    o[0] = v[0];
+}
+
+// gather with a boundary mode (see u8_tiles_to_f32_std_bc_k): the same flat grid and stores over the staging block
+// blk[BZ][BY][BX] at (lz, ly, lx).  A thread of a tile inside the volume runs the plain loop; a thread of a face tile
+// folds its section once, its row once (again where its V pixels wrap onto the next row) and x per pixel.
+template <int V, int MODE>
+__global__ __launch_bounds__(256) void u8_tiles2d_to_f32_std_bc_k(const uint8_t *blk, int BZ, int BY, int BX, int lz,
+                                                                  int ly, int lx, int Z, int Y, int X,
+                                                                  const int32_t *origins, int edge, float *out,
+                                                                  float mean, float std, int64_t ngroup) {
+  const int64_t g = (int64_t)xcd_contiguous_block(blockIdx.x, gridDim.x) * 256 + threadIdx.x;
+  if (g >= ngroup) return;
+  const int per_tile = edge * edge / V;                        // groups per tile (edge * edge % V == 0)
+  const int t = (int)(g / per_tile), e = (int)(g - (int64_t)t * per_tile) * V;
+  const int oz = origins[3 * t], oy = origins[3 * t + 1], ox = origins[3 * t + 2];
+  const int vz = lz + oz, vy = ly + oy, vx = lx + ox;          // the tile's origin in volume coordinates
+  int yy = e / edge, xx = e - yy * edge;
+  float v[V];
+  if ((unsigned)vz < (unsigned)Z && vy >= 0 && vy + edge <= Y && vx >= 0 && vx + edge <= X) {
+    const bool zin = (unsigned)oz < (unsigned)BZ;
+    const uint8_t *plane = blk + (int64_t)(zin ? oz : 0) * BY * BX;
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      if (xx == edge) { xx = 0; ++yy; }
+      const int gy = oy + yy, gx = ox + xx;
+      const bool in = zin && (unsigned)gy < (unsigned)BY && (unsigned)gx < (unsigned)BX;
+      v[j] = u8_std(in ? (float)plane[(int64_t)gy * BX + gx] : 0.f, mean, std);
+      ++xx;
+    }
+  } else {
+    const int bz = bc_fold<MODE>(vz, Z) - lz;
+    const bool zin = (unsigned)bz < (unsigned)BZ;
+    const uint8_t *plane = blk + (int64_t)(zin ? bz : 0) * BY * BX;
+    int by = bc_fold<MODE>(vy + yy, Y) - ly;
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      if (xx == edge) { xx = 0; ++yy; by = bc_fold<MODE>(vy + yy, Y) - ly; }
+      const int bx = bc_fold<MODE>(vx + xx, X) - lx;
+      const bool in = zin && (unsigned)by < (unsigned)BY && (unsigned)bx < (unsigned)BX;
+      v[j] = u8_std(in ? (float)plane[(int64_t)by * BX + bx] : 0.f, mean, std);
+      ++xx;
+    }
   }
   float *o = out + g * V;
   if constexpr (V == 4)
@@ -487,6 +591,76 @@ extern "C" int tem_u8_tiles2d_to_f32_std(const uint8_t *vol, int32_t Z, int32_t 
   else
     hipLaunchKernelGGL(u8_tiles2d_to_f32_std_k<1>, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, vol, Z, Y,
                        X, origins_dev, edge, out, mean, std, ngroup);
+  TEM_CHECK_LAUNCH();
+  return TEM_OK;
+}
+
+namespace {
+// the block lies inside a non-empty volume, the mode is one the kernels fold by
+inline bool bc_args_ok(int32_t BZ, int32_t BY, int32_t BX, int32_t lz, int32_t ly, int32_t lx, int32_t Z, int32_t Y,
+                       int32_t X, int32_t mode) {
+  if (mode != TEM_BOUNDARY_REFLECT && mode != TEM_BOUNDARY_EDGE) return false;
+  if (Z < 1 || Y < 1 || X < 1 || BZ < 1 || BY < 1 || BX < 1 || lz < 0 || ly < 0 || lx < 0) return false;
+  return BZ <= Z - lz && BY <= Y - ly && BX <= X - lx;
+}
+}  // namespace
+
+extern "C" int tem_u8_tiles_to_f32_std_bc(const uint8_t *blk, int32_t BZ, int32_t BY, int32_t BX, int32_t lz, int32_t ly,
+                                          int32_t lx, int32_t Z, int32_t Y, int32_t X, int32_t mode,
+                                          const int32_t *origins_dev, int32_t ntile, int32_t edge, float *out,
+                                          float mean, float std, tem_stream_t stream) {
+  TEM_CLEAR_ERR();
+  if (!blk || !origins_dev || !out || !bc_args_ok(BZ, BY, BX, lz, ly, lx, Z, Y, X, mode) || ntile < 0 || edge < 1 ||
+      edge > 46340)
+    return TEM_EINVAL;
+  if (ntile == 0) return TEM_OK;
+  if (ntile > 65535) return TEM_EUNSUPPORTED;
+  const int64_t per_tile = (int64_t)edge * edge * edge;
+  unsigned gx = grid_for(per_tile); if (gx > 512) gx = 512;
+  const dim3 grid(gx, (unsigned)ntile);
+  if (mode == TEM_BOUNDARY_REFLECT)
+    hipLaunchKernelGGL(u8_tiles_to_f32_std_bc_k<TEM_BOUNDARY_REFLECT>, grid, dim3(256), 0, (hipStream_t)stream, blk, BZ,
+                       BY, BX, lz, ly, lx, Z, Y, X, origins_dev, edge, out, mean, std, per_tile);
+  else
+    hipLaunchKernelGGL(u8_tiles_to_f32_std_bc_k<TEM_BOUNDARY_EDGE>, grid, dim3(256), 0, (hipStream_t)stream, blk, BZ, BY,
+                       BX, lz, ly, lx, Z, Y, X, origins_dev, edge, out, mean, std, per_tile);
+  TEM_CHECK_LAUNCH();
+  return TEM_OK;
+}
+
+namespace {
+template <int V>
+void launch_tiles2d_bc(int32_t mode, unsigned nblk, hipStream_t st, const uint8_t *blk, int BZ, int BY, int BX, int lz,
+                       int ly, int lx, int Z, int Y, int X, const int32_t *origins, int edge, float *out, float mean,
+                       float std, int64_t ngroup) {
+  if (mode == TEM_BOUNDARY_REFLECT)
+    hipLaunchKernelGGL((u8_tiles2d_to_f32_std_bc_k<V, TEM_BOUNDARY_REFLECT>), dim3(nblk), dim3(256), 0, st, blk, BZ, BY,
+                       BX, lz, ly, lx, Z, Y, X, origins, edge, out, mean, std, ngroup);
+  else
+    hipLaunchKernelGGL((u8_tiles2d_to_f32_std_bc_k<V, TEM_BOUNDARY_EDGE>), dim3(nblk), dim3(256), 0, st, blk, BZ, BY, BX,
+                       lz, ly, lx, Z, Y, X, origins, edge, out, mean, std, ngroup);
+}
+}  // namespace
+
+extern "C" int tem_u8_tiles2d_to_f32_std_bc(const uint8_t *blk, int32_t BZ, int32_t BY, int32_t BX, int32_t lz,
+                                            int32_t ly, int32_t lx, int32_t Z, int32_t Y, int32_t X, int32_t mode,
+                                            const int32_t *origins_dev, int32_t ntile, int32_t edge, float *out,
+                                            float mean, float std, tem_stream_t stream) {
+  TEM_CLEAR_ERR();
+  if (!blk || !origins_dev || !out || !bc_args_ok(BZ, BY, BX, lz, ly, lx, Z, Y, X, mode) || ntile < 0 || edge < 1 ||
+      edge > 46340)
+    return TEM_EINVAL;
+  if (ntile == 0) return TEM_OK;
+  const int V = (edge % 2 == 0 && ((uintptr_t)out & 15) == 0) ? 4 : 1;
+  const int64_t ngroup = (int64_t)ntile * edge * edge / V;
+  const int64_t nblk = (ngroup + 255) / 256;
+  if (nblk > 0x7fffffff) return TEM_EUNSUPPORTED;
+  if (V == 4)
+    launch_tiles2d_bc<4>(mode, (unsigned)nblk, (hipStream_t)stream, blk, BZ, BY, BX, lz, ly, lx, Z, Y, X, origins_dev,
+                         edge, out, mean, std, ngroup);
+  else
+    launch_tiles2d_bc<1>(mode, (unsigned)nblk, (hipStream_t)stream, blk, BZ, BY, BX, lz, ly, lx, Z, Y, X, origins_dev,
+                         edge, out, mean, std, ngroup);
   TEM_CHECK_LAUNCH();
   return TEM_OK;
 }

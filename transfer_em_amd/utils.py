@@ -92,11 +92,50 @@ def default_tile_batch(edge, is3d=True):
     return max(1, min(TILE_BATCH_MAX_2D, budget // plan_bytes_per_tile(edge, False)))
 
 
-def _tile_kernels(lib, is3d):
-    """(gather, scatter) C entry points and their names: the cube tiles or the 2-D (one section) tiles."""
-    names = (("tem_u8_tiles_to_f32_std", "tem_f32_tiles_unstd_to_u8") if is3d else
-             ("tem_u8_tiles2d_to_f32_std", "tem_f32_tiles2d_unstd_to_u8"))
-    return tuple((getattr(lib, n), n) for n in names)
+BOUNDARIES = ("zeros", "reflect", "edge")     # what a tile voxel outside the volume reads
+
+
+def fold(i, n, boundary):
+    """Index that coordinate(s) `i` (int or integer array) of an axis of extent `n` read under `boundary`:
+    "edge" clamps to [0, n-1]; "reflect" mirrors without repeating the face voxel (period 2(n-1); extent 1 reads
+    index 0).  These are numpy.pad's modes of the same names for any pad width, wider than the axis included.  The
+    tile gather kernels (tem_u8_tiles*_to_f32_std_bc) fold by the same rule; "zeros" folds nothing and has no index."""
+    if boundary not in BOUNDARIES[1:]:
+        raise ValueError(f"fold: boundary must be 'reflect' or 'edge', got {boundary!r}")
+    if n < 1:
+        raise ValueError(f"boundary={boundary!r} needs a non-empty axis, got extent {n}")
+    if boundary == "edge":
+        return np.clip(i, 0, n - 1) if isinstance(i, np.ndarray) else min(max(i, 0), n - 1)
+    if n == 1:
+        return np.zeros_like(i) if isinstance(i, np.ndarray) else 0
+    m = 2 * (n - 1)
+    r = i % m                                       # non-negative for ints and arrays alike
+    return np.where(r < n, r, m - r) if isinstance(i, np.ndarray) else (r if r < n else m - r)
+
+
+def _check_boundary(boundary, vol_shape):
+    if boundary not in BOUNDARIES:
+        raise ValueError(f"boundary must be one of {BOUNDARIES}, got {boundary!r}")
+    if boundary != "zeros" and min(vol_shape) < 1:
+        raise ValueError(f"boundary={boundary!r} needs a non-empty volume, got shape {tuple(vol_shape)}")
+
+
+def _tile_kernels(lib, is3d, boundary="zeros"):
+    """(gather, scatter) and their names: the cube tiles or the 2-D (one section) tiles.  `scatter` is the C entry
+    point; `gather(blk, block, lo, vol_shape, origins, ntile, edge, out, mean, std, stream)` cuts tiles out of the
+    staging block `blk` of shape `block` that holds the volume's box at `lo` (the resident volume: lo = 0, block =
+    vol_shape): "zeros" calls the zero-mode entry point on the block, the other modes their `_bc` sibling."""
+    from . import _lib
+    gname, sname = (("tem_u8_tiles_to_f32_std", "tem_f32_tiles_unstd_to_u8") if is3d else
+                    ("tem_u8_tiles2d_to_f32_std", "tem_f32_tiles2d_unstd_to_u8"))
+    if boundary == "zeros":
+        fn = getattr(lib, gname)
+        gather = lambda blk, block, lo, vol_shape, *rest: fn(blk, *block, *rest)
+    else:
+        gname += "_bc"
+        fn, mode = getattr(lib, gname), {"reflect": _lib.TEM_BOUNDARY_REFLECT, "edge": _lib.TEM_BOUNDARY_EDGE}[boundary]
+        gather = lambda blk, block, lo, vol_shape, *rest: fn(blk, *block, *lo, *vol_shape, mode, *rest)
+    return (gather, gname), (getattr(lib, sname), sname)
 
 
 class _OneSection:
@@ -131,10 +170,12 @@ def _single_image(model, start, size):
 
 
 def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=False, outdimsize=None, buffer=None,
-                 rank=0, world_size=1, tile_batch=None):
+                 rank=0, world_size=1, tile_batch=None, boundary="zeros"):
     """Predict the subvolume [start, start+size) (x,y,z order as in the reference) of a uint8
     array `volume` indexed [z, y, x].  Voxels outside the array read as 0 (the reference fetches
-    them from the store).  Returns uint8 (zsize, ysize, xsize) [and the input block].
+    them from the store) or, with boundary="reflect" / "edge", the voxel that `fold` names on every axis: the result
+    is that of the same call on numpy.pad(volume, P, mode=boundary) for any P the tiles stay within, without the padded
+    copy.  Returns uint8 (zsize, ysize, xsize) [and the input block: the ROI of that padded volume].
 
     Device-side pipeline (utils.py:77-126 without the per-tile host round trips): the uint8 volume is uploaded
     once; one gather kernel cuts a batch of haloed tiles straight out of it (uint8 -> float, scaled and
@@ -152,7 +193,7 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
     is3d = getattr(gen, "is3d", True)
     if _single_image(model, start, size):
         res = predict_cube(np.asarray(volume)[None], tuple(start) + (0,), tuple(size) + (1,), model, meanstd_x,
-                           meanstd_y, fetch_input, outdimsize, buffer, rank, world_size, tile_batch)
+                           meanstd_y, fetch_input, outdimsize, buffer, rank, world_size, tile_batch, boundary)
         return tuple(r[0] for r in res) if fetch_input else res[0]
     if outdimsize is None:
         outdimsize = model.outdimsize
@@ -164,6 +205,7 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
     rnd = lambda v: v + ((outdimsize - (v % outdimsize)) if (v % outdimsize) != 0 else 0)
     dev = model.device
     vol_host = np.ascontiguousarray(volume, dtype=np.uint8)
+    _check_boundary(boundary, vol_host.shape)
     vol = torch.from_numpy(vol_host).to(dev, non_blocking=True)          # ONE upload of the whole volume
     Z, Y, X = vol_host.shape
     out_buffer = torch.zeros((rnd(z) if is3d else z, rnd(y), rnd(x)), dtype=torch.uint8, device=dev)
@@ -171,7 +213,7 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
     mine = list(range(rank, len(rois), world_size))
     nb = max(1, min(int(tile_batch or default_tile_batch(edge, is3d)), len(mine) or 1))
     tile = (edge, edge, edge) if is3d else (1, edge, edge)               # (D, H, W) of one generator input
-    (gather, gname), (scatter, sname) = _tile_kernels(lib, is3d)
+    (gather, gname), (scatter, sname) = _tile_kernels(lib, is3d, boundary)
     stream = H.current_stream()
     for c0 in range(0, len(mine), nb):
         chunk = mine[c0:c0 + nb]
@@ -183,8 +225,8 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
             tiles = plan.x
         else:
             plan, tiles = None, torch.empty((n,) + tile + (1,), dtype=torch.float32, device=dev)
-        _lib.check(gather(vol.data_ptr(), Z, Y, X, org.data_ptr(), n, edge, tiles.data_ptr(), float(meanstd_x[0]),
-                          float(meanstd_x[1]), stream), gname)
+        _lib.check(gather(vol.data_ptr(), (Z, Y, X), (0, 0, 0), (Z, Y, X), org.data_ptr(), n, edge, tiles.data_ptr(),
+                          float(meanstd_x[0]), float(meanstd_x[1]), stream), gname)
         data_y = plan.run() if plan is not None else model.predict(tiles).contiguous()
         yedge = data_y.shape[2]
         assert yedge - 2 * tpad == outdimsize, (yedge, tpad, outdimsize)
@@ -197,6 +239,9 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
         # the reference returns the RAW uint8 block here after a detour (utils.py:122-125: the standardized float
         # tile is un-standardized, rescaled and truncated into a uint8 buffer -- the original bytes up to float
         # rounding); the bytes themselves are returned instead
+        if boundary != "zeros":                  # what the network saw: the ROI of the folded volume
+            fz, fy, fx = (fold(np.arange(start[d], start[d] + size[d]), n, boundary) for d, n in ((2, Z), (1, Y), (0, X)))
+            return vol_host[np.ix_(fz, fy, fx)], out
         inp = np.zeros((size[2], size[1], size[0]), np.uint8)
         z0, y0, x0 = max(start[2], 0), max(start[1], 0), max(start[0], 0)
         z1, y1, x1 = min(start[2] + size[2], Z), min(start[1] + size[1], Y), min(start[0] + size[0], X)
@@ -258,7 +303,17 @@ def _default_chunk_tiles_2d(grid, cap, od, halo):
     return best
 
 
-def _chunk_plan(start, size, outdimsize, buffer, vol_shape, chunk_tiles, rank=0, world_size=1, is3d=True):
+def _fold_hull(lo, hi, n, boundary):
+    """[min, max + 1) of fold(i, n, boundary) over i in [lo, hi)."""
+    if 0 <= lo and hi <= n:
+        return lo, hi
+    f = fold(np.arange(lo, hi), n, boundary)
+    return int(f.min()), int(f.max()) + 1
+
+
+def _chunk_plan(start, size, outdimsize, buffer, vol_shape, chunk_tiles, rank=0, world_size=1, is3d=True,
+                boundary="zeros"):
+    _check_boundary(boundary, vol_shape)
     outdimsize, buffer, tpad, rois, index = (tile_plan if is3d else tile_plan_2d)(start, size, outdimsize, buffer)
     od, edge = outdimsize, outdimsize + 2 * buffer
     # (z, y, x) extent of one tile's output (`step`) and haloed input (`ext`): a 2-D tile is one section thick
@@ -280,9 +335,13 @@ def _chunk_plan(start, size, outdimsize, buffer, vol_shape, chunk_tiles, rank=0,
                          for a in range(gz, min(gz + kz, grid[0]))]
                 tiles = tuple(sorted(at[c] for c in cells))            # tile_plan order
                 org = [(rois[i][2], rois[i][1], rois[i][0]) for i in tiles]
-                read = tuple((min(max(min(o[d] for o in org), 0), vol_shape[d]),
-                              max(min(max(o[d] for o in org) + ext[d], vol_shape[d]), 0)) for d in range(3))
-                read = tuple((lo, max(lo, hi)) for lo, hi in read)
+                span = tuple((min(o[d] for o in org), max(o[d] for o in org) + ext[d]) for d in range(3))   # halo union
+                if boundary == "zeros":
+                    read = tuple((min(max(lo, 0), vol_shape[d]), max(min(hi, vol_shape[d]), 0))
+                                 for d, (lo, hi) in enumerate(span))
+                    read = tuple((lo, max(lo, hi)) for lo, hi in read)
+                else:                       # mirrored coordinates leave the clipped union: the hull of where they land
+                    read = tuple(_fold_hull(lo, hi, vol_shape[d], boundary) for d, (lo, hi) in enumerate(span))
                 base = (gz * step[0], gy * step[1], gx * step[2])
                 dims = tuple(k * s for k, s in zip((min(kz, grid[0] - gz), min(ky, grid[1] - gy), min(kx, grid[2] - gx)),
                                                    step))
@@ -298,7 +357,8 @@ def _chunk_plan(start, size, outdimsize, buffer, vol_shape, chunk_tiles, rank=0,
     return outdimsize, buffer, tpad, chunks[rank::world_size]
 
 
-def chunk_plan(start, size, outdimsize, buffer, vol_shape, chunk_tiles, rank=0, world_size=1, is3d=True):
+def chunk_plan(start, size, outdimsize, buffer, vol_shape, chunk_tiles, rank=0, world_size=1, is3d=True,
+               boundary="zeros"):
     """Group the tiles of tile_plan(start, size, outdimsize, buffer) into boxes of chunk_tiles = (kz, ky, kx) whole
     tiles (fewer at the ROI's far faces) over a volume of shape vol_shape = (Z, Y, X).  Chunks go round-robin to the
     ranks.  Returns this rank's list of VolumeChunk; chunk_tiles=None picks the box predict_volume uses by default
@@ -311,18 +371,27 @@ def chunk_plan(start, size, outdimsize, buffer, vol_shape, chunk_tiles, rank=0, 
 
     is3d=False groups tile_plan_2d's tiles instead: a chunk is a run of kz sections x (ky x kx) in-plane tiles, its
     footprint is haloed in y and x only (its z extent is exactly its sections, clipped to the volume), and
-    chunk_tiles=None picks at most default_tile_batch(edge, False) tiles, fewest chunks, least halo read per tile."""
+    chunk_tiles=None picks at most default_tile_batch(edge, False) tiles, fewest chunks, least halo read per tile.
+
+    boundary="reflect" / "edge" (see `fold`): a voxel outside the volume reads a voxel inside it, which may lie outside
+    the clipped union (a tile past the far face of a thin volume mirrors back beyond its own near side), so the rule
+    above no longer holds.  A chunk's `read` is then, per axis, the hull [min, max + 1) of fold(i, n) over the union
+    of its tiles' haloed extents: every folded coordinate lies in it, both ends are attained, and it is never empty.
+    `origins` stay relative to read[*][0]; the `_bc` gather kernels get the block, read[*][0] and vol_shape, and fold
+    l + origin + p themselves."""
     return _chunk_plan(start, size, outdimsize, buffer, tuple(int(v) for v in vol_shape), chunk_tiles, rank,
-                       world_size, is3d)[3]
+                       world_size, is3d, boundary)[3]
 
 
 def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, chunk_tiles=None, tile_batch=None,
-                   outdimsize=None, buffer=None, rank=0, world_size=1, stats=None):
+                   outdimsize=None, buffer=None, rank=0, world_size=1, stats=None, boundary="zeros"):
     """Out-of-core predict_cube: the subvolume [start, start+size) (x,y,z order) of a uint8 array-like `volume`
     indexed [z, y, x] (ndarray, np.memmap, h5py / zarr dataset: `.shape` and basic slicing are all it needs) is
     predicted chunk by chunk (chunk_plan) into `out`, a writable uint8 array-like of shape (size[2], size[1], size[0])
     (allocated when None) that is returned.  Only the chunks' footprints are ever read from `volume`; device memory
-    is bounded by the chunk, not by the ROI.  The result equals predict_cube's bit for bit.
+    is bounded by the chunk, not by the ROI.  The result equals predict_cube's bit for bit, for every `boundary`
+    ("zeros", "reflect", "edge": what a voxel outside the volume reads, see predict_cube; the mirrored modes read
+    each chunk's footprint hull, chunk_plan).
 
     Pipeline per chunk: one host thread reads the footprint into a pinned staging buffer -> H2D on a copy stream ->
     gather + generator plan + scatter on the compute stream (the plan's buffers are reused run to run, so these stay
@@ -347,7 +416,7 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
         if out is None:
             out = np.zeros((size[1], size[0]), np.uint8)
         predict_volume(_OneSection(volume), tuple(start) + (0,), tuple(size) + (1,), model, meanstd_x, meanstd_y,
-                       _OneSection(out), chunk_tiles, tile_batch, outdimsize, buffer, rank, world_size, stats)
+                       _OneSection(out), chunk_tiles, tile_batch, outdimsize, buffer, rank, world_size, stats, boundary)
         return out
     is3d = gen.is3d
     vol_shape = tuple(int(v) for v in volume.shape)
@@ -355,10 +424,10 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
         raise ValueError(f"volume must be 3-D [z, y, x], got shape {vol_shape}")
     od, buf, tpad, chunks = _chunk_plan(start, size, model.outdimsize if outdimsize is None else outdimsize,
                                         model.buffer if buffer is None else buffer, vol_shape, chunk_tiles, rank,
-                                        world_size, is3d)
+                                        world_size, is3d, boundary)
     edge = od + 2 * buf
     tile = (edge, edge, edge) if is3d else (1, edge, edge)               # (D, H, W) of one generator input
-    (gather, gname), (scatter, sname) = _tile_kernels(lib, is3d)
+    (gather, gname), (scatter, sname) = _tile_kernels(lib, is3d, boundary)
     if out is None:
         out = np.zeros((size[2], size[1], size[0]), np.uint8)
     elif tuple(out.shape) != (size[2], size[1], size[0]):
@@ -369,7 +438,8 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
     if not chunks:
         return out
     K = len(chunks)
-    # a chunk wholly outside the volume has an empty footprint: it gathers from one zero byte (all voxels read 0)
+    # a chunk wholly outside the volume has an empty footprint: it gathers from one zero byte (all voxels read 0);
+    # with a mirrored boundary no footprint is empty
     gdims = [c.block if min(c.block) > 0 else (1, 1, 1) for c in chunks]
     in_bytes = [int(np.prod(g)) for g in gdims]
     out_bytes = [int(np.prod(c.dims)) for c in chunks]
@@ -421,7 +491,7 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
             compute.wait_event(h2d_done[k])
             if k >= 2:
                 compute.wait_event(d2h_evt[s])               # dev_out[s]: chunk k-2's D2H has read it
-            Z, Y, X = gdims[k]
+            lo = tuple(r[0] for r in c.read)
             OZ, OY, OX = c.dims
             n = len(c.tiles)
             for b0 in range(0, n, nb):
@@ -430,8 +500,9 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
                     plan = None                              # let the plan cache release an evicted plan's buffers
                     plan = gen.plan((m,) + tile + (1,))
                 t = int(first[k]) + b0
-                _lib.check(gather(dev_in[s].data_ptr(), Z, Y, X, org.data_ptr() + 12 * t, m, edge, plan.x.data_ptr(),
-                                  float(meanstd_x[0]), float(meanstd_x[1]), compute.cuda_stream), gname)
+                _lib.check(gather(dev_in[s].data_ptr(), gdims[k], lo, vol_shape, org.data_ptr() + 12 * t, m, edge,
+                                  plan.x.data_ptr(), float(meanstd_x[0]), float(meanstd_x[1]), compute.cuda_stream),
+                           gname)
                 if b0 + m == n:
                     gathered[k] = compute.record_event()
                 data_y = plan.run(compute.cuda_stream)
@@ -498,14 +569,17 @@ def _local_volume(location):
 def predict_ng_cube(location, start, size, model, meanstd_x, meanstd_y, cloudrun=None, fetch_input=False,
                     outdimsize=None, buffer=None):
     """Reference signature (utils.py:41): `location` is the uint8 volume itself (array indexed [z, y, x])
-    instead of a cloud path; `cloudrun` is accepted and ignored."""
+    instead of a cloud path; `cloudrun` is accepted and ignored.  The signature is the reference's, so voxels outside
+    the array always read 0 here: predict_cube(..., boundary="reflect" | "edge") mirrors or clamps at the faces."""
     return predict_cube(_local_volume(location), start, size, model, meanstd_x, meanstd_y, fetch_input=fetch_input,
                         outdimsize=outdimsize, buffer=buffer)
 
 
 def predict_cube_from_saved_model(location, start, size, cloudrun, model_dir, fetch_input=False):
     """Reference signature (utils.py:12-38) over a local array: `location` is the uint8 volume,
-    `cloudrun` is accepted and ignored, `model_dir` is a directory written by save_model."""
+    `cloudrun` is accepted and ignored, `model_dir` is a directory written by save_model.  The signature is the
+    reference's, so voxels outside the array always read 0 here: for boundary="reflect" | "edge" call predict_cube, or
+    predict_volume_from_saved_model, which takes the keyword."""
     volume = _local_volume(location)
     model = _load_saved(model_dir)
     return predict_cube(volume, start, size, model, model.meta["meanstd_x"], model.meta["meanstd_y"],
@@ -514,7 +588,8 @@ def predict_cube_from_saved_model(location, start, size, cloudrun, model_dir, fe
 
 def predict_volume_from_saved_model(volume, start, size, model_dir, out=None, **kw):
     """predict_volume with the generator and statistics exported by save_model to `model_dir` (the out-of-core
-    sibling of predict_cube_from_saved_model); `kw` are predict_volume's chunk_tiles, tile_batch, rank, world_size."""
+    sibling of predict_cube_from_saved_model); `kw` are predict_volume's chunk_tiles, tile_batch, rank, world_size,
+    stats and boundary ("zeros", "reflect" or "edge": what a voxel outside the volume reads)."""
     model = _load_saved(model_dir)
     return predict_volume(_local_volume(volume), start, size, model, model.meta["meanstd_x"], model.meta["meanstd_y"],
                           out=out, outdimsize=model.outdimsize, buffer=model.buffer, **kw)
