@@ -9,6 +9,30 @@ def rel_err(a, b):
     return float(np.abs(a - b).max() / (np.abs(b).max() + 1e-30))
 
 
+def inorm_f32(x, dy, scale, offset, eps=1e-5):
+    """InstanceNormalization and its gradient restated in float32, op for op as csrc/elementwise.hip computes them:
+    mean, deviation, variance, rstd and every product are rounded to float32 where the kernels round them, the
+    sums run in float64.  Pure NumPy -- the yardstick for what float32 itself costs against the float64 oracle
+    (the bars of tests/test_gpu_glue.py that are not the project's standing ones are 4x this function's error).
+    Returns (y, mean, rstd, dx, dscale, doffset)."""
+    f = np.float32
+    x, dy = np.asarray(x, f), np.asarray(dy, f)
+    scale, offset = np.asarray(scale, f), np.asarray(offset, f)
+    ax, vox = (1, 2, 3), x.shape[1] * x.shape[2] * x.shape[3]
+    mean = (x.sum(axis=ax, keepdims=True, dtype=np.float64) / vox).astype(f)
+    d = x - mean
+    var = ((d * d).sum(axis=ax, keepdims=True, dtype=np.float64) / vox).astype(f)
+    rstd = (1.0 / np.sqrt((var + f(eps)).astype(np.float64))).astype(f)
+    xh = d * rstd
+    y = scale * xh + offset
+    s1 = dy.sum(axis=ax, keepdims=True, dtype=np.float64)
+    s2 = (dy * xh).sum(axis=ax, keepdims=True, dtype=np.float64)
+    m1, m2 = (s1 / vox).astype(f), (s2 / vox).astype(f)
+    dx = scale * rstd * (dy - m1 - xh * m2)
+    return (y, mean.reshape(x.shape[0], -1), rstd.reshape(x.shape[0], -1), dx,
+            s2.sum(axis=0).reshape(-1).astype(f), s1.sum(axis=0).reshape(-1).astype(f))
+
+
 def scaled_params(shapes, seed, gain=1.0):
     """Kernels with variance-preserving scale (so that every layer carries signal and gradient:
     the reference's N(0, 0.02) init makes the inner layers' gradients ~1e-10 of the outer ones,
