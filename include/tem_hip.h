@@ -304,6 +304,33 @@ int tem_u8_tiles2d_to_f32_std_bc(const uint8_t *blk, int32_t BZ, int32_t BY, int
                                  int32_t lx, int32_t Z, int32_t Y, int32_t X, int32_t mode, const int32_t *origins_dev,
                                  int32_t ntile, int32_t edge, float *out, float mean, float std, tem_stream_t stream);
 
+/* Tiled inference under a symmetry of the cube (self-ensemble over the training orientations).  A symmetry is
+ * (p0,p1,p2, f0,f1,f2) in tem_augment_f32's convention over a tile's axes (z, y, x):
+ *   T(v) = reverse(transpose(v, perm = (p0,p1,p2)), axes a with f_a != 0), i.e. T(v)[q] = v[j(q)] with
+ *   j[perm[a]] = f_a ? n - 1 - q[a] : q[a]   (n = the tile's edge; 2-D tiles: p0 == 0, f0 == 0, j[0] = q[0] = 0).
+ * Gather: the arguments of the `_bc` gathers plus the symmetry; `mode` may also be 0 (a voxel outside the block reads
+ * 0, as tem_u8_tiles_to_f32_std on blk[BZ][BY][BX]; the block must still lie inside (Z, Y, X) at (lz, ly, lx):
+ * the resident form passes the block as the volume).  Voxel q of tile t of `out` = the value the corresponding gather
+ * (zero-mode or `_bc`) writes at voxel j(q): out[t] = T(tile t), bit for bit.
+ * Accumulate: acc[t][j(q)] = (first ? y[t][q] : acc[t][j(q)] + y[t][q]), then / (float)divisor when divisor > 1 (one
+ * fp32 addition, one fp32 division): acc (+)= T^-1(y[t]).  y and acc are [ntile][yedge]^3 (2-D: ^2) and must not
+ * alias; with `first` acc is written without being read.  Every acc element is written by exactly one thread.
+ * TEM_EINVAL, without a launch: what the `_bc` gathers reject (mode 0 allowed), a perm that is no permutation of
+ * (0,1,2), a flag outside {0,1}, a 2-D symmetry with p0 != 0 or f0 != 0, first outside {0,1}, divisor < 1. */
+int tem_u8_tiles_to_f32_std_sym(const uint8_t *blk, int32_t BZ, int32_t BY, int32_t BX, int32_t lz, int32_t ly,
+                                int32_t lx, int32_t Z, int32_t Y, int32_t X, int32_t mode, const int32_t *origins_dev,
+                                int32_t ntile, int32_t edge, int32_t p0, int32_t p1, int32_t p2, int32_t f0, int32_t f1,
+                                int32_t f2, float *out, float mean, float std, tem_stream_t stream);
+int tem_u8_tiles2d_to_f32_std_sym(const uint8_t *blk, int32_t BZ, int32_t BY, int32_t BX, int32_t lz, int32_t ly,
+                                  int32_t lx, int32_t Z, int32_t Y, int32_t X, int32_t mode, const int32_t *origins_dev,
+                                  int32_t ntile, int32_t edge, int32_t p0, int32_t p1, int32_t p2, int32_t f0,
+                                  int32_t f1, int32_t f2, float *out, float mean, float std, tem_stream_t stream);
+int tem_f32_tiles_sym_accum(const float *y, int32_t ntile, int32_t yedge, int32_t p0, int32_t p1, int32_t p2, int32_t f0,
+                            int32_t f1, int32_t f2, float *acc, int32_t first, int32_t divisor, tem_stream_t stream);
+int tem_f32_tiles2d_sym_accum(const float *y, int32_t ntile, int32_t yedge, int32_t p0, int32_t p1, int32_t p2,
+                              int32_t f0, int32_t f1, int32_t f2, float *acc, int32_t first, int32_t divisor,
+                              tem_stream_t stream);
+
 /* Tiled inference of the 2-D networks, output side: the interior of tile t of y[ntile][yedge][yedge] (`tpad` pixels
  * stripped per side) is converted as tem_f32_unstd_to_u8 and written into section z of the uint8 volume
  * out[OZ][OY][OX] at (z,y,x) = index_dev[3t..3t+2].  Pixels that fall outside `out` are dropped.  Any ntile. */

@@ -129,6 +129,12 @@ _SIGS = {
                                                                       C.c_float, C.c_float, C.c_void_p],
     "tem_u8_tiles2d_to_f32_std_bc": [C.c_void_p] + [C.c_int32] * 10 + [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                                                         C.c_float, C.c_float, C.c_void_p],
+    "tem_u8_tiles_to_f32_std_sym": [C.c_void_p] + [C.c_int32] * 10 + [C.c_void_p] + [C.c_int32] * 8 +
+                                   [C.c_void_p, C.c_float, C.c_float, C.c_void_p],
+    "tem_u8_tiles2d_to_f32_std_sym": [C.c_void_p] + [C.c_int32] * 10 + [C.c_void_p] + [C.c_int32] * 8 +
+                                     [C.c_void_p, C.c_float, C.c_float, C.c_void_p],
+    "tem_f32_tiles_sym_accum": [C.c_void_p] + [C.c_int32] * 8 + [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p],
+    "tem_f32_tiles2d_sym_accum": [C.c_void_p] + [C.c_int32] * 8 + [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p],
     "tem_f32_tiles2d_unstd_to_u8": [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                                     C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p],
     "tem_augment_f32": [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,

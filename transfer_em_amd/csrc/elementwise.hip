@@ -1,6 +1,7 @@
 // elementwise.hip -- losses, optimizer and data-format kernels of the CycleGAN step.
 // All are HBM-streaming kernels (or tiny); float32 storage, float/double accumulation as noted.
 #include "tem_common.h"
+#include "tile_math.h"
 #include <cmath>
 
 namespace {
@@ -121,22 +122,7 @@ __global__ __launch_bounds__(256) void adam_keras_k(float *theta, const float *g
 
 __global__ void step_tick_k(uint32_t *s) { *s += 1u; }
 
-// The per-voxel arithmetic of every uint8 <-> float boundary (whole-array, 3-D tiles, 2-D tiles): one definition, so
-// the kernel pairs cannot drift apart.  Correctly rounded float32 ops as in the reference (datasets.py, utils.py:109),
-// with one exception: y * std + mean is ONE fused multiply-add (hipcc contracts the __fmul_rn / __fadd_rn pair into
-// v_fma_f32, and every release of these kernels has computed it so; it is spelled out here so that it no longer
-// depends on the compiler).  Next to a rounding boundary the reference's two roundings can land one step away: the
-// oracle comparisons allow 1 LSB on under 1 % of the voxels.
-__device__ __forceinline__ float u8_std(float x, float mean, float std) {
-  x = __fsub_rn(__fdiv_rn(x, 127.5f), 1.f);          // datasets.py:200
-  return __fdiv_rn(__fsub_rn(x, mean), std);         // datasets.py:161-162
-}
-
-__device__ __forceinline__ uint8_t unstd_u8(float v, float mean, float std) {
-  v = __fmul_rn(__fadd_rn(__fmaf_rn(v, std, mean), 1.f), 127.5f);             // utils.py:109
-  const int q = (int)rintf(v);                                                  // np.around: half to even
-  return (uint8_t)(q & 0xFF);                                                   // astype(uint8) wraps
-}
+// u8_std / unstd_u8, the per-voxel arithmetic of every uint8 <-> float boundary, and bc_fold: tile_math.h
 
 __global__ __launch_bounds__(256) void u8_to_f32_std_k(const uint8_t *in, float *out, int64_t n, float mean, float std) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
@@ -275,22 +261,6 @@ __global__ __launch_bounds__(256) void u8_tiles_to_f32_std_k(const uint8_t *vol,
     const int gz = oz + z, gy = oy + y, gx = ox + x;
     const bool in = (unsigned)gz < (unsigned)Z && (unsigned)gy < (unsigned)Y && (unsigned)gx < (unsigned)X;
     o[i] = u8_std(in ? (float)vol[((int64_t)gz * Y + gy) * X + gx] : 0.f, mean, std);
-  }
-}
-
-// Index that coordinate i of an axis of extent n >= 1 reads under a boundary mode: clamp (edge) or mirror without
-// repeating the face voxel (reflect, period 2(n-1): numpy.pad's modes for any pad width, extent 1 included).  reflect is
-// even in i, so one bounce costs no division; only a coordinate further than n-1 past a face pays the modulo.
-template <int MODE>
-__device__ __forceinline__ int bc_fold(int i, int n) {
-  if constexpr (MODE == TEM_BOUNDARY_EDGE) {
-    return min(max(i, 0), n - 1);
-  } else {
-    if (n == 1) return 0;
-    const int m = 2 * (n - 1);
-    i = i < 0 ? -i : i;
-    if (i >= m) i %= m;
-    return i < n ? i : m - i;
   }
 }
 

@@ -138,6 +138,104 @@ def _tile_kernels(lib, is3d, boundary="zeros"):
     return (gather, gname), (getattr(lib, sname), sname)
 
 
+def symmetries(is3d=True, kind="flips"):
+    """The symmetries of the cube (is3d) or the square that the training augmentation draws from (datasets.augment,
+    tem_augment_f32), as a list of (perm, flips) over the spatial axes (z, y, x) -- (y, x) for 2-D:
+    T(v) = flip(transpose(v, perm), axes a with flips[a]).
+
+    kind="flips": the identity permutation with every flip combination (8 members in 3-D, 4 in 2-D); kind="all": every
+    permutation with every flip combination (48 / 8).  The order is fixed -- an ensemble accumulates in fp32 in this
+    order: permutations in lexicographic order (itertools.permutations, identity first), and within one permutation
+    the flips as itertools.product((False, True), repeat=n), all-False first and the last axis changing fastest.  The
+    identity is member 0."""
+    import itertools
+    n = 3 if is3d else 2
+    if kind not in ("flips", "all"):
+        raise ValueError(f"symmetries: kind must be 'flips' or 'all', got {kind!r}")
+    perms = [tuple(range(n))] if kind == "flips" else list(itertools.permutations(range(n)))
+    return [(p, f) for p in perms for f in itertools.product((False, True), repeat=n)]
+
+
+def _check_ensemble(ensemble, is3d):
+    """None, or the members of `ensemble` ("flips", "all" or a non-empty sequence of symmetries) as 3-axis
+    ((p0, p1, p2), (f0, f1, f2)) tuples of ints.  A 2-D model takes 2-axis symmetries over (y, x), or 3-axis ones that
+    leave the section axis alone (perm[0] == 0, flips[0] false)."""
+    if ensemble is None:
+        return None
+    if isinstance(ensemble, str):
+        ensemble = symmetries(is3d, ensemble)           # raises on another string
+    try:
+        members = list(ensemble)
+    except TypeError:
+        raise ValueError(f"ensemble must be None, 'flips', 'all' or a sequence of (perm, flips), got {ensemble!r}")
+    if not members:
+        raise ValueError("ensemble must not be empty (None runs without one)")
+    out = []
+    for s in members:
+        try:
+            perm, flips = s
+            perm, flips = tuple(int(p) for p in perm), tuple(bool(f) for f in flips)
+        except (TypeError, ValueError):
+            raise ValueError(f"ensemble member {s!r} is not a (perm, flips) pair")
+        n = len(perm)
+        if n not in ((3,) if is3d else (2, 3)) or sorted(perm) != list(range(n)):
+            raise ValueError(f"ensemble member {s!r}: perm must be a permutation of the {3 if is3d else '2 (or 3)'} "
+                             f"spatial axes")
+        if len(flips) != n:
+            raise ValueError(f"ensemble member {s!r}: flips must have {n} entries, one per axis")
+        if n == 2:                                      # (y, x) of a section
+            perm, flips = (0, perm[0] + 1, perm[1] + 1), (False,) + flips
+        elif not is3d and (perm[0] != 0 or flips[0]):
+            raise ValueError(f"ensemble member {s!r} moves z: a 2-D model predicts section by section")
+        if (perm, flips) in out:
+            raise ValueError(f"ensemble member {s!r} is given twice")
+        out.append((perm, flips))
+    return [(p, tuple(int(f) for f in fl)) for p, fl in out]
+
+
+def _sym_kernels(lib, is3d, boundary="zeros"):
+    """The ensemble's (gather, accumulate) and their names.  gather(blk, block, lo, vol_shape, origins, ntile, edge,
+    sym, out, mean, std, stream) is _tile_kernels' gather under the symmetry sym = (perm, flips); "zeros" hands the
+    block over as the volume, which is what the zero-mode entry point sees.  accum(y, ntile, yedge, sym, acc, first,
+    divisor, stream) folds y back into acc."""
+    from . import _lib
+    gname, aname = (("tem_u8_tiles_to_f32_std_sym", "tem_f32_tiles_sym_accum") if is3d else
+                    ("tem_u8_tiles2d_to_f32_std_sym", "tem_f32_tiles2d_sym_accum"))
+    gfn, afn = getattr(lib, gname), getattr(lib, aname)
+    mode = {"zeros": 0, "reflect": _lib.TEM_BOUNDARY_REFLECT, "edge": _lib.TEM_BOUNDARY_EDGE}[boundary]
+    if mode == 0:
+        gather = lambda blk, block, lo, vol_shape, org, n, edge, sym, *rest: \
+            gfn(blk, *block, 0, 0, 0, *block, 0, org, n, edge, *sym[0], *sym[1], *rest)
+    else:
+        gather = lambda blk, block, lo, vol_shape, org, n, edge, sym, *rest: \
+            gfn(blk, *block, *lo, *vol_shape, mode, org, n, edge, *sym[0], *sym[1], *rest)
+    accum = lambda y, n, yedge, sym, *rest: afn(y, n, yedge, *sym[0], *sym[1], *rest)
+    return (gather, gname), (accum, aname)
+
+
+def _run_ensemble(syms, gather, gname, accum, aname, run, acc_box, stream, last_gather=None):
+    """One tile batch under every member of `syms` in order: gather(sym) cuts T_s(tiles) into the generator's input,
+    `run()` returns the generator's output (overwritten by the next run), and T_s^-1 of it is folded into the fp32
+    accumulator -- written by the first member, added to by the others, divided by len(syms) by the last -- all on
+    `stream`, so each accumulate precedes the run that overwrites y.  `acc_box` (a list) keeps the one accumulator of
+    the call: the first batch, the largest, allocates it and smaller batches use its head.  `last_gather()` is called
+    after the last member's gather.  Returns the accumulator of this batch: the mean."""
+    from . import _lib
+    k, acc = len(syms), None
+    for i, sym in enumerate(syms):
+        _lib.check(gather(sym), gname)
+        if i == k - 1 and last_gather is not None:
+            last_gather()
+        y = run()
+        if acc is None:
+            if not acc_box:
+                acc_box.append(torch.empty_like(y))
+            acc = acc_box[0][:y.shape[0]]
+        _lib.check(accum(y.data_ptr(), y.shape[0], y.shape[2], sym, acc.data_ptr(), int(i == 0),
+                         k if i == k - 1 else 1, stream), aname)
+    return acc
+
+
 class _OneSection:
     """A [y, x] array-like seen as a one-section stack [1, y, x] (basic slicing only, for predict_volume)."""
 
@@ -170,7 +268,7 @@ def _single_image(model, start, size):
 
 
 def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=False, outdimsize=None, buffer=None,
-                 rank=0, world_size=1, tile_batch=None, boundary="zeros"):
+                 rank=0, world_size=1, tile_batch=None, boundary="zeros", ensemble=None):
     """Predict the subvolume [start, start+size) (x,y,z order as in the reference) of a uint8
     array `volume` indexed [z, y, x].  Voxels outside the array read as 0 (the reference fetches
     them from the store) or, with boundary="reflect" / "edge", the voxel that `fold` names on every axis: the result
@@ -186,14 +284,24 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
 
     A 2-D model (generator_g.is3d False) predicts every section of [start[2], start[2] + size[2]) on its own
     (tile_plan_2d) through the 2-D tile kernels; it also takes one image `volume` [y, x] with 2-element (x, y) `start`
-    and `size`, and then returns [y, x] arrays."""
+    and `size`, and then returns [y, x] arrays.
+
+    ensemble=None runs the generator once per tile.  ensemble="flips" | "all" | a sequence of symmetries (see
+    `symmetries`; a 2-D model takes 2-axis members, or 3-axis ones that leave z alone) averages it over those
+    orientations, per tile batch and on the device: for each member s in order the tiles are gathered as T_s(tile)
+    (tem_u8_tiles*_to_f32_std_sym), the generator runs, and T_s^-1 of its output is accumulated in fp32
+    (tem_f32_tiles*_sym_accum: the first member writes, the others add, the last also divides by the member count);
+    the mean goes through the scatter kernel once.  No member is quantised before the mean and no copy of the volume
+    is made.  ValueError, before any GPU work: an empty sequence, a perm that is no permutation, flips of another
+    length, a member given twice, a member that moves z with a 2-D model."""
     from . import _lib
-    lib = H.require_gpu()
     gen = getattr(model, "generator_g", None)
     is3d = getattr(gen, "is3d", True)
+    syms = _check_ensemble(ensemble, is3d)
+    lib = H.require_gpu()
     if _single_image(model, start, size):
         res = predict_cube(np.asarray(volume)[None], tuple(start) + (0,), tuple(size) + (1,), model, meanstd_x,
-                           meanstd_y, fetch_input, outdimsize, buffer, rank, world_size, tile_batch, boundary)
+                           meanstd_y, fetch_input, outdimsize, buffer, rank, world_size, tile_batch, boundary, ensemble)
         return tuple(r[0] for r in res) if fetch_input else res[0]
     if outdimsize is None:
         outdimsize = model.outdimsize
@@ -214,6 +322,9 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
     nb = max(1, min(int(tile_batch or default_tile_batch(edge, is3d)), len(mine) or 1))
     tile = (edge, edge, edge) if is3d else (1, edge, edge)               # (D, H, W) of one generator input
     (gather, gname), (scatter, sname) = _tile_kernels(lib, is3d, boundary)
+    if syms is not None:
+        (sgather, sgname), (accum, aname) = _sym_kernels(lib, is3d, boundary)
+        acc = []                                # the fp32 accumulator, allocated by the first (largest) batch
     stream = H.current_stream()
     for c0 in range(0, len(mine), nb):
         chunk = mine[c0:c0 + nb]
@@ -225,9 +336,16 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
             tiles = plan.x
         else:
             plan, tiles = None, torch.empty((n,) + tile + (1,), dtype=torch.float32, device=dev)
-        _lib.check(gather(vol.data_ptr(), (Z, Y, X), (0, 0, 0), (Z, Y, X), org.data_ptr(), n, edge, tiles.data_ptr(),
-                          float(meanstd_x[0]), float(meanstd_x[1]), stream), gname)
-        data_y = plan.run() if plan is not None else model.predict(tiles).contiguous()
+        run = plan.run if plan is not None else (lambda: model.predict(tiles).contiguous())
+        if syms is None:
+            _lib.check(gather(vol.data_ptr(), (Z, Y, X), (0, 0, 0), (Z, Y, X), org.data_ptr(), n, edge, tiles.data_ptr(),
+                              float(meanstd_x[0]), float(meanstd_x[1]), stream), gname)
+            data_y = run()
+        else:                                   # the mean over the members
+            data_y = _run_ensemble(
+                syms, lambda sym: sgather(vol.data_ptr(), (Z, Y, X), (0, 0, 0), (Z, Y, X), org.data_ptr(), n, edge, sym,
+                                          tiles.data_ptr(), float(meanstd_x[0]), float(meanstd_x[1]), stream),
+                sgname, accum, aname, run, acc, stream)
         yedge = data_y.shape[2]
         assert yedge - 2 * tpad == outdimsize, (yedge, tpad, outdimsize)
         _lib.check(scatter(data_y.data_ptr(), n, yedge, tpad, idx.data_ptr(), out_buffer.data_ptr(), OZ, OY, OX,
@@ -384,7 +502,7 @@ def chunk_plan(start, size, outdimsize, buffer, vol_shape, chunk_tiles, rank=0, 
 
 
 def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, chunk_tiles=None, tile_batch=None,
-                   outdimsize=None, buffer=None, rank=0, world_size=1, stats=None, boundary="zeros"):
+                   outdimsize=None, buffer=None, rank=0, world_size=1, stats=None, boundary="zeros", ensemble=None):
     """Out-of-core predict_cube: the subvolume [start, start+size) (x,y,z order) of a uint8 array-like `volume`
     indexed [z, y, x] (ndarray, np.memmap, h5py / zarr dataset: `.shape` and basic slicing are all it needs) is
     predicted chunk by chunk (chunk_plan) into `out`, a writable uint8 array-like of shape (size[2], size[1], size[0])
@@ -402,12 +520,18 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
     host thread's read and write seconds and the number of chunks.
 
     A 2-D model streams chunks of chunk_plan(..., is3d=False) through the same pipeline with the 2-D tile kernels;
-    it also takes one image `volume` [y, x] with 2-element (x, y) `start` / `size` (`out` is then [y, x])."""
+    it also takes one image `volume` [y, x] with 2-element (x, y) `start` / `size` (`out` is then [y, x]).
+
+    `ensemble` is predict_cube's: every tile batch runs once per member between its gathers and its one scatter, with
+    one fp32 accumulator of a batch's output for the whole call; a chunk's staging buffer is released for the next
+    upload after the last member's gather of its last batch.  The rest of the pipeline, the chunk plan and the
+    footprints are those of ensemble=None, and the result still equals predict_cube's bit for bit."""
     import time
     from concurrent.futures import ThreadPoolExecutor
     from . import _lib
-    lib = H.require_gpu()
     gen = model.generator_g
+    syms = _check_ensemble(ensemble, getattr(gen, "is3d", True))
+    lib = H.require_gpu()
     if not hasattr(gen, "plan"):
         raise TypeError("predict_volume needs a generator with launch plans (EM2EM or a saved model)")
     if _single_image(model, start, size):
@@ -416,7 +540,8 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
         if out is None:
             out = np.zeros((size[1], size[0]), np.uint8)
         predict_volume(_OneSection(volume), tuple(start) + (0,), tuple(size) + (1,), model, meanstd_x, meanstd_y,
-                       _OneSection(out), chunk_tiles, tile_batch, outdimsize, buffer, rank, world_size, stats, boundary)
+                       _OneSection(out), chunk_tiles, tile_batch, outdimsize, buffer, rank, world_size, stats, boundary,
+                       ensemble)
         return out
     is3d = gen.is3d
     vol_shape = tuple(int(v) for v in volume.shape)
@@ -428,6 +553,9 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
     edge = od + 2 * buf
     tile = (edge, edge, edge) if is3d else (1, edge, edge)               # (D, H, W) of one generator input
     (gather, gname), (scatter, sname) = _tile_kernels(lib, is3d, boundary)
+    if syms is not None:
+        (sgather, sgname), (accum, aname) = _sym_kernels(lib, is3d, boundary)
+        acc = []                                # the fp32 accumulator, allocated by the first (largest) batch
     if out is None:
         out = np.zeros((size[2], size[1], size[0]), np.uint8)
     elif tuple(out.shape) != (size[2], size[1], size[0]):
@@ -500,12 +628,21 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
                     plan = None                              # let the plan cache release an evicted plan's buffers
                     plan = gen.plan((m,) + tile + (1,))
                 t = int(first[k]) + b0
-                _lib.check(gather(dev_in[s].data_ptr(), gdims[k], lo, vol_shape, org.data_ptr() + 12 * t, m, edge,
-                                  plan.x.data_ptr(), float(meanstd_x[0]), float(meanstd_x[1]), compute.cuda_stream),
-                           gname)
-                if b0 + m == n:
-                    gathered[k] = compute.record_event()
-                data_y = plan.run(compute.cuda_stream)
+                if syms is None:
+                    _lib.check(gather(dev_in[s].data_ptr(), gdims[k], lo, vol_shape, org.data_ptr() + 12 * t, m, edge,
+                                      plan.x.data_ptr(), float(meanstd_x[0]), float(meanstd_x[1]), compute.cuda_stream),
+                               gname)
+                    if b0 + m == n:
+                        gathered[k] = compute.record_event()
+                    data_y = plan.run(compute.cuda_stream)
+                else:
+                    last_gather = (lambda: gathered.__setitem__(k, compute.record_event())) if b0 + m == n else None
+                    data_y = _run_ensemble(
+                        syms, lambda sym: sgather(dev_in[s].data_ptr(), gdims[k], lo, vol_shape, org.data_ptr() + 12 * t,
+                                                  m, edge, sym, plan.x.data_ptr(), float(meanstd_x[0]),
+                                                  float(meanstd_x[1]), compute.cuda_stream),
+                        sgname, accum, aname, lambda: plan.run(compute.cuda_stream), acc, compute.cuda_stream,
+                        last_gather)
                 assert data_y.shape[2] - 2 * tpad == od, (data_y.shape, tpad, od)
                 _lib.check(scatter(data_y.data_ptr(), m, data_y.shape[2], tpad, idx.data_ptr() + 12 * t,
                                    dev_out[s].data_ptr(), OZ, OY, OX, float(meanstd_y[0]), float(meanstd_y[1]),
@@ -589,7 +726,9 @@ def predict_cube_from_saved_model(location, start, size, cloudrun, model_dir, fe
 def predict_volume_from_saved_model(volume, start, size, model_dir, out=None, **kw):
     """predict_volume with the generator and statistics exported by save_model to `model_dir` (the out-of-core
     sibling of predict_cube_from_saved_model); `kw` are predict_volume's chunk_tiles, tile_batch, rank, world_size,
-    stats and boundary ("zeros", "reflect" or "edge": what a voxel outside the volume reads)."""
+    stats, boundary ("zeros", "reflect" or "edge": what a voxel outside the volume reads) and ensemble (None, "flips",
+    "all" or a sequence of symmetries: the orientations the generator's output is averaged over).  The reference's
+    signatures, predict_ng_cube and predict_cube_from_saved_model, take neither keyword and run unensembled."""
     model = _load_saved(model_dir)
     return predict_volume(_local_volume(volume), start, size, model, model.meta["meanstd_x"], model.meta["meanstd_y"],
                           out=out, outdimsize=model.outdimsize, buffer=model.buffer, **kw)
