@@ -98,6 +98,40 @@ def test_predict_cube_260_config4(tmp_path):
     assert checked == 8 * 72 ** 3
 
 
+def test_predict_is_independent_of_the_tile_batch_past_the_span_limits(tmp_path):
+    """48 tiles of 132^3 (a 384 x 384 x 288 request): tile_batch=40 lies past stable_tile_batch(132) = 31, where g.d1b's
+    input outgrows conv_s2_k's 2^29-element span and a batch of 32 or more would run conv_direct_k while the remainder
+    batch keeps conv_s2_k.  The request is lowered to 31: (1) predict_cube equals its tile-by-tile run bit for bit, (2)
+    predict_volume with chunks of all 48 tiles (batches of 31 + 17) equals predict_cube with the default batch, and
+    reports the batch it used; (3) the kernels of the cached plans are the ones utils.plan_routes names on the host."""
+    from oracle import graph
+    from transfer_em_amd.cgan import EM2EM
+    from transfer_em_amd.utils import plan_routes, predict_cube, predict_volume, stable_tile_batch, tile_plan
+    rng = np.random.default_rng(9)
+    V = rng.integers(0, 256, (324, 420, 420), dtype=np.uint8)               # request + 18 voxels of halo per face
+    model = EM2EM(132, "span", checkpoint_root=str(tmp_path))
+    P = scaled_params(graph.generator_param_shapes(True), 4)
+    P["f2"] = P["f2"] * 20
+    model.generator_g.params.load_dict(P)
+    ms_x, ms_y = (0.02, 0.58), (-0.1, 0.4)
+    start, size = (18, 18, 18), (384, 384, 288)
+    assert len(tile_plan(start, size, model.outdimsize, model.buffer)[3]) == 48
+    assert stable_tile_batch(132, True) == 31
+    big = predict_cube(V, start, size, model, ms_x, ms_y, tile_batch=40)
+    ran = model.generator_g.plan_kernels()
+    assert sorted(ran) == [17, 31]                                          # 40 was lowered: a full batch and the remainder
+    for n, kernels in ran.items():
+        assert kernels == dict(plan_routes(132, n)), (n, kernels)
+    one = predict_cube(V, start, size, model, ms_x, ms_y, tile_batch=1)
+    assert big.shape == (288, 384, 384) and big.dtype == np.uint8 and np.array_equal(big, one)
+    assert big.std() > 20
+    stats = {}
+    vol = predict_volume(V, start, size, model, ms_x, ms_y, chunk_tiles=(3, 4, 4), tile_batch=40, stats=stats)
+    assert stats["chunks"] == 1 and stats["tile_batch"] == 31
+    dflt = predict_cube(V, start, size, model, ms_x, ms_y)
+    assert np.array_equal(vol, dflt) and np.array_equal(dflt, one)
+
+
 def test_simple_training_notebook_flow(tmp_path, capsys):
     """examples/simple_training.ipynb:52-77 end to end on the HIP path: uint8 images -> reflect-padded,
     standardised datasets -> EM2EM(132, 2-D).train(...) with a checkpoint per epoch -> predict -> restore."""

@@ -383,7 +383,10 @@ static int run(const tem_bww_args *a, hipStream_t st, bool dry, int *nslab_out, 
   const int64_t gspan = ((int64_t)(g.D - 1) * g.sD + (int64_t)(g.H - 1) * g.sH + (int64_t)(g.W - 1) * g.sW + g.C) * 4;
   if (gspan > (int64_t)0x7fffffff) return TEM_EUNSUPPORTED;
   p.gspan = (int)gspan;
-  p.xspan = (int)(((int64_t)(x.D - 1) * x.sD + (int64_t)(x.H - 1) * x.sH + (int64_t)(x.W - 1) * x.sW + 1) * 4);
+  // ... and one sample of x: its loads take byte offsets inside the sample's descriptor as well
+  const int64_t xspan = ((int64_t)(x.D - 1) * x.sD + (int64_t)(x.H - 1) * x.sH + (int64_t)(x.W - 1) * x.sW + 1) * 4;
+  if (xspan > (int64_t)0x7fffffff) return TEM_EUNSUPPORTED;
+  p.xspan = (int)xspan;
   { static int dbg = -1; if (dbg < 0) dbg = tem_env_int("TEM_DEBUG_FLAGS", 0); p.dbg = dbg; }
   if (nslab_out) *nslab_out = nblocks;
   if (name) snprintf(name, name_len, "bww_c1m_k<%d>", CO);

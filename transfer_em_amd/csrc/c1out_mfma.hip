@@ -155,7 +155,9 @@ __global__ __launch_bounds__(256, 2) void c1out_mfma_k(Dev p) {
     float gv = 1.f;
     if (GATE && j >= 2) gv = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(grs, gbase, ozf * p.gD * 4, 0));
     if (j + 1 < nplanes) p_phase(anow, (j + 1) & 1);         // block-uniform
-    load_plane(aload, j + 3 < nplanes ? iz0 + j + 3 : -1);   // (past the run: out of range, moves no data)
+    // (past the run: the fragment is never used.  Below 2^30 bytes of input the +2^30 marker is out of range and moves no
+    // data; an unpadded view between 2^30 and 2^31 bytes has it fetch elements of the view, which are dropped)
+    load_plane(aload, j + 3 < nplanes ? iz0 + j + 3 : -1);
     // ---- shifted sum: plane j feeds output planes j (dz 0), j - 1 (dz 1), j - 2 (dz 2): slot (j - dz) mod 3
     const float *pb = pbase + (j & 1) * PBUF;
 #pragma unroll
@@ -391,6 +393,9 @@ static int dispatch(const tem_conv_args *a, hipStream_t st, bool dry, char *name
   if (!enabled) return TEM_EUNSUPPORTED;
   if (o0.N != i0.N) return TEM_ESHAPE;
   if (!fits29(i0) || !fits29(o0)) return TEM_EUNSUPPORTED;
+  // a plane of the zero padding is a plane term of 2^30 bytes added to a valid in-plane offset (load_plane): the sum has to
+  // lie past the descriptor's range, so a padded input stays below 2^30 bytes
+  if (a->pd > 0 && view_span(i0) >= ((int64_t)1 << 28)) return TEM_EUNSUPPORTED;
   if (((uintptr_t)i0.ptr & 15) || i0.sW % 4 || i0.sH % 4 || i0.sD % 4 || i0.sN % 4) return TEM_EUNSUPPORTED;
   Dev p{};
   p.in = i0.ptr; p.iN = (int)i0.sN; p.iD = (int)i0.sD; p.iH = (int)i0.sH; p.iW = (int)i0.sW;

@@ -603,6 +603,12 @@ int dispatch(const tem_conv_args *a, hipStream_t st, bool dry, char *name, int n
     if (i0.C % 8) return TEM_EUNSUPPORTED;                 // a sub-image (8 channels) has one source
   }
   p.N = i0.N; p.D = i0.D; p.H = i0.H; p.W = i0.W;
+  {
+    // the DMA offsets inside a plane are bytes in a signed 32-bit register (voff0 / voff1), and so are span0 / span1
+    const int64_t ps0 = (int64_t)(i0.H - 1) * i0.sH + (int64_t)(i0.W - 1) * i0.sW + i0.C;
+    const int64_t ps1 = a->in1.ptr ? (int64_t)(i0.H - 1) * a->in1.sH + (int64_t)(i0.W - 1) * a->in1.sW + a->in1.C : 0;
+    if (ps0 >= ((int64_t)1 << 29) || ps1 >= ((int64_t)1 << 29)) return TEM_EUNSUPPORTED;
+  }
   p.span0 = (int)(((int64_t)(i0.H - 1) * p.i0H + (int64_t)(i0.W - 1) * p.i0W + i0.C) * 4);
   p.span1 = a->in1.ptr ? (int)(((int64_t)(i0.H - 1) * p.i1H + (int64_t)(i0.W - 1) * p.i1W + a->in1.C) * 4) : p.span0;
   p.u = a->w;

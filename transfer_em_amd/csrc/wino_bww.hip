@@ -482,6 +482,12 @@ static int run_bww(const tem_bww_args *a, hipStream_t st, int mode, int *nslab, 
   if (variant < 0 || dy.N != i0.N) return TEM_EUNSUPPORTED;
   if (dy.D != i0.D + 2 * a->pd - 2 || dy.H != i0.H + 2 * a->ph - 2 || dy.W != i0.W + 2 * a->pw - 2) return TEM_ESHAPE;
   p.N = i0.N; p.D = i0.D; p.H = i0.H; p.W = i0.W;
+  {
+    // the DMA offsets inside a plane are bytes in a signed 32-bit register (voff0 / voff1), and so are span0 / span1
+    const int64_t ps0 = (int64_t)(i0.H - 1) * i0.sH + (int64_t)(i0.W - 1) * i0.sW + i0.C;
+    const int64_t ps1 = a->in1.ptr ? (int64_t)(i0.H - 1) * a->in1.sH + (int64_t)(i0.W - 1) * a->in1.sW + a->in1.C : 0;
+    if (ps0 >= ((int64_t)1 << 29) || ps1 >= ((int64_t)1 << 29)) return TEM_EUNSUPPORTED;
+  }
   p.span0 = (int)(((int64_t)(i0.H - 1) * p.i0H + (int64_t)(i0.W - 1) * p.i0W + i0.C) * 4);
   p.span1 = a->in1.ptr ? (int)(((int64_t)(i0.H - 1) * p.i1H + (int64_t)(i0.W - 1) * p.i1W + a->in1.C) * 4) : p.span0;
   if (((int64_t)(dy.D - 1) * dy.sD + (int64_t)(dy.H - 1) * dy.sH + (int64_t)(dy.W - 1) * dy.sW + dy.C) >= ((int64_t)1 << 29))

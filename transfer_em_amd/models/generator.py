@@ -352,6 +352,13 @@ class UNetGenerator:
 
     MAX_PLANS = 2            # e.g. the full chunk and the remainder chunk of one tiled prediction
 
+    def plan_kernels(self):
+        """{batch N: {layer: kernel symbol}} of the cached inference plans: the convolution each layer's launch runs
+        (Launch.meta["kernel"]), which utils.plan_routes predicts on the host."""
+        return {key[0]: {l.name[2:]: l.meta["kernel"] for l in plan.launches
+                         if l.name.startswith("g.") and "kernel" in l.meta and l.name[2:] in plan.act}
+                for key, plan in self._plans.items()}
+
     def clear_plans(self):
         """Release the cached inference plans (their activation buffers go back to the allocator)."""
         self._plans.clear()

@@ -80,16 +80,128 @@ TILE_BATCH_MAX_2D = 4096     # cap of the 2-D batch (see default_tile_batch)
 
 
 def default_tile_batch(edge, is3d=True):
-    """Tiles per generator launch sequence when the caller gives none.  3-D: TILE_BATCH.  2-D tiles are ~100x smaller,
-    so the batch is sized by bytes instead: as many tiles as fit the activations TILE_BATCH tiles of the 132^3 model
-    pin (~8 GB; 2-D 132: ~2,500 tiles), capped at TILE_BATCH_MAX_2D.  A prediction runs full batches and one remainder,
+    """Tiles per generator launch sequence when the caller gives none.  3-D: TILE_BATCH, or stable_tile_batch where
+    that is smaller (the 260 model: 2).  2-D tiles are ~100x smaller, so the batch is sized by bytes instead: as many
+    tiles as fit the activations TILE_BATCH tiles of the 132^3 model pin (~8 GB; 2-D 132: ~2,500 tiles), capped at
+    TILE_BATCH_MAX_2D.  A prediction runs full batches and one remainder,
     and the generator caches MAX_PLANS = 2 plan shapes; the cap keeps the small models' batch below the size of most
     requests, so that their full-batch plan is reused from request to request instead of every request's size
     becoming a plan of its own."""
     if is3d:
-        return TILE_BATCH
+        return min(TILE_BATCH, stable_tile_batch(edge, True))
     budget = TILE_BATCH * plan_bytes_per_tile(132, True)
     return max(1, min(TILE_BATCH_MAX_2D, budget // plan_bytes_per_tile(edge, False)))
+
+
+def _dry_view(v, ptr, N, dims, C, strides=None):
+    """Fill tem_view `v`: N x dims x C at `ptr` (never dereferenced), dense unless `strides` = (sN, sD, sH, sW)."""
+    D, H, W = dims
+    v.ptr, v.N, v.D, v.H, v.W, v.C = ptr, N, D, H, W, C
+    v.sN, v.sD, v.sH, v.sW = strides or (D * H * W * C, H * W * C, W * C, C)
+
+
+def plan_routes(edge, N, is3d=True, dtype=torch.float32, wf=8):
+    """Kernel symbol of each of the 12 convolution launches of the generator's inference plan (GenForward with
+    in_pad = 0, out_crop = 0) on a batch of N tiles of edge `edge`, as an OrderedDict layer -> name: what
+    Launch.meta["kernel"] of that plan holds (a transposed layer on its direct form reads "convT_direct_k", without the
+    template arguments).  Asked of the library's dry queries (tem_conv_is_tiled, the bf16 describe
+    entry points) on the plan's dense views with made-up pointers, so no device is needed.  The layers, channels and
+    geometry come from generator_blocks / generator_edges / skip_crop, the choice between the Winograd-domain and the
+    plain kernel copy is conv_launch's."""
+    import ctypes as C
+    from collections import OrderedDict
+    from . import _lib
+    from .models.generator import generator_blocks, generator_edges, skip_crop
+    lib = _lib.load()
+    bf16 = dtype == torch.bfloat16
+    esz = 2 if bf16 else 4
+    blocks, e = generator_blocks(is3d, wf), generator_edges(edge)
+    dims = lambda n: (n if is3d else 1, n, n)
+    src = dict(zip(blocks, ["in"] + list(blocks)[:-1]))                 # each layer reads the one before it ...
+    skips = {"mid": "d2a", "f1": "d1a"}                                 # ... and these two a cropped skip tensor as well
+    ptr = {k: 0x7f0000000000 + (i << 40) for i, k in enumerate(e)}     # one made-up 16-byte-aligned base per tensor
+    ch = {"in": 1}
+    routes = OrderedDict()
+    for name, spec in blocks.items():
+        T = spec.kind != "conv"
+        s_in, c1 = src[name], 0
+        a = _lib.tem_conv_args()
+        _dry_view(a.in0, ptr[s_in], N, dims(e[s_in]), ch[s_in])
+        if name in skips:                                               # GenForward.skip0 / skip1: a window of the skip tensor
+            sk = skips[name]
+            c1, n = ch[sk], e[sk]
+            lo, _ = skip_crop(n, e[s_in])
+            st = (dims(n)[0] * n * n * c1, n * n * c1, n * c1, c1)
+            off = lo * ((st[1] if is3d else 0) + st[2] + st[3])
+            _dry_view(a.in1, ptr[sk] + esz * off, N, dims(e[s_in]), c1, st)
+        assert spec.in_ch == ch[s_in] + c1, (name, spec)
+        ch[name] = spec.out_ch
+        _dry_view(a.out0, ptr[name], N, dims(e[name]), spec.out_ch)
+        a.w = 0x7e0000000000
+        k, s, p = spec.kernel, spec.stride, (1 if T else 0)            # VALID convolutions; ConvTranspose 'same'
+        a.kd, a.kh, a.kw = H._k3(k, is3d)
+        a.sd, a.sh, a.sw = H._s3(s, is3d)
+        a.pd, a.ph, a.pw = H._p3(p, is3d)
+        a.ep.slope = 1.0 if spec.activation == "linear" else H.LEAKY
+        buf = C.create_string_buffer(96)
+        if bf16:
+            rc = (lib.tem_conv_transpose_bf16_describe if T else lib.tem_conv_bf16_describe)(C.byref(a), buf, 96)
+            routes[name] = buf.value.decode() if rc == 0 else f"rc={rc}"
+            continue
+        vox = a.out0.D * a.out0.H * a.out0.W
+        if not T and is3d and k == 3 and H.wino_channels(spec.in_ch, spec.out_ch) and vox >= H.WINO_MIN_VOXELS:
+            a.w_layout = _lib.TEM_W_WINOGRAD
+            if lib.tem_conv_is_tiled(C.byref(a), 0, buf, 96) == 1:
+                routes[name] = buf.value.decode()
+                continue
+        a.w_layout = _lib.TEM_W_TAP_CI_CO
+        tiled = lib.tem_conv_is_tiled(C.byref(a), int(T), buf, 96) == 1
+        routes[name] = buf.value.decode() if (tiled or not T) else "convT_direct_k"
+    return routes
+
+
+def route_key(kernel):
+    """What of a kernel symbol decides the order of an output's sum: the kernel function.  Its template arguments past
+    the channel counts (tiles per wave, waves, z-run lengths: conv_lds_k's MTW changes at N = 5 on the 74 model) are
+    picked by the planners' cost models from the block count; they deal outputs to waves and leave each output's own
+    chain of fused multiply-adds alone."""
+    return kernel.split("<", 1)[0]
+
+
+_STABLE_BATCH = {}
+STABLE_BATCH_SEARCH_MAX = 1 << 20     # past any batch a card can hold (2-D 74: 2^20 tiles pin ~0.6 TB)
+
+
+def stable_tile_batch(edge, is3d=True, dtype=torch.float32):
+    """The largest tile batch N for which every launch of the generator's inference plan runs the kernel it runs at
+    N = 1 (plan_routes, compared by route_key).  The tiled kernels address their operands with 32-bit offsets; a view past a kernel's span
+    limit goes to another kernel, which sums in another order.  Up to this N a full batch, a remainder batch and a
+    single tile all run the same kernels, which is what makes the batched pipeline equal the tile-by-tile one bit for
+    bit; predict_cube and predict_volume lower a larger `tile_batch` to it.  A view only grows with N, so every limit
+    is crossed once and the routes change at most once per limit: the search doubles N until a route changes, then
+    bisects.  Host only (dry queries); cached per (edge, is3d, dtype).  STABLE_BATCH_SEARCH_MAX if nothing changes
+    below it."""
+    key = (int(edge), bool(is3d), dtype)
+    if key not in _STABLE_BATCH:
+        keys = lambda n: [route_key(k) for k in plan_routes(edge, n, is3d, dtype).values()]
+        base = keys(1)
+        same = lambda n: keys(n) == base
+        lo = 1
+        while lo < STABLE_BATCH_SEARCH_MAX and same(min(2 * lo, STABLE_BATCH_SEARCH_MAX)):
+            lo = min(2 * lo, STABLE_BATCH_SEARCH_MAX)
+        hi = min(2 * lo, STABLE_BATCH_SEARCH_MAX)          # same(lo), and not same(hi) unless lo reached the cap
+        while hi - lo > 1:
+            mid = (lo + hi) // 2
+            lo, hi = (mid, hi) if same(mid) else (lo, mid)
+        _STABLE_BATCH[key] = lo
+    return _STABLE_BATCH[key]
+
+
+def _effective_batch(requested, edge, is3d, most):
+    """Tiles per generator launch sequence: the request (or the default), at most `most` tiles and at most
+    stable_tile_batch (fp32: the precision the inference plans run in)."""
+    nb = int(requested or default_tile_batch(edge, is3d))
+    return max(1, min(nb, stable_tile_batch(edge, is3d, torch.float32), most))
 
 
 BOUNDARIES = ("zeros", "reflect", "edge")     # what a tile voxel outside the volume reads
@@ -282,6 +394,11 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
     every tile's interior into the uint8 output volume (tem_f32_tiles_unstd_to_u8).  Tile geometry, halo and
     the "multiple of 6" quirk are the reference's (tile_plan).
 
+    `tile_batch` tiles run per launch sequence (default_tile_batch when None).  A request above stable_tile_batch(edge,
+    is3d) is lowered to it, not refused: past it a layer's views outgrow a tiled kernel's 32-bit span, a full batch
+    would run another kernel than the remainder batch, and the result would depend on the batch.  For every
+    `tile_batch` the result is therefore bit-identical to tile_batch=1.
+
     A 2-D model (generator_g.is3d False) predicts every section of [start[2], start[2] + size[2]) on its own
     (tile_plan_2d) through the 2-D tile kernels; it also takes one image `volume` [y, x] with 2-element (x, y) `start`
     and `size`, and then returns [y, x] arrays.
@@ -319,7 +436,7 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
     out_buffer = torch.zeros((rnd(z) if is3d else z, rnd(y), rnd(x)), dtype=torch.uint8, device=dev)
     OZ, OY, OX = out_buffer.shape
     mine = list(range(rank, len(rois), world_size))
-    nb = max(1, min(int(tile_batch or default_tile_batch(edge, is3d)), len(mine) or 1))
+    nb = _effective_batch(tile_batch, edge, is3d, len(mine) or 1)
     tile = (edge, edge, edge) if is3d else (1, edge, edge)               # (D, H, W) of one generator input
     (gather, gname), (scatter, sname) = _tile_kernels(lib, is3d, boundary)
     if syms is not None:
@@ -516,8 +633,10 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
     in order on one stream) -> D2H on a second copy stream into a pinned output buffer -> the host thread writes the
     chunk's interior into `out`.  Staging is double-buffered (pinned and device, input and output), so the reads,
     copies and writes of neighbouring chunks run while the GPU computes.  Ranks (rank / world_size) take chunks
-    round-robin and write disjoint boxes of a shared `out`; no collective is used.  `stats` (a dict) receives the
-    host thread's read and write seconds and the number of chunks.
+    round-robin and write disjoint boxes of a shared `out`; no collective is used.  `tile_batch` is predict_cube's: a
+    chunk runs in batches of at most that many tiles, lowered to stable_tile_batch(edge, is3d) where it is larger.
+    `stats` (a dict) receives the host thread's read and write seconds, the number of chunks and the tile batch used
+    (`tile_batch`).
 
     A 2-D model streams chunks of chunk_plan(..., is3d=False) through the same pipeline with the 2-D tile kernels;
     it also takes one image `volume` [y, x] with 2-element (x, y) `start` / `size` (`out` is then [y, x]).
@@ -571,7 +690,7 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
     gdims = [c.block if min(c.block) > 0 else (1, 1, 1) for c in chunks]
     in_bytes = [int(np.prod(g)) for g in gdims]
     out_bytes = [int(np.prod(c.dims)) for c in chunks]
-    nb = max(1, min(int(tile_batch or default_tile_batch(edge, is3d)), max(len(c.tiles) for c in chunks)))
+    nb = st["tile_batch"] = _effective_batch(tile_batch, edge, is3d, max(len(c.tiles) for c in chunks))
     dev = model.device
     compute = torch.cuda.current_stream(dev)
     h2d, d2h = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
