@@ -338,6 +338,20 @@ int tem_f32_tiles2d_unstd_to_u8(const float *y, int32_t ntile, int32_t yedge, in
                                 uint8_t *out, int32_t OZ, int32_t OY, int32_t OX, float mean, float std,
                                 tem_stream_t stream);
 
+/* One level of a mip pyramid of a uint8 block (tiled inference, after the scatter).  src[D][H][W] is dense; only its
+ * box [0, vD) x [0, vH) x [0, vW) is valid (0 <= v <= dim: a block of whole tiles holds predictions past the ROI).
+ * dst is dense [ceil(D / fz)][ceil(H / 2)][ceil(W / 2)]: y and x pool by 2, z by fz = 2 (3-D models) or 1 (2-D models:
+ * sections are not pooled).  dst voxel (z, y, x) is the mean of its children (fz z + a, 2y + b, 2x + c), a < fz,
+ * b, c < 2, that lie inside the valid box -- cnt = 1, 2, 4 or 8 of them -- rounded half up in integers:
+ *   dst = (sum + (cnt >> 1)) >> log2(cnt);   no valid child: 0
+ * Source bytes outside the valid box are never read.  Every byte of dst is written exactly once and nothing outside
+ * dst is touched; src and dst must not overlap.  Any alignment of src, dst and W (aligned rows take wider loads and
+ * stores; the bytes are the same).  A further level is a further call on dst with the valid extents
+ * (ceil(vD / fz), ceil(vH / 2), ceil(vW / 2)).
+ * TEM_EINVAL, without a launch: a null pointer, a dimension below 1, a valid extent outside [0, dim], fz not 1 or 2. */
+int tem_u8_pool2(const uint8_t *src, int32_t D, int32_t H, int32_t W, int32_t vD, int32_t vH, int32_t vW, int32_t fz,
+                 uint8_t *dst, tem_stream_t stream);
+
 /* Random augmentation of one cached sample (datasets.py:123-155) with host-drawn parameters:
  *   dst = reverse(transpose(src, perm = (p0,p1,p2)), dims with f_k != 0) * scale + shift
  * src is a dense single-channel (D,H,W) volume (2-D: D == 1, p0 must be 0); dst has extents

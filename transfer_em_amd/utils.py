@@ -379,8 +379,100 @@ def _single_image(model, start, size):
     return False
 
 
+def max_mips(outdimsize):
+    """Levels of the mip pyramid that tiles of `outdimsize` voxels allow (the tile plan's outdimsize, i.e. after the
+    "multiple of 6" quirk): the largest L with outdimsize % 2^L == 0.  Chunks are boxes of whole tiles and tiles start
+    at multiples of outdimsize, so up to this L every level-l voxel has all its level-0 voxels in one chunk and a chunk
+    pools on its own.  96 (the 132 model) -> 5, 36 (74) -> 2, 222 (260) -> 1; an odd outdimsize -> 0."""
+    od, n = int(outdimsize), 0
+    while od >= 2 and od % 2 == 0:
+        od, n = od // 2, n + 1
+    return n
+
+
+def _plan_outdimsize(outdimsize):
+    """tile_plan's outdimsize: the "multiple of 6" quirk applied."""
+    return outdimsize - outdimsize % 6 if outdimsize // 6 != 0 else outdimsize
+
+
+def _check_mips(mips, outdimsize):
+    """The number of pooled levels L >= 0 that `mips` (None or an integer) asks for, checked against
+    max_mips(outdimsize) of the tile plan's outdimsize."""
+    import operator
+    if mips is None:
+        return 0
+    limit = max_mips(outdimsize)
+    try:
+        if isinstance(mips, (bool, np.bool_)):
+            raise TypeError
+        L = operator.index(mips)
+    except TypeError:
+        raise ValueError(f"mips must be None or an integer in [0, {limit}], got {mips!r}")
+    if not 0 <= L <= limit:
+        raise ValueError(f"mips={L} is outside [0, {limit}]: tiles of {outdimsize} voxels pool on their own for at most "
+                         f"max_mips({outdimsize}) = {limit} levels (outdimsize % 2^mips must be 0)")
+    return L
+
+
+def mip_shapes(size, mips, is3d=True):
+    """Shapes (z, y, x) of the mips + 1 levels of the pyramid of a prediction of `size` = (x, y, z): level 0 is
+    (size[2], size[1], size[0]) and every further level ceil(n / f) per axis, f = (2, 2, 2) for a 3-D model and
+    (1, 2, 2) for a 2-D one (sections are not pooled).  A 2-element `size` (x, y), the single-image form, gives
+    (y, x) shapes."""
+    if len(size) == 2:
+        return [s[1:] for s in mip_shapes(tuple(size) + (1,), mips, False)]
+    shape, shapes = (int(size[2]), int(size[1]), int(size[0])), []
+    for _ in range(int(mips) + 1):
+        shapes.append(shape)
+        shape = (-(-shape[0] // 2) if is3d else shape[0], -(-shape[1] // 2), -(-shape[2] // 2))
+    return shapes
+
+
+def mip_box(chunk, level, is3d=True):
+    """Where level `level` of a VolumeChunk's pyramid goes: (box, extent) with `box` the (z, y, x) (lo, hi) pairs in
+    that level's output array and `extent` = hi - lo, the leading sub-block of the chunk's level block (chunk.dims
+    divided by 2^level on the pooled axes) that holds it.  A pooled axis has lo = base >> level, exact for level <=
+    max_mips, and extent ceil(out_box extent / 2^level); z of a 2-D model is not pooled."""
+    box = []
+    for d, (lo, hi) in enumerate(chunk.out_box):
+        l = level if (is3d or d > 0) else 0
+        b, n = chunk.base[d] >> l, max(hi - lo, 0)
+        box.append((b, b + -(-n // (1 << l))))
+    return tuple(box), tuple(hi - lo for lo, hi in box)
+
+
+def _check_mip_outs(out, size, L, is3d=True):
+    """predict_volume's `out` under mips = L >= 1: None, or a sequence of L + 1 array-likes of exactly mip_shapes."""
+    if out is None:
+        return None
+    shapes = mip_shapes(size, L, is3d)
+    if hasattr(out, "shape") or not hasattr(out, "__len__"):
+        raise ValueError(f"with mips={L}, out must be None or a sequence of {L + 1} arrays (one per level), got "
+                         f"{type(out).__name__}")
+    outs = list(out)
+    if len(outs) != L + 1:
+        raise ValueError(f"with mips={L}, out must hold {L + 1} levels, got {len(outs)}")
+    for l, (o, s) in enumerate(zip(outs, shapes)):
+        if not hasattr(o, "shape") or tuple(int(v) for v in o.shape) != s:
+            raise ValueError(f"out[{l}] has shape {tuple(getattr(o, 'shape', ()))}, expected {s}")
+    return outs
+
+
+def _pool_levels(lib, src_ptr, dims, valid, L, is3d, dst_ptrs, stream):
+    """The L pooling launches of one block: level l + 1 = tem_u8_pool2 of level l, level 0 at `src_ptr` with dense
+    `dims` and valid extents `valid`, level l at dst_ptrs[l - 1].  Returns the levels' (dims, valid) from level 1 on."""
+    from . import _lib
+    fz, levels = 2 if is3d else 1, []
+    half = lambda v: (-(-v[0] // fz), -(-v[1] // 2), -(-v[2] // 2))
+    for l in range(L):
+        _lib.check(lib.tem_u8_pool2(src_ptr, *dims, *valid, fz, dst_ptrs[l], stream), "tem_u8_pool2")
+        src_ptr, dims, valid = dst_ptrs[l], half(dims), half(valid)
+        levels.append((dims, valid))
+    return levels
+
+
 def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=False, outdimsize=None, buffer=None,
-                 rank=0, world_size=1, tile_batch=None, boundary="zeros", ensemble=None):
+                 rank=0, world_size=1, tile_batch=None, boundary="zeros", ensemble=None, mips=None):
     """Predict the subvolume [start, start+size) (x,y,z order as in the reference) of a uint8
     array `volume` indexed [z, y, x].  Voxels outside the array read as 0 (the reference fetches
     them from the store) or, with boundary="reflect" / "edge", the voxel that `fold` names on every axis: the result
@@ -410,20 +502,35 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
     (tem_f32_tiles*_sym_accum: the first member writes, the others add, the last also divides by the member count);
     the mean goes through the scatter kernel once.  No member is quantised before the mean and no copy of the volume
     is made.  ValueError, before any GPU work: an empty sequence, a perm that is no permutation, flips of another
-    length, a member given twice, a member that moves z with a 2-D model."""
+    length, a member given twice, a member that moves z with a 2-D model.
+
+    mips=None (or 0) returns the array above.  mips=L >= 1 returns the list [level0, ..., levelL] of a mip pyramid of
+    it, built on the device: level 0 is that array, the same bytes, and level l + 1 is level l pooled by (2, 2, 2) over
+    (z, y, x) -- (1, 2, 2) with a 2-D model, whose sections are not pooled -- to the shapes of `mip_shapes`.  A voxel is
+    the mean of its children that exist in the level below (1, 2, 4 or 8 of them: fewer at the far face of an odd
+    extent), rounded half up in integers, (sum + (cnt >> 1)) >> log2(cnt); levels cascade, and voxels past `size`
+    never enter a mean (tem_u8_pool2, one launch per level after the tile loop -- and after the all-reduce of a
+    multi-rank call).  The pyramid is relative to `start`: level-l voxel q covers ROI voxels [q 2^l, (q + 1) 2^l) on
+    each pooled axis; choose `start` as a multiple of 2^L where it has to sit on a global grid.  L is at most
+    max_mips(outdimsize) of the tile plan's outdimsize -- 5 for the 132 model (96), 2 for the 74 model (36), 1 for the
+    260 model (222) -- so that predict_volume's chunks can pool on their own; a larger, negative or non-integer `mips`
+    raises ValueError before any GPU work.  With fetch_input the result is (input block, list)."""
     from . import _lib
     gen = getattr(model, "generator_g", None)
     is3d = getattr(gen, "is3d", True)
     syms = _check_ensemble(ensemble, is3d)
-    lib = H.require_gpu()
-    if _single_image(model, start, size):
-        res = predict_cube(np.asarray(volume)[None], tuple(start) + (0,), tuple(size) + (1,), model, meanstd_x,
-                           meanstd_y, fetch_input, outdimsize, buffer, rank, world_size, tile_batch, boundary, ensemble)
-        return tuple(r[0] for r in res) if fetch_input else res[0]
     if outdimsize is None:
         outdimsize = model.outdimsize
     if buffer is None:
         buffer = model.buffer
+    L = _check_mips(mips, _plan_outdimsize(outdimsize))
+    lib = H.require_gpu()
+    if _single_image(model, start, size):
+        res = predict_cube(np.asarray(volume)[None], tuple(start) + (0,), tuple(size) + (1,), model, meanstd_x,
+                           meanstd_y, fetch_input, outdimsize, buffer, rank, world_size, tile_batch, boundary, ensemble,
+                           mips)
+        one = lambda r: [v[0] for v in r] if isinstance(r, list) else r[0]
+        return tuple(one(r) for r in res) if fetch_input else one(res)
     outdimsize, buffer, tpad, rois, index = (tile_plan if is3d else tile_plan_2d)(start, size, outdimsize, buffer)
     edge = outdimsize + buffer * 2
     z, y, x = size[2], size[1], size[0]
@@ -470,6 +577,15 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
     if world_size > 1 and torch.distributed.is_initialized():
         torch.distributed.all_reduce(out_buffer, op=torch.distributed.ReduceOp.MAX)   # disjoint tiles, zeros elsewhere
     out = out_buffer[0:size[2], 0:size[1], 0:size[0]].cpu().numpy()
+    if L:                                       # the pyramid of the resident result: one launch per level
+        fz = 2 if is3d else 1
+        shapes = mip_shapes(size, L, is3d)
+        bufs, dims = [], (OZ, OY, OX)
+        for _ in range(L):
+            dims = (-(-dims[0] // fz), -(-dims[1] // 2), -(-dims[2] // 2))
+            bufs.append(torch.empty(dims, dtype=torch.uint8, device=dev))
+        _pool_levels(lib, out_buffer.data_ptr(), (OZ, OY, OX), shapes[0], L, is3d, [b.data_ptr() for b in bufs], stream)
+        out = [out] + [b[:s[0], :s[1], :s[2]].cpu().numpy() for b, s in zip(bufs, shapes[1:])]
     if fetch_input:
         # the reference returns the RAW uint8 block here after a detour (utils.py:122-125: the standardized float
         # tile is un-standardized, rescaled and truncated into a uint8 buffer -- the original bytes up to float
@@ -619,7 +735,8 @@ def chunk_plan(start, size, outdimsize, buffer, vol_shape, chunk_tiles, rank=0, 
 
 
 def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, chunk_tiles=None, tile_batch=None,
-                   outdimsize=None, buffer=None, rank=0, world_size=1, stats=None, boundary="zeros", ensemble=None):
+                   outdimsize=None, buffer=None, rank=0, world_size=1, stats=None, boundary="zeros", ensemble=None,
+                   mips=None):
     """Out-of-core predict_cube: the subvolume [start, start+size) (x,y,z order) of a uint8 array-like `volume`
     indexed [z, y, x] (ndarray, np.memmap, h5py / zarr dataset: `.shape` and basic slicing are all it needs) is
     predicted chunk by chunk (chunk_plan) into `out`, a writable uint8 array-like of shape (size[2], size[1], size[0])
@@ -644,12 +761,27 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
     `ensemble` is predict_cube's: every tile batch runs once per member between its gathers and its one scatter, with
     one fp32 accumulator of a batch's output for the whole call; a chunk's staging buffer is released for the next
     upload after the last member's gather of its last batch.  The rest of the pipeline, the chunk plan and the
-    footprints are those of ensemble=None, and the result still equals predict_cube's bit for bit."""
+    footprints are those of ensemble=None, and the result still equals predict_cube's bit for bit.
+
+    `mips` is predict_cube's: mips=L >= 1 writes and returns the list of the L + 1 levels of the result's mip pyramid,
+    equal to predict_cube's at every level.  `out` is then None (every level is allocated) or a sequence of L + 1
+    writable uint8 array-likes of exactly mip_shapes(size, L, is3d) (memmap, h5py, zarr as for one array); anything else
+    raises ValueError, as a `mips` beyond max_mips does, before any GPU work.  A chunk is a box of whole tiles whose
+    origin and extents are multiples of 2^L on the pooled axes, so it pools on its own: after its last scatter the
+    compute stream runs L launches of tem_u8_pool2 (level l + 1 from level l, valid extents = the chunk's `out_box`, so
+    predictions past `size` never enter a mean) into the same device buffer, which holds the chunk's levels back to
+    back; the one D2H copy moves them all and the host thread writes each level's box (`mip_box`).  The device and
+    pinned output buffers grow by at most 1/7 (1/3 for a 2-D model); nothing else changes, and `boundary` and
+    `ensemble` compose as they are (pooling comes after the scatter).  `stats["mips"]` reports L."""
     import time
     from concurrent.futures import ThreadPoolExecutor
     from . import _lib
     gen = model.generator_g
-    syms = _check_ensemble(ensemble, getattr(gen, "is3d", True))
+    is3d = getattr(gen, "is3d", True)
+    syms = _check_ensemble(ensemble, is3d)
+    L = _check_mips(mips, _plan_outdimsize(model.outdimsize if outdimsize is None else outdimsize))
+    if L and len(size) in (2, 3):
+        out = _check_mip_outs(out, size, L, is3d)
     lib = H.require_gpu()
     if not hasattr(gen, "plan"):
         raise TypeError("predict_volume needs a generator with launch plans (EM2EM or a saved model)")
@@ -657,12 +789,12 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
         if len(volume.shape) != 2:
             raise ValueError(f"a 2-element start / size needs one image [y, x], got shape {tuple(volume.shape)}")
         if out is None:
-            out = np.zeros((size[1], size[0]), np.uint8)
+            out = ([np.zeros(s, np.uint8) for s in mip_shapes(size, L, False)] if L else
+                   np.zeros((size[1], size[0]), np.uint8))
         predict_volume(_OneSection(volume), tuple(start) + (0,), tuple(size) + (1,), model, meanstd_x, meanstd_y,
-                       _OneSection(out), chunk_tiles, tile_batch, outdimsize, buffer, rank, world_size, stats, boundary,
-                       ensemble)
+                       [_OneSection(o) for o in out] if L else _OneSection(out), chunk_tiles, tile_batch, outdimsize,
+                       buffer, rank, world_size, stats, boundary, ensemble, mips)
         return out
-    is3d = gen.is3d
     vol_shape = tuple(int(v) for v in volume.shape)
     if len(vol_shape) != 3:
         raise ValueError(f"volume must be 3-D [z, y, x], got shape {vol_shape}")
@@ -675,11 +807,14 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
     if syms is not None:
         (sgather, sgname), (accum, aname) = _sym_kernels(lib, is3d, boundary)
         acc = []                                # the fp32 accumulator, allocated by the first (largest) batch
-    if out is None:
+    if L:
+        if out is None:
+            out = [np.zeros(s, np.uint8) for s in mip_shapes(size, L, is3d)]
+    elif out is None:
         out = np.zeros((size[2], size[1], size[0]), np.uint8)
     elif tuple(out.shape) != (size[2], size[1], size[0]):
         raise ValueError(f"out has shape {tuple(out.shape)}, expected {(size[2], size[1], size[0])}")
-    st = {"read_s": 0.0, "write_s": 0.0, "chunks": len(chunks)}
+    st = {"read_s": 0.0, "write_s": 0.0, "chunks": len(chunks), "mips": L}
     if stats is not None:
         stats.update(st)
     if not chunks:
@@ -689,7 +824,13 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
     # with a mirrored boundary no footprint is empty
     gdims = [c.block if min(c.block) > 0 else (1, 1, 1) for c in chunks]
     in_bytes = [int(np.prod(g)) for g in gdims]
-    out_bytes = [int(np.prod(c.dims)) for c in chunks]
+    # a chunk's output block on the device and in pinned memory: its L + 1 levels back to back, level l at
+    # lvl_off[k][l] with the dense dims lvl_dims[k][l] = c.dims divided by 2^l on the pooled axes (exact: dims are
+    # whole tiles and outdimsize % 2^L == 0)
+    lvl_dims = [[tuple(v >> (l if (is3d or d) else 0) for d, v in enumerate(c.dims)) for l in range(L + 1)]
+                for c in chunks]
+    lvl_off = [np.cumsum([0] + [int(np.prod(d)) for d in dd]) for dd in lvl_dims]
+    out_bytes = [int(o[-1]) for o in lvl_off]
     nb = st["tile_batch"] = _effective_batch(tile_batch, edge, is3d, max(len(c.tiles) for c in chunks))
     dev = model.device
     compute = torch.cuda.current_stream(dev)
@@ -718,9 +859,15 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
     def write(k):                       # host thread: pin_out[k % 2] -> the chunk's box of `out`
         d2h_done.pop(k).synchronize()
         t0 = time.perf_counter()
-        c, src = chunks[k], pin_out[k % 2][:out_bytes[k]].numpy().reshape(chunks[k].dims)
-        (z0, z1), (y0, y1), (x0, x1) = c.out_box
-        out[z0:z1, y0:y1, x0:x1] = src[:z1 - z0, :y1 - y0, :x1 - x0]
+        c, buf = chunks[k], pin_out[k % 2].numpy()
+        if not L:
+            src = buf[:out_bytes[k]].reshape(c.dims)
+            (z0, z1), (y0, y1), (x0, x1) = c.out_box
+            out[z0:z1, y0:y1, x0:x1] = src[:z1 - z0, :y1 - y0, :x1 - x0]
+        for l in range(L + 1 if L else 0):      # with a pyramid: each level's box into its own array
+            src = buf[lvl_off[k][l]:lvl_off[k][l + 1]].reshape(lvl_dims[k][l])
+            ((z0, z1), (y0, y1), (x0, x1)), (nz, ny, nx) = mip_box(c, l, is3d)
+            out[l][z0:z1, y0:y1, x0:x1] = src[:nz, :ny, :nx]
         st["write_s"] += time.perf_counter() - t0
 
     pool = ThreadPoolExecutor(max_workers=1)
@@ -766,6 +913,10 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
                 _lib.check(scatter(data_y.data_ptr(), m, data_y.shape[2], tpad, idx.data_ptr() + 12 * t,
                                    dev_out[s].data_ptr(), OZ, OY, OX, float(meanstd_y[0]), float(meanstd_y[1]),
                                    compute.cuda_stream), sname)
+            if L:                                            # the chunk's pyramid, level by level behind its scatters
+                base = dev_out[s].data_ptr()
+                _pool_levels(lib, base, c.dims, tuple(hi - lo for lo, hi in c.out_box), L, is3d,
+                             [base + int(o) for o in lvl_off[k][1:L + 1]], compute.cuda_stream)
             scattered = compute.record_event()
             if k >= 2:
                 writes.pop(k - 2).result()                   # pin_out[s]: chunk k-2 is in `out`
@@ -826,7 +977,8 @@ def predict_ng_cube(location, start, size, model, meanstd_x, meanstd_y, cloudrun
                     outdimsize=None, buffer=None):
     """Reference signature (utils.py:41): `location` is the uint8 volume itself (array indexed [z, y, x])
     instead of a cloud path; `cloudrun` is accepted and ignored.  The signature is the reference's, so voxels outside
-    the array always read 0 here: predict_cube(..., boundary="reflect" | "edge") mirrors or clamps at the faces."""
+    the array always read 0 here: predict_cube(..., boundary="reflect" | "edge") mirrors or clamps at the faces.
+    It takes no `mips` either: predict_cube(..., mips=L) returns the mip pyramid of the prediction."""
     return predict_cube(_local_volume(location), start, size, model, meanstd_x, meanstd_y, fetch_input=fetch_input,
                         outdimsize=outdimsize, buffer=buffer)
 
@@ -835,7 +987,8 @@ def predict_cube_from_saved_model(location, start, size, cloudrun, model_dir, fe
     """Reference signature (utils.py:12-38) over a local array: `location` is the uint8 volume,
     `cloudrun` is accepted and ignored, `model_dir` is a directory written by save_model.  The signature is the
     reference's, so voxels outside the array always read 0 here: for boundary="reflect" | "edge" call predict_cube, or
-    predict_volume_from_saved_model, which takes the keyword."""
+    predict_volume_from_saved_model, which takes the keyword.  The same holds for `mips` (the mip pyramid of the
+    prediction): this signature has none and returns the full-resolution array alone."""
     volume = _local_volume(location)
     model = _load_saved(model_dir)
     return predict_cube(volume, start, size, model, model.meta["meanstd_x"], model.meta["meanstd_y"],
@@ -845,9 +998,11 @@ def predict_cube_from_saved_model(location, start, size, cloudrun, model_dir, fe
 def predict_volume_from_saved_model(volume, start, size, model_dir, out=None, **kw):
     """predict_volume with the generator and statistics exported by save_model to `model_dir` (the out-of-core
     sibling of predict_cube_from_saved_model); `kw` are predict_volume's chunk_tiles, tile_batch, rank, world_size,
-    stats, boundary ("zeros", "reflect" or "edge": what a voxel outside the volume reads) and ensemble (None, "flips",
-    "all" or a sequence of symmetries: the orientations the generator's output is averaged over).  The reference's
-    signatures, predict_ng_cube and predict_cube_from_saved_model, take neither keyword and run unensembled."""
+    stats, boundary ("zeros", "reflect" or "edge": what a voxel outside the volume reads), ensemble (None, "flips",
+    "all" or a sequence of symmetries: the orientations the generator's output is averaged over) and mips (None, or
+    the number of pooled levels of the result's mip pyramid: `out` and the return value are then lists of levels).
+    The reference's signatures, predict_ng_cube and predict_cube_from_saved_model, take none of these keywords; they
+    run unensembled and return the full-resolution array alone."""
     model = _load_saved(model_dir)
     return predict_volume(_local_volume(volume), start, size, model, model.meta["meanstd_x"], model.meta["meanstd_y"],
                           out=out, outdimsize=model.outdimsize, buffer=model.buffer, **kw)
