@@ -4,30 +4,9 @@ import numpy as np
 import pytest
 import torch
 
-from util import scaled_params
+from util import reference_predict as _reference_predict, scaled_params
 
 pytestmark = pytest.mark.gpu
-
-
-def _reference_predict(volume, start, size, P, meanstd_x, meanstd_y, outdim, buffer):
-    """utils.py:62-130 with the cloud fetch replaced by array slicing (zeros outside)."""
-    from oracle import graph, ops
-    from transfer_em_amd.utils import tile_plan
-    outdim, buffer, tpad, rois, index = tile_plan(start, size, outdim, buffer)
-    edge = outdim + 2 * buffer
-    rnd = lambda v: v + ((outdim - v % outdim) if v % outdim else 0)
-    out = np.zeros((rnd(size[2]), rnd(size[1]), rnd(size[0])), np.uint8)
-    Z, Y, X = volume.shape
-    for (rx, ry, rz), (ix, iy, iz) in zip(rois, index):
-        tile = np.zeros((edge, edge, edge), np.uint8)
-        z0, y0, x0, z1, y1, x1 = max(rz, 0), max(ry, 0), max(rx, 0), min(rz + edge, Z), min(ry + edge, Y), min(rx + edge, X)
-        tile[z0 - rz:z1 - rz, y0 - ry:y1 - ry, x0 - rx:x1 - rx] = volume[z0:z1, y0:y1, x0:x1]
-        x = ops.standardize(ops.scale_u8(tile), meanstd_x)[None]
-        y, _ = graph.generator_forward(P, x, True, training=False)
-        if tpad:
-            y = y[:, tpad:-tpad, tpad:-tpad, tpad:-tpad, :]
-        out[iz:iz + outdim, iy:iy + outdim, ix:ix + outdim] = ops.to_u8(y, meanstd_y)[0, ..., 0]
-    return out[:size[2], :size[1], :size[0]]
 
 
 def test_predict_cube_matches_tilewise_oracle(oracle_lib, tmp_path):

@@ -126,6 +126,11 @@ def test_2d_fp32_plans_run_the_direct_kernels_at_every_batch(ladders):
     for edge in (74, 132, 260):
         last, vary = ladders[(edge, False, torch.float32)]
         assert not any(last.values()) and not vary, (edge, last, vary)
+    # the transposed layers' direct form, which no query names, as conv_launch spells it in Launch.meta["kernel"]
+    # (the 2-D step's launch tables in test_gpu_2d_fullsize_oracle.py; plan_kernels() in test_gpu_model260.py)
+    from transfer_em_amd.utils import plan_routes
+    r = plan_routes(260, 3, False)
+    assert (r["u2b"], r["u1b"]) == ("convT_direct_k<32, 16, 0, 16>", "convT_direct_k<16, 8, 0, 8>")
 
 
 def test_template_arguments_vary_only_where_audited(ladders):

@@ -76,6 +76,78 @@ def gate_flips(cs, saved, is3d=True):
 FLIP_BOUND = 1e-5       # gate flips allowed per compared activation (measured: ~1e-6, pre-activations within rounding of 0)
 
 
+def _saved_pairs(fwd, sv, generator, is3d):
+    """(layer, HIP activation, oracle activation) of one call site: every saved LeakyReLU output that both sides hold,
+    the oracle's cut to the region the forward evaluated (a generator's fwd.regions; the full tensor for an inference
+    plan, whose in_pad and out_crop are 0)."""
+    for layer, key in (_GEN_SAVED if generator else _DISC_SAVED).items():
+        if key not in sv or layer not in fwd.act:
+            continue
+        ref = np.asarray(sv[key])
+        if generator:
+            lo, hi = fwd.regions[layer]
+            ref = ref[:, lo:hi, lo:hi, lo:hi, :] if is3d else ref[:, :, lo:hi, lo:hi, :]
+        got = fwd.act[layer].float().cpu().numpy()
+        assert got.shape == ref.shape, (layer, got.shape, ref.shape)
+        yield layer, got, ref
+
+
+def compare_stats(got, ref):
+    """(rel_err, l2_err, sign flips) of two equally shaped float32 arrays in one pass over slabs of the second axis:
+    the float64 temporaries of a 226^3 x 16 activation stay at one plane's size.  rel_err is exactly util.rel_err's;
+    the sums of l2_err run in float64."""
+    dmax = rmax = d2 = r2 = 0.0
+    flips = 0
+    for g, r in zip(np.moveaxis(got, 1, 0), np.moveaxis(ref, 1, 0)):
+        flips += int(np.count_nonzero((g > 0) != (r > 0)))
+        g, r = g.astype(np.float64), r.astype(np.float64)
+        d = g - r
+        dmax, rmax = max(dmax, float(np.abs(d).max())), max(rmax, float(np.abs(r).max()))
+        d2, r2 = d2 + float(np.vdot(d, d)), r2 + float(np.vdot(r, r))
+    return dmax / (rmax + 1e-30), float(np.sqrt(d2) / (np.sqrt(r2) + 1e-30)), flips
+
+
+def l2_err(a, b):
+    """|a-b|_2 / |b|_2 -- the norm the bf16 comparisons use (one bf16 ulp moves single entries past any max-norm bar)."""
+    return compare_stats(np.asarray(a, np.float32), np.asarray(b, np.float32))[1]
+
+
+def forward_stats(fwd, sv, y_ref, is3d=True):
+    """activation_stats for one bare GenForward (an inference plan of UNetGenerator.plan, or one call site of a step):
+    OrderedDict layer -> (rel_err, l2_err, sign flips, elements) of the eleven saved activations of the oracle's
+    generator_forward `sv` and, under "y", of the output against `y_ref`."""
+    from collections import OrderedDict
+    out = OrderedDict()
+    for layer, got, ref in _saved_pairs(fwd, sv, True, is3d):
+        out[layer] = compare_stats(got, ref) + (got.size,)
+    lo, hi = fwd.regions["f2"]
+    ref = np.asarray(y_ref)
+    ref = ref[:, lo:hi, lo:hi, lo:hi, :] if is3d else ref[:, :, lo:hi, lo:hi, :]
+    got = fwd.y.float().cpu().numpy()
+    assert got.shape == ref.shape, (got.shape, ref.shape)
+    out["y"] = compare_stats(got, ref) + (got.size,)
+    return out
+
+
+def failed_bars(stats, rel_tol=None, l2_bars=None, flip_bound=None):
+    """The layers of a forward_stats result that miss a bar, as {layer: (figure, bar)}: rel_err < rel_tol (a number for
+    every layer, or a dict for some), l2_err < l2_bars[layer], and under "flips" the sign flips of the activations (the
+    output has no gate) against max(2, flip_bound * elements), the bound of activation_stats.  Empty: all bars hold."""
+    bad = {}
+    for layer, (rel, l2, _, _) in stats.items():
+        tol = rel_tol.get(layer) if isinstance(rel_tol, dict) else rel_tol
+        if tol is not None and not rel < tol:
+            bad[layer] = (rel, tol)
+        if l2_bars is not None and layer in l2_bars and not l2 < l2_bars[layer]:
+            bad[layer] = (l2, l2_bars[layer])
+    if flip_bound is not None:
+        n = sum(s[2] for k, s in stats.items() if k != "y")
+        total = sum(s[3] for k, s in stats.items() if k != "y")
+        if n > max(2, flip_bound * total):
+            bad["flips"] = (n, max(2, flip_bound * total))
+    return bad
+
+
 def activation_stats(cs, saved, is3d=True, tol=None):
     """(gate flips, compared elements, worst relative activation error, its (call, layer)) over every saved LeakyReLU
     output of the step: the HIP forward's activation buffers against the oracle's (on the evaluated region for the
@@ -85,17 +157,7 @@ def activation_stats(cs, saved, is3d=True, tol=None):
     n = total = 0
     worst, where = 0.0, None
     for call, sv in saved.items():
-        fwd = cs.fwd[call]
-        table = _GEN_SAVED if call[0] in "gf" else _DISC_SAVED
-        for layer, key in table.items():
-            if key not in sv or layer not in fwd.act:
-                continue
-            ref = np.asarray(sv[key])
-            if call[0] in "gf":
-                lo, hi = fwd.regions[layer]
-                ref = ref[:, lo:hi, lo:hi, lo:hi, :] if is3d else ref[:, :, lo:hi, lo:hi, :]
-            got = fwd.act[layer].float().cpu().numpy()
-            assert got.shape == ref.shape, (call, layer, got.shape, ref.shape)
+        for layer, got, ref in _saved_pairs(cs.fwd[call], sv, call[0] in "gf", is3d):
             n += int(np.count_nonzero((got > 0) != (ref > 0)))
             total += got.size
             e = rel_err(got, ref)
@@ -141,6 +203,38 @@ def hip_gates(cs, is3d=True):
             out[call] = g
         return out
     return build
+
+
+def reference_tile(volume, roi, edge, meanstd_x):
+    """The generator input (1, edge, edge, edge, 1) of the 3-D tile whose haloed box starts at roi = (x, y, z) of the
+    uint8 `volume` [z, y, x]: zeros outside the volume, scaled and standardised on the host by the oracle's ops."""
+    from oracle import ops
+    rx, ry, rz = roi
+    Z, Y, X = volume.shape
+    tile = np.zeros((edge, edge, edge), np.uint8)
+    z0, y0, x0, z1, y1, x1 = max(rz, 0), max(ry, 0), max(rx, 0), min(rz + edge, Z), min(ry + edge, Y), min(rx + edge, X)
+    tile[z0 - rz:z1 - rz, y0 - ry:y1 - ry, x0 - rx:x1 - rx] = volume[z0:z1, y0:y1, x0:x1]
+    return ops.standardize(ops.scale_u8(tile), meanstd_x)[None]
+
+
+def reference_predict(volume, start, size, P, meanstd_x, meanstd_y, outdim, buffer, tiles=None):
+    """utils.py:62-130 with the cloud fetch replaced by array slicing (zeros outside).  `tiles`: the indices into
+    tile_plan's rois of the tiles to predict (None: all of them); the others' voxels stay 0."""
+    from oracle import graph, ops
+    from transfer_em_amd.utils import tile_plan
+    outdim, buffer, tpad, rois, index = tile_plan(start, size, outdim, buffer)
+    edge = outdim + 2 * buffer
+    rnd = lambda v: v + ((outdim - v % outdim) if v % outdim else 0)
+    out = np.zeros((rnd(size[2]), rnd(size[1]), rnd(size[0])), np.uint8)
+    for i, (roi, (ix, iy, iz)) in enumerate(zip(rois, index)):
+        if tiles is not None and i not in tiles:
+            continue
+        x = reference_tile(volume, roi, edge, meanstd_x)
+        y, _ = graph.generator_forward(P, x, True, training=False)
+        if tpad:
+            y = y[:, tpad:-tpad, tpad:-tpad, tpad:-tpad, :]
+        out[iz:iz + outdim, iy:iy + outdim, ix:ix + outdim] = ops.to_u8(y, meanstd_y)[0, ..., 0]
+    return out[:size[2], :size[1], :size[0]]
 
 
 def prior_layers(is3d, seed=5, extra_tail=True):

@@ -103,8 +103,8 @@ def _dry_view(v, ptr, N, dims, C, strides=None):
 def plan_routes(edge, N, is3d=True, dtype=torch.float32, wf=8):
     """Kernel symbol of each of the 12 convolution launches of the generator's inference plan (GenForward with
     in_pad = 0, out_crop = 0) on a batch of N tiles of edge `edge`, as an OrderedDict layer -> name: what
-    Launch.meta["kernel"] of that plan holds (a transposed layer on its direct form reads "convT_direct_k", without the
-    template arguments).  Asked of the library's dry queries (tem_conv_is_tiled, the bf16 describe
+    Launch.meta["kernel"] of that plan holds (a transposed layer on its direct form, which no query names, is spelled
+    as conv_launch spells it).  Asked of the library's dry queries (tem_conv_is_tiled, the bf16 describe
     entry points) on the plan's dense views with made-up pointers, so no device is needed.  The layers, channels and
     geometry come from generator_blocks / generator_edges / skip_crop, the choice between the Winograd-domain and the
     plain kernel copy is conv_launch's."""
@@ -156,7 +156,8 @@ def plan_routes(edge, N, is3d=True, dtype=torch.float32, wf=8):
                 continue
         a.w_layout = _lib.TEM_W_TAP_CI_CO
         tiled = lib.tem_conv_is_tiled(C.byref(a), int(T), buf, 96) == 1
-        routes[name] = buf.value.decode() if (tiled or not T) else "convT_direct_k"
+        co = spec.out_ch
+        routes[name] = buf.value.decode() if (tiled or not T) else f"convT_direct_k<{ch[s_in]}, {co}, 0, {8 if co == 32 else co}>"
     return routes
 
 
