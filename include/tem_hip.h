@@ -352,6 +352,33 @@ int tem_f32_tiles2d_unstd_to_u8(const float *y, int32_t ntile, int32_t yedge, in
 int tem_u8_pool2(const uint8_t *src, int32_t D, int32_t H, int32_t W, int32_t vD, int32_t vH, int32_t vW, int32_t fz,
                  uint8_t *dst, tem_stream_t stream);
 
+/* Intensity histogram of a box of a uint8 block (tiled inference: of a volume before it, of the prediction after the
+ * scatter).  src[D][H][W] is dense.  counts[v] += the number of voxels of the box [z0, z1) x [y0, y1) x [x0, x1) whose
+ * byte is v: counts holds 256 entries, or with per_section = 1 (z1 - z0) rows of 256, row z - z0 counting section z.
+ * The kernel ADDS (64-bit global atomic adds): the caller clears counts once and any number of calls, from any number
+ * of streams, accumulate into it.  Source bytes outside the box are never read and nothing but counts is written.  Any
+ * alignment of src, W and the box (16-byte lines that lie inside a row of the box take one wide load, a row's cut
+ * ends byte loads; the counts are the same); counts must be 8-byte aligned.  An empty box (lo == hi on an axis)
+ * returns TEM_OK without a launch.
+ * TEM_EINVAL, without a launch: a null pointer, counts off 8-byte alignment, a dimension below 1, a box outside
+ * [0, dim] or with lo > hi, per_section outside {0, 1}, and a box too large for the workgroups' 32-bit counters: the
+ * box's (z1 - z0)(y1 - y0) rows are dealt in equal contiguous runs to at most 1024 workgroups, and
+ *   ceil(rows / workgroups) x max(x1 - x0, (x1 - x0 + 30) / 16)  must stay below 2^31
+ * (a workgroup flushes at the end of its run, and with per_section at every change of section: no counter can see
+ * more voxels than that).  A box of fewer than 2^40 voxels always passes. */
+int tem_u8_hist(const uint8_t *src, int32_t D, int32_t H, int32_t W, int32_t z0, int32_t z1, int32_t y0, int32_t y1,
+                int32_t x0, int32_t x1, uint64_t *counts, int32_t per_section, tem_stream_t stream);
+
+/* Intensity remapping of a dense uint8 block in place (tiled inference: the uploaded bytes, ahead of the gather).
+ *   per_section = 0:  buf[z][y][x] = lut[buf[z][y][x]]                          lut: 256 bytes
+ *   per_section = 1:  buf[z][y][x] = lut[(zsec0 + z) * 256 + buf[z][y][x]]      lut: at least zsec0 + D rows of 256
+ * (zsec0: the section of the caller's volume that buf's section 0 is).  A workgroup reads its section's table once
+ * into LDS; every byte of buf is read exactly once and written exactly once, and nothing outside buf is touched.  Any
+ * alignment of buf, lut and W (16-byte lines inside a section take one wide load and store).
+ * TEM_EINVAL, without a launch: a null pointer, a dimension below 1, a negative zsec0, per_section outside {0, 1}. */
+int tem_u8_lut(uint8_t *buf, int32_t D, int32_t H, int32_t W, const uint8_t *lut, int32_t per_section, int32_t zsec0,
+               tem_stream_t stream);
+
 /* Random augmentation of one cached sample (datasets.py:123-155) with host-drawn parameters:
  *   dst = reverse(transpose(src, perm = (p0,p1,p2)), dims with f_k != 0) * scale + shift
  * src is a dense single-channel (D,H,W) volume (2-D: D == 1, p0 must be 0); dst has extents

@@ -1,0 +1,433 @@
+"""Intensity histograms and lookup tables on the device: tem_u8_hist and tem_u8_lut against numpy (np.bincount, fancy
+indexing), volume_histogram out of core, and predict_cube / predict_volume with `lut` and `histogram`.  Everything is
+integers or bytes, so every comparison is exact."""
+import numpy as np
+import pytest
+import torch
+
+from util import scaled_params
+
+pytestmark = pytest.mark.gpu
+
+GUARD, GUARD_BYTE = 64, 0xA5
+
+
+def _env():
+    from transfer_em_amd import _lib as L
+    from transfer_em_amd import hip_ops as H
+    return L, H.require_gpu(), H.current_stream()
+
+
+def _upload(a, off=0):
+    """The bytes of `a` on the device, `off` bytes into a 256-byte-aligned allocation; (tensor kept alive, pointer)."""
+    flat = np.ascontiguousarray(a).reshape(-1)
+    t = torch.zeros(flat.size + off + 16, dtype=torch.uint8, device="cuda")
+    assert t.data_ptr() % 256 == 0
+    t[off:off + flat.size] = torch.from_numpy(flat).cuda()
+    return t, t.data_ptr() + off
+
+
+def _hist(ptr, dims, box, per_section=False, counts=None):
+    L, lib, stream = _env()
+    (z0, z1), (y0, y1), (x0, x1) = box
+    if counts is None:
+        counts = torch.zeros(((z1 - z0) if per_section else 1, 256), dtype=torch.int64, device="cuda")
+    L.check(lib.tem_u8_hist(ptr, *dims, z0, z1, y0, y1, x0, x1, counts.data_ptr(), int(per_section), stream), "tem_u8_hist")
+    return counts
+
+
+def _bincount(a):
+    return np.bincount(a.ravel(), minlength=256).astype(np.int64)
+
+
+def _boxes(dims):
+    """The whole buffer, a one-voxel box, and boxes at an odd x0 of widths 1, 15, 16, 17 (where they fit)."""
+    D, H, W = dims
+    boxes = [((0, D), (0, H), (0, W)), ((D - 1, D), (H // 2, H // 2 + 1), (W - 1, W))]
+    for w in (1, 15, 16, 17):
+        for x0 in (1, 3):
+            if x0 + w <= W:
+                boxes.append(((0, D), (0, H), (x0, x0 + w)))
+                boxes.append(((D // 2, D), (H // 3, H - H // 4), (x0, x0 + w)))
+    return [b for b in boxes if all(hi > lo for lo, hi in b)]
+
+
+HIST_DIMS = [(1, 1, 1), (3, 5, 17), (2, 7, 16), (5, 33, 131)]
+
+
+@pytest.mark.parametrize("off", [0, 1], ids=["aligned", "off1"])
+@pytest.mark.parametrize("dims", HIST_DIMS, ids=[str(d).replace(" ", "") for d in HIST_DIMS])
+def test_hist_equals_bincount(dims, off):
+    src = np.random.default_rng(sum(dims)).integers(0, 256, dims, dtype=np.uint8)
+    keep, ptr = _upload(src, off)
+    for box in _boxes(dims):
+        (z0, z1), (y0, y1), (x0, x1) = box
+        want = _bincount(src[z0:z1, y0:y1, x0:x1])
+        got = _hist(ptr, dims, box).cpu().numpy()[0]
+        assert np.array_equal(got, want), (box, np.flatnonzero(got != want)[:5])
+
+
+def test_hist_calls_add_and_many_workgroups_flush_into_one():
+    dims = (7, 64, 300)                                  # 448 rows of 20 segments: 35 workgroups
+    src = np.random.default_rng(1).integers(0, 256, dims, dtype=np.uint8)
+    keep, ptr = _upload(src)
+    whole = ((0, 7), (0, 64), (0, 300))
+    counts = _hist(ptr, dims, whole)
+    assert np.array_equal(counts.cpu().numpy()[0], _bincount(src))
+    _hist(ptr, dims, ((1, 5), (3, 60), (7, 208)), counts=counts)
+    assert np.array_equal(counts.cpu().numpy()[0], _bincount(src) + _bincount(src[1:5, 3:60, 7:208]))
+
+
+@pytest.mark.parametrize("value", [255, 0])
+def test_hist_of_a_constant_volume(value):
+    """Every lane adds to the same bin: the contention case of the workgroup-private counters."""
+    src = np.full((64, 64, 64), value, np.uint8)
+    keep, ptr = _upload(src)
+    got = _hist(ptr, src.shape, ((0, 64),) * 3).cpu().numpy()[0]
+    want = np.zeros(256, np.int64)
+    want[value] = 262144
+    assert np.array_equal(got, want)
+
+
+@pytest.mark.parametrize("off", [0, 1], ids=["aligned", "off1"])
+def test_hist_per_section_reads_nothing_outside_the_box(off):
+    """Inside the box every byte is below 200; everything around it is 233, whose bin must stay empty."""
+    dims, box = (9, 40, 150), ((2, 8), (5, 37), (3, 140))
+    src = np.full(dims, 233, np.uint8)
+    (z0, z1), (y0, y1), (x0, x1) = box
+    src[z0:z1, y0:y1, x0:x1] = np.random.default_rng(2).integers(0, 200, (z1 - z0, y1 - y0, x1 - x0), dtype=np.uint8)
+    keep, ptr = _upload(src, off)
+    want = np.stack([_bincount(src[z, y0:y1, x0:x1]) for z in range(z0, z1)])
+    assert want[:, 233].sum() == 0 and len({tuple(r) for r in want}) == z1 - z0          # distinct rows
+    got = _hist(ptr, dims, box, per_section=True).cpu().numpy()
+    assert got.shape == (z1 - z0, 256) and np.array_equal(got, want)
+    assert np.array_equal(_hist(ptr, dims, box).cpu().numpy()[0], want.sum(axis=0))
+    # many short sections: a workgroup's run of rows crosses sections and flushes at each
+    dims2 = (40, 3, 21)
+    src2 = np.random.default_rng(3).integers(0, 256, dims2, dtype=np.uint8)
+    keep2, ptr2 = _upload(src2, off)
+    got = _hist(ptr2, dims2, ((0, 40), (0, 3), (0, 21)), per_section=True).cpu().numpy()
+    assert np.array_equal(got, np.stack([_bincount(s) for s in src2]))
+
+
+def test_hist_rejects_malformed_arguments():
+    """TEM_EINVAL from the host-side checks, nothing launched: counts keeps its fill."""
+    L, lib, stream = _env()
+    src = torch.zeros(4 * 6 * 8, dtype=torch.uint8, device="cuda")
+    counts = torch.full((4, 256), 7, dtype=torch.int64, device="cuda")
+    base = (4, 6, 8)
+
+    def call(ptr=None, dims=base, box=(0, 4, 0, 6, 0, 8), out=None, per_section=0):
+        return lib.tem_u8_hist(src.data_ptr() if ptr is None else ptr, *dims, *box,
+                               counts.data_ptr() if out is None else out, per_section, stream)
+    assert call(ptr=0) == L.TEM_EINVAL and call(out=0) == L.TEM_EINVAL
+    for a in range(3):
+        at = lambda v: tuple(v if d == a else n for d, n in enumerate(base))
+
+        def box(lo, hi):
+            b = [0, 4, 0, 6, 0, 8]
+            b[2 * a], b[2 * a + 1] = lo, hi
+            return tuple(b)
+        assert call(dims=at(0), box=box(0, 0)) == L.TEM_EINVAL and call(dims=at(-1), box=box(0, 0)) == L.TEM_EINVAL
+        assert call(box=box(-1, 2)) == L.TEM_EINVAL and call(box=box(0, base[a] + 1)) == L.TEM_EINVAL
+        assert call(box=box(3, 2)) == L.TEM_EINVAL
+    # too many voxels for a workgroup's 32-bit counters (the bound of include/tem_hip.h); refused on the host, so the
+    # extents need no memory behind them
+    M = 2 ** 31 - 1
+    for per_section in (0, 1):
+        assert call(dims=(1, M, M), box=(0, 1, 0, M, 0, M), per_section=per_section) == L.TEM_EINVAL
+    torch.cuda.synchronize()
+    assert (counts.cpu().numpy() == 7).all()
+    for b in ((2, 2, 0, 6, 0, 8), (0, 4, 6, 6, 0, 8), (0, 4, 0, 6, 3, 3)):              # empty boxes: fine, nothing counted
+        assert call(box=b) == L.TEM_OK and call(box=b, per_section=1) == L.TEM_OK
+    torch.cuda.synchronize()
+    assert (counts.cpu().numpy() == 7).all()
+    assert call() == L.TEM_OK
+    torch.cuda.synchronize()
+    got = counts.cpu().numpy()
+    assert got[0, 0] == 7 + 192 and (got.ravel()[1:] == 7).all()
+
+
+# -------------------------------------------------------------------------------------------------------- tem_u8_lut
+def _lut(buf_np, table, per_section=False, zsec0=0, off=0):
+    """tem_u8_lut on a copy of buf_np placed `off` bytes into an aligned allocation between two guards."""
+    L, lib, stream = _env()
+    n = buf_np.size
+    t = torch.full((GUARD + off + n + GUARD,), GUARD_BYTE, dtype=torch.uint8, device="cuda")
+    assert t.data_ptr() % 256 == 0
+    t[GUARD + off:GUARD + off + n] = torch.from_numpy(buf_np.reshape(-1)).cuda()
+    keep, lut_ptr = _upload(table, off)                                  # the table is as misaligned as the buffer
+    L.check(lib.tem_u8_lut(t.data_ptr() + GUARD + off, *buf_np.shape, lut_ptr, int(per_section), zsec0, stream),
+            "tem_u8_lut")
+    got = t.cpu().numpy()
+    assert (got[:GUARD + off] == GUARD_BYTE).all() and (got[GUARD + off + n:] == GUARD_BYTE).all(), "guards were written"
+    return got[GUARD + off:GUARD + off + n].reshape(buf_np.shape)
+
+
+LUT_DIMS = HIST_DIMS + [(3, 50, 1111)]                                   # the last: several workgroups per buffer
+
+
+@pytest.mark.parametrize("off", [0, 1], ids=["aligned", "off1"])
+@pytest.mark.parametrize("dims", LUT_DIMS, ids=[str(d).replace(" ", "") for d in LUT_DIMS])
+def test_lut_equals_fancy_indexing(dims, off):
+    rng = np.random.default_rng(sum(dims) + 1)
+    buf = rng.integers(0, 256, dims, dtype=np.uint8)
+    perm = rng.permutation(256).astype(np.uint8)
+    assert not np.array_equal(perm, np.arange(256))
+    assert np.array_equal(_lut(buf, perm, off=off), perm[buf])
+    const = np.full(256, 99, np.uint8)
+    assert np.array_equal(_lut(buf, const, off=off), const[buf])
+    # one table per section, the buffer starting at section 2 of a taller volume
+    tables = np.stack([rng.permutation(256).astype(np.uint8) for _ in range(dims[0] + 3)])
+    want = np.stack([tables[2 + z][buf[z]] for z in range(dims[0])])
+    assert np.array_equal(_lut(buf, tables, per_section=True, zsec0=2, off=off), want)
+    if dims[0] > 1:
+        assert not np.array_equal(want, np.stack([tables[z][buf[z]] for z in range(dims[0])]))
+
+
+def test_lut_rejects_malformed_arguments():
+    L, lib, stream = _env()
+    buf = torch.full((4 * 6 * 8,), 5, dtype=torch.uint8, device="cuda")
+    table = torch.zeros(4 * 256, dtype=torch.uint8, device="cuda")
+
+    def call(ptr=None, dims=(4, 6, 8), lut=None, per_section=0, zsec0=0):
+        return lib.tem_u8_lut(buf.data_ptr() if ptr is None else ptr, *dims, table.data_ptr() if lut is None else lut,
+                              per_section, zsec0, stream)
+    assert call(ptr=0) == L.TEM_EINVAL and call(lut=0) == L.TEM_EINVAL
+    for a in range(3):
+        for v in (0, -1):
+            assert call(dims=tuple(v if d == a else n for d, n in enumerate((4, 6, 8)))) == L.TEM_EINVAL
+    assert call(zsec0=-1) == L.TEM_EINVAL and call(per_section=1, zsec0=-1) == L.TEM_EINVAL
+    torch.cuda.synchronize()
+    assert (buf.cpu().numpy() == 5).all()
+    assert call(per_section=1) == L.TEM_OK
+    torch.cuda.synchronize()
+    assert not buf.cpu().numpy().any()
+
+
+# -------------------------------------------------------------------------------------------------- volume_histogram
+@pytest.fixture(scope="module")
+def memmap(tmp_path_factory):
+    path = str(tmp_path_factory.mktemp("hist") / "vol.npy")
+    m = np.lib.format.open_memmap(path, mode="w+", dtype=np.uint8, shape=(40, 50, 70))
+    m[...] = np.clip(np.random.default_rng(8).normal(120, 30, m.shape), 0, 255).astype(np.uint8)
+    m.flush()
+    return np.load(path, mmap_mode="r")
+
+
+def test_volume_histogram(memmap):
+    from transfer_em_amd.utils import hist_chunks, volume_histogram
+    vol = np.asarray(memmap)
+    budget = 3 * 50 * 70 + 100                                           # 3 sections per slab: 14 z-slabs
+    st = {}
+    got = volume_histogram(memmap, chunk_bytes=budget, stats=st)
+    assert got.dtype == np.int64 and got.shape == (256,) and np.array_equal(got, _bincount(vol))
+    assert st["chunks"] == 14 and st["read_s"] > 0
+    assert np.array_equal(volume_histogram(memmap), _bincount(vol))                     # the default budget: one slab
+    start, size = (9, 5, 3), (53, 39, 14)                                               # an inner ROI, (x, y, z)
+    roi = vol[3:17, 5:44, 9:62]
+    ysplit = 10 * 53 + 7                                                 # below one section of the ROI: split along y
+    assert len(hist_chunks(((3, 17), (5, 44), (9, 62)), ysplit)) == 14 * 4
+    for budget in (ysplit, 2 * 39 * 53):
+        assert np.array_equal(volume_histogram(memmap, start, size, chunk_bytes=budget), _bincount(roi))
+        got = volume_histogram(memmap, start, size, per_section=True, chunk_bytes=budget)
+        assert got.shape == (14, 256) and np.array_equal(got, np.stack([_bincount(s) for s in roi]))
+    parts = [volume_histogram(memmap, start, size, per_section=True, chunk_bytes=ysplit, rank=r, world_size=2, stats=st)
+             for r in range(2)]
+    assert st["chunks"] == 28 and all(p.any() for p in parts)
+    assert np.array_equal(parts[0] + parts[1], np.stack([_bincount(s) for s in roi]))
+    parts = [volume_histogram(memmap, chunk_bytes=budget, rank=r, world_size=2) for r in range(2)]
+    assert not np.array_equal(parts[0], parts[1]) and np.array_equal(parts[0] + parts[1], _bincount(vol))
+    img = vol[7]
+    assert np.array_equal(volume_histogram(img), _bincount(img))
+    assert np.array_equal(volume_histogram(img, (3, 4), (60, 41), chunk_bytes=500), _bincount(img[4:45, 3:63]))
+    assert volume_histogram(img, per_section=True).shape == (1, 256)
+    for start, size in (((0, 0, 0), (71, 50, 40)), ((-1, 0, 0), (5, 5, 5)), ((0, 0, 38), (5, 5, 3))):
+        with pytest.raises(ValueError):
+            volume_histogram(memmap, start, size)
+    assert not volume_histogram(memmap, (0, 0, 0), (0, 50, 40)).any()                   # an empty ROI counts nothing
+
+
+# ------------------------------------------------------------------------------------------------------- end to end
+# the 74 model: tiles of 36 + a halo of 19 (tpad 2)
+MS_X, MS_Y = (0.02, 0.58), (-0.1, 0.4)
+VOL, START, SIZE = (45, 60, 64), (-5, 3, -4), (50, 41, 40)           # (z,y,x); (x,y,z): 2 x 2 x 2 tiles past two faces
+VOL2, START2, SIZE2 = (3, 60, 64), (-3, 4, 0), (50, 41, 3)           # 2-D: 2 x 2 tiles in each of 3 sections
+THIN, THIN_START, THIN_SIZE = (20, 40, 45), (0, 0, 0), (36, 36, 100)  # tiles at z = 0, 36, 72: the last reads [53, 127)
+
+
+def _model(tmp_path, name, is3d):
+    from oracle import graph
+    from transfer_em_amd.cgan import EM2EM
+    model = EM2EM(74, name, is3d=is3d, checkpoint_root=str(tmp_path))
+    Pm = scaled_params(graph.generator_param_shapes(is3d), 4)
+    Pm["f2"] = Pm["f2"] * 20                                                 # spread outputs over the uint8 range
+    model.generator_g.params.load_dict(Pm)
+    return model
+
+
+@pytest.fixture(scope="module")
+def model3(tmp_path_factory):
+    return _model(tmp_path_factory.mktemp("hist3"), "hist3", True)
+
+
+@pytest.fixture(scope="module")
+def model2(tmp_path_factory):
+    return _model(tmp_path_factory.mktemp("hist2"), "hist2", False)
+
+
+@pytest.fixture(scope="module")
+def vol3():
+    return np.random.default_rng(31).integers(0, 256, VOL, dtype=np.uint8)
+
+
+@pytest.fixture(scope="module")
+def table():
+    """A table that moves every value, 0 included (lut[0] = 255 - 0 = 255 != 0), and is no bijection."""
+    t = (255 - (np.arange(256) // 2) * 2).astype(np.uint8)
+    assert t[0] != 0
+    return t
+
+
+@pytest.fixture(scope="module")
+def tables():
+    """One table per section of VOL, all different."""
+    rng = np.random.default_rng(32)
+    t = np.stack([rng.permutation(256).astype(np.uint8) for _ in range(VOL[0])])
+    assert len({r.tobytes() for r in t}) == VOL[0] and (t[:, 0] != 0).any()
+    return t
+
+
+def _guard(pred):
+    """A flat prediction would make the comparisons vacuous."""
+    assert pred.std() > 20 and len(np.unique(pred)) >= 16, (pred.std(), len(np.unique(pred)))
+
+
+def _eq(a, b):
+    assert a.shape == b.shape and np.array_equal(a, b), np.argwhere(a != b)[:5]
+
+
+@pytest.mark.parametrize("boundary", ["zeros", "reflect", "edge"])
+def test_cube_with_a_lut_equals_cube_on_the_remapped_volume(model3, vol3, table, boundary):
+    from transfer_em_amd.utils import predict_cube
+    want_in, want = predict_cube(table[vol3], START, SIZE, model3, MS_X, MS_Y, boundary=boundary, fetch_input=True)
+    _guard(want)
+    got_in, got = predict_cube(vol3, START, SIZE, model3, MS_X, MS_Y, boundary=boundary, lut=table, fetch_input=True)
+    _eq(got, want)
+    _eq(got_in, want_in)                                 # fetch_input: the remapped bytes, zeros outside under "zeros"
+    if boundary == "zeros":
+        assert (want_in[:4] == 0).all() and (want_in[:, :, :5] == 0).all()             # outside: 0, not lut[0] = 255
+        plain = predict_cube(vol3, START, SIZE, model3, MS_X, MS_Y)
+        assert not np.array_equal(plain, want)
+
+
+@pytest.mark.parametrize("kw", [dict(ensemble="flips"), dict(mips=1), dict(tile_batch=3)], ids=["flips", "mips1", "batch3"])
+def test_cube_with_a_lut_composes(model3, vol3, table, kw):
+    from transfer_em_amd.utils import predict_cube
+    want = predict_cube(table[vol3], START, SIZE, model3, MS_X, MS_Y, **kw)
+    got = predict_cube(vol3, START, SIZE, model3, MS_X, MS_Y, lut=table, **kw)
+    if "mips" in kw:
+        assert len(got) == len(want) == 2
+        _guard(want[0])
+        for a, b in zip(got, want):
+            _eq(a, b)
+    else:
+        _guard(want)
+        _eq(got, want)
+
+
+def test_cube_with_a_table_per_section_under_reflect(model3, vol3, tables):
+    from transfer_em_amd.utils import predict_cube
+    remapped = np.stack([tables[z][vol3[z]] for z in range(VOL[0])])
+    want_in, want = predict_cube(remapped, START, SIZE, model3, MS_X, MS_Y, boundary="reflect", fetch_input=True)
+    _guard(want)
+    got_in, got = predict_cube(vol3, START, SIZE, model3, MS_X, MS_Y, boundary="reflect", lut=tables, fetch_input=True)
+    _eq(got, want)
+    _eq(got_in, want_in)
+    assert not np.array_equal(want, predict_cube(tables[0][vol3], START, SIZE, model3, MS_X, MS_Y, boundary="reflect"))
+
+
+@pytest.mark.parametrize("boundary", ["zeros", "reflect"])
+def test_volume_with_a_lut_equals_cube(model3, vol3, table, tables, boundary):
+    from transfer_em_amd.utils import predict_cube, predict_volume
+    for t in (table, tables):
+        want = predict_cube(vol3, START, SIZE, model3, MS_X, MS_Y, boundary=boundary, lut=t)
+        _guard(want)
+        got = predict_volume(vol3, START, SIZE, model3, MS_X, MS_Y, chunk_tiles=(1, 1, 2), boundary=boundary, lut=t)
+        _eq(got, want)
+
+
+def test_volume_with_a_lut_and_a_chunk_outside_the_volume(model3, table):
+    """A chunk wholly outside the volume gathers from one stand-in zero byte, which must not become lut[0]."""
+    from transfer_em_amd.utils import chunk_plan, predict_cube, predict_volume
+    thin = np.random.default_rng(33).integers(0, 256, THIN, dtype=np.uint8)
+    chunks = chunk_plan(THIN_START, THIN_SIZE, model3.outdimsize, model3.buffer, THIN, (1, 1, 1))
+    assert len(chunks) == 3 and sum(min(c.block) == 0 for c in chunks) == 1
+    want = predict_cube(table[thin], THIN_START, THIN_SIZE, model3, MS_X, MS_Y)
+    _guard(want)
+    _eq(predict_cube(thin, THIN_START, THIN_SIZE, model3, MS_X, MS_Y, lut=table), want)
+    per_section = np.tile(table, (THIN[0], 1))
+    for t in (table, per_section):
+        _eq(predict_volume(thin, THIN_START, THIN_SIZE, model3, MS_X, MS_Y, chunk_tiles=(1, 1, 1), lut=t), want)
+
+
+def test_2d_model_with_a_lut(model2, table):
+    from transfer_em_amd.utils import predict_cube, predict_volume
+    vol = np.random.default_rng(34).integers(0, 256, VOL2, dtype=np.uint8)
+    rows = np.stack([table, table[::-1].copy(), np.roll(table, 7)])
+    for t, remapped in ((table, table[vol]), (rows, np.stack([rows[z][vol[z]] for z in range(3)]))):
+        want = predict_cube(remapped, START2, SIZE2, model2, MS_X, MS_Y)
+        _guard(want)
+        _eq(predict_cube(vol, START2, SIZE2, model2, MS_X, MS_Y, lut=t), want)
+        _eq(predict_volume(vol, START2, SIZE2, model2, MS_X, MS_Y, chunk_tiles=(2, 1, 2), lut=t), want)
+    img = predict_cube(vol[1], START2[:2], SIZE2[:2], model2, MS_X, MS_Y, lut=table)     # one image
+    _eq(img, predict_cube(table[vol[1]], START2[:2], SIZE2[:2], model2, MS_X, MS_Y))
+    _eq(predict_volume(vol[1], START2[:2], SIZE2[:2], model2, MS_X, MS_Y, lut=table[None]), img)
+
+
+def test_histogram_of_the_prediction(model3, vol3, model2):
+    """SIZE is no multiple of the 36-voxel tile: the margin of the rounded-up blocks must not be counted."""
+    from transfer_em_amd.utils import predict_cube, predict_volume
+    assert all(n % 36 for n in SIZE)
+    st = {}
+    out = predict_cube(vol3, START, SIZE, model3, MS_X, MS_Y, histogram=True, stats=st)
+    _guard(out)
+    want = _bincount(out)
+    assert st["histogram"].dtype == np.int64 and np.array_equal(st["histogram"], want) and want.sum() == out.size
+    st = {}
+    _eq(predict_volume(vol3, START, SIZE, model3, MS_X, MS_Y, chunk_tiles=(1, 1, 2), histogram=True, stats=st), out)
+    assert np.array_equal(st["histogram"], want) and st["chunks"] == 4
+    st = {}
+    levels = predict_cube(vol3, START, SIZE, model3, MS_X, MS_Y, mips=1, histogram=True, stats=st)
+    _eq(levels[0], out)
+    assert np.array_equal(st["histogram"], want)                                       # level 0 only
+    st = {}
+    predict_volume(vol3, START, SIZE, model3, MS_X, MS_Y, chunk_tiles=(1, 2, 1), mips=1, histogram=True, stats=st)
+    assert np.array_equal(st["histogram"], want)
+    parts = []
+    for rank in range(2):                                                              # the ranks' histograms add
+        st = {}
+        predict_volume(vol3, START, SIZE, model3, MS_X, MS_Y, chunk_tiles=(1, 1, 2), rank=rank, world_size=2,
+                       histogram=True, stats=st)
+        parts.append(st["histogram"])
+    assert parts[0].sum() + parts[1].sum() == out.size and np.array_equal(parts[0] + parts[1], want)
+    vol2 = np.random.default_rng(35).integers(0, 256, VOL2, dtype=np.uint8)
+    st, st2 = {}, {}
+    out2 = predict_cube(vol2, START2, SIZE2, model2, MS_X, MS_Y, histogram=True, stats=st)
+    predict_volume(vol2, START2, SIZE2, model2, MS_X, MS_Y, chunk_tiles=(2, 1, 2), histogram=True, stats=st2)
+    assert np.array_equal(st["histogram"], _bincount(out2)) and np.array_equal(st2["histogram"], _bincount(out2))
+
+
+def test_defaults_are_the_plain_call(model3, vol3):
+    from transfer_em_amd.utils import predict_cube, predict_volume
+    plain = predict_cube(vol3, START, SIZE, model3, MS_X, MS_Y)
+    _guard(plain)
+    st = {}
+    _eq(predict_cube(vol3, START, SIZE, model3, MS_X, MS_Y, lut=None, histogram=False, stats=st), plain)
+    assert st == {}
+    _eq(predict_volume(vol3, START, SIZE, model3, MS_X, MS_Y, chunk_tiles=(1, 1, 2)), plain)
+    _eq(predict_volume(vol3, START, SIZE, model3, MS_X, MS_Y, chunk_tiles=(1, 1, 2), lut=None, histogram=False, stats=st),
+        plain)
+    assert "histogram" not in st
+    identity = np.arange(256, dtype=np.uint8)
+    _eq(predict_cube(vol3, START, SIZE, model3, MS_X, MS_Y, lut=identity), plain)

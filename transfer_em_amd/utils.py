@@ -14,6 +14,10 @@ streamed through the same kernels with the I/O of neighbouring chunks overlapped
 Every entry point dispatches on `model.generator_g.is3d`.  A 2-D model predicts a stack of sections [z, y, x] section
 by section (`tile_plan_2d`: tile_plan's in-plane tiling in every section, no halo and no rounding along z) through the
 2-D tile kernels, or one image [y, x] given 2-element start / size.
+
+`volume_histogram`, `meanstd_from_histogram` and `match_lut` measure a volume's intensities out of core and turn them into
+the statistics and lookup tables that `predict_cube` / `predict_volume` take (`lut=`: remapped on the device ahead of the
+gather; `histogram=True`: the histogram of the prediction, counted on the device).
 """
 import json
 import os
@@ -472,8 +476,231 @@ def _pool_levels(lib, src_ptr, dims, valid, L, is3d, dst_ptrs, stream):
     return levels
 
 
+HIST_CHUNK_BYTES = 64 << 20      # volume_histogram's default slab: two pinned and two device buffers of this size
+
+
+def hist_box(vol_shape, start=None, size=None):
+    """The (z, y, x) (lo, hi) box of the ROI `start` / `size` ((x, y, z) order; None: the whole volume) of a volume of
+    shape (Z, Y, X).  One image: a 2-element shape with 2-element (x, y) start / size, returned as the box of a
+    one-section stack.  The ROI must lie inside the volume -- a voxel that does not exist has no intensity --
+    ValueError otherwise, as for a negative size or a wrong number of elements."""
+    shape = tuple(int(v) for v in vol_shape)
+    if len(shape) not in (2, 3):
+        raise ValueError(f"volume must be [z, y, x] or one image [y, x], got shape {shape}")
+    nd = len(shape)
+    start = (0,) * nd if start is None else tuple(int(v) for v in start)
+    size = tuple(reversed(shape)) if size is None else tuple(int(v) for v in size)
+    if len(start) != nd or len(size) != nd:
+        raise ValueError(f"start and size must have {nd} elements for a volume of shape {shape}: got {start}, {size}")
+    box = []
+    for d in range(nd):                               # d over (x, y[, z]); axis nd - 1 - d of the volume
+        lo, n, ext = start[d], size[d], shape[nd - 1 - d]
+        if n < 0 or lo < 0 or lo + n > ext:
+            raise ValueError(f"the ROI start={start}, size={size} (x, y, z) reaches outside the volume of shape {shape}: "
+                             f"voxels that do not exist have no intensity")
+        box.append((lo, lo + n))
+    box = tuple(reversed(box))
+    return box if nd == 3 else ((0, 1),) + box
+
+
+def hist_chunks(box, chunk_bytes=None, rank=0, world_size=1):
+    """Cut the (z, y, x) (lo, hi) `box` into disjoint slabs of at most `chunk_bytes` bytes (HIST_CHUNK_BYTES when None)
+    whose union is the box: runs of whole sections, or, where one section of the box is larger than the budget, runs of
+    whole rows of one section (one row at the least: a budget below a row's bytes gives one-row slabs).  x is never
+    cut.  Slabs are in (z, y) order and go round-robin to the ranks; returns this rank's list of boxes.  Pure host
+    function."""
+    budget = HIST_CHUNK_BYTES if chunk_bytes is None else int(chunk_bytes)
+    if budget < 1:
+        raise ValueError(f"chunk_bytes must be positive, got {chunk_bytes}")
+    if not 0 <= rank < world_size:
+        raise ValueError(f"rank {rank} is outside [0, {world_size})")
+    (z0, z1), (y0, y1), (x0, x1) = box
+    ny, nx = y1 - y0, x1 - x0
+    if z1 <= z0 or ny <= 0 or nx <= 0:
+        return []
+    slabs = []
+    if ny * nx <= budget:
+        kz = budget // (ny * nx)
+        slabs = [((z, min(z + kz, z1)), (y0, y1), (x0, x1)) for z in range(z0, z1, kz)]
+    else:
+        ky = max(1, budget // nx)
+        slabs = [((z, z + 1), (y, min(y + ky, y1)), (x0, x1)) for z in range(z0, z1) for y in range(y0, y1, ky)]
+    return slabs[rank::world_size]
+
+
+def volume_histogram(volume, start=None, size=None, per_section=False, chunk_bytes=None, rank=0, world_size=1,
+                     device=None, stats=None):
+    """Intensity histogram of the ROI [start, start + size) ((x, y, z) order; default: the whole volume) of a uint8
+    array-like `volume` indexed [z, y, x] (ndarray, np.memmap, h5py / zarr dataset: `.shape` and basic slicing are all
+    it needs), or of one image [y, x] with 2-element start / size.  Returns np.int64[256], or with per_section
+    np.int64[size_z, 256] whose row i counts section start_z + i.  The ROI must lie inside the volume: ValueError
+    otherwise, before any GPU work.
+
+    Out of core, through the input side of predict_volume's pipeline: the ROI is cut into slabs of at most
+    `chunk_bytes` (hist_chunks); one host thread reads each slab into double-buffered pinned memory -> H2D on a copy
+    stream -> tem_u8_hist on the compute stream, adding into ONE device accumulator that is read back once at the end.
+    The pass is bound by the read (`stats` receives the read seconds `read_s` and the slab count `chunks`).  Ranks
+    (rank / world_size) take slabs round-robin: each returns the counts of its own slabs, the ranks' results add up to
+    the whole, and no collective is used."""
+    import time
+    from concurrent.futures import ThreadPoolExecutor
+    from . import _lib
+    box = hist_box(volume.shape, start, size)
+    if getattr(volume, "dtype", np.dtype(np.uint8)) != np.uint8:
+        raise ValueError(f"volume must be uint8, got {volume.dtype}")
+    slabs = hist_chunks(box, chunk_bytes, rank, world_size)
+    lib = H.require_gpu()
+    if len(volume.shape) == 2:
+        volume = _OneSection(volume)
+    nz = box[0][1] - box[0][0]
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    st = {"read_s": 0.0, "chunks": len(slabs)}
+    K = len(slabs)
+    dims = [tuple(hi - lo for lo, hi in b) for b in slabs]
+    nbytes = [int(np.prod(d)) for d in dims]
+    with torch.cuda.device(dev):
+        compute, h2d = torch.cuda.current_stream(dev), torch.cuda.Stream(dev)
+        acc = torch.zeros((nz if per_section else 1, 256), dtype=torch.int64, device=dev)
+        if K:
+            pin = [torch.empty(max(nbytes), dtype=torch.uint8, pin_memory=True) for _ in range(min(2, K))]
+            buf = [torch.empty(max(nbytes), dtype=torch.uint8, device=dev) for _ in range(min(2, K))]
+        h2d_done, counted = {}, {}
+
+        def read(k):                        # host thread: slab k -> pin[k % 2]
+            if k >= 2:
+                h2d_done.pop(k - 2).synchronize()           # the buffer's previous H2D has finished
+            t0 = time.perf_counter()
+            (z0, z1), (y0, y1), (x0, x1) = slabs[k]
+            pin[k % 2][:nbytes[k]].numpy().reshape(dims[k])[...] = volume[z0:z1, y0:y1, x0:x1]
+            st["read_s"] += time.perf_counter() - t0
+
+        pool = ThreadPoolExecutor(max_workers=1)
+        reads = {k: pool.submit(read, k) for k in range(min(2, K))}
+        try:
+            for k in range(K):
+                s = k % 2
+                reads.pop(k).result()
+                if k >= 2:
+                    h2d.wait_event(counted.pop(k - 2))       # buf[s]: slab k-2 has been counted
+                with torch.cuda.stream(h2d):
+                    buf[s][:nbytes[k]].copy_(pin[s][:nbytes[k]], non_blocking=True)
+                h2d_done[k] = h2d.record_event()
+                compute.wait_event(h2d_done[k])
+                d = dims[k]
+                row = (slabs[k][0][0] - box[0][0]) if per_section else 0
+                _lib.check(lib.tem_u8_hist(buf[s].data_ptr(), *d, 0, d[0], 0, d[1], 0, d[2], acc.data_ptr() + 2048 * row,
+                                           int(bool(per_section)), compute.cuda_stream), "tem_u8_hist")
+                counted[k] = compute.record_event()
+                if k + 2 < K:
+                    reads[k + 2] = pool.submit(read, k + 2)
+        except BaseException:
+            pool.shutdown(wait=True, cancel_futures=True)
+            torch.cuda.synchronize(dev)                      # nothing in flight on the buffers about to be freed
+            raise
+        pool.shutdown(wait=True)
+        out = acc.cpu().numpy()                              # the one read-back
+    if stats is not None:
+        stats.update(st)
+    return out if per_section else out[0]
+
+
+def meanstd_from_histogram(h):
+    """(np.float32 mean, np.float32 std) of the SCALED values v / 127.5 - 1 of the voxels a 256-bin histogram `h`
+    counts (a [Z, 256] per-section histogram is summed over its rows first): the unit `meanstd_x` / `meanstd_y` are
+    in.  The standard deviation is the population one; both are computed in float64 from the counts and rounded once.
+    This is datasets.get_meanstd of a dataset that holds the ROI as ONE tensor (which accumulates in float32, so the
+    last bits may differ).  Over several tensors get_meanstd is another quantity: it averages the per-tensor means and
+    the per-tensor variances, which leaves the spread of the tensors' means out of the variance.  ValueError on an
+    empty histogram."""
+    h = np.asarray(h)
+    if h.ndim not in (1, 2) or h.shape[-1] != 256:
+        raise ValueError(f"a histogram has 256 bins ([256] or [Z, 256]), got shape {h.shape}")
+    h = h.reshape(-1, 256).astype(np.float64).sum(axis=0)
+    n = h.sum()
+    if not n > 0:
+        raise ValueError("meanstd_from_histogram: the histogram is empty")
+    v = np.arange(256, dtype=np.float64) / 127.5 - 1.0
+    mean = (h * v).sum() / n
+    var = (h * (v - mean) ** 2).sum() / n
+    return np.float32(mean), np.float32(np.sqrt(var))
+
+
+def _match_row(hs, hr):
+    cs, cr, a = [], [], 0
+    for c in hs:
+        a += int(c)
+        cs.append(a)
+    a = 0
+    for c in hr:
+        a += int(c)
+        cr.append(a)
+    ns, nr = cs[-1], cr[-1]
+    if nr == 0:
+        raise ValueError("match_lut: the reference histogram is empty")
+    if ns == 0:
+        return list(range(256))
+    lut, w = [], 0
+    for v in range(256):                    # cs is non-decreasing, so w only moves up; cr[255] nr == nr ns ends it
+        while cs[v] * nr > cr[w] * ns:
+            w += 1
+        lut.append(w)
+    return lut
+
+
+def match_lut(h_src, h_ref):
+    """The classical histogram match as a lookup table: np.uint8[256] with lut[v] = the smallest w whose reference CDF
+    reaches the source CDF of v, cdf_ref(w) >= cdf_src(v), decided in exact integer arithmetic on the cumulative
+    counts (cs[v] N_ref <= cr[w] N_src, Python ints).  The table is non-decreasing, and the identity on the occupied
+    bins when both histograms are the same.  Row-wise for an h_src of shape [Z, 256] (per-section histograms), against
+    one h_ref [256] or [Z, 256] of them: returns [Z, 256], the form predict_cube / predict_volume take as `lut`.  A
+    source row without voxels gets the identity; an empty reference raises ValueError, as negative counts do."""
+    hs, hr = np.asarray(h_src), np.asarray(h_ref)
+    for name, h in (("h_src", hs), ("h_ref", hr)):
+        if h.ndim not in (1, 2) or h.shape[-1] != 256 or h.dtype.kind not in "iu":
+            raise ValueError(f"match_lut: {name} must be integer counts of shape [256] or [Z, 256], got {h.dtype} "
+                             f"{h.shape}")
+        if h.size and int(h.min()) < 0:
+            raise ValueError(f"match_lut: {name} has negative counts")
+    if hs.ndim == 1:
+        if hr.ndim != 1:
+            raise ValueError("match_lut: a [Z, 256] h_ref needs a [Z, 256] h_src")
+        return np.array(_match_row(hs, hr), np.uint8)
+    if hr.ndim == 2 and hr.shape[0] != hs.shape[0]:
+        raise ValueError(f"match_lut: h_src has {hs.shape[0]} rows, h_ref {hr.shape[0]}")
+    return np.array([_match_row(hs[z], hr[z] if hr.ndim == 2 else hr) for z in range(hs.shape[0])],
+                    np.uint8).reshape(hs.shape[0], 256)
+
+
+def _check_lut(lut, vol_shape):
+    """None, or `lut` as a C-contiguous np.uint8 array: [256], or [Z, 256] with Z the section count of the volume of
+    shape `vol_shape` ([z, y, x]; one image [y, x] has one section).  ValueError for anything else."""
+    if lut is None:
+        return None
+    if not isinstance(lut, np.ndarray) or lut.dtype != np.uint8:
+        raise ValueError(f"lut must be a numpy uint8 array, got {getattr(lut, 'dtype', type(lut).__name__)}")
+    Z = int(vol_shape[0]) if len(vol_shape) == 3 else 1
+    if lut.shape != (256,) and lut.shape != (Z, 256):
+        raise ValueError(f"lut must have shape (256,) or ({Z}, 256) -- one row per section of the volume -- got "
+                         f"{lut.shape}")
+    return np.ascontiguousarray(lut)
+
+
+def _check_histogram(histogram, stats):
+    if not isinstance(histogram, (bool, np.bool_)):
+        raise ValueError(f"histogram must be True or False, got {histogram!r}")
+    if histogram and not isinstance(stats, dict):
+        raise ValueError("histogram=True reports in stats['histogram']: pass a dict as `stats`")
+    return bool(histogram)
+
+
+def _lut_host(vol, lut):
+    """lut[vol], or lut[z][vol[z]] for a [Z, 256] table: what tem_u8_lut leaves on the device."""
+    return lut[vol] if lut.ndim == 1 else lut[np.arange(vol.shape[0])[:, None, None], vol]
+
+
 def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=False, outdimsize=None, buffer=None,
-                 rank=0, world_size=1, tile_batch=None, boundary="zeros", ensemble=None, mips=None):
+                 rank=0, world_size=1, tile_batch=None, boundary="zeros", ensemble=None, mips=None, lut=None,
+                 histogram=False, stats=None):
     """Predict the subvolume [start, start+size) (x,y,z order as in the reference) of a uint8
     array `volume` indexed [z, y, x].  Voxels outside the array read as 0 (the reference fetches
     them from the store) or, with boundary="reflect" / "edge", the voxel that `fold` names on every axis: the result
@@ -515,11 +742,26 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
     each pooled axis; choose `start` as a multiple of 2^L where it has to sit on a global grid.  L is at most
     max_mips(outdimsize) of the tile plan's outdimsize -- 5 for the 132 model (96), 2 for the 74 model (36), 1 for the
     260 model (222) -- so that predict_volume's chunks can pool on their own; a larger, negative or non-integer `mips`
-    raises ValueError before any GPU work.  With fetch_input the result is (input block, list)."""
+    raises ValueError before any GPU work.  With fetch_input the result is (input block, list).
+
+    lut=None reads the volume as it is.  lut = a np.uint8 table [256], or [Z, 256] with one row per section of the
+    volume (match_lut builds either from histograms), remaps the intensities first: the result is, bit for bit, that of
+    the same call on lut[volume] (lut[z][volume[z]]) for every boundary, ensemble, mips and tile_batch, without a
+    remapped copy -- one tem_u8_lut launch runs in place on the uploaded bytes ahead of the first gather.  Only voxels
+    of the volume are remapped: a voxel outside it still reads 0 under "zeros", not lut[0], and under the mirrored modes
+    the remapped voxel it folds to.  fetch_input returns what the network saw, the remapped bytes.  A table of another
+    dtype or shape raises ValueError before any GPU work.
+
+    histogram=True puts the 256-bin histogram of the level-0 prediction into stats["histogram"] (np.int64[256]; `stats`
+    must then be a dict): the voxels of the returned array and no others -- nothing past `size`, nothing from the
+    rounded-up tile margin -- counted on the device by one tem_u8_hist launch over the cropped box of the result,
+    after the all-reduce of a multi-rank call.  meanstd_from_histogram turns it into the unit of meanstd_y."""
     from . import _lib
     gen = getattr(model, "generator_g", None)
     is3d = getattr(gen, "is3d", True)
     syms = _check_ensemble(ensemble, is3d)
+    lut = _check_lut(lut, np.shape(volume))
+    histogram = _check_histogram(histogram, stats)
     if outdimsize is None:
         outdimsize = model.outdimsize
     if buffer is None:
@@ -529,7 +771,7 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
     if _single_image(model, start, size):
         res = predict_cube(np.asarray(volume)[None], tuple(start) + (0,), tuple(size) + (1,), model, meanstd_x,
                            meanstd_y, fetch_input, outdimsize, buffer, rank, world_size, tile_batch, boundary, ensemble,
-                           mips)
+                           mips, lut, histogram, stats)
         one = lambda r: [v[0] for v in r] if isinstance(r, list) else r[0]
         return tuple(one(r) for r in res) if fetch_input else one(res)
     outdimsize, buffer, tpad, rois, index = (tile_plan if is3d else tile_plan_2d)(start, size, outdimsize, buffer)
@@ -541,6 +783,11 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
     _check_boundary(boundary, vol_host.shape)
     vol = torch.from_numpy(vol_host).to(dev, non_blocking=True)          # ONE upload of the whole volume
     Z, Y, X = vol_host.shape
+    stream = H.current_stream()
+    if lut is not None and vol_host.size:       # remapped in place, once, behind the upload
+        lut_dev = torch.from_numpy(lut).to(dev)
+        _lib.check(lib.tem_u8_lut(vol.data_ptr(), Z, Y, X, lut_dev.data_ptr(), int(lut.ndim == 2), 0, stream),
+                   "tem_u8_lut")
     out_buffer = torch.zeros((rnd(z) if is3d else z, rnd(y), rnd(x)), dtype=torch.uint8, device=dev)
     OZ, OY, OX = out_buffer.shape
     mine = list(range(rank, len(rois), world_size))
@@ -550,7 +797,6 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
     if syms is not None:
         (sgather, sgname), (accum, aname) = _sym_kernels(lib, is3d, boundary)
         acc = []                                # the fp32 accumulator, allocated by the first (largest) batch
-    stream = H.current_stream()
     for c0 in range(0, len(mine), nb):
         chunk = mine[c0:c0 + nb]
         n = len(chunk)
@@ -578,6 +824,12 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
     if world_size > 1 and torch.distributed.is_initialized():
         torch.distributed.all_reduce(out_buffer, op=torch.distributed.ReduceOp.MAX)   # disjoint tiles, zeros elsewhere
     out = out_buffer[0:size[2], 0:size[1], 0:size[0]].cpu().numpy()
+    if histogram:                               # of the cropped box: the voxels of `out`
+        counts = torch.zeros(256, dtype=torch.int64, device=dev)
+        if out.size:
+            _lib.check(lib.tem_u8_hist(out_buffer.data_ptr(), OZ, OY, OX, 0, size[2], 0, size[1], 0, size[0],
+                                       counts.data_ptr(), 0, stream), "tem_u8_hist")
+        stats["histogram"] = counts.cpu().numpy()
     if L:                                       # the pyramid of the resident result: one launch per level
         fz = 2 if is3d else 1
         shapes = mip_shapes(size, L, is3d)
@@ -591,6 +843,8 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
         # the reference returns the RAW uint8 block here after a detour (utils.py:122-125: the standardized float
         # tile is un-standardized, rescaled and truncated into a uint8 buffer -- the original bytes up to float
         # rounding); the bytes themselves are returned instead
+        if lut is not None:                      # ... as the network saw them: remapped
+            vol_host = _lut_host(vol_host, lut)
         if boundary != "zeros":                  # what the network saw: the ROI of the folded volume
             fz, fy, fx = (fold(np.arange(start[d], start[d] + size[d]), n, boundary) for d, n in ((2, Z), (1, Y), (0, X)))
             return vol_host[np.ix_(fz, fy, fx)], out
@@ -737,7 +991,7 @@ def chunk_plan(start, size, outdimsize, buffer, vol_shape, chunk_tiles, rank=0, 
 
 def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, chunk_tiles=None, tile_batch=None,
                    outdimsize=None, buffer=None, rank=0, world_size=1, stats=None, boundary="zeros", ensemble=None,
-                   mips=None):
+                   mips=None, lut=None, histogram=False):
     """Out-of-core predict_cube: the subvolume [start, start+size) (x,y,z order) of a uint8 array-like `volume`
     indexed [z, y, x] (ndarray, np.memmap, h5py / zarr dataset: `.shape` and basic slicing are all it needs) is
     predicted chunk by chunk (chunk_plan) into `out`, a writable uint8 array-like of shape (size[2], size[1], size[0])
@@ -773,7 +1027,20 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
     predictions past `size` never enter a mean) into the same device buffer, which holds the chunk's levels back to
     back; the one D2H copy moves them all and the host thread writes each level's box (`mip_box`).  The device and
     pinned output buffers grow by at most 1/7 (1/3 for a 2-D model); nothing else changes, and `boundary` and
-    `ensemble` compose as they are (pooling comes after the scatter).  `stats["mips"]` reports L."""
+    `ensemble` compose as they are (pooling comes after the scatter).  `stats["mips"]` reports L.
+
+    `lut` is predict_cube's ([256], or [Z, 256] indexed by the volume's own section): each chunk's footprint is remapped
+    in place on the device by one tem_u8_lut launch on the compute stream, behind the wait for the chunk's H2D and ahead
+    of its first gather, with the footprint's first section as the table's row offset.  The one zero byte that stands in
+    for a chunk wholly outside the volume is not remapped, so voxels outside the volume read 0 as before; under the
+    mirrored modes the footprint hull holds real sections, remapped by their own rows.  The result equals
+    predict_cube(lut=...)'s, i.e. that of the same call on the remapped volume, which is never made.
+
+    histogram=True puts the 256-bin histogram of the level-0 result (np.int64[256]) into stats["histogram"]: one
+    tem_u8_hist launch per chunk behind its last scatter, over the chunk's `out_box` extents of its device block, adding
+    into one device accumulator that is read back once at the end -- no voxel is copied for it, and predictions past
+    `size` are not counted.  In a multi-rank call each rank reports the histogram of its own chunks: the ranks'
+    histograms add up to that of the whole result."""
     import time
     from concurrent.futures import ThreadPoolExecutor
     from . import _lib
@@ -783,6 +1050,8 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
     L = _check_mips(mips, _plan_outdimsize(model.outdimsize if outdimsize is None else outdimsize))
     if L and len(size) in (2, 3):
         out = _check_mip_outs(out, size, L, is3d)
+    lut = _check_lut(lut, tuple(volume.shape))
+    histogram = _check_histogram(histogram, stats)
     lib = H.require_gpu()
     if not hasattr(gen, "plan"):
         raise TypeError("predict_volume needs a generator with launch plans (EM2EM or a saved model)")
@@ -794,7 +1063,7 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
                    np.zeros((size[1], size[0]), np.uint8))
         predict_volume(_OneSection(volume), tuple(start) + (0,), tuple(size) + (1,), model, meanstd_x, meanstd_y,
                        [_OneSection(o) for o in out] if L else _OneSection(out), chunk_tiles, tile_batch, outdimsize,
-                       buffer, rank, world_size, stats, boundary, ensemble, mips)
+                       buffer, rank, world_size, stats, boundary, ensemble, mips, lut, histogram)
         return out
     vol_shape = tuple(int(v) for v in volume.shape)
     if len(vol_shape) != 3:
@@ -816,6 +1085,8 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
     elif tuple(out.shape) != (size[2], size[1], size[0]):
         raise ValueError(f"out has shape {tuple(out.shape)}, expected {(size[2], size[1], size[0])}")
     st = {"read_s": 0.0, "write_s": 0.0, "chunks": len(chunks), "mips": L}
+    if histogram:
+        st["histogram"] = np.zeros(256, np.int64)
     if stats is not None:
         stats.update(st)
     if not chunks:
@@ -844,6 +1115,8 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
     org = torch.tensor([o for c in chunks for o in c.origins], dtype=torch.int32).to(dev)     # every chunk's, once
     idx = torch.tensor([o for c in chunks for o in c.offsets], dtype=torch.int32).to(dev)
     h2d_done, gathered, d2h_done, d2h_evt = {}, {}, {}, [None, None]
+    lut_dev = None if lut is None else torch.from_numpy(lut).to(dev)
+    counts = torch.zeros(256, dtype=torch.int64, device=dev) if histogram else None
 
     def read(k):                        # host thread: footprint of chunk k -> pin_in[k % 2]
         if k >= 2:
@@ -887,6 +1160,9 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
             if k >= 2:
                 compute.wait_event(d2h_evt[s])               # dev_out[s]: chunk k-2's D2H has read it
             lo = tuple(r[0] for r in c.read)
+            if lut_dev is not None and min(c.block) > 0:     # the footprint, in place; never the stand-in zero byte
+                _lib.check(lib.tem_u8_lut(dev_in[s].data_ptr(), *gdims[k], lut_dev.data_ptr(), int(lut.ndim == 2), lo[0],
+                                          compute.cuda_stream), "tem_u8_lut")
             OZ, OY, OX = c.dims
             n = len(c.tiles)
             for b0 in range(0, n, nb):
@@ -918,6 +1194,10 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
                 base = dev_out[s].data_ptr()
                 _pool_levels(lib, base, c.dims, tuple(hi - lo for lo, hi in c.out_box), L, is3d,
                              [base + int(o) for o in lvl_off[k][1:L + 1]], compute.cuda_stream)
+            if histogram:                                    # of the chunk's part of the result, where it lies
+                oz, oy, ox = (max(hi - lo_, 0) for lo_, hi in c.out_box)
+                _lib.check(lib.tem_u8_hist(dev_out[s].data_ptr(), OZ, OY, OX, 0, oz, 0, oy, 0, ox, counts.data_ptr(), 0,
+                                           compute.cuda_stream), "tem_u8_hist")
             scattered = compute.record_event()
             if k >= 2:
                 writes.pop(k - 2).result()                   # pin_out[s]: chunk k-2 is in `out`
@@ -935,6 +1215,8 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
         torch.cuda.synchronize(dev)                          # nothing in flight on the buffers about to be freed
         raise
     pool.shutdown(wait=True)
+    if histogram:
+        st["histogram"] = counts.cpu().numpy()               # the one read-back
     if stats is not None:
         stats.update(st)
     return out
@@ -1000,8 +1282,10 @@ def predict_volume_from_saved_model(volume, start, size, model_dir, out=None, **
     """predict_volume with the generator and statistics exported by save_model to `model_dir` (the out-of-core
     sibling of predict_cube_from_saved_model); `kw` are predict_volume's chunk_tiles, tile_batch, rank, world_size,
     stats, boundary ("zeros", "reflect" or "edge": what a voxel outside the volume reads), ensemble (None, "flips",
-    "all" or a sequence of symmetries: the orientations the generator's output is averaged over) and mips (None, or
-    the number of pooled levels of the result's mip pyramid: `out` and the return value are then lists of levels).
+    "all" or a sequence of symmetries: the orientations the generator's output is averaged over), mips (None, or
+    the number of pooled levels of the result's mip pyramid: `out` and the return value are then lists of levels),
+    lut (None, or a uint8 table [256] or [Z, 256] the volume's intensities are remapped by on the device) and
+    histogram (True: stats["histogram"] receives the 256-bin histogram of the result).
     The reference's signatures, predict_ng_cube and predict_cube_from_saved_model, take none of these keywords; they
     run unensembled and return the full-resolution array alone."""
     model = _load_saved(model_dir)
