@@ -87,7 +87,7 @@ seen = set()
 for fname, (entry, nd, table) in T.TABLES.items():
     for ci, co, k, s in table:
         for n in SIZES[entry, nd, k]:
-            if n in (100, 132) and max(ci, co) == 32:                          # (32 channels: past the patch the loaders' registers hold)
+            if n in (100, 132) and max(ci, co) == 32:                          # (32 channels: past the row one band holds -- the "wide" cases below)
                 n = 60 if nd == 3 else 68
             p = 1 if entry == "convT" else 0
             if (entry, nd, ci, co, k, s, n) not in seen:                      # the plain layer: the first kernel of the route that takes it
@@ -228,6 +228,32 @@ for entry in ("conv", "convT", "bww"):
         case(b + "mask_below_2^33", entry, nd, ci, co, k, s, n, tags=["mask_below_2^33"], ep={**DROP[1], "drop_dims": below}, **kw)
         case(b + "mask_at_2^33", entry, nd, ci, co, k, s, n, tags=["mask_at_2^33"], ep={**DROP[1], "drop_dims": dd}, **kw)
         case(b + "mask_at_2^33_no_dropout", entry, nd, ci, co, k, s, n, ep={"drop_dims": dd}, **kw)
+
+# ---------------------------------------------------------------- kernel gradients of rows wider than one band
+# A pad-0 row whose single-row band overflows the loaders' registers is cut into column segments (run() of bww_bf16.hip /
+# bww2d_bf16.hip); only the width matters, so the other extents are small (3-D: D 8, H = W; 2-D: H 12).  Per layer form the
+# last width that is one launch, the first that is segmented, and the widest at which the 260 model launches the form.
+def wide(nd, ci, co, k, s, w, ci1=0, p=0):
+    d, h = (8, w) if nd == 3 else (1, 12)
+    o = lambda n: (n + 2 * p - k) // s + 1
+    kk, ss, pp = ([k] * 3, [s] * 3, [p] * 3) if nd == 3 else ([1, k, k], [1, s, s], [0, p, p])
+    cid = f"bww{nd}d_{ci}{'+' + str(ci1) if ci1 else ''}to{co}_k{k}s{s}_wide{w}" + (f"_p{p}" if p else "")
+    cases.append(dict(id=cid, entry="bww", k=kk, s=ss, p=pp, w=0x50000000, w_layout=0, nslab=8192, tags=["wide"],
+                      in0=view("in0", 1, d, h, w, ci), in1=view("in1", 1, d, h, w, ci1) if ci1 else None,
+                      out0=view("out0", 1, o(d) if nd == 3 else 1, o(h), o(w), co), out1=None, ep=json.loads(json.dumps(NO_EP))))
+
+
+WIDE = [(3, 8, 16, 3, 1, 8, 171, 228), (3, 16, 32, 3, 1, 0, 171, 108), (3, 32, 16, 3, 1, 0, 86, 116), (3, 32, 32, 3, 1, 0, 86, 118),
+        (3, 8, 8, 4, 2, 0, 258, 254), (3, 16, 16, 4, 2, 0, 130, 124), (3, 32, 32, 4, 2, 0, 66, 106),
+        (2, 32, 16, 3, 1, 0, 171, 116), (2, 32, 32, 3, 1, 0, 171, 118), (2, 16, 16, 4, 2, 0, 258, 124), (2, 32, 32, 4, 2, 0, 130, 220)]
+for nd, ci, co, k, s, ci1, limit, model in WIDE:
+    for w in (limit - 1, limit, model):
+        wide(nd, ci, co, k, s, w, ci1=ci1)
+# (the 260 model's cycle cone launches three of the forms at a second width past the limit)
+for nd, ci, co, k, s, w, ci1 in ((3, 8, 16, 3, 1, 192, 8), (3, 32, 16, 3, 1, 100, 0), (3, 16, 32, 3, 1, 102, 16)):
+    wide(nd, ci, co, k, s, w, ci1=ci1)
+wide(3, 32, 32, 3, 1, 86, p=1)                     # a padded row that is too wide stays refused
+wide(2, 32, 32, 4, 2, 130, p=1)
 
 
 def main():

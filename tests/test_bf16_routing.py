@@ -170,3 +170,22 @@ def test_table_covers_the_rejections():
     for tag in ("span_below_2^31", "gate_below_2^30", "add_below_2^30", "mask_below_2^33"):
         assert tags.get(tag), tag
         assert all(c["rc"] >= 0 and c["name"] for c in tags[tag]), tag
+
+
+def test_rows_wider_than_one_band_are_segmented_not_refused():
+    """Kernel gradients whose row overflows a single-row band (tag "wide", tests/golden/make_bf16_routing.py): admitted
+    with pad 0 -- on both sides of each form's limit and at the 260 model's widths --, refused with a pad.  And for
+    every admitted kernel gradient of the table the count is what the launch will be held to: tem_conv_bwd_weight_bf16
+    asks the same query with nslab = that count and refuses any other answer."""
+    from transfer_em_amd import _lib
+    lib = _lib.load()
+    cases = _cases()
+    wide = [c for c in cases if "wide" in c.get("tags", [])]
+    assert len(wide) >= 30
+    for c in wide:
+        assert (c["rc"] >= 1 and c["name"]) if not any(c["p"]) else c["rc"] == EUNSUPPORTED, (c["id"], c["rc"])
+    for fam in ("bww_bf16_k<", "bww2d_bf16_k<"):
+        assert sum(c["name"].startswith(fam) for c in wide) >= 12, fam
+    for c in cases:
+        if c["entry"] == "bww" and c["rc"] >= 1:
+            assert query(lib, dict(c, nslab=c["rc"])) == (c["rc"], c["name"]), c["id"]

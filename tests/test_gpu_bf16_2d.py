@@ -288,15 +288,17 @@ def test_generator_inference_bf16_2d(oracle_lib):
     assert 1e-4 < _l2(y, y32) < 3e-2
 
 
-def _step_bf16_2d_matches_oracle(tmp_path, n, batch):
+def _step_bf16_2d_matches_oracle(tmp_path, n, batch, amplitude=1.0):
     """EM2EM(n, is3d=False, precision='bf16').train_step at `batch` against the oracle's bf16 storage mode with the HIP
-    forward's LeakyReLU branches (util.hip_gates): the thresholds of test_train_step_bf16_matches_oracle."""
+    forward's LeakyReLU branches (util.hip_gates): the thresholds of test_train_step_bf16_matches_oracle.  amplitude
+    scales the two input images; an instance that scales them claims to stay clear of the pole of the cycle / identity
+    terms and is held to that, as in test_gpu_step._step_matches_oracle."""
     from oracle import graph
     from transfer_em_amd.cgan import EM2EM
-    from test_gpu_step import _load, _state
+    from test_gpu_step import _load, _pole_margin, _state
     from util import activation_stats, hip_gates
     shape = (batch, 1, n, n, 1)
-    rx, ry = _inputs(shape, 1234), _inputs(shape, 5678)
+    rx, ry = np.float32(amplitude) * _inputs(shape, 1234), np.float32(amplitude) * _inputs(shape, 5678)
     st = _state(graph, False, True)
     model = EM2EM(n, "bf16_2d", is3d=False, seed=42, checkpoint_root=str(tmp_path), precision="bf16")
     _load(model, st)
@@ -311,6 +313,10 @@ def _step_bf16_2d_matches_oracle(tmp_path, n, batch):
     assert rel_err(got, losses) < 5e-3, (got, losses)
     b = model.buffer
     crop = lambda t: t[:, :, b:-b, b:-b, :]
+    if amplitude != 1.0:
+        margin = _pole_margin(aux, rx, ry, b, lambda t, c: t[:, :, c:-c, c:-c, :])
+        print(f"smallest 1 - |a - b| / 2 of the cycle / identity terms (oracle, bf16 storage mode): {margin:.3g}")
+        assert margin >= 0.05, margin
     for key, plan in (("fake_y", "g1"), ("cyc_x", "f2"), ("fake_x", "f1"), ("cyc_y", "g2"), ("same_x", "f3"), ("same_y", "g3")):
         ref = crop(aux[key]) if key.startswith("cyc") else aux[key]
         e = _l2(cs.fwd[plan].y.float().cpu().numpy(), ref)
@@ -345,6 +351,14 @@ def test_train_step_bf16_2d_notebook_config_matches_oracle(tmp_path, oracle_lib)
     """The reference's training example at its own size, 132^2 batch 64, with every assertion and bar of the 74^2
     instance: the only check of the bf16 step's gradients, moments and activations at the configuration users run."""
     _step_bf16_2d_matches_oracle(tmp_path, 132, 64)
+
+
+def test_train_step_bf16_2d_260_matches_oracle(tmp_path, oracle_lib):
+    """The largest compatible size, 260^2 at batch 1, with every assertion and bar of the 74^2 instance: the discriminators'
+    32 -> 32 k4 s2 kernel gradient at 220^2 is the one 2-D launch whose row is wider than one band (cut into column
+    segments, csrc/bww2d_bf16.hip).  Half amplitude keeps the oracle's 1 - |a - b| / 2 at 0.37 (asserted >= 0.05); at
+    amplitude 1 it crosses the pole with these weights."""
+    _step_bf16_2d_matches_oracle(tmp_path, 260, 1, amplitude=0.5)
 
 
 def test_train_step_bf16_2d_notebook_config(tmp_path):

@@ -159,6 +159,107 @@ def test_kernel_gradient_bf16_long_z_segments_under_a_small_slab_budget(H, T, mo
     assert e < 2e-5
 
 
+# ------------------------------------------------------------------------------------------------ rows wider than one band
+# A band of one output row must fit the loaders' prefetch registers and the LDS; a pad-0 row that does not is cut into column
+# segments of a multiple of 16 output pixels, one launch of the same kernel per segment into its own slab range (run() in
+# csrc/bww_bf16.hip and csrc/bww2d_bf16.hip).  Per layer form: the first input width that is segmented (`limit`, from the
+# kernels' own arithmetic: K rows x ((OW - 1) S + K) columns x C_in / 8 chunks against 1024 (3-D) / 2048 (2-D) per plane),
+# and the width at which the 260 model launches the form (the widest, where it has several).
+#         nd ci0 ci1 co  k  s limit model
+WIDE = [(3, 8, 8, 16, 3, 1, 171, 228), (3, 16, 0, 32, 3, 1, 171, 108), (3, 32, 0, 16, 3, 1, 86, 116), (3, 16, 16, 32, 3, 1, 86, 118),
+        (3, 8, 0, 8, 4, 2, 258, 254), (3, 16, 0, 16, 4, 2, 130, 124), (3, 32, 0, 32, 4, 2, 66, 106),
+        (2, 32, 0, 16, 3, 1, 171, 116), (2, 16, 16, 32, 3, 1, 171, 118), (2, 16, 0, 16, 4, 2, 258, 124), (2, 32, 0, 32, 4, 2, 130, 220)]
+TOL_SLAB, TOL_SLAB_L2 = 2e-5, 3e-6        # the standing kernel-gradient bars (fullsize_cases.TOL_BF16_SLAB; L2 as for fp32 slabs)
+
+
+def _wide_operands(rng, nd, ci0, ci1, co, k, s, w):
+    """Operands at input width w with the smallest other extents: (x0, skip or None, g) as bf16-rounded numpy arrays.
+    A concat form's second half is the crop [1, -2) of `skip`, 3 wider on every cropped axis."""
+    N, D, Hh = (2, 6, 10) if nd == 3 else (3, 1, 12)
+    od = (D - k) // s + 1 if nd == 3 else 1
+    oh, ow = (Hh - k) // s + 1, (w - k) // s + 1
+    x0 = rb(rnd(rng, N, D, Hh, w, ci0))
+    skip = rb(rnd(rng, N, D + 3 if nd == 3 else 1, Hh + 3, w + 3, ci1)) if ci1 else None
+    return x0, skip, rb(rnd(rng, N, od, oh, ow, co))
+
+
+def _crop_skip(t, nd):
+    return t[:, 1:-2, 1:-2, 1:-2, :] if nd == 3 else t[:, :, 1:-2, 1:-2, :]
+
+
+def _wide_run(H, T, nd, ci0, ci1, co, k, s, x0, skip, g, w, tag):
+    """The kernel gradient of the operands cut to input width w -> (float64 slab sum, oracle, slab count, kernel name).
+    The slabs land in a NaN-filled allocation one row longer than the query's count: every counted row must come back
+    finite and the extra row untouched."""
+    from transfer_em_amd import _lib
+    lib = _lib.load()
+    ow = (w - k) // s + 1
+    x0, g = x0[:, :, :, :w, :], g[:, :, :, :ow, :]
+    crop1 = None if skip is None else _crop_skip(skip, nd)[:, :, :, :w, :]
+    x = x0 if skip is None else np.concatenate([x0, crop1], -1)
+    ks, ss = ((k, k, k), (s, s, s)) if nd == 3 else ((1, k, k), (1, s, s))
+    ref = T.conv_bwd_weight(x, g, ks, ss, 0)
+    t0, tg = devb(x0), devb(g)
+    keep = [t0, tg]
+    a = _lib.tem_bww_args()
+    a.in0, a.dout = H.view(t0), H.view(tg)
+    if skip is not None:
+        tskip = devb(skip)
+        t1 = _crop_skip(tskip, nd)[:, :, :, :w, :]             # a strided view: origin and row pitch are the parent's
+        assert not t1.is_contiguous()
+        a.in1 = H.view(t1)
+        keep.append(tskip)
+    a.kd, a.kh, a.kw = ks
+    a.sd, a.sh, a.sw = ss
+    a.pd = a.ph = a.pw = 0
+    a.nslab = H.MAX_SLABS
+    name = C.create_string_buffer(96)
+    nsl = lib.tem_conv_bwd_weight_bf16_nslab(C.byref(a), name, 96)
+    assert nsl >= 1, (tag, w, nsl)
+    kern = name.value.decode()
+    fam = "bww_bf16_k" if nd == 3 else "bww2d_bf16_k"
+    assert kern.startswith(f"{fam}<{ci0 + ci1}, {co}, {k}, {s},"), kern
+    slabs = torch.full((nsl + 1, ref.size), float("nan"), device="cuda")
+    a.slabs, a.slab_stride, a.nslab, a.accumulate = slabs.data_ptr(), 0, nsl, 0
+    rc = lib.tem_conv_bwd_weight_bf16(C.byref(a), H.current_stream())
+    assert rc == 0, (tag, w, rc)
+    torch.cuda.synchronize()
+    host = slabs.cpu().numpy()
+    assert np.isfinite(host[:nsl]).all(), (tag, w, "a slab the launch did not write", np.flatnonzero(~np.isfinite(host[:nsl]).all(1)))
+    assert np.isnan(host[nsl]).all(), (tag, w, "the launch wrote more slabs than the query counts")
+    got = host[:nsl].astype(np.float64).sum(0).reshape(ref.shape)
+    e, l2 = rel_err(got, ref), float(np.linalg.norm(got - ref) / np.linalg.norm(ref))
+    print(f"wide {tag} W={w}: {kern} nslab {nsl}, rel_err {e:.2e} l2 {l2:.2e}")
+    assert e < TOL_SLAB and l2 < TOL_SLAB_L2, (tag, w, e, l2)
+    return got, ref, nsl, kern
+
+
+@pytest.mark.parametrize("nd,ci0,ci1,co,k,s,limit,model", WIDE,
+                         ids=[f"{nd}d-{ci0}{'+' + str(ci1) if ci1 else ''}to{co}-k{k}s{s}" for nd, ci0, ci1, co, k, s, _, _ in WIDE])
+def test_kernel_gradient_bf16_rows_wider_than_one_band(H, T, nd, ci0, ci1, co, k, s, limit, model):
+    """Each form at limit - 1 (the widest single launch), at limit (the narrowest segmented one) and at the 260 model's
+    width, against the float64 oracle on the same bf16-rounded operands; and the single launch against the segmented
+    one on operands that make the two sums equal: those of limit - 1, and the same at width limit with the gradient's
+    last column -- the only one limit - 1 lacks -- set to zero."""
+    tag = f"{nd}d {ci0}+{ci1}->{co} k{k} s{s}"
+    rng = np.random.default_rng(1000 * nd + 10 * (ci0 + ci1) + co + k)
+    wmax = max(limit, model)
+    x0, skip, g = _wide_operands(rng, nd, ci0, ci1, co, k, s, wmax)
+    ow = lambda w: (w - k) // s + 1
+    assert ow(limit) == ow(limit - 1) + 1
+    single, ref1, _, _ = _wide_run(H, T, nd, ci0, ci1, co, k, s, x0, skip, g, limit - 1, tag)
+    _wide_run(H, T, nd, ci0, ci1, co, k, s, x0, skip, g, limit, tag)
+    if model not in (limit, limit - 1):
+        _wide_run(H, T, nd, ci0, ci1, co, k, s, x0, skip, g, model, tag)
+    gz = g.copy()
+    gz[:, :, :, ow(limit) - 1:, :] = 0
+    segmented, _, _, _ = _wide_run(H, T, nd, ci0, ci1, co, k, s, x0, skip, gz, limit, tag + " (last column 0)")
+    d = np.abs(single - segmented).max() / np.abs(ref1).max()
+    l2 = float(np.linalg.norm(single - segmented) / np.linalg.norm(ref1))
+    print(f"wide {tag}: single launch vs segmented on the common width: {d:.2e} l2 {l2:.2e}")
+    assert d < TOL_SLAB and l2 < TOL_SLAB_L2, (tag, d, l2)
+
+
 # ------------------------------------------------------------------------------------------------ large grids
 @pytest.mark.parametrize("N", list(range(57, 66)))
 @pytest.mark.parametrize("CI,CO,k,s,pad,h,w", [(8, 16, 3, 1, 0, 15, 13), (16, 16, 3, 1, 2, 21, 33), (32, 32, 4, 2, 0, 37, 27),

@@ -58,7 +58,7 @@ def _step_matches_oracle(tmp_path, n, batch, is3d, scaled, amplitude=1.0, gtol_n
     st = _state(graph, is3d, scaled)
     model = EM2EM(n, "parity", is3d=is3d, seed=42, checkpoint_root=str(tmp_path))
     _load(model, st)
-    assert (model.outdimsize, model.buffer) == {74: (40, 17), 132: (96, 18)}[n]     # generator.py:20, cgan.py:65
+    assert (model.outdimsize, model.buffer) == {74: (40, 17), 132: (96, 18), 260: (224, 18)}[n]     # generator.py:20, cgan.py:65
 
     for step in range(2):                                           # 2 steps: Adam t=1,2 and dropout step 0,1
         _load(model, st)          # every step starts from the oracle's exact state (no drift amplification)
@@ -155,6 +155,13 @@ def test_train_step_2d_notebook_config_matches_oracle_away_from_the_pole(tmp_pat
     cycle / identity terms at 1 - |a - b| / 2 >= 0.05 (asserted), so an output error delta moves no gradient entry by
     more than 10 delta of itself and the 74^2 bars apply to every network."""
     _step_matches_oracle(tmp_path, 132, 64, False, True, amplitude=0.5)
+
+
+def test_train_step_2d_260_matches_oracle(tmp_path, oracle_lib):
+    """The largest compatible size in 2-D -- 260^2, batch 1, fp32 -- with every assertion and bar of the 74^2 instances:
+    rows of 254 .. 256 pixels in every tile plan.  Half amplitude: at amplitude 1 the oracle's own 1 - |a - b| / 2 crosses
+    the pole with these weights (-0.26 at batch 2); at 0.5 it stays at 0.37, asserted >= 0.05 by the helper."""
+    _step_matches_oracle(tmp_path, 260, 1, False, True, amplitude=0.5)
 
 
 def test_train_step_3d_batch2_one_step(tmp_path, oracle_lib):

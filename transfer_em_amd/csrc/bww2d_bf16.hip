@@ -227,31 +227,43 @@ __global__ __launch_bounds__(256) void bww2d_bf16_k(Dev p) {
 }
 
 // ------------------------------------------------------------------------------------------ host
+// Rows per band for output rows of OW pixels: the largest band (<= 16 rows) whose rows fit the loaders' prefetch registers
+// and the LDS; 0 when not even a band of one row fits.
 template <int CI, int CO, int K, int S, int PFX, int PFG>
-int run(Dev p, int N, int max_slabs, hipStream_t st, bool dry, int *nslab_out, char *name, int name_len) {
-  constexpr int NTAP = K * K;
+int band_rows(int OW, int OH, size_t *lds_bytes) {
   constexpr int PITCH = CI >= 8 ? (CI <= 16 ? CI : CI + 4) : 1, GP = CO <= 16 ? CO : CO + 4, CPX = CI >= 8 ? CI / 8 : 1, CPG = CO / 8;
+  const int OWp = (OW + 15) & ~15, colsR = (OW - 1) * S + K, colsA = (OWp - 1) * S + K + 4;
+  int TY = 0;
+  for (int ty = 1; ty <= 16 && ty <= OH; ++ty) {
+    const int rows = (ty - 1) * S + K;
+    const size_t xel = (((size_t)rows * colsA * PITCH) + 7) & ~(size_t)7, gel = (size_t)ty * OWp * GP + 16;
+    const size_t bytes = ((xel + gel) * 2 + 15) & ~(size_t)15;
+    // two workgroups per CU (<= 72 KB each) where the rows allow; a single row may take up to 120 KB
+    if ((size_t)rows * colsR * CPX > (size_t)PFX * 256 || (size_t)ty * OW * CPG > (size_t)PFG * 256 ||
+        bytes > (ty == 1 ? 120 : 72) * 1024) break;
+    TY = ty; *lds_bytes = bytes;
+  }
+  return TY;
+}
+
+// One launch over output rows of p.OW pixels.  nseg: the number of column segments the row was cut into (run(), below);
+// the segments share the workgroup budget.
+template <int CI, int CO, int K, int S, int PFX, int PFG>
+int run_seg(Dev p, int N, int max_slabs, int nseg, hipStream_t st, bool dry, int *nslab_out, char *name, int name_len) {
+  constexpr int NTAP = K * K;
   p.OWp = (p.OW + 15) & ~15;
   p.colsR = (p.OW - 1) * S + K;
   p.colsA = (p.OWp - 1) * S + K + 4;                      // the last k-block reads up to OWp pixels (+ C_in == 1: 4-pixel reads)
-  int TY = 0;
   size_t lds_bytes = 0;
-  for (int ty = 1; ty <= 16 && ty <= p.OH; ++ty) {
-    const int rows = (ty - 1) * S + K;
-    const size_t xel = (((size_t)rows * p.colsA * PITCH) + 7) & ~(size_t)7, gel = (size_t)ty * p.OWp * GP + 16;
-    const size_t bytes = ((xel + gel) * 2 + 15) & ~(size_t)15;
-    // two workgroups per CU (<= 72 KB each) where the rows allow; a single row may take up to 120 KB
-    if ((size_t)rows * p.colsR * CPX > (size_t)PFX * 256 || (size_t)ty * p.OW * CPG > (size_t)PFG * 256 ||
-        bytes > (ty == 1 ? 120 : 72) * 1024) break;
-    TY = ty; lds_bytes = bytes;
-  }
+  const int TY = band_rows<CI, CO, K, S, PFX, PFG>(p.OW, p.OH, &lds_bytes);
   if (TY < 1) return TEM_EUNSUPPORTED;
   p.TY = TY; p.rows = (TY - 1) * S + K;
   p.nband = (p.OH + TY - 1) / TY;
   p.units = N * p.nband;
   // workgroup budget as in bww_bf16.hip: every workgroup costs a slab that tem_reduce_slabs_multi reads again
   const bool small_slab = NTAP * CI * CO * 4 <= 32 * 1024;
-  int want = small_slab ? 256 : 128;
+  int want = (small_slab ? 256 : 128) / nseg;
+  if (want < 1) want = 1;
   if (want > max_slabs) want = max_slabs;
   p.per = (p.units + want - 1) / want;
   const int nblocks = (p.units + p.per - 1) / p.per;
@@ -275,6 +287,36 @@ int run(Dev p, int N, int max_slabs, hipStream_t st, bool dry, int *nslab_out, c
   }
   hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(256), lds_bytes, st, p);
   TEM_CHECK_LAUNCH();
+  return TEM_OK;
+}
+
+// A row that fits one band is one launch.  A wider row (pad 0 only: the 260 model's layers) is cut into column segments of a
+// multiple of 16 output pixels, as in bww_bf16.hip: one launch per segment on the offset views, each into its own slab range.
+template <int CI, int CO, int K, int S, int PFX, int PFG>
+int run(Dev p, int N, int max_slabs, hipStream_t st, bool dry, int *nslab_out, char *name, int name_len) {
+  size_t unused = 0;
+  if (p.OW < 1 || band_rows<CI, CO, K, S, PFX, PFG>(p.OW, 1, &unused) >= 1)
+    return run_seg<CI, CO, K, S, PFX, PFG>(p, N, max_slabs, 1, st, dry, nslab_out, name, name_len);
+  if (p.P != 0) return TEM_EUNSUPPORTED;                   // the zero frame of a padded row belongs to its first and last segment only
+  int seg = p.OW & ~15;
+  while (seg >= 16 && band_rows<CI, CO, K, S, PFX, PFG>(seg, 1, &unused) < 1) seg -= 16;
+  if (seg < 16) return TEM_EUNSUPPORTED;
+  const int nseg = (p.OW + seg - 1) / seg;
+  seg = ((p.OW + nseg - 1) / nseg + 15) & ~15;             // equal segments, not one sliver at the end
+  int total = 0;
+  for (int x0 = 0; x0 < p.OW; x0 += seg) {
+    Dev q = p;
+    q.in0 += (int64_t)x0 * S * p.i0W; q.in1 += (int64_t)x0 * S * p.i1W; q.g += (int64_t)x0 * p.gW;
+    q.W = p.W - x0 * S;
+    q.OW = p.OW - x0 < seg ? p.OW - x0 : seg;
+    if (p.slabs) q.slabs = p.slabs + (int64_t)total * p.slab_stride;
+    if (max_slabs - total < 1) return TEM_EUNSUPPORTED;
+    int n = 0;
+    const int rc = run_seg<CI, CO, K, S, PFX, PFG>(q, N, max_slabs - total, nseg, st, dry, &n, name, name_len);
+    if (rc != TEM_OK) return rc;
+    total += n;
+  }
+  if (nslab_out) *nslab_out = total;
   return TEM_OK;
 }
 
