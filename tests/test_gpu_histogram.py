@@ -431,3 +431,144 @@ def test_defaults_are_the_plain_call(model3, vol3):
     assert "histogram" not in st
     identity = np.arange(256, dtype=np.uint8)
     _eq(predict_cube(vol3, START, SIZE, model3, MS_X, MS_Y, lut=identity), plain)
+
+
+# ------------------------------------------------------------------------- every option at once; launches; read errors
+# 3 x 2 x 1 tiles; chunk_tiles (1, 1, 2) cuts them into 4 chunks of 2, 2, 1 and 1 tiles, so with tile_batch = 1 the
+# double buffers are reused and two chunks run two batches each
+ALL_VOL, ALL_START, ALL_SIZE = (30, 55, 90), (-3, 2, 1), (100, 60, 36)
+ALL_ENSEMBLE = (((0, 1, 2), (0, 0, 0)), ((0, 2, 1), (0, 1, 0)))        # the identity, and a member that moves x
+ALL_VOL2, ALL_START2, ALL_SIZE2 = (3, 55, 90), (-3, 2, 0), (100, 60, 3)  # 2-D: 3 x 2 tiles in each of 3 sections
+ALL_ENSEMBLE2 = (((0, 1), (0, 0)), ((1, 0), (0, 1)))                     # (y, x): the identity and a transposing member
+
+
+def _counted(fn):
+    """fn()'s result and its launches: calls of _lib.check per entry-point name, generator runs under "run"."""
+    import collections
+    from transfer_em_amd import _lib, hip_ops
+    counts = collections.Counter()
+    check, run = _lib.check, hip_ops.run
+
+    def counting_check(rc, what):
+        counts[what] += 1
+        return check(rc, what)
+
+    def counting_run(launches, stream=None):
+        counts["run"] += 1
+        return run(launches, stream)
+
+    with pytest.MonkeyPatch.context() as mp:
+        mp.setattr(_lib, "check", counting_check)
+        mp.setattr(hip_ops, "run", counting_run)
+        return fn(), counts
+
+
+@pytest.fixture(scope="module")
+def all3(model3):
+    """The 3-D case under every option, resident and streamed, each once and with its launches counted."""
+    from transfer_em_amd.utils import predict_cube, predict_volume
+    rng = np.random.default_rng(36)
+    vol = rng.integers(0, 256, ALL_VOL, dtype=np.uint8)
+    lut = np.stack([rng.permutation(256).astype(np.uint8) for _ in range(ALL_VOL[0])])
+    kw = dict(boundary="reflect", ensemble=ALL_ENSEMBLE, mips=2, lut=lut, histogram=True, tile_batch=1)
+    st_c, st_v = {}, {}
+    cube, n_cube = _counted(lambda: predict_cube(vol, ALL_START, ALL_SIZE, model3, MS_X, MS_Y, stats=st_c, **kw))
+    streamed, n_vol = _counted(lambda: predict_volume(vol, ALL_START, ALL_SIZE, model3, MS_X, MS_Y,
+                                                      chunk_tiles=(1, 1, 2), stats=st_v, **kw))
+    return dict(vol=vol, kw=kw, cube=cube, streamed=streamed, n_cube=n_cube, n_vol=n_vol, st_cube=st_c, st_vol=st_v)
+
+
+def test_every_option_at_once_streamed_equals_resident(all3, model3):
+    from transfer_em_amd.utils import chunk_plan, mip_shapes
+    chunks = chunk_plan(ALL_START, ALL_SIZE, model3.outdimsize, model3.buffer, ALL_VOL, (1, 1, 2), boundary="reflect")
+    assert [len(c.tiles) for c in chunks] == [2, 2, 1, 1]
+    cube, streamed = all3["cube"], all3["streamed"]
+    assert len(cube) == len(streamed) == 3 and [c.shape for c in cube] == mip_shapes(ALL_SIZE, 2)
+    _guard(cube[0])
+    for a, b in zip(streamed, cube):
+        _eq(a, b)
+    assert all3["st_vol"]["chunks"] == 4 and all3["st_vol"]["tile_batch"] == 1
+    want = _bincount(cube[0])
+    assert np.array_equal(all3["st_vol"]["histogram"], want) and np.array_equal(all3["st_cube"]["histogram"], want)
+
+
+def test_every_option_at_once_2d(model2):
+    from transfer_em_amd.utils import chunk_plan, predict_cube, predict_volume
+    chunks = chunk_plan(ALL_START2, ALL_SIZE2, model2.outdimsize, model2.buffer, ALL_VOL2, (2, 1, 2), is3d=False,
+                        boundary="reflect")
+    assert [len(c.tiles) for c in chunks] == [4, 4, 2, 2, 2, 2, 1, 1]
+    rng = np.random.default_rng(37)
+    vol = rng.integers(0, 256, ALL_VOL2, dtype=np.uint8)
+    lut = np.stack([rng.permutation(256).astype(np.uint8) for _ in range(ALL_VOL2[0])])
+    kw = dict(boundary="reflect", ensemble=ALL_ENSEMBLE2, mips=2, lut=lut, histogram=True, tile_batch=3)
+    st_c, st_v = {}, {}
+    cube = predict_cube(vol, ALL_START2, ALL_SIZE2, model2, MS_X, MS_Y, stats=st_c, **kw)
+    streamed = predict_volume(vol, ALL_START2, ALL_SIZE2, model2, MS_X, MS_Y, chunk_tiles=(2, 1, 2), stats=st_v, **kw)
+    assert len(cube) == len(streamed) == 3 and st_v["chunks"] == 8 and st_v["tile_batch"] == 3
+    _guard(cube[0])
+    for a, b in zip(streamed, cube):
+        _eq(a, b)
+    want = _bincount(cube[0])
+    assert np.array_equal(st_v["histogram"], want) and np.array_equal(st_c["histogram"], want)
+
+
+GATHER, GATHER_BC, GATHER_SYM = "tem_u8_tiles_to_f32_std", "tem_u8_tiles_to_f32_std_bc", "tem_u8_tiles_to_f32_std_sym"
+ACCUM, SCATTER = "tem_f32_tiles_sym_accum", "tem_f32_tiles_unstd_to_u8"
+
+
+def test_launch_counts_follow_the_plan(all3, model3):
+    """6 tiles in batches of 1 under 2 members: 12 gathers, runs and accumulates and 6 scatters, resident or streamed;
+    the table, the 2 pooled levels and the histogram once for the resident result and once per chunk (4) streamed."""
+    from transfer_em_amd.utils import predict_cube, predict_volume
+    per_call = {"predict_cube": 1, "predict_volume": 4}
+    for name, n in (("predict_cube", all3["n_cube"]), ("predict_volume", all3["n_vol"])):
+        got = {k: n[k] for k in (GATHER_SYM, ACCUM, "run", SCATTER, "tem_u8_lut", "tem_u8_pool2", "tem_u8_hist", GATHER,
+                                 GATHER_BC)}
+        want = {GATHER_SYM: 12, ACCUM: 12, "run": 12, SCATTER: 6, "tem_u8_lut": per_call[name],
+                "tem_u8_pool2": 2 * per_call[name], "tem_u8_hist": per_call[name], GATHER: 0, GATHER_BC: 0}
+        assert got == want, name
+    kw = dict(all3["kw"], ensemble=None)
+    calls = {"predict_cube": lambda: predict_cube(all3["vol"], ALL_START, ALL_SIZE, model3, MS_X, MS_Y, stats={}, **kw),
+             "predict_volume": lambda: predict_volume(all3["vol"], ALL_START, ALL_SIZE, model3, MS_X, MS_Y,
+                                                      chunk_tiles=(1, 1, 2), stats={}, **kw)}
+    levels = {}
+    for name, fn in calls.items():
+        levels[name], n = _counted(fn)
+        got = {k: n[k] for k in (GATHER_BC, GATHER_SYM, ACCUM, GATHER, "run", SCATTER)}
+        assert got == {GATHER_BC: 6, GATHER_SYM: 0, ACCUM: 0, GATHER: 0, "run": 6, SCATTER: 6}, name
+    for a, b in zip(levels["predict_volume"], levels["predict_cube"]):
+        _eq(a, b)
+
+
+class FailingReads:
+    """Array-like over a numpy array whose third read raises OSError: a host error, nothing faults on the device."""
+
+    def __init__(self, a):
+        self.a, self.shape, self.dtype, self.reads = a, a.shape, a.dtype, 0
+
+    def __getitem__(self, key):
+        self.reads += 1
+        if self.reads == 3:
+            raise OSError("the third read fails")
+        return self.a[key]
+
+
+def test_a_failing_read_surfaces_and_leaves_nothing_behind(all3, model3):
+    import threading
+    from transfer_em_amd.utils import hist_box, hist_chunks, predict_cube, predict_volume, volume_histogram
+    vol = all3["vol"]
+    threads = threading.active_count()
+    bad = FailingReads(vol)
+    with pytest.raises(OSError, match="the third read fails"):
+        predict_volume(bad, ALL_START, ALL_SIZE, model3, MS_X, MS_Y, chunk_tiles=(1, 1, 2), tile_batch=1)
+    assert bad.reads >= 3 and threading.active_count() == threads               # the reader thread has ended
+    got = predict_volume(vol, ALL_START, ALL_SIZE, model3, MS_X, MS_Y, chunk_tiles=(1, 1, 2), tile_batch=1)
+    _guard(got)
+    _eq(got, predict_cube(vol, ALL_START, ALL_SIZE, model3, MS_X, MS_Y, tile_batch=1))
+    budget = 8 * 55 * 90                                                        # 8 of 30 sections per slab
+    assert len(hist_chunks(hist_box(ALL_VOL), budget)) == 4
+    bad = FailingReads(vol)
+    with pytest.raises(OSError, match="the third read fails"):
+        volume_histogram(bad, chunk_bytes=budget)
+    assert bad.reads >= 3 and threading.active_count() == threads
+    assert np.array_equal(volume_histogram(vol, chunk_bytes=budget), _bincount(vol))

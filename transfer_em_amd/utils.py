@@ -29,21 +29,31 @@ import torch
 from . import hip_ops as H
 
 
+def _plan_outdimsize(outdimsize):
+    """tile_plan's outdimsize: the "multiple of 6" quirk applied ("make sure outdimsize is a multiple of 8" -- the code
+    uses 6)."""
+    return outdimsize - outdimsize % 6 if outdimsize // 6 != 0 else outdimsize
+
+
+def _tile_plan(start, size, outdimsize, buffer, is3d):
+    """tile_plan (is3d) or tile_plan_2d: the same in-plane tiling; along z a step of outdimsize under the halo, or a
+    step of one section and no halo."""
+    od = _plan_outdimsize(outdimsize)
+    tpad = (outdimsize - od) // 2
+    buffer += tpad
+    zstep, zhalo = (od, buffer) if is3d else (1, 0)
+    rois, index = [], []
+    for xiter in range(start[0], start[0] + size[0], od):
+        for yiter in range(start[1], start[1] + size[1], od):
+            for ziter in range(start[2], start[2] + size[2], zstep):
+                rois.append((xiter - buffer, yiter - buffer, ziter - zhalo))
+                index.append((xiter - start[0], yiter - start[1], ziter - start[2]))
+    return od, buffer, tpad, rois, index
+
+
 def tile_plan(start, size, outdimsize, buffer):
     """Tile origins of utils.py:68-84.  Returns (outdimsize, buffer, tpad, rois, index)."""
-    tpad = 0
-    if (outdimsize // 6) != 0:            # "make sure outdimsize is a multiple of 8" -- the code uses 6
-        diff = outdimsize % 6
-        outdimsize -= diff
-        tpad = diff // 2
-        buffer += tpad
-    rois, index = [], []
-    for xiter in range(start[0], start[0] + size[0], outdimsize):
-        for yiter in range(start[1], start[1] + size[1], outdimsize):
-            for ziter in range(start[2], start[2] + size[2], outdimsize):
-                rois.append((xiter - buffer, yiter - buffer, ziter - buffer))
-                index.append((xiter - start[0], yiter - start[1], ziter - start[2]))
-    return outdimsize, buffer, tpad, rois, index
+    return _tile_plan(start, size, outdimsize, buffer, True)
 
 
 TILE_BATCH = 27      # tiles per generator launch sequence (27 x 132^3: ~10 GB of activations; 288 GB HBM)
@@ -54,19 +64,7 @@ def tile_plan_2d(start, size, outdimsize, buffer):
     tile_plan's in-plane rules (same "multiple of 6" quirk, tpad, halo, rounding up to whole tiles in y and x); no
     halo and no rounding along z.  Returns (outdimsize, buffer, tpad, rois, index) with (x, y, z) rois / index whose z
     is the section itself (absolute in rois, relative to start[2] in index)."""
-    tpad = 0
-    if (outdimsize // 6) != 0:
-        diff = outdimsize % 6
-        outdimsize -= diff
-        tpad = diff // 2
-        buffer += tpad
-    rois, index = [], []
-    for xiter in range(start[0], start[0] + size[0], outdimsize):
-        for yiter in range(start[1], start[1] + size[1], outdimsize):
-            for ziter in range(start[2], start[2] + size[2]):
-                rois.append((xiter - buffer, yiter - buffer, ziter))
-                index.append((xiter - start[0], yiter - start[1], ziter - start[2]))
-    return outdimsize, buffer, tpad, rois, index
+    return _tile_plan(start, size, outdimsize, buffer, False)
 
 
 def plan_bytes_per_tile(edge, is3d=True, wf=8):
@@ -237,24 +235,6 @@ def _check_boundary(boundary, vol_shape):
         raise ValueError(f"boundary={boundary!r} needs a non-empty volume, got shape {tuple(vol_shape)}")
 
 
-def _tile_kernels(lib, is3d, boundary="zeros"):
-    """(gather, scatter) and their names: the cube tiles or the 2-D (one section) tiles.  `scatter` is the C entry
-    point; `gather(blk, block, lo, vol_shape, origins, ntile, edge, out, mean, std, stream)` cuts tiles out of the
-    staging block `blk` of shape `block` that holds the volume's box at `lo` (the resident volume: lo = 0, block =
-    vol_shape): "zeros" calls the zero-mode entry point on the block, the other modes their `_bc` sibling."""
-    from . import _lib
-    gname, sname = (("tem_u8_tiles_to_f32_std", "tem_f32_tiles_unstd_to_u8") if is3d else
-                    ("tem_u8_tiles2d_to_f32_std", "tem_f32_tiles2d_unstd_to_u8"))
-    if boundary == "zeros":
-        fn = getattr(lib, gname)
-        gather = lambda blk, block, lo, vol_shape, *rest: fn(blk, *block, *rest)
-    else:
-        gname += "_bc"
-        fn, mode = getattr(lib, gname), {"reflect": _lib.TEM_BOUNDARY_REFLECT, "edge": _lib.TEM_BOUNDARY_EDGE}[boundary]
-        gather = lambda blk, block, lo, vol_shape, *rest: fn(blk, *block, *lo, *vol_shape, mode, *rest)
-    return (gather, gname), (getattr(lib, sname), sname)
-
-
 def symmetries(is3d=True, kind="flips"):
     """The symmetries of the cube (is3d) or the square that the training augmentation draws from (datasets.augment,
     tem_augment_f32), as a list of (perm, flips) over the spatial axes (z, y, x) -- (y, x) for 2-D:
@@ -310,47 +290,81 @@ def _check_ensemble(ensemble, is3d):
     return [(p, tuple(int(f) for f in fl)) for p, fl in out]
 
 
-def _sym_kernels(lib, is3d, boundary="zeros"):
-    """The ensemble's (gather, accumulate) and their names.  gather(blk, block, lo, vol_shape, origins, ntile, edge,
-    sym, out, mean, std, stream) is _tile_kernels' gather under the symmetry sym = (perm, flips); "zeros" hands the
-    block over as the volume, which is what the zero-mode entry point sees.  accum(y, ntile, yedge, sym, acc, first,
-    divisor, stream) folds y back into acc."""
-    from . import _lib
-    gname, aname = (("tem_u8_tiles_to_f32_std_sym", "tem_f32_tiles_sym_accum") if is3d else
-                    ("tem_u8_tiles2d_to_f32_std_sym", "tem_f32_tiles2d_sym_accum"))
-    gfn, afn = getattr(lib, gname), getattr(lib, aname)
-    mode = {"zeros": 0, "reflect": _lib.TEM_BOUNDARY_REFLECT, "edge": _lib.TEM_BOUNDARY_EDGE}[boundary]
-    if mode == 0:
-        gather = lambda blk, block, lo, vol_shape, org, n, edge, sym, *rest: \
-            gfn(blk, *block, 0, 0, 0, *block, 0, org, n, edge, *sym[0], *sym[1], *rest)
-    else:
-        gather = lambda blk, block, lo, vol_shape, org, n, edge, sym, *rest: \
-            gfn(blk, *block, *lo, *vol_shape, mode, org, n, edge, *sym[0], *sym[1], *rest)
-    accum = lambda y, n, yedge, sym, *rest: afn(y, n, yedge, *sym[0], *sym[1], *rest)
-    return (gather, gname), (accum, aname)
+class _TileRunner:
+    """The tile loop of predict_cube and predict_volume, made once per call: gather -> generator -> scatter over the
+    tiles of a source block, in batches, all enqueued on `stream`.  It owns the choice of the gather entry point and
+    its argument order, the ensemble's fp32 accumulator, the generator plan per batch size and the scatter.
 
+    The gather without an ensemble is the zero-mode entry point under "zeros" and its `_bc` sibling under the mirrored
+    modes; with one (`syms`: _check_ensemble's members) it is the `_sym` entry point, which under "zeros" gets mode 0
+    with the block handed over as the volume -- what the zero-mode entry point sees.  A source block of shape `block`
+    holds the volume's box at `lo` (the resident volume: lo = 0, block = vol_shape)."""
 
-def _run_ensemble(syms, gather, gname, accum, aname, run, acc_box, stream, last_gather=None):
-    """One tile batch under every member of `syms` in order: gather(sym) cuts T_s(tiles) into the generator's input,
-    `run()` returns the generator's output (overwritten by the next run), and T_s^-1 of it is folded into the fp32
-    accumulator -- written by the first member, added to by the others, divided by len(syms) by the last -- all on
-    `stream`, so each accumulate precedes the run that overwrites y.  `acc_box` (a list) keeps the one accumulator of
-    the call: the first batch, the largest, allocates it and smaller batches use its head.  `last_gather()` is called
-    after the last member's gather.  Returns the accumulator of this batch: the mean."""
-    from . import _lib
-    k, acc = len(syms), None
-    for i, sym in enumerate(syms):
-        _lib.check(gather(sym), gname)
-        if i == k - 1 and last_gather is not None:
-            last_gather()
-        y = run()
-        if acc is None:
-            if not acc_box:
-                acc_box.append(torch.empty_like(y))
-            acc = acc_box[0][:y.shape[0]]
-        _lib.check(accum(y.data_ptr(), y.shape[0], y.shape[2], sym, acc.data_ptr(), int(i == 0),
-                         k if i == k - 1 else 1, stream), aname)
-    return acc
+    def __init__(self, lib, model, is3d, edge, tpad, outdimsize, boundary, syms, meanstd_x, meanstd_y, vol_shape,
+                 stream):
+        from . import _lib
+        gname, self.sname, self.aname = (
+            ("tem_u8_tiles_to_f32_std", "tem_f32_tiles_unstd_to_u8", "tem_f32_tiles_sym_accum") if is3d else
+            ("tem_u8_tiles2d_to_f32_std", "tem_f32_tiles2d_unstd_to_u8", "tem_f32_tiles2d_sym_accum"))
+        self.gname = gname + ("_sym" if syms is not None else "" if boundary == "zeros" else "_bc")
+        self.gather, self.scatter, self.accum = (getattr(lib, n) for n in (self.gname, self.sname, self.aname))
+        self.mode = {"zeros": 0, "reflect": _lib.TEM_BOUNDARY_REFLECT, "edge": _lib.TEM_BOUNDARY_EDGE}[boundary]
+        self.model, self.gen = model, getattr(model, "generator_g", None)
+        self.shape = ((edge, edge, edge) if is3d else (1, edge, edge)) + (1,)      # (D, H, W, C) of one generator input
+        self.edge, self.tpad, self.outdimsize, self.syms, self.vol_shape, self.stream = \
+            edge, tpad, outdimsize, syms, vol_shape, stream
+        self.ms_x = (float(meanstd_x[0]), float(meanstd_x[1]))
+        self.ms_y = (float(meanstd_y[0]), float(meanstd_y[1]))
+        self.plan = self.acc = None             # acc: allocated by the first batch, the largest; smaller use its head
+
+    def _input(self, m):
+        """(x, run) of a batch of m tiles: the generator's input tensor, and run() -> its output (overwritten by the
+        next run).  A plan of another batch size is asked for with none held, so that an evicted plan's buffers are
+        released first.  A generator without plans goes through model.predict: only predict_cube gets there,
+        predict_volume refuses such a generator."""
+        if not hasattr(self.gen, "plan"):
+            x = torch.empty((m,) + self.shape, dtype=torch.float32, device=self.model.device)
+            return x, lambda: self.model.predict(x).contiguous()
+        if self.plan is None or self.plan.x.shape[0] != m:
+            self.plan = None
+            self.plan = self.gen.plan((m,) + self.shape)                        # static launch plan, buffers reused
+        return self.plan.x, lambda: self.plan.run(self.stream)
+
+    def run(self, src, block, lo, origins, offsets, n, nb, dst, dims, last_gather=None):
+        """Run the n tiles of the source block at `src` (shape `block`, at `lo` in the volume) into the destination
+        block at `dst` (shape `dims` = (OZ, OY, OX)) in batches of nb.  `origins` / `offsets` point to the tiles' int32
+        (z, y, x) haloed origins in the source block and interior offsets in the destination block.  last_gather() is
+        called after the last gather of the last batch: nothing enqueued later reads the source block.
+
+        Under an ensemble a batch runs once per member s in order: the gather cuts T_s(tiles), and T_s^-1 of the
+        generator's output is folded into the accumulator -- written by the first member, added to by the others,
+        divided by the member count by the last -- whose mean is scattered once."""
+        from . import _lib
+        members = self.syms or [None]
+        for b0 in range(0, n, nb):
+            m = min(nb, n - b0)
+            x, run = self._input(m)
+            if self.mode:                       # the kernel folds lo + origin + p into the volume
+                where = (*block, *lo, *self.vol_shape, self.mode)
+            else:
+                where = block if self.syms is None else (*block, 0, 0, 0, *block, 0)
+            for i, sym in enumerate(members):
+                last = i == len(members) - 1
+                _lib.check(self.gather(src, *where, origins + 12 * b0, m, self.edge, *(sym[0] + sym[1] if sym else ()),
+                                       x.data_ptr(), *self.ms_x, self.stream), self.gname)
+                if last and b0 + m == n and last_gather is not None:
+                    last_gather()
+                y = run()
+                if sym is not None:
+                    if self.acc is None:
+                        self.acc = torch.empty_like(y)
+                    acc = self.acc[:m]
+                    _lib.check(self.accum(y.data_ptr(), m, y.shape[2], *sym[0], *sym[1], acc.data_ptr(), int(i == 0),
+                                          len(members) if last else 1, self.stream), self.aname)
+                    y = acc
+            assert y.shape[2] - 2 * self.tpad == self.outdimsize, (y.shape, self.tpad, self.outdimsize)
+            _lib.check(self.scatter(y.data_ptr(), m, y.shape[2], self.tpad, offsets + 12 * b0, dst, *dims, *self.ms_y,
+                                    self.stream), self.sname)
 
 
 class _OneSection:
@@ -393,11 +407,6 @@ def max_mips(outdimsize):
     while od >= 2 and od % 2 == 0:
         od, n = od // 2, n + 1
     return n
-
-
-def _plan_outdimsize(outdimsize):
-    """tile_plan's outdimsize: the "multiple of 6" quirk applied."""
-    return outdimsize - outdimsize % 6 if outdimsize // 6 != 0 else outdimsize
 
 
 def _check_mips(mips, outdimsize):
@@ -528,6 +537,65 @@ def hist_chunks(box, chunk_bytes=None, rank=0, world_size=1):
     return slabs[rank::world_size]
 
 
+class _InputStream:
+    """The double-buffered input side of an out-of-core pass over K blocks of `nbytes[k]` bytes: block k is read on
+    the executor's thread into pinned buffer k % 2 by read_into(k, flat uint8 ndarray), copied to device buffer k % 2
+    on a copy stream, and waited for by the compute stream (the current stream of `dev`).  The read seconds add up in
+    st["read_s"].  Used as a context manager around the pass, it owns the executor's end: on any exception it cancels
+    what is queued, waits for the thread, synchronises the device -- nothing is in flight on the buffers about to be
+    freed -- and re-raises; otherwise it waits for the queued work.
+
+    The consumer's loop over k: `get(k)`, its kernels on the compute stream, `release(k, event)` once nothing
+    enqueued later reads the buffer, `prefetch(k + 2)`.  The executor is the caller's, so that it can queue work of
+    its own on the same thread in an order of its choice.  Buffer k % 2 is reused in this order: the read of block k
+    waits for the H2D of block k - 2, and the H2D of block k for the release event of block k - 2."""
+
+    def __init__(self, nbytes, read_into, dev, pool, st):
+        self.nbytes, self.read_into, self.dev, self.pool, self.st = nbytes, read_into, dev, pool, st
+        self.compute, self.h2d = torch.cuda.current_stream(dev), torch.cuda.Stream(dev)
+        size, n = max(nbytes, default=0), min(2, len(nbytes))
+        self.pin = [torch.empty(size, dtype=torch.uint8, pin_memory=True) for _ in range(n)]
+        self.buf = [torch.empty(size, dtype=torch.uint8, device=dev) for _ in range(n)]
+        self.reads, self.h2d_done, self.released = {}, {}, {}
+
+    def __enter__(self):
+        for k in range(len(self.pin)):
+            self.prefetch(k)
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        self.pool.shutdown(wait=True, cancel_futures=exc_type is not None)
+        if exc_type is not None:
+            torch.cuda.synchronize(self.dev)
+
+    def _read(self, k):                     # host thread: block k -> pin[k % 2]
+        import time
+        if k >= 2:
+            self.h2d_done.pop(k - 2).synchronize()          # the buffer's previous H2D has finished
+        t0 = time.perf_counter()
+        self.read_into(k, self.pin[k % 2][:self.nbytes[k]].numpy())
+        self.st["read_s"] += time.perf_counter() - t0
+
+    def prefetch(self, k):
+        if k < len(self.nbytes):
+            self.reads[k] = self.pool.submit(self._read, k)
+
+    def get(self, k):
+        """The device buffer that holds block k in its first nbytes[k] bytes, once the compute stream gets there."""
+        s, n = k % 2, self.nbytes[k]
+        self.reads.pop(k).result()
+        if k >= 2:
+            self.h2d.wait_event(self.released.pop(k - 2))   # buf[s]: the consumer is done with block k - 2
+        with torch.cuda.stream(self.h2d):
+            self.buf[s][:n].copy_(self.pin[s][:n], non_blocking=True)
+        self.h2d_done[k] = self.h2d.record_event()
+        self.compute.wait_event(self.h2d_done[k])
+        return self.buf[s]
+
+    def release(self, k, event):
+        self.released[k] = event
+
+
 def volume_histogram(volume, start=None, size=None, per_section=False, chunk_bytes=None, rank=0, world_size=1,
                      device=None, stats=None):
     """Intensity histogram of the ROI [start, start + size) ((x, y, z) order; default: the whole volume) of a uint8
@@ -542,7 +610,6 @@ def volume_histogram(volume, start=None, size=None, per_section=False, chunk_byt
     The pass is bound by the read (`stats` receives the read seconds `read_s` and the slab count `chunks`).  Ranks
     (rank / world_size) take slabs round-robin: each returns the counts of its own slabs, the ranks' results add up to
     the whole, and no collective is used."""
-    import time
     from concurrent.futures import ThreadPoolExecutor
     from . import _lib
     box = hist_box(volume.shape, start, size)
@@ -555,49 +622,24 @@ def volume_histogram(volume, start=None, size=None, per_section=False, chunk_byt
     nz = box[0][1] - box[0][0]
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     st = {"read_s": 0.0, "chunks": len(slabs)}
-    K = len(slabs)
     dims = [tuple(hi - lo for lo, hi in b) for b in slabs]
-    nbytes = [int(np.prod(d)) for d in dims]
+
+    def read_into(k, flat):
+        (z0, z1), (y0, y1), (x0, x1) = slabs[k]
+        flat.reshape(dims[k])[...] = volume[z0:z1, y0:y1, x0:x1]
+
     with torch.cuda.device(dev):
-        compute, h2d = torch.cuda.current_stream(dev), torch.cuda.Stream(dev)
+        compute = torch.cuda.current_stream(dev)
         acc = torch.zeros((nz if per_section else 1, 256), dtype=torch.int64, device=dev)
-        if K:
-            pin = [torch.empty(max(nbytes), dtype=torch.uint8, pin_memory=True) for _ in range(min(2, K))]
-            buf = [torch.empty(max(nbytes), dtype=torch.uint8, device=dev) for _ in range(min(2, K))]
-        h2d_done, counted = {}, {}
-
-        def read(k):                        # host thread: slab k -> pin[k % 2]
-            if k >= 2:
-                h2d_done.pop(k - 2).synchronize()           # the buffer's previous H2D has finished
-            t0 = time.perf_counter()
-            (z0, z1), (y0, y1), (x0, x1) = slabs[k]
-            pin[k % 2][:nbytes[k]].numpy().reshape(dims[k])[...] = volume[z0:z1, y0:y1, x0:x1]
-            st["read_s"] += time.perf_counter() - t0
-
-        pool = ThreadPoolExecutor(max_workers=1)
-        reads = {k: pool.submit(read, k) for k in range(min(2, K))}
-        try:
-            for k in range(K):
-                s = k % 2
-                reads.pop(k).result()
-                if k >= 2:
-                    h2d.wait_event(counted.pop(k - 2))       # buf[s]: slab k-2 has been counted
-                with torch.cuda.stream(h2d):
-                    buf[s][:nbytes[k]].copy_(pin[s][:nbytes[k]], non_blocking=True)
-                h2d_done[k] = h2d.record_event()
-                compute.wait_event(h2d_done[k])
-                d = dims[k]
+        nbytes = [int(np.prod(d)) for d in dims]
+        with _InputStream(nbytes, read_into, dev, ThreadPoolExecutor(max_workers=1), st) as inp:
+            for k, d in enumerate(dims):
+                src = inp.get(k)
                 row = (slabs[k][0][0] - box[0][0]) if per_section else 0
-                _lib.check(lib.tem_u8_hist(buf[s].data_ptr(), *d, 0, d[0], 0, d[1], 0, d[2], acc.data_ptr() + 2048 * row,
+                _lib.check(lib.tem_u8_hist(src.data_ptr(), *d, 0, d[0], 0, d[1], 0, d[2], acc.data_ptr() + 2048 * row,
                                            int(bool(per_section)), compute.cuda_stream), "tem_u8_hist")
-                counted[k] = compute.record_event()
-                if k + 2 < K:
-                    reads[k + 2] = pool.submit(read, k + 2)
-        except BaseException:
-            pool.shutdown(wait=True, cancel_futures=True)
-            torch.cuda.synchronize(dev)                      # nothing in flight on the buffers about to be freed
-            raise
-        pool.shutdown(wait=True)
+                inp.release(k, compute.record_event())               # counted
+                inp.prefetch(k + 2)
         out = acc.cpu().numpy()                              # the one read-back
     if stats is not None:
         stats.update(st)
@@ -770,11 +812,12 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
     lib = H.require_gpu()
     if _single_image(model, start, size):
         res = predict_cube(np.asarray(volume)[None], tuple(start) + (0,), tuple(size) + (1,), model, meanstd_x,
-                           meanstd_y, fetch_input, outdimsize, buffer, rank, world_size, tile_batch, boundary, ensemble,
-                           mips, lut, histogram, stats)
+                           meanstd_y, fetch_input=fetch_input, outdimsize=outdimsize, buffer=buffer, rank=rank,
+                           world_size=world_size, tile_batch=tile_batch, boundary=boundary, ensemble=ensemble,
+                           mips=mips, lut=lut, histogram=histogram, stats=stats)
         one = lambda r: [v[0] for v in r] if isinstance(r, list) else r[0]
         return tuple(one(r) for r in res) if fetch_input else one(res)
-    outdimsize, buffer, tpad, rois, index = (tile_plan if is3d else tile_plan_2d)(start, size, outdimsize, buffer)
+    outdimsize, buffer, tpad, rois, index = _tile_plan(start, size, outdimsize, buffer, is3d)
     edge = outdimsize + buffer * 2
     z, y, x = size[2], size[1], size[0]
     rnd = lambda v: v + ((outdimsize - (v % outdimsize)) if (v % outdimsize) != 0 else 0)
@@ -792,35 +835,12 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
     OZ, OY, OX = out_buffer.shape
     mine = list(range(rank, len(rois), world_size))
     nb = _effective_batch(tile_batch, edge, is3d, len(mine) or 1)
-    tile = (edge, edge, edge) if is3d else (1, edge, edge)               # (D, H, W) of one generator input
-    (gather, gname), (scatter, sname) = _tile_kernels(lib, is3d, boundary)
-    if syms is not None:
-        (sgather, sgname), (accum, aname) = _sym_kernels(lib, is3d, boundary)
-        acc = []                                # the fp32 accumulator, allocated by the first (largest) batch
-    for c0 in range(0, len(mine), nb):
-        chunk = mine[c0:c0 + nb]
-        n = len(chunk)
-        org = torch.tensor([[rois[i][2], rois[i][1], rois[i][0]] for i in chunk], dtype=torch.int32).to(dev)   # (z,y,x)
-        idx = torch.tensor([[index[i][2], index[i][1], index[i][0]] for i in chunk], dtype=torch.int32).to(dev)
-        if hasattr(gen, "plan"):
-            plan = gen.plan((n,) + tile + (1,))                            # static launch plan, buffers reused
-            tiles = plan.x
-        else:
-            plan, tiles = None, torch.empty((n,) + tile + (1,), dtype=torch.float32, device=dev)
-        run = plan.run if plan is not None else (lambda: model.predict(tiles).contiguous())
-        if syms is None:
-            _lib.check(gather(vol.data_ptr(), (Z, Y, X), (0, 0, 0), (Z, Y, X), org.data_ptr(), n, edge, tiles.data_ptr(),
-                              float(meanstd_x[0]), float(meanstd_x[1]), stream), gname)
-            data_y = run()
-        else:                                   # the mean over the members
-            data_y = _run_ensemble(
-                syms, lambda sym: sgather(vol.data_ptr(), (Z, Y, X), (0, 0, 0), (Z, Y, X), org.data_ptr(), n, edge, sym,
-                                          tiles.data_ptr(), float(meanstd_x[0]), float(meanstd_x[1]), stream),
-                sgname, accum, aname, run, acc, stream)
-        yedge = data_y.shape[2]
-        assert yedge - 2 * tpad == outdimsize, (yedge, tpad, outdimsize)
-        _lib.check(scatter(data_y.data_ptr(), n, yedge, tpad, idx.data_ptr(), out_buffer.data_ptr(), OZ, OY, OX,
-                           float(meanstd_y[0]), float(meanstd_y[1]), stream), sname)
+    org = torch.tensor([rois[i][::-1] for i in mine], dtype=torch.int32).to(dev)       # this rank's (z, y, x), once
+    idx = torch.tensor([index[i][::-1] for i in mine], dtype=torch.int32).to(dev)
+    runner = _TileRunner(lib, model, is3d, edge, tpad, outdimsize, boundary, syms, meanstd_x, meanstd_y, (Z, Y, X),
+                         stream)
+    runner.run(vol.data_ptr(), (Z, Y, X), (0, 0, 0), org.data_ptr(), idx.data_ptr(), len(mine), nb,
+               out_buffer.data_ptr(), (OZ, OY, OX))
     if world_size > 1 and torch.distributed.is_initialized():
         torch.distributed.all_reduce(out_buffer, op=torch.distributed.ReduceOp.MAX)   # disjoint tiles, zeros elsewhere
     out = out_buffer[0:size[2], 0:size[1], 0:size[0]].cpu().numpy()
@@ -920,7 +940,7 @@ def _fold_hull(lo, hi, n, boundary):
 def _chunk_plan(start, size, outdimsize, buffer, vol_shape, chunk_tiles, rank=0, world_size=1, is3d=True,
                 boundary="zeros"):
     _check_boundary(boundary, vol_shape)
-    outdimsize, buffer, tpad, rois, index = (tile_plan if is3d else tile_plan_2d)(start, size, outdimsize, buffer)
+    outdimsize, buffer, tpad, rois, index = _tile_plan(start, size, outdimsize, buffer, is3d)
     od, edge = outdimsize, outdimsize + 2 * buffer
     # (z, y, x) extent of one tile's output (`step`) and haloed input (`ext`): a 2-D tile is one section thick
     step, ext = ((od, od, od), (edge, edge, edge)) if is3d else ((1, od, od), (1, edge, edge))
@@ -1062,8 +1082,9 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
             out = ([np.zeros(s, np.uint8) for s in mip_shapes(size, L, False)] if L else
                    np.zeros((size[1], size[0]), np.uint8))
         predict_volume(_OneSection(volume), tuple(start) + (0,), tuple(size) + (1,), model, meanstd_x, meanstd_y,
-                       [_OneSection(o) for o in out] if L else _OneSection(out), chunk_tiles, tile_batch, outdimsize,
-                       buffer, rank, world_size, stats, boundary, ensemble, mips, lut, histogram)
+                       out=[_OneSection(o) for o in out] if L else _OneSection(out), chunk_tiles=chunk_tiles,
+                       tile_batch=tile_batch, outdimsize=outdimsize, buffer=buffer, rank=rank, world_size=world_size,
+                       stats=stats, boundary=boundary, ensemble=ensemble, mips=mips, lut=lut, histogram=histogram)
         return out
     vol_shape = tuple(int(v) for v in volume.shape)
     if len(vol_shape) != 3:
@@ -1072,11 +1093,6 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
                                         model.buffer if buffer is None else buffer, vol_shape, chunk_tiles, rank,
                                         world_size, is3d, boundary)
     edge = od + 2 * buf
-    tile = (edge, edge, edge) if is3d else (1, edge, edge)               # (D, H, W) of one generator input
-    (gather, gname), (scatter, sname) = _tile_kernels(lib, is3d, boundary)
-    if syms is not None:
-        (sgather, sgname), (accum, aname) = _sym_kernels(lib, is3d, boundary)
-        acc = []                                # the fp32 accumulator, allocated by the first (largest) batch
     if L:
         if out is None:
             out = [np.zeros(s, np.uint8) for s in mip_shapes(size, L, is3d)]
@@ -1091,7 +1107,6 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
         stats.update(st)
     if not chunks:
         return out
-    K = len(chunks)
     # a chunk wholly outside the volume has an empty footprint: it gathers from one zero byte (all voxels read 0);
     # with a mirrored boundary no footprint is empty
     gdims = [c.block if min(c.block) > 0 else (1, 1, 1) for c in chunks]
@@ -1105,30 +1120,25 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
     out_bytes = [int(o[-1]) for o in lvl_off]
     nb = st["tile_batch"] = _effective_batch(tile_batch, edge, is3d, max(len(c.tiles) for c in chunks))
     dev = model.device
-    compute = torch.cuda.current_stream(dev)
-    h2d, d2h = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
-    pin_in = [torch.empty(max(in_bytes), dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+    compute, d2h = torch.cuda.current_stream(dev), torch.cuda.Stream(dev)
     pin_out = [torch.empty(max(out_bytes), dtype=torch.uint8, pin_memory=True) for _ in range(2)]
-    dev_in = [torch.empty(max(in_bytes), dtype=torch.uint8, device=dev) for _ in range(2)]
     dev_out = [torch.empty(max(out_bytes), dtype=torch.uint8, device=dev) for _ in range(2)]
     first = np.cumsum([0] + [len(c.tiles) for c in chunks])
     org = torch.tensor([o for c in chunks for o in c.origins], dtype=torch.int32).to(dev)     # every chunk's, once
     idx = torch.tensor([o for c in chunks for o in c.offsets], dtype=torch.int32).to(dev)
-    h2d_done, gathered, d2h_done, d2h_evt = {}, {}, {}, [None, None]
+    d2h_done, d2h_evt = {}, [None, None]
     lut_dev = None if lut is None else torch.from_numpy(lut).to(dev)
     counts = torch.zeros(256, dtype=torch.int64, device=dev) if histogram else None
+    runner = _TileRunner(lib, model, is3d, edge, tpad, od, boundary, syms, meanstd_x, meanstd_y, vol_shape,
+                         compute.cuda_stream)
 
-    def read(k):                        # host thread: footprint of chunk k -> pin_in[k % 2]
-        if k >= 2:
-            h2d_done.pop(k - 2).synchronize()           # the buffer's previous H2D has finished
-        t0 = time.perf_counter()
-        c, dst = chunks[k], pin_in[k % 2][:in_bytes[k]].numpy().reshape(gdims[k])
+    def read_into(k, flat):             # host thread: footprint of chunk k
+        c, dst = chunks[k], flat.reshape(gdims[k])
         if min(c.block) > 0:
             (z0, z1), (y0, y1), (x0, x1) = c.read
             dst[...] = volume[z0:z1, y0:y1, x0:x1]
         else:
             dst[...] = 0
-        st["read_s"] += time.perf_counter() - t0
 
     def write(k):                       # host thread: pin_out[k % 2] -> the chunk's box of `out`
         d2h_done.pop(k).synchronize()
@@ -1144,52 +1154,22 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
             out[l][z0:z1, y0:y1, x0:x1] = src[:nz, :ny, :nx]
         st["write_s"] += time.perf_counter() - t0
 
-    pool = ThreadPoolExecutor(max_workers=1)
-    reads, writes = {k: pool.submit(read, k) for k in range(min(2, K))}, {}
-    try:
-        plan = None
+    pool, writes = ThreadPoolExecutor(max_workers=1), {}     # one thread for reads and writes: write(k), read(k + 2)
+    with _InputStream(in_bytes, read_into, dev, pool, st) as inp:
         for k, c in enumerate(chunks):
             s = k % 2
-            reads.pop(k).result()
-            if k >= 2:
-                h2d.wait_event(gathered.pop(k - 2))          # dev_in[s]: chunk k-2 has been gathered from it
-            with torch.cuda.stream(h2d):
-                dev_in[s][:in_bytes[k]].copy_(pin_in[s][:in_bytes[k]], non_blocking=True)
-            h2d_done[k] = h2d.record_event()
-            compute.wait_event(h2d_done[k])
+            src = inp.get(k).data_ptr()
             if k >= 2:
                 compute.wait_event(d2h_evt[s])               # dev_out[s]: chunk k-2's D2H has read it
             lo = tuple(r[0] for r in c.read)
             if lut_dev is not None and min(c.block) > 0:     # the footprint, in place; never the stand-in zero byte
-                _lib.check(lib.tem_u8_lut(dev_in[s].data_ptr(), *gdims[k], lut_dev.data_ptr(), int(lut.ndim == 2), lo[0],
+                _lib.check(lib.tem_u8_lut(src, *gdims[k], lut_dev.data_ptr(), int(lut.ndim == 2), lo[0],
                                           compute.cuda_stream), "tem_u8_lut")
             OZ, OY, OX = c.dims
-            n = len(c.tiles)
-            for b0 in range(0, n, nb):
-                m = min(nb, n - b0)
-                if plan is None or plan.x.shape[0] != m:
-                    plan = None                              # let the plan cache release an evicted plan's buffers
-                    plan = gen.plan((m,) + tile + (1,))
-                t = int(first[k]) + b0
-                if syms is None:
-                    _lib.check(gather(dev_in[s].data_ptr(), gdims[k], lo, vol_shape, org.data_ptr() + 12 * t, m, edge,
-                                      plan.x.data_ptr(), float(meanstd_x[0]), float(meanstd_x[1]), compute.cuda_stream),
-                               gname)
-                    if b0 + m == n:
-                        gathered[k] = compute.record_event()
-                    data_y = plan.run(compute.cuda_stream)
-                else:
-                    last_gather = (lambda: gathered.__setitem__(k, compute.record_event())) if b0 + m == n else None
-                    data_y = _run_ensemble(
-                        syms, lambda sym: sgather(dev_in[s].data_ptr(), gdims[k], lo, vol_shape, org.data_ptr() + 12 * t,
-                                                  m, edge, sym, plan.x.data_ptr(), float(meanstd_x[0]),
-                                                  float(meanstd_x[1]), compute.cuda_stream),
-                        sgname, accum, aname, lambda: plan.run(compute.cuda_stream), acc, compute.cuda_stream,
-                        last_gather)
-                assert data_y.shape[2] - 2 * tpad == od, (data_y.shape, tpad, od)
-                _lib.check(scatter(data_y.data_ptr(), m, data_y.shape[2], tpad, idx.data_ptr() + 12 * t,
-                                   dev_out[s].data_ptr(), OZ, OY, OX, float(meanstd_y[0]), float(meanstd_y[1]),
-                                   compute.cuda_stream), sname)
+            t = 12 * int(first[k])
+            # the staging buffer is free for the next upload once the chunk's last gather is enqueued
+            runner.run(src, gdims[k], lo, org.data_ptr() + t, idx.data_ptr() + t, len(c.tiles), nb,
+                       dev_out[s].data_ptr(), c.dims, lambda: inp.release(k, compute.record_event()))
             if L:                                            # the chunk's pyramid, level by level behind its scatters
                 base = dev_out[s].data_ptr()
                 _pool_levels(lib, base, c.dims, tuple(hi - lo for lo, hi in c.out_box), L, is3d,
@@ -1206,15 +1186,9 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
                 pin_out[s][:out_bytes[k]].copy_(dev_out[s][:out_bytes[k]], non_blocking=True)
             d2h_done[k] = d2h_evt[s] = d2h.record_event()
             writes[k] = pool.submit(write, k)
-            if k + 2 < K:
-                reads[k + 2] = pool.submit(read, k + 2)
+            inp.prefetch(k + 2)
         for k in sorted(writes):
             writes.pop(k).result()
-    except BaseException:
-        pool.shutdown(wait=True, cancel_futures=True)
-        torch.cuda.synchronize(dev)                          # nothing in flight on the buffers about to be freed
-        raise
-    pool.shutdown(wait=True)
     if histogram:
         st["histogram"] = counts.cpu().numpy()               # the one read-back
     if stats is not None:
