@@ -379,6 +379,35 @@ int tem_u8_hist(const uint8_t *src, int32_t D, int32_t H, int32_t W, int32_t z0,
 int tem_u8_lut(uint8_t *buf, int32_t D, int32_t H, int32_t W, const uint8_t *lut, int32_t per_section, int32_t zsec0,
                tem_stream_t stream);
 
+/* Contrast-limited adaptive histogram equalisation (CLAHE) of uint8 sections, the two device passes; the tables
+ * between them are host work (utils.clahe_tables).  The tile is (th, tw) pixels over (y, x), and the grid of gy x gx
+ * tiles is anchored at (0, 0) of the caller's volume.  Both calls cover a dense block [D][H][W] of it whose voxel
+ * (d, y, x) sits at in-plane volume coordinates (y_org + y, x_org + x); the last row and column of tiles may be partial.
+ *
+ * tem_u8_hist_tiles: counts[((d * gy + (y_org + y) / th) * gx + (x_org + x) / tw) * 256 + v] += 1 for every voxel of
+ * value v.  counts (4-byte aligned) points at the rows of the block's first section.  The kernel ADDS (32-bit global
+ * atomic adds): the caller clears counts once, and blocks that cut a tile between them accumulate into it.  No
+ * counter may pass 2^32 - 1; a tile holds at most 2048 x 2048 voxels.
+ *
+ * tem_u8_clahe: buf is remapped in place by tables[zsec0 + d][i][j][256] (uint8, at least zsec0 + D sections of
+ * gy x gx tables).  With v the voxel's value at volume coordinates (y, x):
+ *   f = 2 y + 1 - th,  i0 = floor(f / (2 th)),  wy = f - i0 2 th,  i1 = clip(i0 + 1, 0, gy - 1),  i0 = clip(i0, 0, gy - 1)
+ * (x likewise with tw and gx: j0, j1, wx), a, b, c, d = T[i0][j0][v], T[i0][j1][v], T[i1][j0][v], T[i1][j1][v],
+ * Dn = 4 th tw:
+ *   out = ((2 th - wy) ((2 tw - wx) a + wx b) + wy ((2 tw - wx) c + wx d) + Dn / 2) / Dn        (integers)
+ * -- bilinear interpolation between the tile centres, rounded half up, clamped to the nearest centre in the half
+ * tile along each face; exact for every tile size allowed.  Every byte of buf is read once and written once, and
+ * nothing outside buf is touched.  Any alignment of the pointers, W and the origins.
+ *
+ * TEM_EINVAL, without a launch: a null pointer, a dimension, gy or gx below 1, th or tw outside [1, 2048], a negative
+ * origin, a block that reaches past the grid (y_org + H > gy th, x_org + W > gx tw), a negative zsec0, counts off
+ * 4-byte alignment.  TEM_EUNSUPPORTED: a remap of more than 2^31 - 1 workgroups (one per section, interpolation cell
+ * and run of about 2048 16-byte lines). */
+int tem_u8_hist_tiles(const uint8_t *src, int32_t D, int32_t H, int32_t W, int32_t y_org, int32_t x_org, int32_t th,
+                      int32_t tw, int32_t gy, int32_t gx, uint32_t *counts, tem_stream_t stream);
+int tem_u8_clahe(uint8_t *buf, int32_t D, int32_t H, int32_t W, int32_t zsec0, int32_t y_org, int32_t x_org,
+                 const uint8_t *tables, int32_t gy, int32_t gx, int32_t th, int32_t tw, tem_stream_t stream);
+
 /* Random augmentation of one cached sample (datasets.py:123-155) with host-drawn parameters:
  *   dst = reverse(transpose(src, perm = (p0,p1,p2)), dims with f_k != 0) * scale + shift
  * src is a dense single-channel (D,H,W) volume (2-D: D == 1, p0 must be 0); dst has extents

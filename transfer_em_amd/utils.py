@@ -18,6 +18,13 @@ by section (`tile_plan_2d`: tile_plan's in-plane tiling in every section, no hal
 `volume_histogram`, `meanstd_from_histogram` and `match_lut` measure a volume's intensities out of core and turn them into
 the statistics and lookup tables that `predict_cube` / `predict_volume` take (`lut=`: remapped on the device ahead of the
 gather; `histogram=True`: the histogram of the prediction, counted on the device).
+
+`clahe_histograms`, `clahe_tables` (together: `clahe_fit`) and `clahe_volume` are contrast-limited adaptive histogram
+equalisation, section by section, the usual preparation of electron-microscopy volumes: tile histograms counted out of
+core on the device, the clipped and cumulated tables in exact integers on the host, and the remap -- bilinear
+interpolation between the tile centres, in integers -- on the device, written out (`clahe_volume`, for training volumes)
+or applied to the uploaded bytes ahead of the gather (`clahe=` of `predict_cube` / `predict_volume`), so that a model
+trained on equalised data sees equalised data without an equalised copy of the volume.
 """
 import json
 import os
@@ -740,9 +747,287 @@ def _lut_host(vol, lut):
     return lut[vol] if lut.ndim == 1 else lut[np.arange(vol.shape[0])[:, None, None], vol]
 
 
+CLAHE_MAX_TILE = 2048            # th, tw of a CLAHE tile: the remap's numerator then stays below 2^32
+CLAHE_ACC_BYTES = 1 << 30        # clahe_histograms: one device accumulator for the volume up to this size, else one per slab
+
+
+class ClaheTables(NamedTuple):
+    """What the `clahe=` keyword takes: the np.uint8[Z, gy, gx, 256] tables of clahe_tables and the tile they belong to."""
+    tables: np.ndarray
+    tile: tuple          # (th, tw), or an int for a square tile
+
+
+def _clahe_tile(tile):
+    """(th, tw) of `tile`, an int or a pair of ints in [1, CLAHE_MAX_TILE]."""
+    import operator
+    try:
+        th, tw = (tile, tile) if not hasattr(tile, "__len__") else tile
+        if isinstance(th, (bool, np.bool_)) or isinstance(tw, (bool, np.bool_)):
+            raise TypeError
+        th, tw = operator.index(th), operator.index(tw)
+    except (TypeError, ValueError):
+        raise ValueError(f"tile must be an int or (th, tw), got {tile!r}")
+    if not (1 <= th <= CLAHE_MAX_TILE and 1 <= tw <= CLAHE_MAX_TILE):
+        raise ValueError(f"tile {(th, tw)} is outside [1, {CLAHE_MAX_TILE}]")
+    return th, tw
+
+
+def clahe_grid(vol_shape, tile):
+    """(gy, gx) = (ceil(Y / th), ceil(X / tw)): the tiles of (th, tw) pixels over (y, x) -- `tile`, an int or (th, tw) in
+    [1, 2048] -- that cover a section of a volume of shape [Z, Y, X] or an image [Y, X].  The grid is anchored at the
+    volume's (0, 0); its last row and column may be partial.  Pure host function."""
+    th, tw = _clahe_tile(tile)
+    shape = tuple(int(v) for v in vol_shape)
+    if len(shape) not in (2, 3) or min(shape) < 1:
+        raise ValueError(f"volume must be a non-empty [z, y, x] or one image [y, x], got shape {shape}")
+    return -(-shape[-2] // th), -(-shape[-1] // tw)
+
+
+def _check_u8(volume):
+    if getattr(volume, "dtype", np.dtype(np.uint8)) != np.uint8:
+        raise ValueError(f"volume must be uint8, got {volume.dtype}")
+
+
+def clahe_histograms(volume, tile=128, chunk_bytes=None, rank=0, world_size=1, device=None, stats=None):
+    """The tile histograms CLAHE starts from: np.uint32[Z, gy, gx, 256] with h[z, i, j, v] the count of value v in
+    volume[z, i*th:(i+1)*th, j*tw:(j+1)*tw], over the WHOLE uint8 `volume` [z, y, x] (one image [y, x]: Z = 1), since
+    the tiles outside an ROI still feed a prediction's halo and its folded boundaries.
+
+    Out of core exactly as volume_histogram: slabs of at most `chunk_bytes` (hist_chunks; a slab of rows may cut a
+    tile), one host thread -> pinned -> H2D -> tem_u8_hist_tiles adding into a device accumulator.  The accumulator
+    holds the whole volume's Z*gy*gx*1024 bytes and is read back once where that is at most CLAHE_ACC_BYTES; else it
+    holds one slab's sections and is read back, and added on the host, per slab.  Ranks take slabs round-robin and
+    their results add up to the whole.  `stats` receives `read_s` and `chunks`."""
+    from concurrent.futures import ThreadPoolExecutor
+    from . import _lib
+    th, tw = _clahe_tile(tile)
+    gy, gx = clahe_grid(volume.shape, (th, tw))
+    box = hist_box(volume.shape)
+    _check_u8(volume)
+    slabs = hist_chunks(box, chunk_bytes, rank, world_size)
+    lib = H.require_gpu()
+    if len(volume.shape) == 2:
+        volume = _OneSection(volume)
+    Z, sec = box[0][1], gy * gx * 256
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    st = {"read_s": 0.0, "chunks": len(slabs)}
+    dims = [tuple(hi - lo for lo, hi in b) for b in slabs]
+    whole = Z * sec * 4 <= CLAHE_ACC_BYTES
+    out = None if whole else np.zeros((Z, gy, gx, 256), np.uint32)
+
+    def read_into(k, flat):
+        (z0, z1), (y0, y1), (x0, x1) = slabs[k]
+        flat.reshape(dims[k])[...] = volume[z0:z1, y0:y1, x0:x1]
+
+    with torch.cuda.device(dev):
+        compute = torch.cuda.current_stream(dev)
+        acc = torch.zeros((Z if whole else max((d[0] for d in dims), default=1), sec), dtype=torch.int32, device=dev)
+        nbytes = [int(np.prod(d)) for d in dims]
+        with _InputStream(nbytes, read_into, dev, ThreadPoolExecutor(max_workers=1), st) as inp:
+            for k, d in enumerate(dims):
+                (z0, z1), (y0, _), (x0, _) = slabs[k]
+                src = inp.get(k)
+                if not whole:
+                    acc[:d[0]].zero_()
+                _lib.check(lib.tem_u8_hist_tiles(src.data_ptr(), *d, y0, x0, th, tw, gy, gx,
+                                                 acc.data_ptr() + 4 * sec * (z0 if whole else 0), compute.cuda_stream),
+                           "tem_u8_hist_tiles")
+                inp.release(k, compute.record_event())               # counted
+                inp.prefetch(k + 2)
+                if not whole:                                        # this slab's sections, added on the host
+                    out[z0:z1] += acc[:d[0]].cpu().numpy().view(np.uint32).reshape(d[0], gy, gx, 256)
+        if whole:
+            out = acc.cpu().numpy().view(np.uint32).reshape(Z, gy, gx, 256)        # the one read-back
+    if stats is not None:
+        stats.update(st)
+    return out
+
+
+def _clahe_params(clip_limit, z_radius):
+    import operator
+    try:
+        if isinstance(z_radius, (bool, np.bool_)):
+            raise TypeError
+        r = operator.index(z_radius)
+    except TypeError:
+        raise ValueError(f"z_radius must be a non-negative integer, got {z_radius!r}")
+    if r < 0:
+        raise ValueError(f"z_radius must be a non-negative integer, got {z_radius!r}")
+    if clip_limit is not None:
+        clip_limit = float(clip_limit)
+        if not clip_limit > 0:
+            raise ValueError(f"clip_limit must be positive (None: no clipping), got {clip_limit!r}")
+    return clip_limit, r
+
+
+# _CLAHE_SPREAD[r, k] = 1 where bin k is one of the r bins {floor(j * 256 / r) : j < r} that take one count of a
+# remainder of r
+_CLAHE_SPREAD = np.zeros((256, 256), np.int64)
+for _r in range(1, 256):
+    _CLAHE_SPREAD[_r, (np.arange(_r) * 256) // _r] = 1
+del _r
+
+
+def clahe_tables(h, clip_limit=3.0, z_radius=0):
+    """The equalisation tables np.uint8[Z, gy, gx, 256] of the tile histograms `h` (integer counts [Z, gy, gx, 256],
+    clahe_histograms' result), in exact integer arithmetic on the host:
+
+      * z_radius = r > 0 replaces h[z] by the sum of h[max(z - r, 0) : min(z + r + 1, Z)] (damps section-to-section
+        flicker); n = h.sum(-1) is the tile's voxel count;
+      * clip_limit = c clips every bin at clip = max(1, floor(c * n / 256)) (float64) and spreads the excess evenly:
+        h = min(h, clip) + excess // 256, and with rem = excess % 256 the bins {floor(j * 256 / rem) : j < rem} get one
+        more -- the total stays n.  c = 1 flattens the histogram (the identity, nearly), large c leaves it alone;
+        clip_limit=None does not clip: plain adaptive equalisation;
+      * T[v] = (cdf[v] * 255 + n // 2) // n with cdf = cumsum(h): non-decreasing, T[255] = 255.
+
+    A tile without voxels (n = 0: only in the partial result of one rank) gets the identity.  ValueError for a negative
+    or non-integer z_radius, clip_limit <= 0, and an `h` that is no integer array of shape [Z, gy, gx, 256]."""
+    clip_limit, r = _clahe_params(clip_limit, z_radius)
+    h = np.asarray(h)
+    if h.ndim != 4 or h.shape[-1] != 256 or h.dtype.kind not in "iu":
+        raise ValueError(f"clahe_tables: h must be integer counts of shape [Z, gy, gx, 256], got {h.dtype} {h.shape}")
+    h = h.astype(np.int64)
+    if h.size and int(h.min()) < 0:
+        raise ValueError("clahe_tables: h has negative counts")
+    Z = h.shape[0]
+    if r > 0 and Z:
+        c = np.concatenate([np.zeros((1,) + h.shape[1:], np.int64), np.cumsum(h, axis=0)])
+        z = np.arange(Z)
+        h = c[np.minimum(z + r + 1, Z)] - c[np.maximum(z - r, 0)]
+    n = h.sum(-1)
+    if clip_limit is not None:
+        clip = np.maximum(1, np.floor(clip_limit * n.astype(np.float64) / 256.0).astype(np.int64))[..., None]
+        excess = np.maximum(h - clip, 0).sum(-1)
+        h = np.minimum(h, clip) + (excess // 256)[..., None] + _CLAHE_SPREAD[excess % 256]
+    cdf = np.cumsum(h, axis=-1)
+    n1 = np.maximum(n, 1)[..., None]
+    T = (cdf * 255 + n1 // 2) // n1
+    T = np.where(n[..., None] > 0, T, np.arange(256))
+    return T.astype(np.uint8)
+
+
+def _check_clahe(clahe, vol_shape):
+    """None, or (tables, th, tw, gy, gx) of a ClaheTables (any (tables, tile) pair) for a volume of shape `vol_shape`
+    ([z, y, x]; one image [y, x] has one section): tables as a C-contiguous np.uint8[Z, gy, gx, 256].  ValueError for
+    anything else."""
+    if clahe is None:
+        return None
+    try:
+        tables, tile = clahe
+    except (TypeError, ValueError):
+        raise ValueError(f"clahe must be None or a ClaheTables (tables, tile), got {type(clahe).__name__}")
+    th, tw = _clahe_tile(tile)
+    if not isinstance(tables, np.ndarray) or tables.dtype != np.uint8:
+        raise ValueError(f"clahe tables must be a numpy uint8 array, got {getattr(tables, 'dtype', type(tables).__name__)}")
+    gy, gx = clahe_grid(vol_shape, (th, tw))
+    Z = int(vol_shape[0]) if len(vol_shape) == 3 else 1
+    if tables.shape != (Z, gy, gx, 256):
+        raise ValueError(f"clahe tables must have shape {(Z, gy, gx, 256)} -- (Z, gy, gx, 256) of a volume of shape "
+                         f"{tuple(vol_shape)} under tile {(th, tw)} -- got {tables.shape}")
+    return np.ascontiguousarray(tables), th, tw, gy, gx
+
+
+def clahe_fit(volume, tile=128, clip_limit=3.0, z_radius=0, **kw):
+    """clahe_histograms(volume, tile, **kw) -> clahe_tables(..., clip_limit, z_radius) as a ClaheTables: what
+    clahe_volume, predict_cube and predict_volume take as `clahe`.  The tables hold Z*gy*gx*256 bytes."""
+    _clahe_params(clip_limit, z_radius)
+    tile = _clahe_tile(tile)
+    return ClaheTables(clahe_tables(clahe_histograms(volume, tile, **kw), clip_limit, z_radius), tile)
+
+
+def clahe_volume(volume, clahe, out=None, start=None, size=None, chunk_bytes=None, histogram=False, stats=None, rank=0,
+                 world_size=1, device=None):
+    """Contrast-limited adaptive histogram equalisation of the ROI [start, start + size) ((x, y, z) order; default: the
+    whole volume) of a uint8 array-like `volume` [z, y, x] (or one image [y, x] with 2-element start / size) by the
+    tables `clahe` (a ClaheTables of the WHOLE volume: clahe_fit), written into `out`: a writable uint8 array-like of
+    the ROI's shape (ndarray, memmap, h5py, zarr; allocated when None), which is returned.  This is how training
+    volumes are prepared, so that the datasets crop equalised data, and what predict_*(clahe=...) sees without the copy.
+
+    Every voxel of value v at (z, y, x) becomes the bilinear interpolation, in integers and rounded half up, of the
+    tables of the four tiles whose centres surround it, at v (tem_u8_clahe; include/tem_hip.h has the formula).  The
+    tile grid belongs to the volume, so the result of an ROI is the ROI of the whole result, however it is cut.
+
+    Out of core: the ROI is cut into slabs of at most `chunk_bytes` (hist_chunks); host thread -> pinned -> H2D ->
+    tem_u8_clahe in place -> D2H -> host write, on double buffers, the I/O of neighbouring slabs overlapped.  The
+    tables are uploaded once: Z*gy*gx*256 bytes.  histogram=True adds one tem_u8_hist launch over each remapped slab
+    and puts the 256 bins of the equalised ROI (np.int64) into stats["histogram"], so that a match_lut towards another
+    domain can follow without another pass.  Ranks take slabs round-robin and write disjoint boxes of a shared `out`
+    (each reports the histogram of its own slabs).  `stats` also receives `read_s`, `write_s` and `chunks`.
+    ValueError, before any GPU work: an ROI outside the volume, a non-uint8 volume, tables of another dtype or shape,
+    an `out` of another shape."""
+    import time
+    from concurrent.futures import ThreadPoolExecutor
+    from . import _lib
+    box = hist_box(volume.shape, start, size)
+    _check_u8(volume)
+    tables, th, tw, gy, gx = _check_clahe(clahe, tuple(volume.shape))
+    histogram = _check_histogram(histogram, stats)
+    one = len(volume.shape) == 2
+    shape = tuple(hi - lo for lo, hi in box)
+    if out is None:
+        out = np.zeros(shape[1:] if one else shape, np.uint8)
+    elif tuple(out.shape) != (shape[1:] if one else shape):
+        raise ValueError(f"out has shape {tuple(out.shape)}, expected {shape[1:] if one else shape}")
+    slabs = hist_chunks(box, chunk_bytes, rank, world_size)
+    lib = H.require_gpu()
+    src_vol, dst_vol = (_OneSection(volume), _OneSection(out)) if one else (volume, out)
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    st = {"read_s": 0.0, "write_s": 0.0, "chunks": len(slabs)}
+    dims = [tuple(hi - lo for lo, hi in b) for b in slabs]
+    nbytes = [int(np.prod(d)) for d in dims]
+
+    def read_into(k, flat):
+        (z0, z1), (y0, y1), (x0, x1) = slabs[k]
+        flat.reshape(dims[k])[...] = src_vol[z0:z1, y0:y1, x0:x1]
+
+    with torch.cuda.device(dev):
+        compute, d2h = torch.cuda.current_stream(dev), torch.cuda.Stream(dev)
+        tab = torch.from_numpy(tables).to(dev)
+        counts = torch.zeros(256, dtype=torch.int64, device=dev) if histogram else None
+        pin_out = [torch.empty(max(nbytes, default=0), dtype=torch.uint8, pin_memory=True) for _ in range(min(2, len(slabs)))]
+        d2h_done = {}
+
+        def write(k):                   # host thread: pin_out[k % 2] -> the slab's box of `out`
+            d2h_done.pop(k).synchronize()
+            t0 = time.perf_counter()
+            (z0, z1), (y0, y1), (x0, x1) = slabs[k]
+            (oz, _), (oy, _), (ox, _) = box
+            dst_vol[z0 - oz:z1 - oz, y0 - oy:y1 - oy, x0 - ox:x1 - ox] = pin_out[k % 2][:nbytes[k]].numpy().reshape(dims[k])
+            st["write_s"] += time.perf_counter() - t0
+
+        pool, writes = ThreadPoolExecutor(max_workers=1), {}     # one thread for reads and writes: write(k), read(k + 2)
+        with _InputStream(nbytes, read_into, dev, pool, st) as inp:
+            for k, d in enumerate(dims):
+                s, n = k % 2, nbytes[k]
+                (z0, _), (y0, _), (x0, _) = slabs[k]
+                buf = inp.get(k)
+                _lib.check(lib.tem_u8_clahe(buf.data_ptr(), *d, z0, y0, x0, tab.data_ptr(), gy, gx, th, tw,
+                                            compute.cuda_stream), "tem_u8_clahe")
+                if histogram:
+                    _lib.check(lib.tem_u8_hist(buf.data_ptr(), *d, 0, d[0], 0, d[1], 0, d[2], counts.data_ptr(), 0,
+                                               compute.cuda_stream), "tem_u8_hist")
+                remapped = compute.record_event()
+                if k >= 2:
+                    writes.pop(k - 2).result()                   # pin_out[s]: slab k-2 is in `out`
+                d2h.wait_event(remapped)
+                with torch.cuda.stream(d2h):
+                    pin_out[s][:n].copy_(buf[:n], non_blocking=True)
+                d2h_done[k] = d2h.record_event()
+                inp.release(k, d2h_done[k])                      # the device buffer: free once it has been copied out
+                writes[k] = pool.submit(write, k)
+                inp.prefetch(k + 2)
+            for k in sorted(writes):
+                writes.pop(k).result()
+        if histogram:
+            st["histogram"] = counts.cpu().numpy()
+    if stats is not None:
+        stats.update(st)
+    return out
+
+
 def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=False, outdimsize=None, buffer=None,
                  rank=0, world_size=1, tile_batch=None, boundary="zeros", ensemble=None, mips=None, lut=None,
-                 histogram=False, stats=None):
+                 histogram=False, stats=None, clahe=None):
     """Predict the subvolume [start, start+size) (x,y,z order as in the reference) of a uint8
     array `volume` indexed [z, y, x].  Voxels outside the array read as 0 (the reference fetches
     them from the store) or, with boundary="reflect" / "edge", the voxel that `fold` names on every axis: the result
@@ -794,6 +1079,14 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
     the remapped voxel it folds to.  fetch_input returns what the network saw, the remapped bytes.  A table of another
     dtype or shape raises ValueError before any GPU work.
 
+    clahe=None reads the volume as it is.  clahe = a ClaheTables (clahe_fit of this volume: np.uint8 tables
+    [Z, gy, gx, 256] and their tile; Z*gy*gx*256 bytes, uploaded once per call) equalises it first: one tem_u8_clahe
+    launch runs in place on the uploaded bytes ahead of the first gather -- and ahead of `lut`, which then remaps the
+    equalised bytes -- and the result is, bit for bit, that of the same call on clahe_volume(volume, clahe) for every
+    boundary, ensemble, mips, tile_batch and lut.  As with `lut`, a voxel outside the volume still reads 0 under "zeros"
+    and the equalised voxel it folds to under the mirrored modes, and fetch_input returns what the network saw.  Tables
+    of another dtype or shape, a tile outside [1, 2048] and a non-uint8 volume raise ValueError before any GPU work.
+
     histogram=True puts the 256-bin histogram of the level-0 prediction into stats["histogram"] (np.int64[256]; `stats`
     must then be a dict): the voxels of the returned array and no others -- nothing past `size`, nothing from the
     rounded-up tile margin -- counted on the device by one tem_u8_hist launch over the cropped box of the result,
@@ -803,6 +1096,9 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
     is3d = getattr(gen, "is3d", True)
     syms = _check_ensemble(ensemble, is3d)
     lut = _check_lut(lut, np.shape(volume))
+    if clahe is not None:
+        _check_u8(volume)
+    cl = _check_clahe(clahe, np.shape(volume))
     histogram = _check_histogram(histogram, stats)
     if outdimsize is None:
         outdimsize = model.outdimsize
@@ -814,7 +1110,7 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
         res = predict_cube(np.asarray(volume)[None], tuple(start) + (0,), tuple(size) + (1,), model, meanstd_x,
                            meanstd_y, fetch_input=fetch_input, outdimsize=outdimsize, buffer=buffer, rank=rank,
                            world_size=world_size, tile_batch=tile_batch, boundary=boundary, ensemble=ensemble,
-                           mips=mips, lut=lut, histogram=histogram, stats=stats)
+                           mips=mips, lut=lut, histogram=histogram, stats=stats, clahe=clahe)
         one = lambda r: [v[0] for v in r] if isinstance(r, list) else r[0]
         return tuple(one(r) for r in res) if fetch_input else one(res)
     outdimsize, buffer, tpad, rois, index = _tile_plan(start, size, outdimsize, buffer, is3d)
@@ -827,6 +1123,10 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
     vol = torch.from_numpy(vol_host).to(dev, non_blocking=True)          # ONE upload of the whole volume
     Z, Y, X = vol_host.shape
     stream = H.current_stream()
+    if cl is not None and vol_host.size:        # equalised in place, once, behind the upload and ahead of the lut
+        tab_dev = torch.from_numpy(cl[0]).to(dev)
+        _lib.check(lib.tem_u8_clahe(vol.data_ptr(), Z, Y, X, 0, 0, 0, tab_dev.data_ptr(), cl[3], cl[4], cl[1], cl[2],
+                                    stream), "tem_u8_clahe")
     if lut is not None and vol_host.size:       # remapped in place, once, behind the upload
         lut_dev = torch.from_numpy(lut).to(dev)
         _lib.check(lib.tem_u8_lut(vol.data_ptr(), Z, Y, X, lut_dev.data_ptr(), int(lut.ndim == 2), 0, stream),
@@ -863,7 +1163,9 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
         # the reference returns the RAW uint8 block here after a detour (utils.py:122-125: the standardized float
         # tile is un-standardized, rescaled and truncated into a uint8 buffer -- the original bytes up to float
         # rounding); the bytes themselves are returned instead
-        if lut is not None:                      # ... as the network saw them: remapped
+        if cl is not None:                       # ... as the network saw them: the bytes the kernels left
+            vol_host = vol.cpu().numpy()
+        elif lut is not None:                    # ... remapped
             vol_host = _lut_host(vol_host, lut)
         if boundary != "zeros":                  # what the network saw: the ROI of the folded volume
             fz, fy, fx = (fold(np.arange(start[d], start[d] + size[d]), n, boundary) for d, n in ((2, Z), (1, Y), (0, X)))
@@ -1011,7 +1313,7 @@ def chunk_plan(start, size, outdimsize, buffer, vol_shape, chunk_tiles, rank=0, 
 
 def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, chunk_tiles=None, tile_batch=None,
                    outdimsize=None, buffer=None, rank=0, world_size=1, stats=None, boundary="zeros", ensemble=None,
-                   mips=None, lut=None, histogram=False):
+                   mips=None, lut=None, histogram=False, clahe=None):
     """Out-of-core predict_cube: the subvolume [start, start+size) (x,y,z order) of a uint8 array-like `volume`
     indexed [z, y, x] (ndarray, np.memmap, h5py / zarr dataset: `.shape` and basic slicing are all it needs) is
     predicted chunk by chunk (chunk_plan) into `out`, a writable uint8 array-like of shape (size[2], size[1], size[0])
@@ -1056,6 +1358,13 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
     mirrored modes the footprint hull holds real sections, remapped by their own rows.  The result equals
     predict_cube(lut=...)'s, i.e. that of the same call on the remapped volume, which is never made.
 
+    `clahe` is predict_cube's (a ClaheTables of the whole volume; its Z*gy*gx*256 bytes are uploaded once per call, not
+    per chunk): each chunk's footprint is equalised in place by one tem_u8_clahe launch on the compute stream, behind
+    the wait for the chunk's H2D and ahead of `lut` and the first gather, with the footprint's `read` origin as the
+    launch's (zsec0, y_org, x_org) -- the tile grid belongs to the volume, so a voxel's value does not depend on the
+    chunk it arrives in.  The stand-in zero byte of a chunk wholly outside the volume is not touched.  The result equals
+    predict_cube(clahe=...)'s, i.e. that of the same call on the equalised volume, which is never made.
+
     histogram=True puts the 256-bin histogram of the level-0 result (np.int64[256]) into stats["histogram"]: one
     tem_u8_hist launch per chunk behind its last scatter, over the chunk's `out_box` extents of its device block, adding
     into one device accumulator that is read back once at the end -- no voxel is copied for it, and predictions past
@@ -1071,6 +1380,9 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
     if L and len(size) in (2, 3):
         out = _check_mip_outs(out, size, L, is3d)
     lut = _check_lut(lut, tuple(volume.shape))
+    if clahe is not None:
+        _check_u8(volume)
+    cl = _check_clahe(clahe, tuple(volume.shape))
     histogram = _check_histogram(histogram, stats)
     lib = H.require_gpu()
     if not hasattr(gen, "plan"):
@@ -1084,7 +1396,8 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
         predict_volume(_OneSection(volume), tuple(start) + (0,), tuple(size) + (1,), model, meanstd_x, meanstd_y,
                        out=[_OneSection(o) for o in out] if L else _OneSection(out), chunk_tiles=chunk_tiles,
                        tile_batch=tile_batch, outdimsize=outdimsize, buffer=buffer, rank=rank, world_size=world_size,
-                       stats=stats, boundary=boundary, ensemble=ensemble, mips=mips, lut=lut, histogram=histogram)
+                       stats=stats, boundary=boundary, ensemble=ensemble, mips=mips, lut=lut, histogram=histogram,
+                       clahe=clahe)
         return out
     vol_shape = tuple(int(v) for v in volume.shape)
     if len(vol_shape) != 3:
@@ -1128,6 +1441,7 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
     idx = torch.tensor([o for c in chunks for o in c.offsets], dtype=torch.int32).to(dev)
     d2h_done, d2h_evt = {}, [None, None]
     lut_dev = None if lut is None else torch.from_numpy(lut).to(dev)
+    tab_dev = None if cl is None else torch.from_numpy(cl[0]).to(dev)       # every section's tables, once
     counts = torch.zeros(256, dtype=torch.int64, device=dev) if histogram else None
     runner = _TileRunner(lib, model, is3d, edge, tpad, od, boundary, syms, meanstd_x, meanstd_y, vol_shape,
                          compute.cuda_stream)
@@ -1162,7 +1476,10 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
             if k >= 2:
                 compute.wait_event(d2h_evt[s])               # dev_out[s]: chunk k-2's D2H has read it
             lo = tuple(r[0] for r in c.read)
-            if lut_dev is not None and min(c.block) > 0:     # the footprint, in place; never the stand-in zero byte
+            if tab_dev is not None and min(c.block) > 0:     # the footprint, in place; never the stand-in zero byte
+                _lib.check(lib.tem_u8_clahe(src, *gdims[k], *lo, tab_dev.data_ptr(), cl[3], cl[4], cl[1], cl[2],
+                                            compute.cuda_stream), "tem_u8_clahe")
+            if lut_dev is not None and min(c.block) > 0:     # ... and the table behind it
                 _lib.check(lib.tem_u8_lut(src, *gdims[k], lut_dev.data_ptr(), int(lut.ndim == 2), lo[0],
                                           compute.cuda_stream), "tem_u8_lut")
             OZ, OY, OX = c.dims
@@ -1235,7 +1552,7 @@ def predict_ng_cube(location, start, size, model, meanstd_x, meanstd_y, cloudrun
     """Reference signature (utils.py:41): `location` is the uint8 volume itself (array indexed [z, y, x])
     instead of a cloud path; `cloudrun` is accepted and ignored.  The signature is the reference's, so voxels outside
     the array always read 0 here: predict_cube(..., boundary="reflect" | "edge") mirrors or clamps at the faces.
-    It takes no `mips` either: predict_cube(..., mips=L) returns the mip pyramid of the prediction."""
+    It takes no `mips` either: predict_cube(..., mips=L) returns the mip pyramid of the prediction; nor `lut` or `clahe`."""
     return predict_cube(_local_volume(location), start, size, model, meanstd_x, meanstd_y, fetch_input=fetch_input,
                         outdimsize=outdimsize, buffer=buffer)
 
@@ -1258,8 +1575,9 @@ def predict_volume_from_saved_model(volume, start, size, model_dir, out=None, **
     stats, boundary ("zeros", "reflect" or "edge": what a voxel outside the volume reads), ensemble (None, "flips",
     "all" or a sequence of symmetries: the orientations the generator's output is averaged over), mips (None, or
     the number of pooled levels of the result's mip pyramid: `out` and the return value are then lists of levels),
-    lut (None, or a uint8 table [256] or [Z, 256] the volume's intensities are remapped by on the device) and
-    histogram (True: stats["histogram"] receives the 256-bin histogram of the result).
+    lut (None, or a uint8 table [256] or [Z, 256] the volume's intensities are remapped by on the device),
+    histogram (True: stats["histogram"] receives the 256-bin histogram of the result) and clahe (None, or the
+    ClaheTables of the volume, clahe_fit: the volume is equalised on the device, ahead of lut).
     The reference's signatures, predict_ng_cube and predict_cube_from_saved_model, take none of these keywords; they
     run unensembled and return the full-resolution array alone."""
     model = _load_saved(model_dir)
