@@ -369,6 +369,30 @@ int tem_u8_pool2(const uint8_t *src, int32_t D, int32_t H, int32_t W, int32_t vD
 int tem_u8_hist(const uint8_t *src, int32_t D, int32_t H, int32_t W, int32_t z0, int32_t z1, int32_t y0, int32_t y1,
                 int32_t x0, int32_t x1, uint64_t *counts, int32_t per_section, tem_stream_t stream);
 
+/* Joint histogram of two uint8 blocks (a prediction against its ground truth): a[Da][Ha][Wa] and b[Db][Hb][Wb] are
+ * dense, each with its own dims, row stride and pointer alignment.
+ *   counts[256 u + v] += #{(z, y, x) in [0, nz) x [0, ny) x [0, nx) :
+ *                          a[az0 + z][ay0 + y][ax0 + x] == u  and  b[bz0 + z][by0 + y][bx0 + x] == v}
+ * counts holds 65,536 entries, 8-byte aligned.  The kernel ADDS (64-bit global atomic adds, one per non-zero bin and
+ * workgroup): the caller clears counts once and any number of calls, from any number of streams, accumulate into it.
+ * Exact for any data -- a constant pair (every lane on one bin) and a pair that fills all 65,536 bins included.  Bytes
+ * outside the two boxes are never counted and nothing but counts is written; a load touches only naturally aligned
+ * words (up to 16 bytes) that hold at least one byte of that side's box.  An empty box (nz, ny or nx == 0) returns
+ * TEM_OK without a launch.
+ * TEM_EINVAL, without a launch: a null pointer, counts off 8-byte alignment, a dimension below 1, a negative origin
+ * or extent, a box that leaves either block, and a box too large for the workgroups' 32-bit counters.  The table is
+ * split by the high bit of a, and each half's workgroups see every voxel of their run: with rows = nz * ny and
+ * S = (nx + 30) / 16 segments per row, the rows are dealt in equal contiguous runs of
+ *   rpw = ceil(rows / P),  P = min(128, max(1, ceil(rows * S / 4096)))
+ * rows to ceil(rows / rpw) workgroups per half, and
+ *   rpw x max(nx, S)  must stay below 2^31
+ * (a workgroup flushes once, at the end of its run: no counter can see more voxels than that, and its 32-bit index of
+ * (row, segment) items, split exactly for every value below 2^31, stays in range).  A box of fewer than 2^37 voxels
+ * always passes. */
+int tem_u8_hist2(const uint8_t *a, int32_t Da, int32_t Ha, int32_t Wa, int32_t az0, int32_t ay0, int32_t ax0,
+                 const uint8_t *b, int32_t Db, int32_t Hb, int32_t Wb, int32_t bz0, int32_t by0, int32_t bx0,
+                 int32_t nz, int32_t ny, int32_t nx, uint64_t *counts, tem_stream_t stream);
+
 /* Intensity remapping of a dense uint8 block in place (tiled inference: the uploaded bytes, ahead of the gather).
  *   per_section = 0:  buf[z][y][x] = lut[buf[z][y][x]]                          lut: 256 bytes
  *   per_section = 1:  buf[z][y][x] = lut[(zsec0 + z) * 256 + buf[z][y][x]]      lut: at least zsec0 + D rows of 256

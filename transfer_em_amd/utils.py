@@ -25,6 +25,11 @@ core on the device, the clipped and cumulated tables in exact integers on the ho
 interpolation between the tile centres, in integers -- on the device, written out (`clahe_volume`, for training volumes)
 or applied to the uploaded bytes ahead of the gather (`clahe=` of `predict_cube` / `predict_volume`), so that a model
 trained on equalised data sees equalised data without an equalised copy of the volume.
+
+`volume_joint_histogram` holds two uint8 volumes against each other out of core: the 256 x 256 joint histogram, counted
+on the device, from which `compare_from_joint` derives RMSE, MAE, PSNR, correlation and mutual information and
+`regression_lut` the paired intensity map (a table for `lut=`); `compare=gt` of `predict_cube` / `predict_volume` counts
+it for a prediction against its ground truth while the prediction is still on the device.
 """
 import json
 import os
@@ -653,6 +658,160 @@ def volume_histogram(volume, start=None, size=None, per_section=False, chunk_byt
     return out if per_section else out[0]
 
 
+def volume_joint_histogram(a, b, start=None, size=None, b_start=None, chunk_bytes=None, rank=0, world_size=1,
+                           device=None, stats=None):
+    """Joint histogram of two uint8 array-likes `a` and `b` indexed [z, y, x] (ndarray, np.memmap, h5py / zarr dataset;
+    they may differ in shape), or of two images [y, x] with 2-element arguments: np.int64[256, 256] with J[u, v] the
+    number of voxels p of the ROI with a[start + p] == u and b[b_start + p] == v.  The ROI is [start, start + size) of
+    `a` ((x, y, z) order; default: all of `a`) against [b_start, b_start + size) of `b` (b_start=None: the same start).
+    Both boxes must lie inside their volumes (hist_box's rule): ValueError otherwise, as for a dtype other than uint8,
+    before any GPU work.  compare_from_joint turns the table into RMSE, MAE, PSNR, correlation and mutual
+    information, regression_lut into the paired intensity map.
+
+    Out of core exactly as volume_histogram: the ROI is cut into slabs of at most `chunk_bytes` per volume
+    (hist_chunks on a's box; b's slab is the same box shifted), one host thread reads both slabs of a pair into
+    double-buffered pinned memory (two _InputStreams, two pinned and two device buffers each) -> H2D on copy streams ->
+    tem_u8_hist2 on the compute stream, adding into ONE device accumulator that is read back once at the end.  `stats`
+    receives the read seconds `read_s` and the slab count `chunks`.  Ranks (rank / world_size) take slabs round-robin:
+    each returns the counts of its own slabs, the ranks' results add up to the whole, and no collective is used."""
+    from concurrent.futures import ThreadPoolExecutor
+    from . import _lib
+    box = hist_box(a.shape, start, size)
+    nd = len(a.shape)
+    extent = tuple(hi - lo for lo, hi in reversed(box))[:nd]             # (x, y[, z])
+    box_b = hist_box(b.shape, tuple(lo for lo, _ in reversed(box))[:nd] if b_start is None else b_start, extent)
+    _check_u8(a)
+    _check_u8(b)
+    slabs = hist_chunks(box, chunk_bytes, rank, world_size)
+    shift = tuple(lb[0] - la[0] for la, lb in zip(box, box_b))
+    lib = H.require_gpu()
+    if nd == 2:
+        a, b = _OneSection(a), _OneSection(b)
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    st = {"read_s": 0.0, "chunks": len(slabs)}
+    dims = [tuple(hi - lo for lo, hi in s) for s in slabs]
+
+    def reader(vol, off):
+        def read_into(k, flat):
+            (z0, z1), (y0, y1), (x0, x1) = (tuple(v + o for v in r) for r, o in zip(slabs[k], off))
+            flat.reshape(dims[k])[...] = vol[z0:z1, y0:y1, x0:x1]
+        return read_into
+
+    with torch.cuda.device(dev):
+        compute = torch.cuda.current_stream(dev)
+        acc = torch.zeros((256, 256), dtype=torch.int64, device=dev)
+        nbytes = [int(np.prod(d)) for d in dims]
+        pool = ThreadPoolExecutor(max_workers=1)                         # one reader thread for both volumes
+        with _InputStream(nbytes, reader(a, (0, 0, 0)), dev, pool, st) as ina, \
+                _InputStream(nbytes, reader(b, shift), dev, pool, st) as inb:
+            for k, d in enumerate(dims):
+                pa, pb = ina.get(k), inb.get(k)
+                _lib.check(lib.tem_u8_hist2(pa.data_ptr(), *d, 0, 0, 0, pb.data_ptr(), *d, 0, 0, 0, *d, acc.data_ptr(),
+                                            compute.cuda_stream), "tem_u8_hist2")
+                done = compute.record_event()                            # counted
+                ina.release(k, done)
+                inb.release(k, done)
+                ina.prefetch(k + 2)
+                inb.prefetch(k + 2)
+        out = acc.cpu().numpy()                                  # the one read-back
+    if stats is not None:
+        stats.update(st)
+    return out
+
+
+def _check_joint(J, who):
+    J = np.asarray(J)
+    if J.shape != (256, 256) or J.dtype.kind not in "iu":
+        raise ValueError(f"{who}: a joint histogram is integer counts of shape [256, 256], got {J.dtype} {J.shape}")
+    if int(J.min()) < 0:
+        raise ValueError(f"{who}: the joint histogram has negative counts")
+    if not J.any():
+        raise ValueError(f"{who}: the joint histogram is empty")
+    return J
+
+
+def _entropy_bits(counts, n):
+    p = counts[counts > 0].astype(np.float64) / n
+    return float(-(p * np.log2(p)).sum())
+
+
+def compare_from_joint(J):
+    """What a joint histogram J[u, v] (np integer [256, 256]: volume_joint_histogram(a, b), or stats["joint_histogram"]
+    of predict_cube / predict_volume(compare=gt) with u = ground truth, v = prediction) says about the pair, as a dict.
+    The sums are exact Python integers; every float is derived from them once, in float64:
+        n                                   voxels counted
+        sum_abs_diff, sum_sq_diff           sum of |v - u| and of (v - u)^2 (integers)
+        mae, rmse, bias                     sum_abs_diff / n, sqrt(sum_sq_diff / n), mean of v - u
+        psnr                                20 log10(255 / rmse) in dB; inf when the volumes are equal
+        rmse_scaled                         rmse / 127.5: debug.accuracy of the two volumes as scaled tensors
+                                            v / 127.5 - 1, the reference's metric
+        pearson                             the correlation coefficient; nan when either side is constant
+        entropy_a, entropy_b, mutual_information    in bits; H(a) + H(b) - H(a, b), not below 0
+        hist_a, hist_b                      the marginals J.sum(1) and J.sum(0) (np.int64[256])
+    ValueError for another shape or dtype kind, a negative count or an empty table."""
+    import math
+    J = _check_joint(J, "compare_from_joint").astype(np.int64)
+    hist_a, hist_b = J.sum(axis=1), J.sum(axis=0)
+    n = int(hist_a.sum())
+    diag = {k: int(np.trace(J, offset=k)) for k in range(-255, 256)}     # voxels with v - u == k
+    sum_abs = sum(abs(k) * c for k, c in diag.items())
+    sum_sq = sum(k * k * c for k, c in diag.items())
+    su = sum(u * int(c) for u, c in enumerate(hist_a))
+    sv = sum(v * int(c) for v, c in enumerate(hist_b))
+    suu = sum(u * u * int(c) for u, c in enumerate(hist_a))
+    svv = sum(v * v * int(c) for v, c in enumerate(hist_b))
+    suv = sum(u * int(c) for u, c in enumerate(J @ np.arange(256, dtype=np.int64)))
+    var_a, var_b, cov = n * suu - su * su, n * svv - sv * sv, n * suv - su * sv       # each times n^2
+    rmse = math.sqrt(sum_sq / n)
+    h_a, h_b, h_ab = _entropy_bits(hist_a, n), _entropy_bits(hist_b, n), _entropy_bits(J.ravel(), n)
+    return {"n": n, "sum_abs_diff": sum_abs, "sum_sq_diff": sum_sq, "mae": sum_abs / n, "rmse": rmse,
+            "bias": (sv - su) / n, "psnr": math.inf if sum_sq == 0 else 20.0 * math.log10(255.0 / rmse),
+            "rmse_scaled": rmse / 127.5,
+            "pearson": math.nan if var_a == 0 or var_b == 0 else cov / math.sqrt(var_a * var_b),
+            "entropy_a": h_a, "entropy_b": h_b, "mutual_information": max(h_a + h_b - h_ab, 0.0),
+            "hist_a": hist_a, "hist_b": hist_b}
+
+
+def regression_lut(J):
+    """The paired intensity map of a joint histogram J[u, v] of (a, b) -- volume_joint_histogram(a, b), in that order of
+    the arguments -- as a lookup table: np.uint8[256] with t[u] = the mean of b over the voxels where a == u, rounded
+    half up in integers, (2 sum_v v J[u, v] + n_u) // (2 n_u).  A value u that never occurs in `a` takes the entry of
+    the nearest value that does, the lower one on a tie.  The result is a table for `lut=` of predict_cube /
+    predict_volume (and tem_u8_lut): applied to `a` it gives the least-squares estimate of `b` from a's intensities
+    alone; to map b towards a, pass the transposed table J.T.  ValueError as compare_from_joint."""
+    J = _check_joint(J, "regression_lut").astype(np.int64)
+    n_u = [int(c) for c in J.sum(axis=1)]
+    s_u = [int(c) for c in J @ np.arange(256, dtype=np.int64)]
+    seen = [u for u in range(256) if n_u[u]]
+    t = np.zeros(256, np.uint8)
+    for u in range(256):
+        w = min(seen, key=lambda s: (abs(s - u), s))
+        t[u] = (2 * s_u[w] + n_u[w]) // (2 * n_u[w])
+    return t
+
+
+def _check_compare(compare, vol_shape, stats):
+    """None, or `compare` itself: a uint8 array-like of the volume's shape, reported in a dict `stats`.  A _OneSection
+    is the image that the single-image form has checked already and passes on as a one-section stack."""
+    if compare is None or isinstance(compare, _OneSection):
+        return compare
+    if not isinstance(stats, dict):
+        raise ValueError("compare= reports in stats['joint_histogram']: pass a dict as `stats`")
+    shape, dtype = getattr(compare, "shape", None), getattr(compare, "dtype", None)
+    if shape is None or dtype is None or dtype != np.uint8:
+        raise ValueError(f"compare must be a uint8 array-like, got {type(compare).__name__} of dtype {dtype}")
+    if tuple(int(v) for v in shape) != tuple(int(v) for v in vol_shape):
+        raise ValueError(f"compare must have the volume's shape {tuple(vol_shape)}, got {tuple(shape)}")
+    return compare
+
+
+def _inside(lo, hi, shift, vol_shape):
+    """The (z, y, x) (lo, hi) box [lo + shift, hi + shift) clipped to a volume of shape vol_shape, or None where it
+    misses the volume."""
+    box = tuple((max(l + s, 0), min(h + s, n)) for l, h, s, n in zip(lo, hi, shift, vol_shape))
+    return box if all(h > l for l, h in box) else None
+
+
 def meanstd_from_histogram(h):
     """(np.float32 mean, np.float32 std) of the SCALED values v / 127.5 - 1 of the voxels a 256-bin histogram `h`
     counts (a [Z, 256] per-section histogram is summed over its rows first): the unit `meanstd_x` / `meanstd_y` are
@@ -1027,7 +1186,7 @@ def clahe_volume(volume, clahe, out=None, start=None, size=None, chunk_bytes=Non
 
 def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=False, outdimsize=None, buffer=None,
                  rank=0, world_size=1, tile_batch=None, boundary="zeros", ensemble=None, mips=None, lut=None,
-                 histogram=False, stats=None, clahe=None):
+                 histogram=False, stats=None, clahe=None, compare=None):
     """Predict the subvolume [start, start+size) (x,y,z order as in the reference) of a uint8
     array `volume` indexed [z, y, x].  Voxels outside the array read as 0 (the reference fetches
     them from the store) or, with boundary="reflect" / "edge", the voxel that `fold` names on every axis: the result
@@ -1090,7 +1249,16 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
     histogram=True puts the 256-bin histogram of the level-0 prediction into stats["histogram"] (np.int64[256]; `stats`
     must then be a dict): the voxels of the returned array and no others -- nothing past `size`, nothing from the
     rounded-up tile margin -- counted on the device by one tem_u8_hist launch over the cropped box of the result,
-    after the all-reduce of a multi-rank call.  meanstd_from_histogram turns it into the unit of meanstd_y."""
+    after the all-reduce of a multi-rank call.  meanstd_from_histogram turns it into the unit of meanstd_y.
+
+    compare=None compares nothing.  compare = gt, a uint8 array-like of the volume's own shape and in the volume's
+    frame (the ground truth of the prediction), puts the joint histogram of (gt, level-0 prediction) into
+    stats["joint_histogram"] (np.int64[256, 256], J[u, v] with u = ground truth, v = prediction; `stats` must then be
+    a dict): compare_from_joint turns it into RMSE, MAE, PSNR, correlation and mutual information, regression_lut into
+    the paired intensity map.  It is counted over the ROI voxels that lie inside the volume -- a voxel the ROI reaches
+    outside the volume has no ground truth and is not compared, under every `boundary` -- by one tem_u8_hist2 launch on
+    the cropped result against gt's ROI-within-the-volume box, uploaded once; after the all-reduce of a multi-rank
+    call.  Anything else raises ValueError before any GPU work."""
     from . import _lib
     gen = getattr(model, "generator_g", None)
     is3d = getattr(gen, "is3d", True)
@@ -1100,6 +1268,7 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
         _check_u8(volume)
     cl = _check_clahe(clahe, np.shape(volume))
     histogram = _check_histogram(histogram, stats)
+    compare = _check_compare(compare, np.shape(volume), stats)
     if outdimsize is None:
         outdimsize = model.outdimsize
     if buffer is None:
@@ -1110,7 +1279,8 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
         res = predict_cube(np.asarray(volume)[None], tuple(start) + (0,), tuple(size) + (1,), model, meanstd_x,
                            meanstd_y, fetch_input=fetch_input, outdimsize=outdimsize, buffer=buffer, rank=rank,
                            world_size=world_size, tile_batch=tile_batch, boundary=boundary, ensemble=ensemble,
-                           mips=mips, lut=lut, histogram=histogram, stats=stats, clahe=clahe)
+                           mips=mips, lut=lut, histogram=histogram, stats=stats, clahe=clahe,
+                           compare=None if compare is None else np.asarray(compare)[None])
         one = lambda r: [v[0] for v in r] if isinstance(r, list) else r[0]
         return tuple(one(r) for r in res) if fetch_input else one(res)
     outdimsize, buffer, tpad, rois, index = _tile_plan(start, size, outdimsize, buffer, is3d)
@@ -1150,6 +1320,16 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
             _lib.check(lib.tem_u8_hist(out_buffer.data_ptr(), OZ, OY, OX, 0, size[2], 0, size[1], 0, size[0],
                                        counts.data_ptr(), 0, stream), "tem_u8_hist")
         stats["histogram"] = counts.cpu().numpy()
+    if compare is not None:                     # against the ground truth, where the ROI lies inside the volume
+        joint = torch.zeros((256, 256), dtype=torch.int64, device=dev)
+        box = _inside((0, 0, 0), (size[2], size[1], size[0]), (start[2], start[1], start[0]), (Z, Y, X))
+        if box is not None:
+            (z0, z1), (y0, y1), (x0, x1) = box
+            n = (z1 - z0, y1 - y0, x1 - x0)
+            gt = torch.from_numpy(np.ascontiguousarray(compare[z0:z1, y0:y1, x0:x1], dtype=np.uint8)).to(dev)
+            _lib.check(lib.tem_u8_hist2(gt.data_ptr(), *n, 0, 0, 0, out_buffer.data_ptr(), OZ, OY, OX, z0 - start[2],
+                                        y0 - start[1], x0 - start[0], *n, joint.data_ptr(), stream), "tem_u8_hist2")
+        stats["joint_histogram"] = joint.cpu().numpy()
     if L:                                       # the pyramid of the resident result: one launch per level
         fz = 2 if is3d else 1
         shapes = mip_shapes(size, L, is3d)
@@ -1313,7 +1493,7 @@ def chunk_plan(start, size, outdimsize, buffer, vol_shape, chunk_tiles, rank=0, 
 
 def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, chunk_tiles=None, tile_batch=None,
                    outdimsize=None, buffer=None, rank=0, world_size=1, stats=None, boundary="zeros", ensemble=None,
-                   mips=None, lut=None, histogram=False, clahe=None):
+                   mips=None, lut=None, histogram=False, clahe=None, compare=None):
     """Out-of-core predict_cube: the subvolume [start, start+size) (x,y,z order) of a uint8 array-like `volume`
     indexed [z, y, x] (ndarray, np.memmap, h5py / zarr dataset: `.shape` and basic slicing are all it needs) is
     predicted chunk by chunk (chunk_plan) into `out`, a writable uint8 array-like of shape (size[2], size[1], size[0])
@@ -1369,7 +1549,16 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
     tem_u8_hist launch per chunk behind its last scatter, over the chunk's `out_box` extents of its device block, adding
     into one device accumulator that is read back once at the end -- no voxel is copied for it, and predictions past
     `size` are not counted.  In a multi-rank call each rank reports the histogram of its own chunks: the ranks'
-    histograms add up to that of the whole result."""
+    histograms add up to that of the whole result.
+
+    `compare` is predict_cube's (gt: a uint8 array-like of the volume's shape, e.g. a memmap): stats["joint_histogram"]
+    receives the np.int64[256, 256] joint histogram of (gt, level-0 result) over the ROI voxels inside the volume.  Per
+    chunk the host thread also reads gt's box -- the chunk's `out_box` shifted by `start` and clipped to the volume --
+    through a second double-buffered input stream, and one tem_u8_hist2 launch behind the chunk's last scatter (and its
+    tem_u8_hist, with `histogram`) adds it into one device table that is read back once at the end; a chunk whose box
+    misses the volume launches nothing.  The table does not depend on chunk_tiles or tile_batch; each rank reports its
+    own chunks, and the ranks' tables add up to that of the whole result."""
+    import contextlib
     import time
     from concurrent.futures import ThreadPoolExecutor
     from . import _lib
@@ -1384,6 +1573,7 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
         _check_u8(volume)
     cl = _check_clahe(clahe, tuple(volume.shape))
     histogram = _check_histogram(histogram, stats)
+    compare = _check_compare(compare, tuple(volume.shape), stats)
     lib = H.require_gpu()
     if not hasattr(gen, "plan"):
         raise TypeError("predict_volume needs a generator with launch plans (EM2EM or a saved model)")
@@ -1397,7 +1587,7 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
                        out=[_OneSection(o) for o in out] if L else _OneSection(out), chunk_tiles=chunk_tiles,
                        tile_batch=tile_batch, outdimsize=outdimsize, buffer=buffer, rank=rank, world_size=world_size,
                        stats=stats, boundary=boundary, ensemble=ensemble, mips=mips, lut=lut, histogram=histogram,
-                       clahe=clahe)
+                       clahe=clahe, compare=None if compare is None else _OneSection(compare))
         return out
     vol_shape = tuple(int(v) for v in volume.shape)
     if len(vol_shape) != 3:
@@ -1416,6 +1606,8 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
     st = {"read_s": 0.0, "write_s": 0.0, "chunks": len(chunks), "mips": L}
     if histogram:
         st["histogram"] = np.zeros(256, np.int64)
+    if compare is not None:
+        st["joint_histogram"] = np.zeros((256, 256), np.int64)
     if stats is not None:
         stats.update(st)
     if not chunks:
@@ -1445,6 +1637,18 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
     counts = torch.zeros(256, dtype=torch.int64, device=dev) if histogram else None
     runner = _TileRunner(lib, model, is3d, edge, tpad, od, boundary, syms, meanstd_x, meanstd_y, vol_shape,
                          compute.cuda_stream)
+    if compare is not None:
+        # the ground truth of chunk k: its out_box in the volume's frame, clipped to the volume (None: it misses it)
+        gt_box = [_inside(tuple(b[0] for b in c.out_box), tuple(b[1] for b in c.out_box),
+                          (start[2], start[1], start[0]), vol_shape) for c in chunks]
+        gt_dims = [None if b is None else tuple(hi - lo for lo, hi in b) for b in gt_box]
+        gt_bytes = [1 if d is None else int(np.prod(d)) for d in gt_dims]
+        joint = torch.zeros((256, 256), dtype=torch.int64, device=dev)
+
+    def read_gt(k, flat):               # host thread: the ground-truth box of chunk k (one unused byte where none)
+        if gt_box[k] is not None:
+            (z0, z1), (y0, y1), (x0, x1) = gt_box[k]
+            flat.reshape(gt_dims[k])[...] = compare[z0:z1, y0:y1, x0:x1]
 
     def read_into(k, flat):             # host thread: footprint of chunk k
         c, dst = chunks[k], flat.reshape(gdims[k])
@@ -1469,7 +1673,8 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
         st["write_s"] += time.perf_counter() - t0
 
     pool, writes = ThreadPoolExecutor(max_workers=1), {}     # one thread for reads and writes: write(k), read(k + 2)
-    with _InputStream(in_bytes, read_into, dev, pool, st) as inp:
+    with _InputStream(in_bytes, read_into, dev, pool, st) as inp, \
+            (contextlib.nullcontext() if compare is None else _InputStream(gt_bytes, read_gt, dev, pool, st)) as gt_inp:
         for k, c in enumerate(chunks):
             s = k % 2
             src = inp.get(k).data_ptr()
@@ -1495,7 +1700,16 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
                 oz, oy, ox = (max(hi - lo_, 0) for lo_, hi in c.out_box)
                 _lib.check(lib.tem_u8_hist(dev_out[s].data_ptr(), OZ, OY, OX, 0, oz, 0, oy, 0, ox, counts.data_ptr(), 0,
                                            compute.cuda_stream), "tem_u8_hist")
+            if compare is not None:                          # the chunk's part of the result against its ground truth
+                gt = gt_inp.get(k)
+                if gt_box[k] is not None:
+                    at = tuple(b[0] - s0 - o for b, s0, o in zip(gt_box[k], (start[2], start[1], start[0]), c.base))
+                    _lib.check(lib.tem_u8_hist2(gt.data_ptr(), *gt_dims[k], 0, 0, 0, dev_out[s].data_ptr(), OZ, OY, OX,
+                                                *at, *gt_dims[k], joint.data_ptr(), compute.cuda_stream),
+                               "tem_u8_hist2")
             scattered = compute.record_event()
+            if compare is not None:
+                gt_inp.release(k, scattered)
             if k >= 2:
                 writes.pop(k - 2).result()                   # pin_out[s]: chunk k-2 is in `out`
             d2h.wait_event(scattered)
@@ -1504,10 +1718,14 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
             d2h_done[k] = d2h_evt[s] = d2h.record_event()
             writes[k] = pool.submit(write, k)
             inp.prefetch(k + 2)
+            if compare is not None:
+                gt_inp.prefetch(k + 2)
         for k in sorted(writes):
             writes.pop(k).result()
     if histogram:
         st["histogram"] = counts.cpu().numpy()               # the one read-back
+    if compare is not None:
+        st["joint_histogram"] = joint.cpu().numpy()          # ... and the table's
     if stats is not None:
         stats.update(st)
     return out
@@ -1552,7 +1770,8 @@ def predict_ng_cube(location, start, size, model, meanstd_x, meanstd_y, cloudrun
     """Reference signature (utils.py:41): `location` is the uint8 volume itself (array indexed [z, y, x])
     instead of a cloud path; `cloudrun` is accepted and ignored.  The signature is the reference's, so voxels outside
     the array always read 0 here: predict_cube(..., boundary="reflect" | "edge") mirrors or clamps at the faces.
-    It takes no `mips` either: predict_cube(..., mips=L) returns the mip pyramid of the prediction; nor `lut` or `clahe`."""
+    It takes no `mips` either: predict_cube(..., mips=L) returns the mip pyramid of the prediction; nor `lut`, `clahe` or
+    `compare`."""
     return predict_cube(_local_volume(location), start, size, model, meanstd_x, meanstd_y, fetch_input=fetch_input,
                         outdimsize=outdimsize, buffer=buffer)
 
@@ -1576,8 +1795,10 @@ def predict_volume_from_saved_model(volume, start, size, model_dir, out=None, **
     "all" or a sequence of symmetries: the orientations the generator's output is averaged over), mips (None, or
     the number of pooled levels of the result's mip pyramid: `out` and the return value are then lists of levels),
     lut (None, or a uint8 table [256] or [Z, 256] the volume's intensities are remapped by on the device),
-    histogram (True: stats["histogram"] receives the 256-bin histogram of the result) and clahe (None, or the
-    ClaheTables of the volume, clahe_fit: the volume is equalised on the device, ahead of lut).
+    histogram (True: stats["histogram"] receives the 256-bin histogram of the result), clahe (None, or the
+    ClaheTables of the volume, clahe_fit: the volume is equalised on the device, ahead of lut) and compare (None, or
+    the ground truth as a uint8 array-like of the volume's shape: stats["joint_histogram"] receives the 256 x 256
+    joint histogram of (ground truth, result), see compare_from_joint).
     The reference's signatures, predict_ng_cube and predict_cube_from_saved_model, take none of these keywords; they
     run unensembled and return the full-resolution array alone."""
     model = _load_saved(model_dir)
