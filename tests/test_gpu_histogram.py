@@ -572,3 +572,53 @@ def test_a_failing_read_surfaces_and_leaves_nothing_behind(all3, model3):
         volume_histogram(bad, chunk_bytes=budget)
     assert bad.reads >= 3 and threading.active_count() == threads
     assert np.array_equal(volume_histogram(vol, chunk_bytes=budget), _bincount(vol))
+
+
+class FailingWrites:
+    """Array-like over a numpy array whose third write raises OSError: a host error, nothing faults on the device."""
+
+    def __init__(self, a):
+        self.a, self.shape, self.dtype, self.writes = a, a.shape, a.dtype, 0
+
+    def __setitem__(self, key, value):
+        self.writes += 1
+        if self.writes == 3:
+            raise OSError("the third write fails")
+        self.a[key] = value
+
+
+def test_a_failing_write_surfaces_and_leaves_nothing_behind(all3, model3):
+    """4 chunks / 4 slabs, so the failing write is that of a reused pinned buffer and writes are queued behind it."""
+    import threading
+    from clahe_ref import ref_remap, ref_tables, ref_tile_hist
+    from transfer_em_amd.utils import (clahe_fit, clahe_volume, hist_box, hist_chunks, mip_shapes, predict_cube,
+                                       predict_volume)
+    vol = all3["vol"]
+    shape = (ALL_SIZE[2], ALL_SIZE[1], ALL_SIZE[0])
+    threads = threading.active_count()
+    bad = FailingWrites(np.zeros(shape, np.uint8))
+    with pytest.raises(OSError, match="the third write fails"):
+        predict_volume(vol, ALL_START, ALL_SIZE, model3, MS_X, MS_Y, out=bad, chunk_tiles=(1, 1, 2), tile_batch=1)
+    assert bad.writes >= 3 and threading.active_count() == threads              # the host thread has ended
+    want = predict_cube(vol, ALL_START, ALL_SIZE, model3, MS_X, MS_Y, tile_batch=1)
+    _guard(want)
+    _eq(predict_volume(vol, ALL_START, ALL_SIZE, model3, MS_X, MS_Y, chunk_tiles=(1, 1, 2), tile_batch=1), want)
+    levels = [np.zeros(s, np.uint8) for s in mip_shapes(ALL_SIZE, 2)]           # the per-level write loop
+    bad = levels[1] = FailingWrites(levels[1])
+    with pytest.raises(OSError, match="the third write fails"):
+        predict_volume(vol, ALL_START, ALL_SIZE, model3, MS_X, MS_Y, out=levels, chunk_tiles=(1, 1, 2), tile_batch=1,
+                       mips=2)
+    assert bad.writes >= 3 and threading.active_count() == threads
+    _eq(predict_volume(vol, ALL_START, ALL_SIZE, model3, MS_X, MS_Y, chunk_tiles=(1, 1, 2), tile_batch=1), want)
+    budget = 8 * 55 * 90                                                        # 8 of 30 sections per slab
+    assert len(hist_chunks(hist_box(ALL_VOL), budget)) == 4
+    c = clahe_fit(vol, tile=32)
+    T = ref_tables(ref_tile_hist(vol, 32, 32), 3.0)
+    assert np.array_equal(c.tables, T)
+    bad = FailingWrites(np.zeros(ALL_VOL, np.uint8))
+    with pytest.raises(OSError, match="the third write fails"):
+        clahe_volume(vol, c, out=bad, chunk_bytes=budget)
+    assert bad.writes >= 3 and threading.active_count() == threads
+    fresh = np.zeros(ALL_VOL, np.uint8)
+    assert clahe_volume(vol, c, out=fresh, chunk_bytes=budget) is fresh
+    assert np.array_equal(fresh, ref_remap(vol, T, 32, 32))

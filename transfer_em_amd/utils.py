@@ -31,13 +31,17 @@ on the device, from which `compare_from_joint` derives RMSE, MAE, PSNR, correlat
 `regression_lut` the paired intensity map (a table for `lut=`); `compare=gt` of `predict_cube` / `predict_volume` counts
 it for a prediction against its ground truth while the prediction is still on the device.
 """
+import contextlib
 import json
 import os
+import time
+from concurrent.futures import ThreadPoolExecutor
 from typing import NamedTuple
 
 import numpy as np
 import torch
 
+from . import _lib
 from . import hip_ops as H
 
 
@@ -124,7 +128,6 @@ def plan_routes(edge, N, is3d=True, dtype=torch.float32, wf=8):
     plain kernel copy is conv_launch's."""
     import ctypes as C
     from collections import OrderedDict
-    from . import _lib
     from .models.generator import generator_blocks, generator_edges, skip_crop
     lib = _lib.load()
     bf16 = dtype == torch.bfloat16
@@ -314,7 +317,6 @@ class _TileRunner:
 
     def __init__(self, lib, model, is3d, edge, tpad, outdimsize, boundary, syms, meanstd_x, meanstd_y, vol_shape,
                  stream):
-        from . import _lib
         gname, self.sname, self.aname = (
             ("tem_u8_tiles_to_f32_std", "tem_f32_tiles_unstd_to_u8", "tem_f32_tiles_sym_accum") if is3d else
             ("tem_u8_tiles2d_to_f32_std", "tem_f32_tiles2d_unstd_to_u8", "tem_f32_tiles2d_sym_accum"))
@@ -351,7 +353,6 @@ class _TileRunner:
         Under an ensemble a batch runs once per member s in order: the gather cuts T_s(tiles), and T_s^-1 of the
         generator's output is folded into the accumulator -- written by the first member, added to by the others,
         divided by the member count by the last -- whose mean is scattered once."""
-        from . import _lib
         members = self.syms or [None]
         for b0 in range(0, n, nb):
             m = min(nb, n - b0)
@@ -377,6 +378,63 @@ class _TileRunner:
             assert y.shape[2] - 2 * self.tpad == self.outdimsize, (y.shape, self.tpad, self.outdimsize)
             _lib.check(self.scatter(y.data_ptr(), m, y.shape[2], self.tpad, offsets + 12 * b0, dst, *dims, *self.ms_y,
                                     self.stream), self.sname)
+
+
+class _Prepare:
+    """What predict_cube and predict_volume do to uploaded bytes ahead of the gather, made once per call: `clahe`
+    (_check_clahe's tuple) and `lut` (_check_lut's table), either may be None, are uploaded here, once.  apply() remaps
+    a block in place on `stream`: tem_u8_clahe first, then tem_u8_lut on the equalised bytes.  clahe_volume uses the
+    first half alone."""
+
+    def __init__(self, lib, clahe, lut, dev, stream):
+        self.lib, self.clahe, self.lut, self.stream = lib, clahe, lut, stream
+        self.tab_dev = None if clahe is None else torch.from_numpy(clahe[0]).to(dev)    # every section's tables
+        self.lut_dev = None if lut is None else torch.from_numpy(lut).to(dev)
+
+    def apply(self, ptr, block, lo):
+        """Remap the dense uint8 block of shape `block` at `ptr` that holds the volume's box at `lo`: the tile grid and
+        the rows of a [Z, 256] table belong to the volume (the resident volume: lo = 0, block = its shape).  A block
+        with an empty side is not there -- an empty volume, or a chunk wholly outside the volume, whose one stand-in
+        zero byte has to stay 0 -- and nothing is launched."""
+        if min(block) < 1:
+            return
+        if self.tab_dev is not None:
+            _, th, tw, gy, gx = self.clahe
+            _lib.check(self.lib.tem_u8_clahe(ptr, *block, *lo, self.tab_dev.data_ptr(), gy, gx, th, tw, self.stream),
+                       "tem_u8_clahe")
+        if self.lut_dev is not None:
+            _lib.check(self.lib.tem_u8_lut(ptr, *block, self.lut_dev.data_ptr(), int(self.lut.ndim == 2), lo[0],
+                                           self.stream), "tem_u8_lut")
+
+
+class _Measure:
+    """What is counted on a uint8 result while it is on the device, made once per call: the int64[256] histogram
+    (`histogram`) and the int64[256, 256] joint histogram against a ground truth (`joint`), each one device accumulator
+    that add() launches into on `stream` and report() reads back once."""
+
+    def __init__(self, lib, histogram, joint, dev, stream):
+        self.lib, self.stream = lib, stream
+        self.counts = torch.zeros(256, dtype=torch.int64, device=dev) if histogram else None
+        self.joint = torch.zeros((256, 256), dtype=torch.int64, device=dev) if joint else None
+
+    def add(self, ptr, dims, valid, gt=None):
+        """Count the leading `valid` extents of the dense block of shape `dims` at `ptr` (tem_u8_hist) and, with
+        gt = (pointer, dims, at), hold its box of gt's dims at offset `at` against the dense ground-truth block
+        (tem_u8_hist2: J[u, v] with u from gt).  gt=None where there is no ground truth for the block."""
+        if self.counts is not None and min(valid) > 0:
+            _lib.check(self.lib.tem_u8_hist(ptr, *dims, 0, valid[0], 0, valid[1], 0, valid[2], self.counts.data_ptr(), 0,
+                                            self.stream), "tem_u8_hist")
+        if self.joint is not None and gt is not None:
+            gt_ptr, n, at = gt
+            _lib.check(self.lib.tem_u8_hist2(gt_ptr, *n, 0, 0, 0, ptr, *dims, *at, *n, self.joint.data_ptr(),
+                                             self.stream), "tem_u8_hist2")
+
+    def report(self, st):
+        """The one read-back of each accumulator, into st["histogram"] / st["joint_histogram"]."""
+        if self.counts is not None:
+            st["histogram"] = self.counts.cpu().numpy()
+        if self.joint is not None:
+            st["joint_histogram"] = self.joint.cpu().numpy()
 
 
 class _OneSection:
@@ -487,7 +545,6 @@ def _check_mip_outs(out, size, L, is3d=True):
 def _pool_levels(lib, src_ptr, dims, valid, L, is3d, dst_ptrs, stream):
     """The L pooling launches of one block: level l + 1 = tem_u8_pool2 of level l, level 0 at `src_ptr` with dense
     `dims` and valid extents `valid`, level l at dst_ptrs[l - 1].  Returns the levels' (dims, valid) from level 1 on."""
-    from . import _lib
     fz, levels = 2 if is3d else 1, []
     half = lambda v: (-(-v[0] // fz), -(-v[1] // 2), -(-v[2] // 2))
     for l in range(L):
@@ -581,7 +638,6 @@ class _InputStream:
             torch.cuda.synchronize(self.dev)
 
     def _read(self, k):                     # host thread: block k -> pin[k % 2]
-        import time
         if k >= 2:
             self.h2d_done.pop(k - 2).synchronize()          # the buffer's previous H2D has finished
         t0 = time.perf_counter()
@@ -608,6 +664,118 @@ class _InputStream:
         self.released[k] = event
 
 
+class _OutputStream:
+    """The double-buffered output side of an out-of-core pass over K blocks of `nbytes[k]` bytes, the counterpart of
+    _InputStream: block k is copied from the device into pinned buffer k % 2 on a copy stream and handed to
+    write_from(k, flat uint8 ndarray) on the executor's thread.  The write seconds add up in st["write_s"].  With
+    `own_buffers` it also holds two device buffers for the consumer's kernels to write block k into (`device(k)`);
+    without, put() is given the device tensor to copy out of.  Used as a context manager inside the _InputStream's
+    (the same executor: one host thread, whose work the consumer queues in the order write(k), read(k + 2)): leaving
+    the pass waits for the queued writes, and a failed one raises there; on an exception it does nothing, the
+    _InputStream around it owns the executor's end.
+
+    The consumer's loop over k: [`device(k)`,] its kernels on the compute stream (the current stream of `dev`),
+    `put(k, event)` with the event behind the last of them.  Buffers k % 2 are reused in this order: the D2H of block
+    k waits for that event and, on the host, for the write of block k - 2 to have returned; the write of block k waits
+    for that D2H; and the compute stream waits for the D2H of block k - 2 before `device(k)` is written again."""
+
+    def __init__(self, nbytes, write_from, dev, pool, st, own_buffers=False):
+        self.nbytes, self.write_from, self.pool, self.st = nbytes, write_from, pool, st
+        self.compute, self.d2h = torch.cuda.current_stream(dev), torch.cuda.Stream(dev)
+        size, n = max(nbytes, default=0), min(2, len(nbytes))
+        self.pin = [torch.empty(size, dtype=torch.uint8, pin_memory=True) for _ in range(n)]
+        self.buf = [torch.empty(size, dtype=torch.uint8, device=dev) for _ in range(n)] if own_buffers else None
+        self.writes, self.copied = {}, [None, None]
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None:
+            for k in sorted(self.writes):
+                self.writes.pop(k).result()
+
+    def _write(self, k, copied):            # host thread: pin[k % 2] -> wherever write_from puts block k
+        copied.synchronize()
+        t0 = time.perf_counter()
+        self.write_from(k, self.pin[k % 2][:self.nbytes[k]].numpy())
+        self.st["write_s"] += time.perf_counter() - t0
+
+    def device(self, k):
+        """The own device buffer that block k goes into, once the compute stream gets there."""
+        if k >= 2:
+            self.compute.wait_event(self.copied[k % 2])         # buf[k % 2]: block k - 2's D2H has read it
+        return self.buf[k % 2]
+
+    def put(self, k, ready, src=None):
+        """Copy block k out of `src` (default: the own device buffer) once `ready` and queue its write.  Returns the
+        D2H's event: `src` is free when it has passed."""
+        s, n = k % 2, self.nbytes[k]
+        src = self.buf[s] if src is None else src
+        if k >= 2:
+            self.writes.pop(k - 2).result()                     # pin[s]: block k - 2 has been written
+        self.d2h.wait_event(ready)
+        with torch.cuda.stream(self.d2h):
+            self.pin[s][:n].copy_(src[:n], non_blocking=True)
+        self.copied[s] = self.d2h.record_event()
+        self.writes[k] = self.pool.submit(self._write, k, self.copied[s])
+        return self.copied[s]
+
+
+class _SlabPass:
+    """One out-of-core pass over a box of one or more uint8 array-likes [z, y, x] (one image [y, x]: a one-section
+    stack), slab by slab through the input side of predict_volume's pipeline.  Making it is host work and comes ahead
+    of any GPU work: the dtype check (ValueError) and this rank's slabs of boxes[0] (hist_chunks); the slab of
+    volumes[i] is the same box shifted from boxes[0] to boxes[i].  `st` holds the read seconds `read_s` and the slab
+    count `chunks`.
+
+    `with p.streaming():` is the pass, on `device` (None: the current one) as the current device: one host thread
+    (`p.pool`) reads every volume's slab into an _InputStream of its own, which also ends the thread, on an exception
+    as it describes.  Inside, `for k, slab, dims, buffers in p:` gives slab k's box, its shape and one device buffer
+    per volume that holds it, for the caller's launches on `p.compute`; behind them the buffers are released -- on
+    `p.release_on` where the caller has set an event for this slab, else on one recorded there -- and the slabs k + 2
+    are prefetched."""
+
+    def __init__(self, volumes, boxes, chunk_bytes, rank, world_size, device):
+        for v in volumes:
+            _check_u8(v)
+        self.slabs = hist_chunks(boxes[0], chunk_bytes, rank, world_size)
+        self.dims = [tuple(hi - lo for lo, hi in s) for s in self.slabs]
+        self.nbytes = [int(np.prod(d)) for d in self.dims]
+        self.volumes = [_OneSection(v) if len(v.shape) == 2 else v for v in volumes]
+        self.shifts = [tuple(b[0] - a[0] for a, b in zip(boxes[0], box)) for box in boxes]
+        self.device, self.st = device, {"read_s": 0.0, "chunks": len(self.slabs)}
+
+    def _reader(self, vol, shift):
+        slabs, dims = self.slabs, self.dims         # not `self`: the streams, which the pass holds, must not hold it
+
+        def read_into(k, flat):
+            (z0, z1), (y0, y1), (x0, x1) = (tuple(v + o for v in r) for r, o in zip(slabs[k], shift))
+            flat.reshape(dims[k])[...] = vol[z0:z1, y0:y1, x0:x1]
+        return read_into
+
+    @contextlib.contextmanager
+    def streaming(self):
+        dev = self.dev = (torch.device("cuda", torch.cuda.current_device()) if self.device is None else
+                          torch.device(self.device))
+        self.pool = ThreadPoolExecutor(max_workers=1)            # one reader thread, however many volumes
+        with torch.cuda.device(dev), contextlib.ExitStack() as stack:
+            self.compute = torch.cuda.current_stream(dev)
+            self.inputs = [stack.enter_context(_InputStream(self.nbytes, self._reader(v, o), dev, self.pool, self.st))
+                           for v, o in zip(self.volumes, self.shifts)]
+            yield self
+
+    def __iter__(self):
+        for k, (slab, dims) in enumerate(zip(self.slabs, self.dims)):
+            self.release_on = None
+            yield k, slab, dims, [inp.get(k) for inp in self.inputs]
+            done = self.release_on or self.compute.record_event()    # counted
+            for inp in self.inputs:
+                inp.release(k, done)
+            for inp in self.inputs:
+                inp.prefetch(k + 2)
+
+
 def volume_histogram(volume, start=None, size=None, per_section=False, chunk_bytes=None, rank=0, world_size=1,
                      device=None, stats=None):
     """Intensity histogram of the ROI [start, start + size) ((x, y, z) order; default: the whole volume) of a uint8
@@ -622,39 +790,18 @@ def volume_histogram(volume, start=None, size=None, per_section=False, chunk_byt
     The pass is bound by the read (`stats` receives the read seconds `read_s` and the slab count `chunks`).  Ranks
     (rank / world_size) take slabs round-robin: each returns the counts of its own slabs, the ranks' results add up to
     the whole, and no collective is used."""
-    from concurrent.futures import ThreadPoolExecutor
-    from . import _lib
     box = hist_box(volume.shape, start, size)
-    if getattr(volume, "dtype", np.dtype(np.uint8)) != np.uint8:
-        raise ValueError(f"volume must be uint8, got {volume.dtype}")
-    slabs = hist_chunks(box, chunk_bytes, rank, world_size)
+    p = _SlabPass([volume], [box], chunk_bytes, rank, world_size, device)
     lib = H.require_gpu()
-    if len(volume.shape) == 2:
-        volume = _OneSection(volume)
-    nz = box[0][1] - box[0][0]
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    st = {"read_s": 0.0, "chunks": len(slabs)}
-    dims = [tuple(hi - lo for lo, hi in b) for b in slabs]
-
-    def read_into(k, flat):
-        (z0, z1), (y0, y1), (x0, x1) = slabs[k]
-        flat.reshape(dims[k])[...] = volume[z0:z1, y0:y1, x0:x1]
-
-    with torch.cuda.device(dev):
-        compute = torch.cuda.current_stream(dev)
-        acc = torch.zeros((nz if per_section else 1, 256), dtype=torch.int64, device=dev)
-        nbytes = [int(np.prod(d)) for d in dims]
-        with _InputStream(nbytes, read_into, dev, ThreadPoolExecutor(max_workers=1), st) as inp:
-            for k, d in enumerate(dims):
-                src = inp.get(k)
-                row = (slabs[k][0][0] - box[0][0]) if per_section else 0
-                _lib.check(lib.tem_u8_hist(src.data_ptr(), *d, 0, d[0], 0, d[1], 0, d[2], acc.data_ptr() + 2048 * row,
-                                           int(bool(per_section)), compute.cuda_stream), "tem_u8_hist")
-                inp.release(k, compute.record_event())               # counted
-                inp.prefetch(k + 2)
+    with p.streaming():
+        acc = torch.zeros((box[0][1] - box[0][0] if per_section else 1, 256), dtype=torch.int64, device=p.dev)
+        for k, slab, d, (src,) in p:
+            row = (slab[0][0] - box[0][0]) if per_section else 0
+            _lib.check(lib.tem_u8_hist(src.data_ptr(), *d, 0, d[0], 0, d[1], 0, d[2], acc.data_ptr() + 2048 * row,
+                                       int(bool(per_section)), p.compute.cuda_stream), "tem_u8_hist")
         out = acc.cpu().numpy()                              # the one read-back
     if stats is not None:
-        stats.update(st)
+        stats.update(p.st)
     return out if per_section else out[0]
 
 
@@ -674,49 +821,21 @@ def volume_joint_histogram(a, b, start=None, size=None, b_start=None, chunk_byte
     tem_u8_hist2 on the compute stream, adding into ONE device accumulator that is read back once at the end.  `stats`
     receives the read seconds `read_s` and the slab count `chunks`.  Ranks (rank / world_size) take slabs round-robin:
     each returns the counts of its own slabs, the ranks' results add up to the whole, and no collective is used."""
-    from concurrent.futures import ThreadPoolExecutor
-    from . import _lib
     box = hist_box(a.shape, start, size)
     nd = len(a.shape)
     extent = tuple(hi - lo for lo, hi in reversed(box))[:nd]             # (x, y[, z])
     box_b = hist_box(b.shape, tuple(lo for lo, _ in reversed(box))[:nd] if b_start is None else b_start, extent)
-    _check_u8(a)
-    _check_u8(b)
-    slabs = hist_chunks(box, chunk_bytes, rank, world_size)
-    shift = tuple(lb[0] - la[0] for la, lb in zip(box, box_b))
+    p = _SlabPass([a, b], [box, box_b], chunk_bytes, rank, world_size, device)
     lib = H.require_gpu()
-    if nd == 2:
-        a, b = _OneSection(a), _OneSection(b)
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    st = {"read_s": 0.0, "chunks": len(slabs)}
-    dims = [tuple(hi - lo for lo, hi in s) for s in slabs]
-
-    def reader(vol, off):
-        def read_into(k, flat):
-            (z0, z1), (y0, y1), (x0, x1) = (tuple(v + o for v in r) for r, o in zip(slabs[k], off))
-            flat.reshape(dims[k])[...] = vol[z0:z1, y0:y1, x0:x1]
-        return read_into
-
-    with torch.cuda.device(dev):
-        compute = torch.cuda.current_stream(dev)
-        acc = torch.zeros((256, 256), dtype=torch.int64, device=dev)
-        nbytes = [int(np.prod(d)) for d in dims]
-        pool = ThreadPoolExecutor(max_workers=1)                         # one reader thread for both volumes
-        with _InputStream(nbytes, reader(a, (0, 0, 0)), dev, pool, st) as ina, \
-                _InputStream(nbytes, reader(b, shift), dev, pool, st) as inb:
-            for k, d in enumerate(dims):
-                pa, pb = ina.get(k), inb.get(k)
-                _lib.check(lib.tem_u8_hist2(pa.data_ptr(), *d, 0, 0, 0, pb.data_ptr(), *d, 0, 0, 0, *d, acc.data_ptr(),
-                                            compute.cuda_stream), "tem_u8_hist2")
-                done = compute.record_event()                            # counted
-                ina.release(k, done)
-                inb.release(k, done)
-                ina.prefetch(k + 2)
-                inb.prefetch(k + 2)
-        out = acc.cpu().numpy()                                  # the one read-back
+    with p.streaming():
+        measure = _Measure(lib, False, True, p.dev, p.compute.cuda_stream)
+        for k, slab, d, (pa, pb) in p:
+            measure.add(pb.data_ptr(), d, d, gt=(pa.data_ptr(), d, (0, 0, 0)))
+        res = {}
+        measure.report(res)                                      # the one read-back
     if stats is not None:
-        stats.update(st)
-    return out
+        stats.update(p.st)
+    return res["joint_histogram"]
 
 
 def _check_joint(J, who):
@@ -957,48 +1076,28 @@ def clahe_histograms(volume, tile=128, chunk_bytes=None, rank=0, world_size=1, d
     holds the whole volume's Z*gy*gx*1024 bytes and is read back once where that is at most CLAHE_ACC_BYTES; else it
     holds one slab's sections and is read back, and added on the host, per slab.  Ranks take slabs round-robin and
     their results add up to the whole.  `stats` receives `read_s` and `chunks`."""
-    from concurrent.futures import ThreadPoolExecutor
-    from . import _lib
     th, tw = _clahe_tile(tile)
     gy, gx = clahe_grid(volume.shape, (th, tw))
     box = hist_box(volume.shape)
-    _check_u8(volume)
-    slabs = hist_chunks(box, chunk_bytes, rank, world_size)
+    p = _SlabPass([volume], [box], chunk_bytes, rank, world_size, device)
     lib = H.require_gpu()
-    if len(volume.shape) == 2:
-        volume = _OneSection(volume)
     Z, sec = box[0][1], gy * gx * 256
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    st = {"read_s": 0.0, "chunks": len(slabs)}
-    dims = [tuple(hi - lo for lo, hi in b) for b in slabs]
     whole = Z * sec * 4 <= CLAHE_ACC_BYTES
     out = None if whole else np.zeros((Z, gy, gx, 256), np.uint32)
-
-    def read_into(k, flat):
-        (z0, z1), (y0, y1), (x0, x1) = slabs[k]
-        flat.reshape(dims[k])[...] = volume[z0:z1, y0:y1, x0:x1]
-
-    with torch.cuda.device(dev):
-        compute = torch.cuda.current_stream(dev)
-        acc = torch.zeros((Z if whole else max((d[0] for d in dims), default=1), sec), dtype=torch.int32, device=dev)
-        nbytes = [int(np.prod(d)) for d in dims]
-        with _InputStream(nbytes, read_into, dev, ThreadPoolExecutor(max_workers=1), st) as inp:
-            for k, d in enumerate(dims):
-                (z0, z1), (y0, _), (x0, _) = slabs[k]
-                src = inp.get(k)
-                if not whole:
-                    acc[:d[0]].zero_()
-                _lib.check(lib.tem_u8_hist_tiles(src.data_ptr(), *d, y0, x0, th, tw, gy, gx,
-                                                 acc.data_ptr() + 4 * sec * (z0 if whole else 0), compute.cuda_stream),
-                           "tem_u8_hist_tiles")
-                inp.release(k, compute.record_event())               # counted
-                inp.prefetch(k + 2)
-                if not whole:                                        # this slab's sections, added on the host
-                    out[z0:z1] += acc[:d[0]].cpu().numpy().view(np.uint32).reshape(d[0], gy, gx, 256)
+    with p.streaming():
+        acc = torch.zeros((Z if whole else max((d[0] for d in p.dims), default=1), sec), dtype=torch.int32, device=p.dev)
+        for k, ((z0, z1), (y0, _), (x0, _)), d, (src,) in p:
+            if not whole:
+                acc[:d[0]].zero_()
+            _lib.check(lib.tem_u8_hist_tiles(src.data_ptr(), *d, y0, x0, th, tw, gy, gx,
+                                             acc.data_ptr() + 4 * sec * (z0 if whole else 0), p.compute.cuda_stream),
+                       "tem_u8_hist_tiles")
+            if not whole:                                        # this slab's sections, added on the host
+                out[z0:z1] += acc[:d[0]].cpu().numpy().view(np.uint32).reshape(d[0], gy, gx, 256)
         if whole:
             out = acc.cpu().numpy().view(np.uint32).reshape(Z, gy, gx, 256)        # the one read-back
     if stats is not None:
-        stats.update(st)
+        stats.update(p.st)
     return out
 
 
@@ -1114,12 +1213,9 @@ def clahe_volume(volume, clahe, out=None, start=None, size=None, chunk_bytes=Non
     (each reports the histogram of its own slabs).  `stats` also receives `read_s`, `write_s` and `chunks`.
     ValueError, before any GPU work: an ROI outside the volume, a non-uint8 volume, tables of another dtype or shape,
     an `out` of another shape."""
-    import time
-    from concurrent.futures import ThreadPoolExecutor
-    from . import _lib
     box = hist_box(volume.shape, start, size)
-    _check_u8(volume)
-    tables, th, tw, gy, gx = _check_clahe(clahe, tuple(volume.shape))
+    p = _SlabPass([volume], [box], chunk_bytes, rank, world_size, device)
+    cl = tuple(_check_clahe(clahe, tuple(volume.shape)))        # a TypeError for None: here the tables are no option
     histogram = _check_histogram(histogram, stats)
     one = len(volume.shape) == 2
     shape = tuple(hi - lo for lo, hi in box)
@@ -1127,60 +1223,26 @@ def clahe_volume(volume, clahe, out=None, start=None, size=None, chunk_bytes=Non
         out = np.zeros(shape[1:] if one else shape, np.uint8)
     elif tuple(out.shape) != (shape[1:] if one else shape):
         raise ValueError(f"out has shape {tuple(out.shape)}, expected {shape[1:] if one else shape}")
-    slabs = hist_chunks(box, chunk_bytes, rank, world_size)
     lib = H.require_gpu()
-    src_vol, dst_vol = (_OneSection(volume), _OneSection(out)) if one else (volume, out)
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    st = {"read_s": 0.0, "write_s": 0.0, "chunks": len(slabs)}
-    dims = [tuple(hi - lo for lo, hi in b) for b in slabs]
-    nbytes = [int(np.prod(d)) for d in dims]
+    dst_vol = _OneSection(out) if one else out
+    p.st["write_s"] = 0.0
 
-    def read_into(k, flat):
-        (z0, z1), (y0, y1), (x0, x1) = slabs[k]
-        flat.reshape(dims[k])[...] = src_vol[z0:z1, y0:y1, x0:x1]
+    def write_from(k, flat):            # host thread: the slab's box of `out`
+        (z0, z1), (y0, y1), (x0, x1) = p.slabs[k]
+        (oz, _), (oy, _), (ox, _) = box
+        dst_vol[z0 - oz:z1 - oz, y0 - oy:y1 - oy, x0 - ox:x1 - ox] = flat.reshape(p.dims[k])
 
-    with torch.cuda.device(dev):
-        compute, d2h = torch.cuda.current_stream(dev), torch.cuda.Stream(dev)
-        tab = torch.from_numpy(tables).to(dev)
-        counts = torch.zeros(256, dtype=torch.int64, device=dev) if histogram else None
-        pin_out = [torch.empty(max(nbytes, default=0), dtype=torch.uint8, pin_memory=True) for _ in range(min(2, len(slabs)))]
-        d2h_done = {}
-
-        def write(k):                   # host thread: pin_out[k % 2] -> the slab's box of `out`
-            d2h_done.pop(k).synchronize()
-            t0 = time.perf_counter()
-            (z0, z1), (y0, y1), (x0, x1) = slabs[k]
-            (oz, _), (oy, _), (ox, _) = box
-            dst_vol[z0 - oz:z1 - oz, y0 - oy:y1 - oy, x0 - ox:x1 - ox] = pin_out[k % 2][:nbytes[k]].numpy().reshape(dims[k])
-            st["write_s"] += time.perf_counter() - t0
-
-        pool, writes = ThreadPoolExecutor(max_workers=1), {}     # one thread for reads and writes: write(k), read(k + 2)
-        with _InputStream(nbytes, read_into, dev, pool, st) as inp:
-            for k, d in enumerate(dims):
-                s, n = k % 2, nbytes[k]
-                (z0, _), (y0, _), (x0, _) = slabs[k]
-                buf = inp.get(k)
-                _lib.check(lib.tem_u8_clahe(buf.data_ptr(), *d, z0, y0, x0, tab.data_ptr(), gy, gx, th, tw,
-                                            compute.cuda_stream), "tem_u8_clahe")
-                if histogram:
-                    _lib.check(lib.tem_u8_hist(buf.data_ptr(), *d, 0, d[0], 0, d[1], 0, d[2], counts.data_ptr(), 0,
-                                               compute.cuda_stream), "tem_u8_hist")
-                remapped = compute.record_event()
-                if k >= 2:
-                    writes.pop(k - 2).result()                   # pin_out[s]: slab k-2 is in `out`
-                d2h.wait_event(remapped)
-                with torch.cuda.stream(d2h):
-                    pin_out[s][:n].copy_(buf[:n], non_blocking=True)
-                d2h_done[k] = d2h.record_event()
-                inp.release(k, d2h_done[k])                      # the device buffer: free once it has been copied out
-                writes[k] = pool.submit(write, k)
-                inp.prefetch(k + 2)
-            for k in sorted(writes):
-                writes.pop(k).result()
-        if histogram:
-            st["histogram"] = counts.cpu().numpy()
+    with p.streaming():
+        prepare = _Prepare(lib, cl, None, p.dev, p.compute.cuda_stream)          # the tables, once
+        measure = _Measure(lib, histogram, False, p.dev, p.compute.cuda_stream)
+        with _OutputStream(p.nbytes, write_from, p.dev, p.pool, p.st) as outp:   # the reader's thread: write(k), read(k + 2)
+            for k, slab, d, (buf,) in p:
+                prepare.apply(buf.data_ptr(), d, tuple(lo for lo, _ in slab))
+                measure.add(buf.data_ptr(), d, d)
+                p.release_on = outp.put(k, p.compute.record_event(), buf)        # the input buffer: free once copied out
+        measure.report(p.st)
     if stats is not None:
-        stats.update(st)
+        stats.update(p.st)
     return out
 
 
@@ -1259,7 +1321,6 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
     outside the volume has no ground truth and is not compared, under every `boundary` -- by one tem_u8_hist2 launch on
     the cropped result against gt's ROI-within-the-volume box, uploaded once; after the all-reduce of a multi-rank
     call.  Anything else raises ValueError before any GPU work."""
-    from . import _lib
     gen = getattr(model, "generator_g", None)
     is3d = getattr(gen, "is3d", True)
     syms = _check_ensemble(ensemble, is3d)
@@ -1293,14 +1354,8 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
     vol = torch.from_numpy(vol_host).to(dev, non_blocking=True)          # ONE upload of the whole volume
     Z, Y, X = vol_host.shape
     stream = H.current_stream()
-    if cl is not None and vol_host.size:        # equalised in place, once, behind the upload and ahead of the lut
-        tab_dev = torch.from_numpy(cl[0]).to(dev)
-        _lib.check(lib.tem_u8_clahe(vol.data_ptr(), Z, Y, X, 0, 0, 0, tab_dev.data_ptr(), cl[3], cl[4], cl[1], cl[2],
-                                    stream), "tem_u8_clahe")
-    if lut is not None and vol_host.size:       # remapped in place, once, behind the upload
-        lut_dev = torch.from_numpy(lut).to(dev)
-        _lib.check(lib.tem_u8_lut(vol.data_ptr(), Z, Y, X, lut_dev.data_ptr(), int(lut.ndim == 2), 0, stream),
-                   "tem_u8_lut")
+    prepare = _Prepare(lib, cl, lut, dev, stream)
+    prepare.apply(vol.data_ptr(), (Z, Y, X), (0, 0, 0))                  # in place, once, behind the upload
     out_buffer = torch.zeros((rnd(z) if is3d else z, rnd(y), rnd(x)), dtype=torch.uint8, device=dev)
     OZ, OY, OX = out_buffer.shape
     mine = list(range(rank, len(rois), world_size))
@@ -1314,22 +1369,15 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
     if world_size > 1 and torch.distributed.is_initialized():
         torch.distributed.all_reduce(out_buffer, op=torch.distributed.ReduceOp.MAX)   # disjoint tiles, zeros elsewhere
     out = out_buffer[0:size[2], 0:size[1], 0:size[0]].cpu().numpy()
-    if histogram:                               # of the cropped box: the voxels of `out`
-        counts = torch.zeros(256, dtype=torch.int64, device=dev)
-        if out.size:
-            _lib.check(lib.tem_u8_hist(out_buffer.data_ptr(), OZ, OY, OX, 0, size[2], 0, size[1], 0, size[0],
-                                       counts.data_ptr(), 0, stream), "tem_u8_hist")
-        stats["histogram"] = counts.cpu().numpy()
-    if compare is not None:                     # against the ground truth, where the ROI lies inside the volume
-        joint = torch.zeros((256, 256), dtype=torch.int64, device=dev)
-        box = _inside((0, 0, 0), (size[2], size[1], size[0]), (start[2], start[1], start[0]), (Z, Y, X))
-        if box is not None:
-            (z0, z1), (y0, y1), (x0, x1) = box
-            n = (z1 - z0, y1 - y0, x1 - x0)
-            gt = torch.from_numpy(np.ascontiguousarray(compare[z0:z1, y0:y1, x0:x1], dtype=np.uint8)).to(dev)
-            _lib.check(lib.tem_u8_hist2(gt.data_ptr(), *n, 0, 0, 0, out_buffer.data_ptr(), OZ, OY, OX, z0 - start[2],
-                                        y0 - start[1], x0 - start[0], *n, joint.data_ptr(), stream), "tem_u8_hist2")
-        stats["joint_histogram"] = joint.cpu().numpy()
+    measure, gt = _Measure(lib, histogram, compare is not None, dev, stream), None
+    box = None if compare is None else _inside((0, 0, 0), (size[2], size[1], size[0]), (start[2], start[1], start[0]),
+                                               (Z, Y, X))
+    if box is not None:                         # the ground truth where the ROI lies inside the volume, uploaded once
+        (z0, z1), (y0, y1), (x0, x1) = box
+        gt_dev = torch.from_numpy(np.ascontiguousarray(compare[z0:z1, y0:y1, x0:x1], dtype=np.uint8)).to(dev)
+        gt = (gt_dev.data_ptr(), tuple(gt_dev.shape), (z0 - start[2], y0 - start[1], x0 - start[0]))
+    measure.add(out_buffer.data_ptr(), (OZ, OY, OX), (size[2], size[1], size[0]), gt)   # the cropped box: `out`'s voxels
+    measure.report(stats)
     if L:                                       # the pyramid of the resident result: one launch per level
         fz = 2 if is3d else 1
         shapes = mip_shapes(size, L, is3d)
@@ -1558,10 +1606,6 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
     tem_u8_hist, with `histogram`) adds it into one device table that is read back once at the end; a chunk whose box
     misses the volume launches nothing.  The table does not depend on chunk_tiles or tile_batch; each rank reports its
     own chunks, and the ranks' tables add up to that of the whole result."""
-    import contextlib
-    import time
-    from concurrent.futures import ThreadPoolExecutor
-    from . import _lib
     gen = model.generator_g
     is3d = getattr(gen, "is3d", True)
     syms = _check_ensemble(ensemble, is3d)
@@ -1625,16 +1669,12 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
     out_bytes = [int(o[-1]) for o in lvl_off]
     nb = st["tile_batch"] = _effective_batch(tile_batch, edge, is3d, max(len(c.tiles) for c in chunks))
     dev = model.device
-    compute, d2h = torch.cuda.current_stream(dev), torch.cuda.Stream(dev)
-    pin_out = [torch.empty(max(out_bytes), dtype=torch.uint8, pin_memory=True) for _ in range(2)]
-    dev_out = [torch.empty(max(out_bytes), dtype=torch.uint8, device=dev) for _ in range(2)]
+    compute = torch.cuda.current_stream(dev)
     first = np.cumsum([0] + [len(c.tiles) for c in chunks])
     org = torch.tensor([o for c in chunks for o in c.origins], dtype=torch.int32).to(dev)     # every chunk's, once
     idx = torch.tensor([o for c in chunks for o in c.offsets], dtype=torch.int32).to(dev)
-    d2h_done, d2h_evt = {}, [None, None]
-    lut_dev = None if lut is None else torch.from_numpy(lut).to(dev)
-    tab_dev = None if cl is None else torch.from_numpy(cl[0]).to(dev)       # every section's tables, once
-    counts = torch.zeros(256, dtype=torch.int64, device=dev) if histogram else None
+    prepare = _Prepare(lib, cl, lut, dev, compute.cuda_stream)
+    measure = _Measure(lib, histogram, compare is not None, dev, compute.cuda_stream)
     runner = _TileRunner(lib, model, is3d, edge, tpad, od, boundary, syms, meanstd_x, meanstd_y, vol_shape,
                          compute.cuda_stream)
     if compare is not None:
@@ -1643,7 +1683,6 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
                           (start[2], start[1], start[0]), vol_shape) for c in chunks]
         gt_dims = [None if b is None else tuple(hi - lo for lo, hi in b) for b in gt_box]
         gt_bytes = [1 if d is None else int(np.prod(d)) for d in gt_dims]
-        joint = torch.zeros((256, 256), dtype=torch.int64, device=dev)
 
     def read_gt(k, flat):               # host thread: the ground-truth box of chunk k (one unused byte where none)
         if gt_box[k] is not None:
@@ -1658,74 +1697,48 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
         else:
             dst[...] = 0
 
-    def write(k):                       # host thread: pin_out[k % 2] -> the chunk's box of `out`
-        d2h_done.pop(k).synchronize()
-        t0 = time.perf_counter()
-        c, buf = chunks[k], pin_out[k % 2].numpy()
+    def write_from(k, buf):             # host thread: the chunk's box of `out`
+        c = chunks[k]
         if not L:
-            src = buf[:out_bytes[k]].reshape(c.dims)
             (z0, z1), (y0, y1), (x0, x1) = c.out_box
-            out[z0:z1, y0:y1, x0:x1] = src[:z1 - z0, :y1 - y0, :x1 - x0]
+            out[z0:z1, y0:y1, x0:x1] = buf.reshape(c.dims)[:z1 - z0, :y1 - y0, :x1 - x0]
         for l in range(L + 1 if L else 0):      # with a pyramid: each level's box into its own array
             src = buf[lvl_off[k][l]:lvl_off[k][l + 1]].reshape(lvl_dims[k][l])
             ((z0, z1), (y0, y1), (x0, x1)), (nz, ny, nx) = mip_box(c, l, is3d)
             out[l][z0:z1, y0:y1, x0:x1] = src[:nz, :ny, :nx]
-        st["write_s"] += time.perf_counter() - t0
 
-    pool, writes = ThreadPoolExecutor(max_workers=1), {}     # one thread for reads and writes: write(k), read(k + 2)
+    pool = ThreadPoolExecutor(max_workers=1)     # one thread for reads and writes: write(k), read(k + 2)
+    outp = _OutputStream(out_bytes, write_from, dev, pool, st, own_buffers=True)
     with _InputStream(in_bytes, read_into, dev, pool, st) as inp, \
-            (contextlib.nullcontext() if compare is None else _InputStream(gt_bytes, read_gt, dev, pool, st)) as gt_inp:
+            (contextlib.nullcontext() if compare is None else _InputStream(gt_bytes, read_gt, dev, pool, st)) as gt_inp, \
+            outp:
         for k, c in enumerate(chunks):
-            s = k % 2
-            src = inp.get(k).data_ptr()
-            if k >= 2:
-                compute.wait_event(d2h_evt[s])               # dev_out[s]: chunk k-2's D2H has read it
+            src, dst = inp.get(k).data_ptr(), outp.device(k).data_ptr()
             lo = tuple(r[0] for r in c.read)
-            if tab_dev is not None and min(c.block) > 0:     # the footprint, in place; never the stand-in zero byte
-                _lib.check(lib.tem_u8_clahe(src, *gdims[k], *lo, tab_dev.data_ptr(), cl[3], cl[4], cl[1], cl[2],
-                                            compute.cuda_stream), "tem_u8_clahe")
-            if lut_dev is not None and min(c.block) > 0:     # ... and the table behind it
-                _lib.check(lib.tem_u8_lut(src, *gdims[k], lut_dev.data_ptr(), int(lut.ndim == 2), lo[0],
-                                          compute.cuda_stream), "tem_u8_lut")
-            OZ, OY, OX = c.dims
+            prepare.apply(src, c.block, lo)                  # the footprint; never the stand-in zero byte
             t = 12 * int(first[k])
             # the staging buffer is free for the next upload once the chunk's last gather is enqueued
-            runner.run(src, gdims[k], lo, org.data_ptr() + t, idx.data_ptr() + t, len(c.tiles), nb,
-                       dev_out[s].data_ptr(), c.dims, lambda: inp.release(k, compute.record_event()))
-            if L:                                            # the chunk's pyramid, level by level behind its scatters
-                base = dev_out[s].data_ptr()
-                _pool_levels(lib, base, c.dims, tuple(hi - lo for lo, hi in c.out_box), L, is3d,
-                             [base + int(o) for o in lvl_off[k][1:L + 1]], compute.cuda_stream)
-            if histogram:                                    # of the chunk's part of the result, where it lies
-                oz, oy, ox = (max(hi - lo_, 0) for lo_, hi in c.out_box)
-                _lib.check(lib.tem_u8_hist(dev_out[s].data_ptr(), OZ, OY, OX, 0, oz, 0, oy, 0, ox, counts.data_ptr(), 0,
-                                           compute.cuda_stream), "tem_u8_hist")
-            if compare is not None:                          # the chunk's part of the result against its ground truth
-                gt = gt_inp.get(k)
+            runner.run(src, gdims[k], lo, org.data_ptr() + t, idx.data_ptr() + t, len(c.tiles), nb, dst, c.dims,
+                       lambda: inp.release(k, compute.record_event()))
+            valid = tuple(hi - lo_ for lo_, hi in c.out_box)     # the chunk's part of the result
+            if L:                                            # its pyramid, level by level behind its scatters
+                _pool_levels(lib, dst, c.dims, valid, L, is3d, [dst + int(o) for o in lvl_off[k][1:L + 1]],
+                             compute.cuda_stream)
+            gt = None
+            if compare is not None:                          # ... against its ground truth, where there is one
+                gt_buf = gt_inp.get(k)
                 if gt_box[k] is not None:
                     at = tuple(b[0] - s0 - o for b, s0, o in zip(gt_box[k], (start[2], start[1], start[0]), c.base))
-                    _lib.check(lib.tem_u8_hist2(gt.data_ptr(), *gt_dims[k], 0, 0, 0, dev_out[s].data_ptr(), OZ, OY, OX,
-                                                *at, *gt_dims[k], joint.data_ptr(), compute.cuda_stream),
-                               "tem_u8_hist2")
+                    gt = (gt_buf.data_ptr(), gt_dims[k], at)
+            measure.add(dst, c.dims, valid, gt)
             scattered = compute.record_event()
             if compare is not None:
                 gt_inp.release(k, scattered)
-            if k >= 2:
-                writes.pop(k - 2).result()                   # pin_out[s]: chunk k-2 is in `out`
-            d2h.wait_event(scattered)
-            with torch.cuda.stream(d2h):
-                pin_out[s][:out_bytes[k]].copy_(dev_out[s][:out_bytes[k]], non_blocking=True)
-            d2h_done[k] = d2h_evt[s] = d2h.record_event()
-            writes[k] = pool.submit(write, k)
+            outp.put(k, scattered)
             inp.prefetch(k + 2)
             if compare is not None:
                 gt_inp.prefetch(k + 2)
-        for k in sorted(writes):
-            writes.pop(k).result()
-    if histogram:
-        st["histogram"] = counts.cpu().numpy()               # the one read-back
-    if compare is not None:
-        st["joint_histogram"] = joint.cpu().numpy()          # ... and the table's
+    measure.report(st)                                       # the one read-back of each
     if stats is not None:
         stats.update(st)
     return out
