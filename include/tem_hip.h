@@ -393,6 +393,38 @@ int tem_u8_hist2(const uint8_t *a, int32_t Da, int32_t Ha, int32_t Wa, int32_t a
                  const uint8_t *b, int32_t Db, int32_t Hb, int32_t Wb, int32_t bz0, int32_t by0, int32_t bx0,
                  int32_t nz, int32_t ny, int32_t nx, uint64_t *counts, tem_stream_t stream);
 
+/* Windowed structural similarity (SSIM) of two uint8 blocks, the structural companion of tem_u8_hist2: a[Da][Ha][Wa]
+ * and b[Db][Hb][Wb] are dense, each with its own dims, row stride and pointer alignment; the voxel box has extents
+ * (nz, ny, nx) at origin (az0, ay0, ax0) of a and (bz0, by0, bx0) of b.  Windows are uniform boxes of wz x win x win
+ * voxels, win odd in 3...11, wz = win (volumetric) or 1 (flat != 0: section by section), N = wz win win; only windows
+ * that lie wholly inside the box count: the window box is (nz - wz + 1, ny - win + 1, nx - win + 1), a window named by
+ * its first voxel.  Per window, from the integer sums Sa, Sb, Saa, Sbb, Sab over its voxels, all in int64:
+ *   A1 = 20000 Sa Sb           + 65025 N^2        B1 = 10000 (Sa^2 + Sb^2)                     + 65025 N^2
+ *   A2 = 20000 (N Sab - Sa Sb) + 585225 N (N - 1) B2 = 10000 ((N Saa - Sa^2) + (N Sbb - Sb^2)) + 585225 N (N - 1)
+ *   l = double(A1) / double(B1)      cs = double(A2) / double(B2)      s = l cs
+ *   q_x = (int64) rint(x 2^30)  for x in (s, l, cs)                    (round half to even)
+ * -- Wang's SSIM with a uniform window, the sample covariance (N - 1), data range 255, K1 = 0.01, K2 = 0.03
+ * (C1 = 6.5025, C2 = 58.5225, carried x 10^4).  A1...B2 stay below 2^53 for win <= 11, so the conversions are exact;
+ * B1, B2 > 0; the value is two correctly rounded divisions, one multiplication and a scaling by a power of two.
+ *   sums[3 z + 0, 1, 2] += the q_s, q_l, q_cs of all windows whose first section is z       (z < nz - wz + 1)
+ *   map[z][y][x] = (255 max(q_s, 0) + 2^29) >> 30      dense [nz - wz + 1][ny - win + 1][nx - win + 1]; may be null
+ * The kernel ADDS to sums (signed: s < 0 for an anti-correlated pair) with 64-bit global atomic adds, one per workgroup,
+ * window-section and quantity: the caller clears sums once and any number of calls, from any number of streams,
+ * accumulate.  Integer adds: the result does not depend on how the box is cut or launched.  No byte outside the two
+ * boxes is read and nothing but sums and map is written.  Any alignment of a, b, map, Wa and Wb; sums must be 8-byte
+ * aligned.  A box in which no window fits (nz < wz, ny < win or nx < win; an empty box included) returns TEM_OK
+ * without a launch.
+ * TEM_EINVAL, without a launch: a null a, b or sums, sums off 8-byte alignment, win even or outside 3...11, a
+ * dimension below 1, a negative origin or extent, a box that leaves either block, and a window box of more workgroups
+ * than one launch holds: a workgroup takes 8 x 32 window origins over (y, x) and a run of 32 window-sections, and
+ *   ceil((ny - win + 1) / 8) x ceil((nx - win + 1) / 32) x ceil((nz - wz + 1) / 32)  must stay below 2^24
+ * (its 256 threads then stay below 2^32 per launch; the workgroup index is split in 32 bits, every byte offset is 64
+ * bits).  A box of fewer than 2^34 voxels with no extent below 32 always passes. */
+int tem_u8_ssim(const uint8_t *a, int32_t Da, int32_t Ha, int32_t Wa, int32_t az0, int32_t ay0, int32_t ax0,
+                const uint8_t *b, int32_t Db, int32_t Hb, int32_t Wb, int32_t bz0, int32_t by0, int32_t bx0,
+                int32_t nz, int32_t ny, int32_t nx, int32_t win, int32_t flat, int64_t *sums, uint8_t *map,
+                tem_stream_t stream);
+
 /* Intensity remapping of a dense uint8 block in place (tiled inference: the uploaded bytes, ahead of the gather).
  *   per_section = 0:  buf[z][y][x] = lut[buf[z][y][x]]                          lut: 256 bytes
  *   per_section = 1:  buf[z][y][x] = lut[(zsec0 + z) * 256 + buf[z][y][x]]      lut: at least zsec0 + D rows of 256

@@ -30,6 +30,10 @@ trained on equalised data sees equalised data without an equalised copy of the v
 on the device, from which `compare_from_joint` derives RMSE, MAE, PSNR, correlation and mutual information and
 `regression_lut` the paired intensity map (a table for `lut=`); `compare=gt` of `predict_cube` / `predict_volume` counts
 it for a prediction against its ground truth while the prediction is still on the device.
+
+`volume_ssim` is the structural half of that comparison: the windowed structural similarity (SSIM) of two uint8 volumes
+out of core, in integers (tem_u8_ssim), as per-section sums that `ssim_from_sums` turns into the index, and optionally
+as a uint8 map of where the two volumes differ in structure.
 """
 import contextlib
 import json
@@ -725,7 +729,8 @@ class _OutputStream:
 class _SlabPass:
     """One out-of-core pass over a box of one or more uint8 array-likes [z, y, x] (one image [y, x]: a one-section
     stack), slab by slab through the input side of predict_volume's pipeline.  Making it is host work and comes ahead
-    of any GPU work: the dtype check (ValueError) and this rank's slabs of boxes[0] (hist_chunks); the slab of
+    of any GPU work: the dtype check (ValueError) and this rank's slabs of boxes[0] (hist_chunks, or the list `slabs`
+    of boxes inside boxes[0] where the caller cuts them itself: overlapping read slabs, ssim_chunks); the slab of
     volumes[i] is the same box shifted from boxes[0] to boxes[i].  `st` holds the read seconds `read_s` and the slab
     count `chunks`.
 
@@ -736,10 +741,10 @@ class _SlabPass:
     `p.release_on` where the caller has set an event for this slab, else on one recorded there -- and the slabs k + 2
     are prefetched."""
 
-    def __init__(self, volumes, boxes, chunk_bytes, rank, world_size, device):
+    def __init__(self, volumes, boxes, chunk_bytes, rank, world_size, device, slabs=None):
         for v in volumes:
             _check_u8(v)
-        self.slabs = hist_chunks(boxes[0], chunk_bytes, rank, world_size)
+        self.slabs = hist_chunks(boxes[0], chunk_bytes, rank, world_size) if slabs is None else list(slabs)
         self.dims = [tuple(hi - lo for lo, hi in s) for s in self.slabs]
         self.nbytes = [int(np.prod(d)) for d in self.dims]
         self.volumes = [_OneSection(v) if len(v.shape) == 2 else v for v in volumes]
@@ -907,6 +912,172 @@ def regression_lut(J):
         w = min(seen, key=lambda s: (abs(s - u), s))
         t[u] = (2 * s_u[w] + n_u[w]) // (2 * n_u[w])
     return t
+
+
+SSIM_Q = 1 << 30                 # tem_u8_ssim's fixed point: q = rint(x * 2^30)
+
+
+class SsimSums(NamedTuple):
+    """volume_ssim's result: `sums` np.int64[Zw, 3] with the sums of q_s, q_l, q_cs (SSIM, luminance, contrast-structure,
+    each rint(x * 2^30)) over the windows whose first section is the row's, `windows` the number of windows per
+    window-section (Yw * Xw), `win` the window (wz, wy, wx)."""
+    sums: np.ndarray
+    windows: int
+    win: tuple
+
+
+def _ssim_window(win, flat):
+    """(wz, wy, wx) of the in-plane edge `win` (odd, 3...11); ValueError otherwise."""
+    import operator
+    try:
+        if isinstance(win, (bool, np.bool_)):
+            raise TypeError
+        w = operator.index(win)
+    except TypeError:
+        raise ValueError(f"win must be an odd integer in 3...11, got {win!r}")
+    if w < 3 or w > 11 or w % 2 == 0:
+        raise ValueError(f"win must be an odd integer in 3...11, got {win!r}")
+    return (1 if flat else w), w, w
+
+
+def ssim_chunks(box, win=7, flat=False, chunk_bytes=None, rank=0, world_size=1):
+    """Cut the windows of the (z, y, x) (lo, hi) voxel `box` into slabs for volume_ssim.  Windows are wz x win x win
+    voxels (wz = 1 if flat else win), lie wholly inside the box and are named by their first voxel: the window box is
+    the voxel box less (wz - 1, win - 1, win - 1) at the high end.  Returns this rank's list of (window_slab, read_slab),
+    both (z, y, x) (lo, hi) boxes in the box's coordinates: the window slabs are disjoint and their union is the window
+    box; a read slab is the voxels its windows cover, the window slab extended by (wz - 1, win - 1) at the high end of
+    z and y, over the box's full x extent -- x is never cut -- so neighbouring read slabs overlap by the window.  A
+    read slab holds at most `chunk_bytes` bytes (HIST_CHUNK_BYTES when None): runs of whole window-sections, or, where
+    wz sections of the box are larger than the budget, runs of whole rows of windows of one window-section (one row at
+    the least: where wz x win x nx bytes exceed the budget, every slab is one row of windows).  Slabs are in (z, y)
+    order and go round-robin to the ranks.  A box in which no window fits gives [].  Pure host function; ValueError as
+    hist_chunks, and for a `win` that is not odd or outside 3...11."""
+    wz, wy, wx = _ssim_window(win, flat)
+    budget = HIST_CHUNK_BYTES if chunk_bytes is None else int(chunk_bytes)
+    if budget < 1:
+        raise ValueError(f"chunk_bytes must be positive, got {chunk_bytes}")
+    if not 0 <= rank < world_size:
+        raise ValueError(f"rank {rank} is outside [0, {world_size})")
+    (z0, z1), (y0, y1), (x0, x1) = box
+    ny, nx = y1 - y0, x1 - x0
+    zw1, yw1, xw1 = z1 - wz + 1, y1 - wy + 1, x1 - wx + 1                # the window box's high ends
+    if zw1 <= z0 or yw1 <= y0 or xw1 <= x0:
+        return []
+    if wz * ny * nx <= budget:
+        kz = budget // (ny * nx) - (wz - 1)                              # window-sections per slab
+        wins = [((z, min(z + kz, zw1)), (y0, yw1)) for z in range(z0, zw1, kz)]
+    else:
+        ky = max(1, budget // (wz * nx) - (wy - 1))                      # rows of windows per slab
+        wins = [((z, z + 1), (y, min(y + ky, yw1))) for z in range(z0, zw1) for y in range(y0, yw1, ky)]
+    slabs = [((wz_, wy_, (x0, xw1)), ((wz_[0], wz_[1] + wz - 1), (wy_[0], wy_[1] + wy - 1), (x0, x1))) for wz_, wy_ in wins]
+    return slabs[rank::world_size]
+
+
+def volume_ssim(a, b, start=None, size=None, b_start=None, win=7, flat=False, map_out=None, chunk_bytes=None, rank=0,
+                world_size=1, device=None, stats=None):
+    """Windowed structural similarity (SSIM) of two uint8 array-likes `a` and `b` indexed [z, y, x] (ndarray, np.memmap,
+    h5py / zarr dataset; they may differ in shape), or of two images [y, x] with 2-element arguments, as an SsimSums;
+    ssim_from_sums turns it into the index.  It is the structural companion of volume_joint_histogram, whose measures
+    are blind to where a voxel is.  The ROI is volume_joint_histogram's: [start, start + size) of `a` ((x, y, z) order;
+    default: all of `a`) against [b_start, b_start + size) of `b` (b_start=None: the same start), both inside their
+    volumes.
+
+    Windows are uniform boxes of wz x win x win voxels, `win` odd in 3...11; wz = win, or 1 with flat=True: section by
+    section, for 2-D models, anisotropic stacks and images (always flat).  Only windows wholly inside the ROI count --
+    the set skimage's structural_similarity averages after cropping its border -- so the window box is
+    (Zw, Yw, Xw) = (nz - wz + 1, ny - win + 1, nx - win + 1).  Per window the value is Wang's SSIM with skimage's
+    defaults (uniform window, sample covariance, data range 255, K1 = 0.01, K2 = 0.03) from integer window sums, as two
+    correctly rounded float64 divisions, and enters as q = rint(x * 2^30) (include/tem_hip.h has the formula): the
+    sums are integers and do not depend on slab cuts, launch geometry or ranks.
+
+    Out of core as volume_joint_histogram, over read slabs that overlap by the window (ssim_chunks on a's box; b's slab
+    is the same box shifted): one host thread reads both slabs of a pair into double-buffered pinned memory (two
+    _InputStreams) -> H2D on copy streams -> tem_u8_ssim on the compute stream, adding into ONE device accumulator that
+    is read back once.  `map_out`, a writable uint8 array-like of the window box's shape ([Yw, Xw] for images), receives
+    the SSIM map: (255 max(q_s, 0) + 2^29) >> 30 per window, at the window's first voxel; each slab's map goes through
+    an _OutputStream with device buffers of its own into the slab's box of map_out, on the reader's thread in
+    clahe_volume's order, write(k) then read(k + 2).  Ranks (rank / world_size) take slabs round-robin: each returns the
+    sums of its own slabs, the ranks' `sums` add to the whole, no collective is used, and the ranks write disjoint
+    boxes of a shared map_out.  `stats` receives `read_s`, `chunks`, and `write_s` when a map is written.
+
+    There is no ssim= keyword on predict_cube / predict_volume: a streamed chunk does not hold its neighbours'
+    prediction, which the windows across its faces need.  Call volume_ssim(gt, out) on the finished output.
+
+    ValueError, before any GPU work: a side that is not uint8, an ROI outside either volume, `win` even or outside
+    3...11, an ROI in which no window fits, a map_out of another shape or dtype."""
+    one = len(a.shape) == 2
+    wz, wy, wx = _ssim_window(win, flat or one)
+    box = hist_box(a.shape, start, size)
+    nd = len(a.shape)
+    extent = tuple(hi - lo for lo, hi in reversed(box))[:nd]             # (x, y[, z])
+    box_b = hist_box(b.shape, tuple(lo for lo, _ in reversed(box))[:nd] if b_start is None else b_start, extent)
+    wshape = tuple(hi - lo - w + 1 for (lo, hi), w in zip(box, (wz, wy, wx)))
+    if min(wshape) < 1:
+        raise ValueError(f"no {wz} x {wy} x {wx} window fits the ROI of {tuple(hi - lo for lo, hi in box)} voxels (z, y, x)")
+    chunks = ssim_chunks(box, wy, wz == 1, chunk_bytes, rank, world_size)
+    p = _SlabPass([a, b], [box, box_b], chunk_bytes, rank, world_size, device, slabs=[read for _, read in chunks])
+    if map_out is not None:
+        want = wshape[1:] if one else wshape
+        if tuple(map_out.shape) != want or getattr(map_out, "dtype", None) != np.uint8:
+            raise ValueError(f"map_out must be uint8 of the window box's shape {want}, got "
+                             f"{getattr(map_out, 'dtype', None)} {tuple(map_out.shape)}")
+    lib = H.require_gpu()
+    wslabs = [w for w, _ in chunks]
+    wdims = [tuple(hi - lo for lo, hi in w) for w in wslabs]
+    map_vol = _OneSection(map_out) if one and map_out is not None else map_out
+    (oz, _), (oy, _), _ = box
+
+    def write_from(k, flat_bytes):      # host thread: the slab's box of `map_out`
+        (z0, z1), (y0, y1), _ = wslabs[k]
+        map_vol[z0 - oz:z1 - oz, y0 - oy:y1 - oy, 0:wshape[2]] = flat_bytes.reshape(wdims[k])
+
+    with p.streaming():
+        acc = torch.zeros((wshape[0], 3), dtype=torch.int64, device=p.dev)
+        with contextlib.ExitStack() as stack:
+            outp = None
+            if map_out is not None:
+                p.st["write_s"] = 0.0
+                outp = stack.enter_context(_OutputStream([int(np.prod(d)) for d in wdims], write_from, p.dev, p.pool, p.st,
+                                                         own_buffers=True))  # the reader's thread: write(k), read(k + 2)
+            for k, slab, d, (pa, pb) in p:
+                mp = outp.device(k).data_ptr() if outp is not None else None
+                _lib.check(lib.tem_u8_ssim(pa.data_ptr(), *d, 0, 0, 0, pb.data_ptr(), *d, 0, 0, 0, *d, wy, int(wz == 1),
+                                           acc.data_ptr() + 24 * (wslabs[k][0][0] - oz), mp, p.compute.cuda_stream),
+                           "tem_u8_ssim")
+                if outp is not None:
+                    p.release_on = p.compute.record_event()              # behind the kernel: the inputs are free too
+                    outp.put(k, p.release_on)
+        sums = acc.cpu().numpy()                                         # the one read-back
+    if stats is not None:
+        stats.update(p.st)
+    return SsimSums(sums, wshape[1] * wshape[2], (wz, wy, wx))
+
+
+def ssim_from_sums(s):
+    """What an SsimSums (volume_ssim's, or one whose `sums` are the element-wise sum of several ranks') says, as a dict.
+    The totals are exact Python integers; every float is derived from them once, in float64:
+        n                                   windows counted
+        ssim, luminance, contrast_structure the mean over all windows of s, l and cs: total / (n 2^30)
+        per_section                         np.float64[Zw, 3]: the same three per window-section, the profile along z
+    ValueError for `sums` of another shape or dtype kind, a `windows` below 1, and a row whose magnitude exceeds
+    windows * 2^30 (no window's s, l or cs lies outside [-1, 1])."""
+    try:
+        sums, windows, win = s
+        sums = np.asarray(sums)
+    except (TypeError, ValueError):
+        raise ValueError(f"ssim_from_sums takes an SsimSums (sums, windows, win), got {type(s).__name__}")
+    if sums.ndim != 2 or sums.shape[1] != 3 or sums.shape[0] < 1 or sums.dtype.kind not in "iu":
+        raise ValueError(f"ssim_from_sums: sums must be integers of shape [Zw, 3], got {sums.dtype} {sums.shape}")
+    windows = int(windows)
+    if windows < 1:
+        raise ValueError(f"ssim_from_sums: windows must be positive, got {windows}")
+    rows = [[int(v) for v in row] for row in sums]
+    if any(abs(v) > windows * SSIM_Q for row in rows for v in row):
+        raise ValueError(f"ssim_from_sums: a sum exceeds windows * 2^30 = {windows * SSIM_Q} in magnitude")
+    n = windows * len(rows)
+    total = [sum(row[i] for row in rows) / (n * SSIM_Q) for i in range(3)]
+    per = np.array([[v / (windows * SSIM_Q) for v in row] for row in rows], np.float64)
+    return {"n": n, "ssim": total[0], "luminance": total[1], "contrast_structure": total[2], "per_section": per}
 
 
 def _check_compare(compare, vol_shape, stats):
