@@ -338,6 +338,34 @@ int tem_f32_tiles2d_unstd_to_u8(const float *y, int32_t ntile, int32_t yedge, in
                                 uint8_t *out, int32_t OZ, int32_t OY, int32_t OX, float mean, float std,
                                 tem_stream_t stream);
 
+/* Spread of the self-ensemble: how much the members disagree at a voxel, as a uint8 map beside the mean.
+ * Accumulate: the arguments of tem_f32_tiles*_sym_accum plus three more arrays of y's extents.  acc is updated exactly
+ * as by that entry point (same `first` and `divisor`); in the same launch, at the same element j(q), with yv = y[t][q]:
+ *   first:      ref = yv, s1 = 0, s2 = 0                      (written without being read)
+ *   otherwise:  d = yv - ref;  s1 = s1 + d;  p = d * d;  s2 = s2 + p
+ * the moments about the first member, every operation one rounded fp32 operation (no fused multiply-add).  y is read
+ * once.  TEM_EINVAL, without a launch: what tem_f32_tiles*_sym_accum refuses, a null pointer, and any two of y, acc,
+ * ref, s1, s2 that overlap.
+ * Finish and scatter: from the moments of `count` members, k = (float)count,
+ *   t = (s1 * s1) / k;  v = max(s2 - t, 0) / k;  sd = sqrt(v)   (population standard deviation, correctly rounded)
+ *   out = (uint8) rint(min(((sd * |std_y|) * 127.5f) * gain, 255.0f))      (saturates)
+ * again one rounded fp32 operation each: the members' standard deviation in grey levels of the output, times `gain`.
+ * It is written where tem_f32_tiles*_unstd_to_u8 writes the prediction: each tile's interior, `tpad` stripped, at
+ * index_dev[3t..3t+2] of out[OZ][OY][OX], and nowhere else.
+ * TEM_EINVAL, without a launch: what those scatters refuse, count < 1, a gain that is not finite or not above 0. */
+int tem_f32_tiles_sym_accum_spread(const float *y, int32_t ntile, int32_t yedge, int32_t p0, int32_t p1, int32_t p2,
+                                   int32_t f0, int32_t f1, int32_t f2, float *acc, int32_t first, int32_t divisor,
+                                   float *ref, float *s1, float *s2, tem_stream_t stream);
+int tem_f32_tiles2d_sym_accum_spread(const float *y, int32_t ntile, int32_t yedge, int32_t p0, int32_t p1, int32_t p2,
+                                     int32_t f0, int32_t f1, int32_t f2, float *acc, int32_t first, int32_t divisor,
+                                     float *ref, float *s1, float *s2, tem_stream_t stream);
+int tem_f32_tiles_spread_to_u8(const float *s1, const float *s2, int32_t ntile, int32_t yedge, int32_t tpad,
+                               const int32_t *index_dev, uint8_t *out, int32_t OZ, int32_t OY, int32_t OX, int32_t count,
+                               float std_y, float gain, tem_stream_t stream);
+int tem_f32_tiles2d_spread_to_u8(const float *s1, const float *s2, int32_t ntile, int32_t yedge, int32_t tpad,
+                                 const int32_t *index_dev, uint8_t *out, int32_t OZ, int32_t OY, int32_t OX,
+                                 int32_t count, float std_y, float gain, tem_stream_t stream);
+
 /* One level of a mip pyramid of a uint8 block (tiled inference, after the scatter).  src[D][H][W] is dense; only its
  * box [0, vD) x [0, vH) x [0, vW) is valid (0 <= v <= dim: a block of whole tiles holds predictions past the ROI).
  * dst is dense [ceil(D / fz)][ceil(H / 2)][ceil(W / 2)]: y and x pool by 2, z by fz = 2 (3-D models) or 1 (2-D models:

@@ -137,6 +137,14 @@ _SIGS = {
     "tem_f32_tiles2d_sym_accum": [C.c_void_p] + [C.c_int32] * 8 + [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p],
     "tem_f32_tiles2d_unstd_to_u8": [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                                     C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p],
+    "tem_f32_tiles_sym_accum_spread": [C.c_void_p] + [C.c_int32] * 8 + [C.c_void_p, C.c_int32, C.c_int32] +
+                                      [C.c_void_p] * 4,
+    "tem_f32_tiles2d_sym_accum_spread": [C.c_void_p] + [C.c_int32] * 8 + [C.c_void_p, C.c_int32, C.c_int32] +
+                                        [C.c_void_p] * 4,
+    "tem_f32_tiles_spread_to_u8": [C.c_void_p, C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p, C.c_void_p] +
+                                  [C.c_int32] * 4 + [C.c_float, C.c_float, C.c_void_p],
+    "tem_f32_tiles2d_spread_to_u8": [C.c_void_p, C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p, C.c_void_p] +
+                                    [C.c_int32] * 4 + [C.c_float, C.c_float, C.c_void_p],
     "tem_u8_pool2": [C.c_void_p] + [C.c_int32] * 7 + [C.c_void_p, C.c_void_p],
     "tem_u8_hist": [C.c_void_p] + [C.c_int32] * 9 + [C.c_void_p, C.c_int32, C.c_void_p],
     "tem_u8_hist2": ([C.c_void_p] + [C.c_int32] * 6) * 2 + [C.c_int32] * 3 + [C.c_void_p, C.c_void_p],

@@ -304,18 +304,31 @@ __global__ __launch_bounds__(256) void u8_tiles_to_f32_std_bc_k(const uint8_t *b
   }
 }
 
+// The byte a scatter writes for element i of the dense tile batch: the un-standardised prediction, or the spread of the
+// self-ensemble finished from its moments (count members; tile_math.h).
+struct UnstdVal {
+  const float *y; float mean, std;
+  __device__ __forceinline__ uint8_t operator()(int64_t i) const { return unstd_u8(y[i], mean, std); }
+};
+
+struct SpreadVal {
+  const float *s1, *s2; float count, absstd, gain;
+  __device__ __forceinline__ uint8_t operator()(int64_t i) const { return spread_u8(s1[i], s2[i], count, absstd, gain); }
+};
+
 // scatter: the interior (tpad stripped, utils.py:113-116) of tile t of y -> uint8 block of the output volume at index[t]
-__global__ __launch_bounds__(256) void f32_tiles_unstd_to_u8_k(const float *y, int yedge, int tpad, const int32_t *index,
-                                                               uint8_t *out, int OY, int OX, float mean, float std) {
+template <class Val>
+__global__ __launch_bounds__(256) void f32_tiles_to_u8_k(Val val, int yedge, int tpad, const int32_t *index,
+                                                         uint8_t *out, int OY, int OX) {
   const int t = blockIdx.y, od = yedge - 2 * tpad;
   const int iz = index[3 * t], iy = index[3 * t + 1], ix = index[3 * t + 2];
-  const float *src = y + (int64_t)t * yedge * yedge * yedge;
+  const int64_t src = (int64_t)t * yedge * yedge * yedge;
   const int64_t per_tile = (int64_t)od * od * od;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < per_tile; i += (int64_t)gridDim.x * 256) {
     const int x = (int)(i % od); const int64_t r = i / od;
     const int yy = (int)(r % od), z = (int)(r / od);
     out[((int64_t)(iz + z) * OY + (iy + yy)) * OX + (ix + x)] =
-        unstd_u8(src[((int64_t)(z + tpad) * yedge + (yy + tpad)) * yedge + (x + tpad)], mean, std);
+        val(src + ((int64_t)(z + tpad) * yedge + (yy + tpad)) * yedge + (x + tpad));
   }
 }
 
@@ -404,9 +417,9 @@ __global__ __launch_bounds__(256) void u8_tiles2d_to_f32_std_bc_k(const uint8_t 
 // them to out[iz][iy + row][ix + col ...]: one packed dword when the 4 land in the row on a 4-byte boundary, bytes
 // otherwise (the tail of a row whose interior is not a multiple of 4, unaligned offsets).  Pixels outside `out` are
 // dropped.
-__global__ __launch_bounds__(256) void f32_tiles2d_unstd_to_u8_k(const float *y, int yedge, int tpad,
-                                                                 const int32_t *index, uint8_t *out, int OZ, int OY,
-                                                                 int OX, float mean, float std, int64_t ngroup) {
+template <class Val>
+__global__ __launch_bounds__(256) void f32_tiles2d_to_u8_k(Val val, int yedge, int tpad, const int32_t *index,
+                                                           uint8_t *out, int OZ, int OY, int OX, int64_t ngroup) {
   const int64_t g = (int64_t)xcd_contiguous_block(blockIdx.x, gridDim.x) * 256 + threadIdx.x;
   if (g >= ngroup) return;
   const int od = yedge - 2 * tpad, gpr = (od + 3) >> 2, per_tile = od * gpr;
@@ -414,11 +427,11 @@ __global__ __launch_bounds__(256) void f32_tiles2d_unstd_to_u8_k(const float *y,
   const int row = r / gpr, col = (r - row * gpr) * 4;
   const int iz = index[3 * t], oy = index[3 * t + 1] + row, ox = index[3 * t + 2] + col;
   if ((unsigned)iz >= (unsigned)OZ || (unsigned)oy >= (unsigned)OY) return;
-  const float *src = y + (int64_t)t * yedge * yedge + (int64_t)(row + tpad) * yedge + (col + tpad);
+  const int64_t src = (int64_t)t * yedge * yedge + (int64_t)(row + tpad) * yedge + (col + tpad);
   const int n = min(4, od - col);
   uint8_t q[4];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) q[j] = j < n ? unstd_u8(src[j], mean, std) : 0;
+  for (int j = 0; j < 4; ++j) q[j] = j < n ? val(src + j) : 0;
   uint8_t *dst = out + ((int64_t)iz * OY + oy) * OX;
   if (n == 4 && ox >= 0 && ox + 4 <= OX && (((uintptr_t)(dst + ox)) & 3) == 0) {
     *reinterpret_cast<uint32_t *>(dst + ox) = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) |
@@ -528,20 +541,61 @@ extern "C" int tem_u8_tiles_to_f32_std(const uint8_t *vol, int32_t Z, int32_t Y,
   return TEM_OK;
 }
 
-extern "C" int tem_f32_tiles_unstd_to_u8(const float *y, int32_t ntile, int32_t yedge, int32_t tpad,
-                                         const int32_t *index_dev, uint8_t *out, int32_t OZ, int32_t OY, int32_t OX,
-                                         float mean, float std, tem_stream_t stream) {
-  TEM_CLEAR_ERR();
-  if (!y || !index_dev || !out || ntile < 0 || yedge < 1 || tpad < 0 || 2 * tpad >= yedge || OZ < 1 || OY < 1 || OX < 1)
+namespace {
+// the launch of the 3-D scatters; `ok`: the source pointers and the value's own arguments
+template <class Val>
+int scatter_tiles(Val val, bool ok, int32_t ntile, int32_t yedge, int32_t tpad, const int32_t *index_dev, uint8_t *out,
+                  int32_t OZ, int32_t OY, int32_t OX, hipStream_t st) {
+  if (!ok || !index_dev || !out || ntile < 0 || yedge < 1 || tpad < 0 || 2 * tpad >= yedge || OZ < 1 || OY < 1 || OX < 1)
     return TEM_EINVAL;
   if (ntile == 0) return TEM_OK;
   if (ntile > 65535) return TEM_EUNSUPPORTED;
   const int od = yedge - 2 * tpad;
   unsigned gx = grid_for((int64_t)od * od * od); if (gx > 512) gx = 512;
-  hipLaunchKernelGGL(f32_tiles_unstd_to_u8_k, dim3(gx, (unsigned)ntile), dim3(256), 0, (hipStream_t)stream, y, yedge, tpad,
-                     index_dev, out, OY, OX, mean, std);
+  hipLaunchKernelGGL(f32_tiles_to_u8_k<Val>, dim3(gx, (unsigned)ntile), dim3(256), 0, st, val, yedge, tpad, index_dev, out,
+                     OY, OX);
   TEM_CHECK_LAUNCH();
   return TEM_OK;
+}
+
+// ... and of the 2-D ones
+template <class Val>
+int scatter_tiles2d(Val val, bool ok, int32_t ntile, int32_t yedge, int32_t tpad, const int32_t *index_dev, uint8_t *out,
+                    int32_t OZ, int32_t OY, int32_t OX, hipStream_t st) {
+  if (!ok || !index_dev || !out || ntile < 0 || yedge < 1 || yedge > 46340 || tpad < 0 || 2 * tpad >= yedge || OZ < 1 ||
+      OY < 1 || OX < 1)
+    return TEM_EINVAL;
+  if (ntile == 0) return TEM_OK;
+  const int od = yedge - 2 * tpad;
+  const int64_t ngroup = (int64_t)ntile * od * ((od + 3) / 4);
+  const int64_t nblk = (ngroup + 255) / 256;
+  if (nblk > 0x7fffffff) return TEM_EUNSUPPORTED;
+  hipLaunchKernelGGL(f32_tiles2d_to_u8_k<Val>, dim3((unsigned)nblk), dim3(256), 0, st, val, yedge, tpad, index_dev, out,
+                     OZ, OY, OX, ngroup);
+  TEM_CHECK_LAUNCH();
+  return TEM_OK;
+}
+
+// the moments, a member count >= 1 and a finite gain > 0
+inline bool spread_args_ok(const float *s1, const float *s2, int32_t count, float gain) {
+  return s1 && s2 && count >= 1 && gain > 0.f && std::isfinite(gain);
+}
+}  // namespace
+
+extern "C" int tem_f32_tiles_unstd_to_u8(const float *y, int32_t ntile, int32_t yedge, int32_t tpad,
+                                         const int32_t *index_dev, uint8_t *out, int32_t OZ, int32_t OY, int32_t OX,
+                                         float mean, float std, tem_stream_t stream) {
+  TEM_CLEAR_ERR();
+  return scatter_tiles(UnstdVal{y, mean, std}, y != nullptr, ntile, yedge, tpad, index_dev, out, OZ, OY, OX,
+                       (hipStream_t)stream);
+}
+
+extern "C" int tem_f32_tiles_spread_to_u8(const float *s1, const float *s2, int32_t ntile, int32_t yedge, int32_t tpad,
+                                          const int32_t *index_dev, uint8_t *out, int32_t OZ, int32_t OY, int32_t OX,
+                                          int32_t count, float std_y, float gain, tem_stream_t stream) {
+  TEM_CLEAR_ERR();
+  return scatter_tiles(SpreadVal{s1, s2, (float)count, fabsf(std_y), gain}, spread_args_ok(s1, s2, count, gain), ntile,
+                       yedge, tpad, index_dev, out, OZ, OY, OX, (hipStream_t)stream);
 }
 
 extern "C" int tem_u8_tiles2d_to_f32_std(const uint8_t *vol, int32_t Z, int32_t Y, int32_t X, const int32_t *origins_dev,
@@ -639,18 +693,16 @@ extern "C" int tem_f32_tiles2d_unstd_to_u8(const float *y, int32_t ntile, int32_
                                            const int32_t *index_dev, uint8_t *out, int32_t OZ, int32_t OY, int32_t OX,
                                            float mean, float std, tem_stream_t stream) {
   TEM_CLEAR_ERR();
-  if (!y || !index_dev || !out || ntile < 0 || yedge < 1 || yedge > 46340 || tpad < 0 || 2 * tpad >= yedge || OZ < 1 ||
-      OY < 1 || OX < 1)
-    return TEM_EINVAL;
-  if (ntile == 0) return TEM_OK;
-  const int od = yedge - 2 * tpad;
-  const int64_t ngroup = (int64_t)ntile * od * ((od + 3) / 4);
-  const int64_t nblk = (ngroup + 255) / 256;
-  if (nblk > 0x7fffffff) return TEM_EUNSUPPORTED;
-  hipLaunchKernelGGL(f32_tiles2d_unstd_to_u8_k, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, y, yedge, tpad,
-                     index_dev, out, OZ, OY, OX, mean, std, ngroup);
-  TEM_CHECK_LAUNCH();
-  return TEM_OK;
+  return scatter_tiles2d(UnstdVal{y, mean, std}, y != nullptr, ntile, yedge, tpad, index_dev, out, OZ, OY, OX,
+                         (hipStream_t)stream);
+}
+
+extern "C" int tem_f32_tiles2d_spread_to_u8(const float *s1, const float *s2, int32_t ntile, int32_t yedge, int32_t tpad,
+                                            const int32_t *index_dev, uint8_t *out, int32_t OZ, int32_t OY, int32_t OX,
+                                            int32_t count, float std_y, float gain, tem_stream_t stream) {
+  TEM_CLEAR_ERR();
+  return scatter_tiles2d(SpreadVal{s1, s2, (float)count, fabsf(std_y), gain}, spread_args_ok(s1, s2, count, gain), ntile,
+                         yedge, tpad, index_dev, out, OZ, OY, OX, (hipStream_t)stream);
 }
 
 extern "C" int tem_adam_keras(float *theta, const float *grad, float *m, float *v, int64_t n, float lr, float beta1,

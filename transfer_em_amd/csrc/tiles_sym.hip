@@ -1,5 +1,6 @@
 // tiles_sym.hip -- tiled inference under a symmetry of the cube (square): the gather hands the generator T(tile), the
-// accumulate folds the generator's output back with the inverse of T into an fp32 mean.
+// accumulate folds the generator's output back with the inverse of T into an fp32 mean -- and, in its `_spread` form, into
+// the moments of the members' spread (tile_math.h) at the same voxel, in the same launch.
 //   T(v) = flip(transpose(v, perm), axes a with flips[a])            (tem_augment_f32's convention)
 //   T(v)[q] = v[j(q)],   j[perm[a]] = flips[a] ? n - 1 - q[a] : q[a]
 // A tile has extents (D, E, E): D == E (3-D) or D == 1 (2-D: perm[0] == 0, flips[0] == 0, so j[0] == q[0] == 0).
@@ -37,6 +38,27 @@ __device__ __forceinline__ float accum_op(float acc, float y, int first, int div
   return v;
 }
 
+// What the accumulate kernels do with value y of a member at the folded-back element i: the mean alone, or the mean
+// and the spread's moments about the first member (`first` writes ref = y, s1 = s2 = 0 without reading them).
+struct MeanOp {
+  float *acc; int first, divisor;
+  __device__ __forceinline__ void operator()(int64_t i, float y) const {
+    acc[i] = accum_op(first ? 0.f : acc[i], y, first, divisor);
+  }
+};
+
+struct SpreadOp {
+  MeanOp mean; float *ref, *s1, *s2;
+  __device__ __forceinline__ void operator()(int64_t i, float y) const {
+    float r = y, a = 0.f, b = 0.f;
+    if (!mean.first) { r = ref[i]; a = s1[i]; b = s2[i]; }           // every load ahead of the first store
+    mean(i, y);
+    if (mean.first) ref[i] = y;
+    else spread_update(y, r, a, b);
+    s1[i] = a; s2[i] = b;
+  }
+};
+
 // ---------------------------------------------------------------- perm keeps x innermost: one wave per row
 template <int MODE>
 __global__ __launch_bounds__(256) void u8_tiles_sym_row_k(TileSrc s, const int32_t *origins, int D, int E, SymDev m,
@@ -63,8 +85,9 @@ __global__ __launch_bounds__(256) void u8_tiles_sym_row_k(TileSrc s, const int32
   }
 }
 
-__global__ __launch_bounds__(256) void f32_tiles_sym_accum_row_k(const float *y, int D, int E, SymDev m, float *acc,
-                                                                 int first, int divisor, int64_t rows) {
+template <class Op>
+__global__ __launch_bounds__(256) void f32_tiles_sym_accum_row_k(const float *y, int D, int E, SymDev m, Op op,
+                                                                 int64_t rows) {
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
   const int rpt = D * E;
   for (int64_t r = (int64_t)blockIdx.x * 4 + wave; r < rows; r += (int64_t)gridDim.x * 4) {
@@ -74,11 +97,8 @@ __global__ __launch_bounds__(256) void f32_tiles_sym_accum_row_k(const float *y,
     j0 = m.g0 ? D - 1 - j0 : j0;
     j1 = m.g1 ? E - 1 - j1 : j1;
     const float *src = y + r * E;
-    float *dst = acc + (t * rpt + (int64_t)j0 * E + j1) * E;
-    for (int x = lane; x < E; x += 64) {
-      const int jx = m.g2 ? E - 1 - x : x;
-      dst[jx] = accum_op(first ? 0.f : dst[jx], src[x], first, divisor);
-    }
+    const int64_t dst = (t * rpt + (int64_t)j0 * E + j1) * E;
+    for (int x = lane; x < E; x += 64) op(dst + (m.g2 ? E - 1 - x : x), src[x]);
   }
 }
 
@@ -144,8 +164,9 @@ __global__ __launch_bounds__(256) void u8_tiles_sym_tr_k(TileSrc s, const int32_
   }
 }
 
-__global__ __launch_bounds__(256) void f32_tiles_sym_accum_tr_k(const float *y, int D, int E, SymDev m, float *acc,
-                                                                int first, int divisor, int nu, int nv) {
+template <class Op>
+__global__ __launch_bounds__(256) void f32_tiles_sym_accum_tr_k(const float *y, int D, int E, SymDev m, Op op, int nu,
+                                                                int nv) {
   __shared__ float lds[64][65];
   const TrBlock k = tr_block(D, E, m, nu, nv);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -163,15 +184,14 @@ __global__ __launch_bounds__(256) void f32_tiles_sym_accum_tr_k(const float *y, 
     }
   }
   __syncthreads();
-  {                                                                    // drain: lanes along u = x of acc
+  {                                                                    // drain: lanes along u = x of the destinations
     const int u = k.u0 + lane;
     for (int i = wave; i < 64; i += 4) {
       const int v = k.v0 + i;
       if (u < k.U && v < E) {
         int q0, q1, j0, j1, j2;
         tr_j(m, D, E, u, k.w, v, q0, q1, j0, j1, j2);
-        float *dst = acc + base + ((int64_t)j0 * E + j1) * E + j2;
-        *dst = accum_op(first ? 0.f : *dst, lds[lane][i], first, divisor);
+        op(base + ((int64_t)j0 * E + j1) * E + j2, lds[lane][i]);
       }
     }
   }
@@ -250,24 +270,45 @@ int gather_sym(const TileSrc &s, int32_t mode, const int32_t *origins, int32_t n
   return TEM_OK;
 }
 
+// the launch of either accumulate; `spread` null: the mean alone
 int accum_sym(const float *y, int32_t ntile, int32_t yedge, bool is3d, int32_t p0, int32_t p1, int32_t p2, int32_t f0,
-              int32_t f1, int32_t f2, float *acc, int32_t first, int32_t divisor, hipStream_t st) {
+              int32_t f1, int32_t f2, float *acc, int32_t first, int32_t divisor, float *const *spread, hipStream_t st) {
   SymDev m;
   if (!y || !acc || y == acc || ntile < 0 || yedge < 1 || yedge > 46340 || (first != 0 && first != 1) || divisor < 1 ||
       !sym_ok(p0, p1, p2, f0, f1, f2, is3d, m))
     return TEM_EINVAL;
-  if (ntile == 0) return TEM_OK;
   const int D = is3d ? yedge : 1;
+  const int64_t count = (int64_t)ntile * D * yedge * yedge;           // elements of y and of every destination
+  if (spread) {                                                        // five arrays of `count` floats, pairwise disjoint
+    const uintptr_t a[5] = {(uintptr_t)y, (uintptr_t)acc, (uintptr_t)spread[0], (uintptr_t)spread[1],
+                            (uintptr_t)spread[2]};
+    const uintptr_t bytes = (uintptr_t)count * sizeof(float);
+    for (int i = 0; i < 5; ++i) {
+      if (!a[i]) return TEM_EINVAL;
+      for (int j = 0; j < i; ++j)
+        if (a[i] == a[j] || (a[i] < a[j] + bytes && a[j] < a[i] + bytes)) return TEM_EINVAL;
+    }
+  }
+  if (ntile == 0) return TEM_OK;
+  const MeanOp mean{acc, first, divisor};
   if (m.ip2 == 2) {
     const int64_t rows = (int64_t)ntile * D * yedge;
-    hipLaunchKernelGGL(f32_tiles_sym_accum_row_k, dim3(row_grid(rows)), dim3(256), 0, st, y, D, yedge, m, acc, first,
-                       divisor, rows);
+    const dim3 g(row_grid(rows));
+    if (spread)
+      hipLaunchKernelGGL(f32_tiles_sym_accum_row_k<SpreadOp>, g, dim3(256), 0, st, y, D, yedge, m,
+                         SpreadOp{mean, spread[0], spread[1], spread[2]}, rows);
+    else
+      hipLaunchKernelGGL(f32_tiles_sym_accum_row_k<MeanOp>, g, dim3(256), 0, st, y, D, yedge, m, mean, rows);
   } else {
     int nu, nv;
     const int64_t nblk = tr_grid(ntile, D, yedge, m, nu, nv);
     if (!nblk) return TEM_EUNSUPPORTED;
-    hipLaunchKernelGGL(f32_tiles_sym_accum_tr_k, dim3((unsigned)nblk), dim3(256), 0, st, y, D, yedge, m, acc, first,
-                       divisor, nu, nv);
+    const dim3 g((unsigned)nblk);
+    if (spread)
+      hipLaunchKernelGGL(f32_tiles_sym_accum_tr_k<SpreadOp>, g, dim3(256), 0, st, y, D, yedge, m,
+                         SpreadOp{mean, spread[0], spread[1], spread[2]}, nu, nv);
+    else
+      hipLaunchKernelGGL(f32_tiles_sym_accum_tr_k<MeanOp>, g, dim3(256), 0, st, y, D, yedge, m, mean, nu, nv);
   }
   TEM_CHECK_LAUNCH();
   return TEM_OK;
@@ -299,12 +340,29 @@ extern "C" int tem_f32_tiles_sym_accum(const float *y, int32_t ntile, int32_t ye
                                        int32_t f0, int32_t f1, int32_t f2, float *acc, int32_t first, int32_t divisor,
                                        tem_stream_t stream) {
   TEM_CLEAR_ERR();
-  return accum_sym(y, ntile, yedge, true, p0, p1, p2, f0, f1, f2, acc, first, divisor, (hipStream_t)stream);
+  return accum_sym(y, ntile, yedge, true, p0, p1, p2, f0, f1, f2, acc, first, divisor, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int tem_f32_tiles2d_sym_accum(const float *y, int32_t ntile, int32_t yedge, int32_t p0, int32_t p1, int32_t p2,
                                          int32_t f0, int32_t f1, int32_t f2, float *acc, int32_t first, int32_t divisor,
                                          tem_stream_t stream) {
   TEM_CLEAR_ERR();
-  return accum_sym(y, ntile, yedge, false, p0, p1, p2, f0, f1, f2, acc, first, divisor, (hipStream_t)stream);
+  return accum_sym(y, ntile, yedge, false, p0, p1, p2, f0, f1, f2, acc, first, divisor, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int tem_f32_tiles_sym_accum_spread(const float *y, int32_t ntile, int32_t yedge, int32_t p0, int32_t p1,
+                                              int32_t p2, int32_t f0, int32_t f1, int32_t f2, float *acc, int32_t first,
+                                              int32_t divisor, float *ref, float *s1, float *s2, tem_stream_t stream) {
+  TEM_CLEAR_ERR();
+  float *const spread[3] = {ref, s1, s2};
+  return accum_sym(y, ntile, yedge, true, p0, p1, p2, f0, f1, f2, acc, first, divisor, spread, (hipStream_t)stream);
+}
+
+extern "C" int tem_f32_tiles2d_sym_accum_spread(const float *y, int32_t ntile, int32_t yedge, int32_t p0, int32_t p1,
+                                                int32_t p2, int32_t f0, int32_t f1, int32_t f2, float *acc,
+                                                int32_t first, int32_t divisor, float *ref, float *s1, float *s2,
+                                                tem_stream_t stream) {
+  TEM_CLEAR_ERR();
+  float *const spread[3] = {ref, s1, s2};
+  return accum_sym(y, ntile, yedge, false, p0, p1, p2, f0, f1, f2, acc, first, divisor, spread, (hipStream_t)stream);
 }

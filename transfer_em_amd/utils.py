@@ -309,10 +309,41 @@ def _check_ensemble(ensemble, is3d):
     return [(p, tuple(int(f) for f in fl)) for p, fl in out]
 
 
+def _check_spread(spread, spread_gain, syms, size, ndarray=False):
+    """The `spread` / `spread_gain` keywords of predict_cube (ndarray=True) and predict_volume: None, or the gain as a
+    float where `spread` is a writable uint8 array-like of exactly the result's shape -- (size[2], size[1], size[0]), or
+    (size[1], size[0]) for a single image -- and there is an ensemble (`syms`: _check_ensemble's members) to take the
+    spread of.  The gain is a finite number above 0, as a float32 too."""
+    import numbers
+    if not isinstance(spread_gain, numbers.Real) or isinstance(spread_gain, (bool, np.bool_)):
+        raise ValueError(f"spread_gain must be a finite number above 0, got {spread_gain!r}")
+    gain = float(spread_gain)
+    with np.errstate(over="ignore"):
+        g32 = float(np.float32(gain))                  # what the kernel is given
+    if not (np.isfinite(g32) and g32 > 0):
+        raise ValueError(f"spread_gain must be a finite float32 above 0, got {spread_gain!r}")
+    if spread is None:
+        return None
+    if syms is None:
+        raise ValueError("spread= is the spread of the ensemble's members: it needs ensemble=")
+    if ndarray and not isinstance(spread, np.ndarray):
+        raise ValueError(f"spread must be a numpy array, got {type(spread).__name__}")
+    want = tuple(int(v) for v in reversed(size))
+    if not hasattr(spread, "shape") or tuple(int(v) for v in spread.shape) != want:
+        raise ValueError(f"spread has shape {tuple(getattr(spread, 'shape', ()))}, expected {want}")
+    if getattr(spread, "dtype", None) is None or np.dtype(spread.dtype) != np.uint8:
+        raise ValueError(f"spread must be uint8, got dtype {getattr(spread, 'dtype', None)}")
+    if isinstance(spread, np.ndarray) and not spread.flags.writeable:
+        raise ValueError("spread must be writable")
+    return gain
+
+
 class _TileRunner:
     """The tile loop of predict_cube and predict_volume, made once per call: gather -> generator -> scatter over the
     tiles of a source block, in batches, all enqueued on `stream`.  It owns the choice of the gather entry point and
-    its argument order, the ensemble's fp32 accumulator, the generator plan per batch size and the scatter.
+    its argument order, the ensemble's fp32 accumulator, the generator plan per batch size and the scatter.  With
+    `spread_gain` (the members' spread as a second uint8 block, see predict_cube) it also owns the three fp32 moment
+    buffers, folds every member through the `_spread` form of the accumulate and scatters the finished map.
 
     The gather without an ensemble is the zero-mode entry point under "zeros" and its `_bc` sibling under the mirrored
     modes; with one (`syms`: _check_ensemble's members) it is the `_sym` entry point, which under "zeros" gets mode 0
@@ -320,12 +351,18 @@ class _TileRunner:
     holds the volume's box at `lo` (the resident volume: lo = 0, block = vol_shape)."""
 
     def __init__(self, lib, model, is3d, edge, tpad, outdimsize, boundary, syms, meanstd_x, meanstd_y, vol_shape,
-                 stream):
-        gname, self.sname, self.aname = (
-            ("tem_u8_tiles_to_f32_std", "tem_f32_tiles_unstd_to_u8", "tem_f32_tiles_sym_accum") if is3d else
-            ("tem_u8_tiles2d_to_f32_std", "tem_f32_tiles2d_unstd_to_u8", "tem_f32_tiles2d_sym_accum"))
+                 stream, spread_gain=None):
+        gname, self.sname, self.aname, self.fname = (
+            ("tem_u8_tiles_to_f32_std", "tem_f32_tiles_unstd_to_u8", "tem_f32_tiles_sym_accum",
+             "tem_f32_tiles_spread_to_u8") if is3d else
+            ("tem_u8_tiles2d_to_f32_std", "tem_f32_tiles2d_unstd_to_u8", "tem_f32_tiles2d_sym_accum",
+             "tem_f32_tiles2d_spread_to_u8"))
         self.gname = gname + ("_sym" if syms is not None else "" if boundary == "zeros" else "_bc")
-        self.gather, self.scatter, self.accum = (getattr(lib, n) for n in (self.gname, self.sname, self.aname))
+        self.spread_gain = spread_gain
+        if spread_gain is not None:
+            self.aname += "_spread"
+        self.gather, self.scatter, self.accum, self.finish = (
+            getattr(lib, n) for n in (self.gname, self.sname, self.aname, self.fname))
         self.mode = {"zeros": 0, "reflect": _lib.TEM_BOUNDARY_REFLECT, "edge": _lib.TEM_BOUNDARY_EDGE}[boundary]
         self.model, self.gen = model, getattr(model, "generator_g", None)
         self.shape = ((edge, edge, edge) if is3d else (1, edge, edge)) + (1,)      # (D, H, W, C) of one generator input
@@ -334,6 +371,7 @@ class _TileRunner:
         self.ms_x = (float(meanstd_x[0]), float(meanstd_x[1]))
         self.ms_y = (float(meanstd_y[0]), float(meanstd_y[1]))
         self.plan = self.acc = None             # acc: allocated by the first batch, the largest; smaller use its head
+        self.moments = None                     # ref, s1, s2 of the spread: [3, *acc.shape], allocated with acc
 
     def _input(self, m):
         """(x, run) of a batch of m tiles: the generator's input tensor, and run() -> its output (overwritten by the
@@ -348,7 +386,7 @@ class _TileRunner:
             self.plan = self.gen.plan((m,) + self.shape)                        # static launch plan, buffers reused
         return self.plan.x, lambda: self.plan.run(self.stream)
 
-    def run(self, src, block, lo, origins, offsets, n, nb, dst, dims, last_gather=None):
+    def run(self, src, block, lo, origins, offsets, n, nb, dst, dims, last_gather=None, spread_dst=None):
         """Run the n tiles of the source block at `src` (shape `block`, at `lo` in the volume) into the destination
         block at `dst` (shape `dims` = (OZ, OY, OX)) in batches of nb.  `origins` / `offsets` point to the tiles' int32
         (z, y, x) haloed origins in the source block and interior offsets in the destination block.  last_gather() is
@@ -356,7 +394,9 @@ class _TileRunner:
 
         Under an ensemble a batch runs once per member s in order: the gather cuts T_s(tiles), and T_s^-1 of the
         generator's output is folded into the accumulator -- written by the first member, added to by the others,
-        divided by the member count by the last -- whose mean is scattered once."""
+        divided by the member count by the last -- whose mean is scattered once.  With a spread the same launch also
+        folds the member into the moments, and the map finished from them is scattered into the block at `spread_dst`
+        (shape `dims`) behind the prediction's scatter."""
         members = self.syms or [None]
         for b0 in range(0, n, nb):
             m = min(nb, n - b0)
@@ -375,13 +415,19 @@ class _TileRunner:
                 if sym is not None:
                     if self.acc is None:
                         self.acc = torch.empty_like(y)
+                        if self.spread_gain is not None:
+                            self.moments = torch.empty((3,) + tuple(y.shape), dtype=y.dtype, device=y.device)
                     acc = self.acc[:m]
+                    mom = () if self.moments is None else tuple(b[:m].data_ptr() for b in self.moments)
                     _lib.check(self.accum(y.data_ptr(), m, y.shape[2], *sym[0], *sym[1], acc.data_ptr(), int(i == 0),
-                                          len(members) if last else 1, self.stream), self.aname)
+                                          len(members) if last else 1, *mom, self.stream), self.aname)
                     y = acc
             assert y.shape[2] - 2 * self.tpad == self.outdimsize, (y.shape, self.tpad, self.outdimsize)
             _lib.check(self.scatter(y.data_ptr(), m, y.shape[2], self.tpad, offsets + 12 * b0, dst, *dims, *self.ms_y,
                                     self.stream), self.sname)
+            if self.spread_gain is not None:
+                _lib.check(self.finish(mom[1], mom[2], m, y.shape[2], self.tpad, offsets + 12 * b0, spread_dst, *dims,
+                                       len(members), self.ms_y[1], self.spread_gain, self.stream), self.fname)
 
 
 class _Prepare:
@@ -413,12 +459,14 @@ class _Prepare:
 
 class _Measure:
     """What is counted on a uint8 result while it is on the device, made once per call: the int64[256] histogram
-    (`histogram`) and the int64[256, 256] joint histogram against a ground truth (`joint`), each one device accumulator
-    that add() launches into on `stream` and report() reads back once."""
+    (`histogram`), the int64[256, 256] joint histogram against a ground truth (`joint`) and the int64[256] histogram of
+    the ensemble's spread map (`spread`), each one device accumulator that add() / add_spread() launches into on `stream`
+    and report() reads back once."""
 
-    def __init__(self, lib, histogram, joint, dev, stream):
+    def __init__(self, lib, histogram, joint, dev, stream, spread=False):
         self.lib, self.stream = lib, stream
         self.counts = torch.zeros(256, dtype=torch.int64, device=dev) if histogram else None
+        self.spread = torch.zeros(256, dtype=torch.int64, device=dev) if spread else None
         self.joint = torch.zeros((256, 256), dtype=torch.int64, device=dev) if joint else None
 
     def add(self, ptr, dims, valid, gt=None):
@@ -433,8 +481,16 @@ class _Measure:
             _lib.check(self.lib.tem_u8_hist2(gt_ptr, *n, 0, 0, 0, ptr, *dims, *at, *n, self.joint.data_ptr(),
                                              self.stream), "tem_u8_hist2")
 
+    def add_spread(self, ptr, dims, valid):
+        """Count the leading `valid` extents of the dense spread block of shape `dims` at `ptr` (tem_u8_hist)."""
+        if self.spread is not None and min(valid) > 0:
+            _lib.check(self.lib.tem_u8_hist(ptr, *dims, 0, valid[0], 0, valid[1], 0, valid[2], self.spread.data_ptr(), 0,
+                                            self.stream), "tem_u8_hist")
+
     def report(self, st):
-        """The one read-back of each accumulator, into st["histogram"] / st["joint_histogram"]."""
+        """The one read-back of each accumulator, into st["histogram"] / st["joint_histogram"] / st["spread_histogram"]."""
+        if self.spread is not None:
+            st["spread_histogram"] = self.spread.cpu().numpy()
         if self.counts is not None:
             st["histogram"] = self.counts.cpu().numpy()
         if self.joint is not None:
@@ -445,7 +501,7 @@ class _OneSection:
     """A [y, x] array-like seen as a one-section stack [1, y, x] (basic slicing only, for predict_volume)."""
 
     def __init__(self, a):
-        self.a, self.shape = a, (1,) + tuple(int(v) for v in a.shape)
+        self.a, self.shape, self.dtype = a, (1,) + tuple(int(v) for v in a.shape), getattr(a, "dtype", None)
 
     def _key(self, key):
         z, y, x = key
@@ -1419,7 +1475,7 @@ def clahe_volume(volume, clahe, out=None, start=None, size=None, chunk_bytes=Non
 
 def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=False, outdimsize=None, buffer=None,
                  rank=0, world_size=1, tile_batch=None, boundary="zeros", ensemble=None, mips=None, lut=None,
-                 histogram=False, stats=None, clahe=None, compare=None):
+                 histogram=False, stats=None, clahe=None, compare=None, spread=None, spread_gain=8.0):
     """Predict the subvolume [start, start+size) (x,y,z order as in the reference) of a uint8
     array `volume` indexed [z, y, x].  Voxels outside the array read as 0 (the reference fetches
     them from the store) or, with boundary="reflect" / "edge", the voxel that `fold` names on every axis: the result
@@ -1491,10 +1547,28 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
     the paired intensity map.  It is counted over the ROI voxels that lie inside the volume -- a voxel the ROI reaches
     outside the volume has no ground truth and is not compared, under every `boundary` -- by one tem_u8_hist2 launch on
     the cropped result against gt's ROI-within-the-volume box, uploaded once; after the all-reduce of a multi-rank
-    call.  Anything else raises ValueError before any GPU work."""
+    call.  Anything else raises ValueError before any GPU work.
+
+    spread=None measures nothing and runs the launches above.  spread = S, a writable np.uint8 ndarray of the result's
+    shape -- (size[2], size[1], size[0]), or (size[1], size[0]) for one image -- needs an `ensemble` and receives how
+    much its members disagree at every voxel, the test-time-augmentation uncertainty of the translation where there is
+    no ground truth: the population standard deviation of the members' fp32 outputs (after T_s^-1, before any
+    rounding to uint8) in grey levels of the output, times `spread_gain`, rounded and saturated at 255.  The default
+    gain of 8 resolves 1/8 grey level and saturates from 31.9 grey levels on.  The accumulate that folds a member into
+    the mean folds it, in the same launch, into two fp32 moments about the first member (tem_f32_tiles*_sym_accum_spread;
+    the shift keeps fp32 sufficient) in three more batch-sized buffers, and tem_f32_tiles*_spread_to_u8 finishes them
+    into a second device block behind the prediction's scatter: no further generator run, and every operation is one
+    rounded fp32 operation in a fixed order, so numpy float32 reproduces the map bit for bit (include/tem_hip.h) and it
+    stays within 1 of the float64 np.std form.  The prediction is bit-identical to the same call without `spread`; the
+    return values stay as they are; `mips` pools the prediction only (the map has one level); a one-member ensemble
+    gives an all-zero map.  When `stats` is a dict, stats["spread_histogram"] receives the map's np.int64[256]
+    histogram over the ROI's voxels, counted on the device as `histogram` counts the prediction.  `spread` without
+    `ensemble`, another shape or dtype, a read-only array and a `spread_gain` that is not a finite number above 0 raise
+    ValueError before any GPU work."""
     gen = getattr(model, "generator_g", None)
     is3d = getattr(gen, "is3d", True)
     syms = _check_ensemble(ensemble, is3d)
+    gain = _check_spread(spread, spread_gain, syms, size, ndarray=True)
     lut = _check_lut(lut, np.shape(volume))
     if clahe is not None:
         _check_u8(volume)
@@ -1512,7 +1586,8 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
                            meanstd_y, fetch_input=fetch_input, outdimsize=outdimsize, buffer=buffer, rank=rank,
                            world_size=world_size, tile_batch=tile_batch, boundary=boundary, ensemble=ensemble,
                            mips=mips, lut=lut, histogram=histogram, stats=stats, clahe=clahe,
-                           compare=None if compare is None else np.asarray(compare)[None])
+                           compare=None if compare is None else np.asarray(compare)[None],
+                           spread=None if spread is None else spread[None], spread_gain=spread_gain)
         one = lambda r: [v[0] for v in r] if isinstance(r, list) else r[0]
         return tuple(one(r) for r in res) if fetch_input else one(res)
     outdimsize, buffer, tpad, rois, index = _tile_plan(start, size, outdimsize, buffer, is3d)
@@ -1533,14 +1608,25 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
     nb = _effective_batch(tile_batch, edge, is3d, len(mine) or 1)
     org = torch.tensor([rois[i][::-1] for i in mine], dtype=torch.int32).to(dev)       # this rank's (z, y, x), once
     idx = torch.tensor([index[i][::-1] for i in mine], dtype=torch.int32).to(dev)
+    spread_buffer = None if gain is None else torch.zeros_like(out_buffer)
     runner = _TileRunner(lib, model, is3d, edge, tpad, outdimsize, boundary, syms, meanstd_x, meanstd_y, (Z, Y, X),
-                         stream)
+                         stream, gain)
     runner.run(vol.data_ptr(), (Z, Y, X), (0, 0, 0), org.data_ptr(), idx.data_ptr(), len(mine), nb,
-               out_buffer.data_ptr(), (OZ, OY, OX))
+               out_buffer.data_ptr(), (OZ, OY, OX), spread_dst=None if gain is None else spread_buffer.data_ptr())
     if world_size > 1 and torch.distributed.is_initialized():
         torch.distributed.all_reduce(out_buffer, op=torch.distributed.ReduceOp.MAX)   # disjoint tiles, zeros elsewhere
+        if gain is not None:
+            torch.distributed.all_reduce(spread_buffer, op=torch.distributed.ReduceOp.MAX)
     out = out_buffer[0:size[2], 0:size[1], 0:size[0]].cpu().numpy()
-    measure, gt = _Measure(lib, histogram, compare is not None, dev, stream), None
+    measure, gt = _Measure(lib, histogram, compare is not None, dev, stream,
+                           spread=gain is not None and isinstance(stats, dict)), None
+    if gain is not None:
+        measure.add_spread(spread_buffer.data_ptr(), (OZ, OY, OX), (size[2], size[1], size[0]))
+        crop = spread_buffer[0:size[2], 0:size[1], 0:size[0]]
+        try:
+            torch.from_numpy(spread).copy_(crop)                             # the one download, straight into S
+        except ValueError:                                                   # a view with a negative stride
+            spread[...] = crop.cpu().numpy()
     box = None if compare is None else _inside((0, 0, 0), (size[2], size[1], size[0]), (start[2], start[1], start[0]),
                                                (Z, Y, X))
     if box is not None:                         # the ground truth where the ROI lies inside the volume, uploaded once
@@ -1712,7 +1798,7 @@ def chunk_plan(start, size, outdimsize, buffer, vol_shape, chunk_tiles, rank=0, 
 
 def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, chunk_tiles=None, tile_batch=None,
                    outdimsize=None, buffer=None, rank=0, world_size=1, stats=None, boundary="zeros", ensemble=None,
-                   mips=None, lut=None, histogram=False, clahe=None, compare=None):
+                   mips=None, lut=None, histogram=False, clahe=None, compare=None, spread=None, spread_gain=8.0):
     """Out-of-core predict_cube: the subvolume [start, start+size) (x,y,z order) of a uint8 array-like `volume`
     indexed [z, y, x] (ndarray, np.memmap, h5py / zarr dataset: `.shape` and basic slicing are all it needs) is
     predicted chunk by chunk (chunk_plan) into `out`, a writable uint8 array-like of shape (size[2], size[1], size[0])
@@ -1776,10 +1862,20 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
     through a second double-buffered input stream, and one tem_u8_hist2 launch behind the chunk's last scatter (and its
     tem_u8_hist, with `histogram`) adds it into one device table that is read back once at the end; a chunk whose box
     misses the volume launches nothing.  The table does not depend on chunk_tiles or tile_batch; each rank reports its
-    own chunks, and the ranks' tables add up to that of the whole result."""
+    own chunks, and the ranks' tables add up to that of the whole result.
+
+    `spread` / `spread_gain` are predict_cube's: spread = S, a writable uint8 array-like of `out`'s level-0 shape
+    (ndarray, memmap, h5py, zarr), receives the map of the ensemble members' disagreement, equal to predict_cube's bit
+    for bit.  A chunk's device and pinned output block grows by one block of its `dims`, behind the pyramid levels if
+    there are any; the runner scatters the map there behind the prediction, the one D2H copy carries it, and the host
+    thread writes the chunk's `out_box` of S with the chunk's `out`.  stats["spread_histogram"] receives the map's
+    np.int64[256] histogram: one more tem_u8_hist launch per chunk into one device accumulator, read back once; each rank
+    reports its own chunks and the ranks' histograms add up.  One read thread, one output stream and no collective, as
+    before."""
     gen = model.generator_g
     is3d = getattr(gen, "is3d", True)
     syms = _check_ensemble(ensemble, is3d)
+    gain = _check_spread(spread, spread_gain, syms, size)
     L = _check_mips(mips, _plan_outdimsize(model.outdimsize if outdimsize is None else outdimsize))
     if L and len(size) in (2, 3):
         out = _check_mip_outs(out, size, L, is3d)
@@ -1802,7 +1898,8 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
                        out=[_OneSection(o) for o in out] if L else _OneSection(out), chunk_tiles=chunk_tiles,
                        tile_batch=tile_batch, outdimsize=outdimsize, buffer=buffer, rank=rank, world_size=world_size,
                        stats=stats, boundary=boundary, ensemble=ensemble, mips=mips, lut=lut, histogram=histogram,
-                       clahe=clahe, compare=None if compare is None else _OneSection(compare))
+                       clahe=clahe, compare=None if compare is None else _OneSection(compare),
+                       spread=None if spread is None else _OneSection(spread), spread_gain=spread_gain)
         return out
     vol_shape = tuple(int(v) for v in volume.shape)
     if len(vol_shape) != 3:
@@ -1823,6 +1920,8 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
         st["histogram"] = np.zeros(256, np.int64)
     if compare is not None:
         st["joint_histogram"] = np.zeros((256, 256), np.int64)
+    if gain is not None:
+        st["spread_histogram"] = np.zeros(256, np.int64)
     if stats is not None:
         stats.update(st)
     if not chunks:
@@ -1837,7 +1936,8 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
     lvl_dims = [[tuple(v >> (l if (is3d or d) else 0) for d, v in enumerate(c.dims)) for l in range(L + 1)]
                 for c in chunks]
     lvl_off = [np.cumsum([0] + [int(np.prod(d)) for d in dd]) for dd in lvl_dims]
-    out_bytes = [int(o[-1]) for o in lvl_off]
+    # ... and, with a spread, one more block of c.dims behind them: the map, at lvl_off[k][-1]
+    out_bytes = [int(o[-1]) + (int(np.prod(c.dims)) if gain is not None else 0) for o, c in zip(lvl_off, chunks)]
     nb = st["tile_batch"] = _effective_batch(tile_batch, edge, is3d, max(len(c.tiles) for c in chunks))
     dev = model.device
     compute = torch.cuda.current_stream(dev)
@@ -1845,9 +1945,9 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
     org = torch.tensor([o for c in chunks for o in c.origins], dtype=torch.int32).to(dev)     # every chunk's, once
     idx = torch.tensor([o for c in chunks for o in c.offsets], dtype=torch.int32).to(dev)
     prepare = _Prepare(lib, cl, lut, dev, compute.cuda_stream)
-    measure = _Measure(lib, histogram, compare is not None, dev, compute.cuda_stream)
+    measure = _Measure(lib, histogram, compare is not None, dev, compute.cuda_stream, spread=gain is not None)
     runner = _TileRunner(lib, model, is3d, edge, tpad, od, boundary, syms, meanstd_x, meanstd_y, vol_shape,
-                         compute.cuda_stream)
+                         compute.cuda_stream, gain)
     if compare is not None:
         # the ground truth of chunk k: its out_box in the volume's frame, clipped to the volume (None: it misses it)
         gt_box = [_inside(tuple(b[0] for b in c.out_box), tuple(b[1] for b in c.out_box),
@@ -1868,11 +1968,14 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
         else:
             dst[...] = 0
 
-    def write_from(k, buf):             # host thread: the chunk's box of `out`
+    def write_from(k, buf):             # host thread: the chunk's box of `out` (and of `spread`)
         c = chunks[k]
+        if gain is not None:
+            (z0, z1), (y0, y1), (x0, x1) = c.out_box
+            spread[z0:z1, y0:y1, x0:x1] = buf[lvl_off[k][-1]:].reshape(c.dims)[:z1 - z0, :y1 - y0, :x1 - x0]
         if not L:
             (z0, z1), (y0, y1), (x0, x1) = c.out_box
-            out[z0:z1, y0:y1, x0:x1] = buf.reshape(c.dims)[:z1 - z0, :y1 - y0, :x1 - x0]
+            out[z0:z1, y0:y1, x0:x1] = buf[:lvl_off[k][1]].reshape(c.dims)[:z1 - z0, :y1 - y0, :x1 - x0]
         for l in range(L + 1 if L else 0):      # with a pyramid: each level's box into its own array
             src = buf[lvl_off[k][l]:lvl_off[k][l + 1]].reshape(lvl_dims[k][l])
             ((z0, z1), (y0, y1), (x0, x1)), (nz, ny, nx) = mip_box(c, l, is3d)
@@ -1889,8 +1992,9 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
             prepare.apply(src, c.block, lo)                  # the footprint; never the stand-in zero byte
             t = 12 * int(first[k])
             # the staging buffer is free for the next upload once the chunk's last gather is enqueued
+            sdst = None if gain is None else dst + int(lvl_off[k][-1])
             runner.run(src, gdims[k], lo, org.data_ptr() + t, idx.data_ptr() + t, len(c.tiles), nb, dst, c.dims,
-                       lambda: inp.release(k, compute.record_event()))
+                       lambda: inp.release(k, compute.record_event()), sdst)
             valid = tuple(hi - lo_ for lo_, hi in c.out_box)     # the chunk's part of the result
             if L:                                            # its pyramid, level by level behind its scatters
                 _pool_levels(lib, dst, c.dims, valid, L, is3d, [dst + int(o) for o in lvl_off[k][1:L + 1]],
@@ -1902,6 +2006,8 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
                     at = tuple(b[0] - s0 - o for b, s0, o in zip(gt_box[k], (start[2], start[1], start[0]), c.base))
                     gt = (gt_buf.data_ptr(), gt_dims[k], at)
             measure.add(dst, c.dims, valid, gt)
+            if gain is not None:
+                measure.add_spread(sdst, c.dims, valid)
             scattered = compute.record_event()
             if compare is not None:
                 gt_inp.release(k, scattered)
@@ -1954,8 +2060,8 @@ def predict_ng_cube(location, start, size, model, meanstd_x, meanstd_y, cloudrun
     """Reference signature (utils.py:41): `location` is the uint8 volume itself (array indexed [z, y, x])
     instead of a cloud path; `cloudrun` is accepted and ignored.  The signature is the reference's, so voxels outside
     the array always read 0 here: predict_cube(..., boundary="reflect" | "edge") mirrors or clamps at the faces.
-    It takes no `mips` either: predict_cube(..., mips=L) returns the mip pyramid of the prediction; nor `lut`, `clahe` or
-    `compare`."""
+    It takes no `mips` either: predict_cube(..., mips=L) returns the mip pyramid of the prediction; nor `lut`, `clahe`,
+    `compare` or `spread`."""
     return predict_cube(_local_volume(location), start, size, model, meanstd_x, meanstd_y, fetch_input=fetch_input,
                         outdimsize=outdimsize, buffer=buffer)
 
@@ -1982,7 +2088,9 @@ def predict_volume_from_saved_model(volume, start, size, model_dir, out=None, **
     histogram (True: stats["histogram"] receives the 256-bin histogram of the result), clahe (None, or the
     ClaheTables of the volume, clahe_fit: the volume is equalised on the device, ahead of lut) and compare (None, or
     the ground truth as a uint8 array-like of the volume's shape: stats["joint_histogram"] receives the 256 x 256
-    joint histogram of (ground truth, result), see compare_from_joint).
+    joint histogram of (ground truth, result), see compare_from_joint), and spread / spread_gain (None, or a writable
+    uint8 array-like of the result's shape that receives the map of the ensemble members' disagreement, see
+    predict_cube).
     The reference's signatures, predict_ng_cube and predict_cube_from_saved_model, take none of these keywords; they
     run unensembled and return the full-resolution array alone."""
     model = _load_saved(model_dir)
