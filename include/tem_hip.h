@@ -648,6 +648,27 @@ int tem_instance_norm_bwd(const tem_view *x, const tem_view *dy, const float *sc
                           const float *rstd, const tem_view *dx, float *dscale, float *doffset,
                           double *workspace, tem_stream_t stream);
 
+/* ---- launch plans of the z-marching kernels: pin and read back (a test seam; off unless called)
+ * The tile plan of wino_conv_k, wino_bww_k, conv_lds_k and conv3_bf16_k comes from a host-side cost model that searches the
+ * feasible (tile block, z split) candidates of a geometry.  tem_plan_pin restricts that search, for the calling thread and one
+ * family, to the candidates whose pinned fields match (a field of -1 is free; v4 == NULL clears the pin).  Every feasibility
+ * condition of the planner applies unchanged, so a pin only selects among plans the planner could have chosen itself; where no
+ * candidate matches, the family answers TEM_EUNSUPPORTED (and tem_conv / tem_conv_bf16 go on to their next kernel, as for
+ * any geometry the family does not take).  While a pin is set the family's plan memo is neither read nor written.
+ * tem_plan_last reports the plan of the calling thread's most recent successful decision of the family (dry query, slab-count
+ * query or launch); TEM_EINVAL before any, or for an unknown family.
+ *   family               pin v4                   last v8
+ *   TEM_PLAN_WINO        {E, BY, BX, zsegs}       {E, BY, BX, zsegs, zper, nby, nbx, ndma}      (z in tiles of 2 planes)
+ *   TEM_PLAN_WINO_BWW    {E, BY, BX, zsegs}       {E, BY, BX, zsegs, zper, nby, nbx, ndma}
+ *   TEM_PLAN_CONV_LDS    {MTW, R, patch, zsegs}   {MTW, R, patch, zsegs, zper, nych, ntiles, 0}
+ *   TEM_PLAN_CONV3_BF16  {nbx, TY, zsegs, -1}     {nbx, TY, zsegs, zper, nby, RD, ndma, 0} */
+#define TEM_PLAN_WINO       1
+#define TEM_PLAN_WINO_BWW   2
+#define TEM_PLAN_CONV_LDS   3
+#define TEM_PLAN_CONV3_BF16 4
+int tem_plan_pin(int32_t family, const int32_t *v4);
+int tem_plan_last(int32_t family, int32_t *v8);
+
 /* Library identification: returns TEM_ABI_VERSION; *arch (if non-NULL) receives a
  * static string naming the compiled offload target ("gfx950"). */
 int tem_abi_version(const char **arch);

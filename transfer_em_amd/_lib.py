@@ -17,6 +17,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libtem_hip.so")
 TEM_OK, TEM_EINVAL, TEM_EUNSUPPORTED, TEM_ESHAPE = 0, -1, -2, -3
 TEM_W_TAP_CI_CO, TEM_W_FLIP_CO_CI, TEM_W_WINOGRAD = 0, 1, 2
 TEM_BOUNDARY_REFLECT, TEM_BOUNDARY_EDGE = 1, 2
+TEM_PLAN_WINO, TEM_PLAN_WINO_BWW, TEM_PLAN_CONV_LDS, TEM_PLAN_CONV3_BF16 = 1, 2, 3, 4
 _ERR = {TEM_EINVAL: "TEM_EINVAL (malformed descriptor)",
         TEM_EUNSUPPORTED: "TEM_EUNSUPPORTED (geometry outside the compiled set)",
         TEM_ESHAPE: "TEM_ESHAPE (inconsistent tensor extents)"}
@@ -169,6 +170,8 @@ _SIGS = {
     "tem_instance_norm": [_VP, C.c_void_p, C.c_void_p, C.c_float, _VP, C.c_void_p, C.c_void_p, C.c_void_p],
     "tem_instance_norm_bwd": [_VP, _VP, C.c_void_p, C.c_void_p, C.c_void_p, _VP, C.c_void_p, C.c_void_p, C.c_void_p,
                               C.c_void_p],
+    "tem_plan_pin": [C.c_int32, C.POINTER(C.c_int32)],
+    "tem_plan_last": [C.c_int32, C.POINTER(C.c_int32)],
     "tem_abi_version": [C.POINTER(C.c_char_p)],
 }
 EXPORTS = tuple(_SIGS)

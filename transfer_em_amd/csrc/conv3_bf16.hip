@@ -387,7 +387,8 @@ static int run(Dev p, int N, hipStream_t st, bool dry, char *name, int name_len)
   static tem_plan_cache<5, Plan> cache;                     // (the search below costs 5-30 us of host time per launch)
   const std::array<int, 5> key{N, p.OD, p.OH, p.OW, p.in1 != p.in0 ? 1 : 0};
   Plan memo;
-  if (cache.get(key, memo)) {
+  const int32_t *const pin = tem_plan_pinned(TEM_PLAN_CONV3_BF16);   // {nbx, TY, zsegs} of tem_plan_pin or null: other candidates are skipped, no memo
+  if (!pin && cache.get(key, memo)) {
     best = memo.best;
     p.TX = memo.TX; p.TY = memo.TY; p.nbx = memo.nbx; p.nby = memo.nby; p.zsegs = memo.zsegs; p.zper = memo.zper; p.RW = memo.RW;
     p.PV = memo.PV; p.ndma = memo.ndma; p.slot_bytes = memo.slot_bytes; p.RD = memo.RD; p.ndma_cnt = memo.ndma_cnt;
@@ -398,10 +399,11 @@ static int run(Dev p, int N, hipStream_t st, bool dry, char *name, int name_len)
     if (knob_nbx && nbx != knob_nbx) continue;
     const int TX = (p.OW + nbx - 1) / nbx;
     if (nbx > 1 && TX < 16) break;
+    if (!tem_pin_ok(pin, 0, nbx)) continue;
     // stride 1: a tile (16 voxels) never straddles ring rows; stride 2: the row holds the 2 TX + 2 input columns
     const int RW = S == 1 ? (TX + 2 + 15) & ~15 : (S * (TX - 1) + K + 1) & ~1;
     for (int TY = 2; TY <= 24 && TY <= p.OH + 1; ++TY) {
-      if (knob_ty && TY != knob_ty) continue;
+      if ((knob_ty && TY != knob_ty) || !tem_pin_ok(pin, 1, TY)) continue;
       const int PV = (S * (TY - 1) + K) * RW;
       const int slot = (int)((((int64_t)(PV + S * 32 + K + 1) * CI * 2) + 1023) & ~(int64_t)1023);     // + the last pair's over-read
       const int ndma = (PV * CPV + 63) / 64;
@@ -418,7 +420,7 @@ static int run(Dev p, int N, hipStream_t st, bool dry, char *name, int name_len)
         for (int zsegs = 1; zsegs <= p.OD; ++zsegs) {
           if (knob_zs && zsegs != knob_zs) continue;
           const int zper = (p.OD + zsegs - 1) / zsegs, zs = (p.OD + zper - 1) / zper;
-          if (zs != zsegs) continue;
+          if (zs != zsegs || !tem_pin_ok(pin, 2, zsegs)) continue;
           const int64_t wgs = (int64_t)cols * zs;
           const double rounds = (double)((wgs + 255) / 256);
           const double cost = (rounds + knob_cuw / 100.0 * (double)wgs / 256.0) * ((zper + (K - S) / (double)S) * step + 7000.0);
@@ -433,7 +435,7 @@ static int run(Dev p, int N, hipStream_t st, bool dry, char *name, int name_len)
     }
   }
   memo = Plan{best, p.TX, p.TY, p.nbx, p.nby, p.zsegs, p.zper, p.RW, p.PV, p.ndma, p.slot_bytes, p.RD, p.ndma_cnt};
-  cache.put(key, memo);
+  if (!pin) cache.put(key, memo);
   }
   if (best >= 1e30) return TEM_EUNSUPPORTED;
   p.dbg = tem_env_int("TEM_C3B_DBG", 0);
@@ -446,6 +448,7 @@ static int run(Dev p, int N, hipStream_t st, bool dry, char *name, int name_len)
     const int64_t vmax = (int64_t)(S * (p.TY - 1) + K) * p.RW + 64;
     if (vmax >= (1 << 22) / p.RW || vmax * p.magicRW >= ((int64_t)1 << 32) || p.magicRW >= (1u << 24)) return TEM_EUNSUPPORTED;
   }
+  tem_plan_note(TEM_PLAN_CONV3_BF16, p.nbx, p.TY, p.zsegs, p.zper, p.nby, p.RD, p.ndma, 0);
   if (dry) {
     if (name) snprintf(name, name_len, "conv3_bf16_k<%d, %d, %d, %d, %d, %s, %d>", CI, CO, K, S, NW, SPLIT ? "true" : "false", EPI);
     return TEM_OK;

@@ -450,7 +450,7 @@ constexpr int TARGET_BLOCKS = 512;
 
 // mode 0: launch; 1: dry run; 2: only predict (*cost receives the model's cycles)
 template <int CI, int CO, int K, int S, int NW, int MAXPFX, int MTW, bool DROP>
-int run(Dev p, hipStream_t st, int mode, double *cost, char *name, int name_len) {
+int run(Dev p, hipStream_t st, int mode, double *cost, char *name, int name_len, const int32_t *pin) {
   constexpr int CIP = CI + 2, NT = (CO + 15) / 16;
   const int NTHR = NW * 64;
   p.WX = (p.OW - 1) * S + K;
@@ -468,12 +468,16 @@ int run(Dev p, hipStream_t st, int mode, double *cost, char *name, int name_len)
   int R = 0;
   double best = 1e300;
   const int NTAPS = K * K * K, KSTEPS = CI / 4;
+  // pin: the {MTW, R, patch, zsegs} of tem_plan_pin or null -- candidates whose pinned fields differ are skipped
+  if (!tem_pin_ok(pin, 0, MTW)) return TEM_EUNSUPPORTED;
   for (int r = 1; r <= (p.OH < 16 ? p.OH : 16); ++r) {
+    if (!tem_pin_ok(pin, 1, r)) continue;
     int YR = (r - 1) * S + K;
     int ntiles = S == 1 ? (r * p.WP + 15) / 16 : r * p.nseg;
    for (int patch = 20; patch >= 0; patch = patch == 20 ? 16 : (patch == 16 ? 0 : -1)) {
     // ring + tail the last tiles over-read (+ one 16-row transpose patch per wave)
     size_t bytes = ((((size_t)K * YR * p.WP * CIP + (S == 1 ? 18 : 40) * CIP + 3) & ~(size_t)3) + NW * 16 * patch) * 4;
+    if (!tem_pin_ok(pin, 2, patch)) continue;
     bool fits = bytes <= (size_t)LDS_MAX && (size_t)S * YR * p.chunksX <= (size_t)MAXPFX * (LOADER_ALL ? NTHR : NTHR / 2) &&
                 ntiles * NT <= MTW * NW;
     if (!fits) continue;
@@ -487,7 +491,7 @@ int run(Dev p, hipStream_t st, int mode, double *cost, char *name, int name_len)
     double pro = 12000.0 + bytes / 12.0;              // first K planes arrive at the CU's HBM share (~12 B/clk)
     for (int zs = 1; zs <= p.OD; ++zs) {
       int zper = (p.OD + zs - 1) / zs, zsegs = (p.OD + zper - 1) / zper;
-      if (zsegs != zs) continue;
+      if (zsegs != zs || !tem_pin_ok(pin, 3, zsegs)) continue;
       double t = std::ceil(cols * zsegs / 256.0) * (pro + zper * step);
       if (t < best) {
         best = t; R = r; p.R = r; p.YR = YR; p.ntiles = ntiles; lds_bytes = (bytes + 15) & ~(size_t)15;
@@ -499,6 +503,7 @@ int run(Dev p, hipStream_t st, int mode, double *cost, char *name, int name_len)
   if (R < 1) return TEM_EUNSUPPORTED;
   if (cost) *cost = best;
   if (mode == 2) return TEM_OK;
+  tem_plan_note(TEM_PLAN_CONV_LDS, MTW, p.R, p.patch, p.zsegs, p.zper, p.nych, p.ntiles, 0);
   const bool dry = mode == 1;
   int nblocks = p.N * p.nych * p.zsegs;
   if (dry) {
@@ -526,13 +531,14 @@ int run(Dev p, hipStream_t st, int mode, double *cost, char *name, int name_len)
 template <int CI, int CO, int K, int S, int NW, int MAXPFX, bool DROP>
 int run_best(const Dev &p, hipStream_t st, bool dry, char *name, int name_len) {
   double c4 = 1e300, c2 = 1e300, c1 = 1e300;
-  run<CI, CO, K, S, NW, MAXPFX, 4, DROP>(p, st, 2, &c4, nullptr, 0);
-  run<CI, CO, K, S, NW, MAXPFX, 2, DROP>(p, st, 2, &c2, nullptr, 0);
-  run<CI, CO, K, S, NW, MAXPFX, 1, DROP>(p, st, 2, &c1, nullptr, 0);
+  const int32_t *const pin = tem_plan_pinned(TEM_PLAN_CONV_LDS);
+  run<CI, CO, K, S, NW, MAXPFX, 4, DROP>(p, st, 2, &c4, nullptr, 0, pin);
+  run<CI, CO, K, S, NW, MAXPFX, 2, DROP>(p, st, 2, &c2, nullptr, 0, pin);
+  run<CI, CO, K, S, NW, MAXPFX, 1, DROP>(p, st, 2, &c1, nullptr, 0, pin);
   if (c4 >= 1e300 && c2 >= 1e300 && c1 >= 1e300) return TEM_EUNSUPPORTED;
-  if (c4 <= c2 && c4 <= c1) return run<CI, CO, K, S, NW, MAXPFX, 4, DROP>(p, st, dry ? 1 : 0, nullptr, name, name_len);
-  if (c2 <= c1) return run<CI, CO, K, S, NW, MAXPFX, 2, DROP>(p, st, dry ? 1 : 0, nullptr, name, name_len);
-  return run<CI, CO, K, S, NW, MAXPFX, 1, DROP>(p, st, dry ? 1 : 0, nullptr, name, name_len);
+  if (c4 <= c2 && c4 <= c1) return run<CI, CO, K, S, NW, MAXPFX, 4, DROP>(p, st, dry ? 1 : 0, nullptr, name, name_len, pin);
+  if (c2 <= c1) return run<CI, CO, K, S, NW, MAXPFX, 2, DROP>(p, st, dry ? 1 : 0, nullptr, name, name_len, pin);
+  return run<CI, CO, K, S, NW, MAXPFX, 1, DROP>(p, st, dry ? 1 : 0, nullptr, name, name_len, pin);
 }
 
 #define CONV_CASE(ci, co, k, s, nw, pfx, mtw) \

@@ -218,3 +218,25 @@ template <size_t NK, typename R> struct tem_plan_cache {
     if (m.size() < 4096) m[k] = r;
   }
 };
+
+// ---------------------------------------------------------------- plan pins (tem_plan_pin / tem_plan_last, dispatch.hip)
+// A test seam: per thread and planner family, an optional pin of up to four plan fields and the plan of the last decision.
+// While a family's pin is set its planner keeps every feasibility condition and merely skips the candidates whose pinned
+// fields differ (a field of -1 is free), so a pin selects among plans the planner could have chosen itself; the memo above is
+// neither read nor written then.  Unpinned, a planner pays one thread-local read (tem_plan_pinned) and the note of its plan.
+struct tem_plan_slot { bool pinned, have; int32_t pin[4], last[8]; };
+inline tem_plan_slot *tem_plan_slots() {            // one array per thread for the whole library (inline: one definition)
+  static thread_local tem_plan_slot s[TEM_PLAN_CONV3_BF16 + 1] = {};
+  return s;
+}
+static inline const int32_t *tem_plan_pinned(int family) {
+  const tem_plan_slot &s = tem_plan_slots()[family];
+  return s.pinned ? s.pin : nullptr;
+}
+static inline bool tem_pin_ok(const int32_t *pin, int field, int value) { return !pin || pin[field] < 0 || pin[field] == value; }
+static inline void tem_plan_note(int family, int v0, int v1, int v2, int v3, int v4, int v5, int v6, int v7) {
+  tem_plan_slot &s = tem_plan_slots()[family];
+  const int32_t v[8] = {v0, v1, v2, v3, v4, v5, v6, v7};
+  for (int i = 0; i < 8; ++i) s.last[i] = v[i];
+  s.have = true;
+}

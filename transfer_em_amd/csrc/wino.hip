@@ -468,8 +468,9 @@ __global__ __launch_bounds__(256) void wino_weights_k(const float *theta, float 
 // ------------------------------------------------------------------------------------------ host
 constexpr int LDS_MAX = 160 * 1024;
 
+// pin: the {E, BY, BX, zsegs} of tem_plan_pin or null -- candidates whose pinned fields differ are skipped, nothing else changes
 template <int CI, int CO, int NI>
-int plan(Dev &p, double *cost, size_t *lds_bytes, int EE) {
+int plan(Dev &p, double *cost, size_t *lds_bytes, int EE, const int32_t *pin = nullptr) {
   constexpr int NH = CI / 8, NB = (CO + 15) / 16;
   constexpr bool PAIR = CI == 8 && CO == 8;
   const size_t ubytes = CI == 32 ? (size_t)2 * (2 * NB * 16 * 128) * 4                       // streamed: two chunk buffers
@@ -482,6 +483,7 @@ int plan(Dev &p, double *cost, size_t *lds_bytes, int EE) {
       const int nt = by * bx;
       if (nt > (PAIR ? 128 : 64 / NB)) continue;
       if (bx + 1 > EE) continue;                             // the kernel's compile-time row pitch
+      if (!tem_pin_ok(pin, 1, by) || !tem_pin_ok(pin, 2, bx)) continue;
       const int E = EE, plv = (2 * by + 2) * 2 * E;
       const int subb = (plv * 32 + 1023) & ~1023, slotb = NH * subb;
       const size_t bytes = (size_t)4 * slotb + ubytes;
@@ -498,7 +500,7 @@ int plan(Dev &p, double *cost, size_t *lds_bytes, int EE) {
       const double pro = 6000.0 + (4.0 * slotb + ubytes) / 10.0;
       for (int zs = 1; zs <= p.NTZ; ++zs) {
         const int zper = (p.NTZ + zs - 1) / zs, zsegs = (p.NTZ + zper - 1) / zper;
-        if (zsegs != zs) continue;
+        if (zsegs != zs || !tem_pin_ok(pin, 3, zsegs)) continue;
         // latency of the launch alone (rounds of 256 workgroups) + 4 x its CU-time share: the step runs four streams that end
         // together (cgan.py), so a launch's CU-time is what it costs -- a plan with fewer, longer z-runs pays fewer prologues
         // (four planes + U: ~1.2 steps) even where it leaves CUs idle when the launch is timed alone.  fp32 step by this weight
@@ -556,19 +558,22 @@ int run_best(Dev p, hipStream_t st, bool dry, char *name, int name_len) {
   static int force = -1;
   if (force < 0) force = tem_env_int("TEM_WINO_EE", 0);
   const int pitches[2] = {9, 17};      // (11 measured too: never better than 9 on the step's shapes)
+  const int32_t *const pin = tem_plan_pinned(TEM_PLAN_WINO);
   Dev best = p;
   double cbest = 1e300;
   size_t lds_bytes = 0;
   for (int i = 0; i < 2; ++i) {
-    if (force && pitches[i] != force) continue;
+    if ((force && pitches[i] != force) || !tem_pin_ok(pin, 0, pitches[i])) continue;
     Dev q = p;
     double c = 1e300;
     size_t l = 0;
-    if (plan_memo<CI, CO, NI>(q, &c, &l, pitches[i]) == TEM_OK && c < cbest) { best = q; cbest = c; lds_bytes = l; }
+    const int rc = pin ? plan<CI, CO, NI>(q, &c, &l, pitches[i], pin) : plan_memo<CI, CO, NI>(q, &c, &l, pitches[i]);
+    if (rc == TEM_OK && c < cbest) { best = q; cbest = c; lds_bytes = l; }
   }
   if (cbest >= 1e300) return TEM_EUNSUPPORTED;
   p = best;
   p.magicBX = magic_for(p.BX); p.magicE = magic_for(p.E);
+  tem_plan_note(TEM_PLAN_WINO, p.E, p.BY, p.BX, p.zsegs, p.zper, p.nby, p.nbx, p.ndma);
   if (dry) {
     if (name) snprintf(name, name_len, "wino_conv_k<%d, %d, %d, %d, %d>", CI, CO, NI, EP, p.E);
     return TEM_OK;

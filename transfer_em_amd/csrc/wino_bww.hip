@@ -389,7 +389,7 @@ __global__ __launch_bounds__(512) void wino_bww_k(BDev p) {
 constexpr int LDS_MAX_B = 160 * 1024;
 
 template <int CI, int CO, int NI>
-static int plan_bww(BDev &p, size_t *lds_bytes, int EE, double *cost) {
+static int plan_bww(BDev &p, size_t *lds_bytes, int EE, double *cost, const int32_t *pin = nullptr) {   // pin: as in wino.hip plan()
   constexpr int NH = CI / 8, MT = CI >= 16 ? 3 : 2;
   constexpr int CIH = CI >= 16 ? CI / 16 : 1, NB = CO / 16 > 0 ? CO / 16 : 1, NC = CIH * NB, TB = CI == 32 ? 32 : 64;
   const int TY = (p.OH + 1) / 2, TX = (p.OW + 1) / 2;
@@ -404,6 +404,7 @@ static int plan_bww(BDev &p, size_t *lds_bytes, int EE, double *cost) {
       const int E = EE, plv = (2 * by + 2) * 2 * E;
       const int ndma = (plv * 32 + 1023) / 1024;
       if (bx & 1) continue;                                            // tile pairs (t, t + 1) must not wrap rows
+      if (!tem_pin_ok(pin, 1, by) || !tem_pin_ok(pin, 2, bx)) continue;
       const int subb = ndma * 1024 + 32, slotb = ((NH * subb + 127) / 128) * 128 + (NH == 1 ? 32 : 0);
       const size_t bytes = std::max((size_t)4 * slotb, (size_t)2 * MT * 8 * 256 * 4);   // ring; reused by the final sums
       if (bytes > (size_t)LDS_MAX_B || ndma > 8 * NI) continue;
@@ -413,7 +414,7 @@ static int plan_bww(BDev &p, size_t *lds_bytes, int EE, double *cost) {
       const double pro = 8000.0 + 4.0 * slotb / 10.0 + 6000.0;         // prologue + the final LDS reduction and slab write
       for (int zs = 1; zs <= p.NTZ; ++zs) {
         const int zper = (p.NTZ + zs - 1) / zs, zsegs = (p.NTZ + zper - 1) / zper;
-        if (zsegs != zs) continue;
+        if (zsegs != zs || !tem_pin_ok(pin, 3, zsegs)) continue;
         // + the slabs' way to HBM and back (written here, read by reduce_multi_k) at ~2 KB per cycle for the whole chip: g.mid 252 ->
         // 216 slabs of 110 KB per call, 7.39 -> 7.32 ms/step.  [Rounds of 128 instead of 256 workgroups (half the prologues,
         // Winograd-domain finishes and slab bytes; the kernel gradients run beside the dependent chains, so their CU-time counts, not
@@ -504,12 +505,16 @@ static int run_bww(const tem_bww_args *a, hipStream_t st, int mode, int *nslab, 
     if (force < 0) force = tem_env_int("TEM_WINO_EE", 0);
     BDev best = p;
     double cbest = 1e300;
+    const int32_t *const pin = tem_plan_pinned(TEM_PLAN_WINO_BWW);
     for (int EE : {9, 17}) {
-      if (force && EE != force) continue;
+      if ((force && EE != force) || !tem_pin_ok(pin, 0, EE)) continue;
       BDev q = p;
       double c = 1e300;
       size_t l = 0;
-      const int r = variant == 0 ? plan_bww_memo<8, 8, 2>(q, &l, EE, &c) : variant == 1 ? plan_bww_memo<16, 16, 2>(q, &l, EE, &c)
+      const int r = pin ? (variant == 0 ? plan_bww<8, 8, 2>(q, &l, EE, &c, pin) : variant == 1 ? plan_bww<16, 16, 2>(q, &l, EE, &c, pin)
+                          : variant == 2 ? plan_bww<8, 16, 2>(q, &l, EE, &c, pin) : variant == 3 ? plan_bww<16, 32, 2>(q, &l, EE, &c, pin)
+                          : variant == 4 ? plan_bww<32, 16, 2>(q, &l, EE, &c, pin) : plan_bww<32, 32, 2>(q, &l, EE, &c, pin))
+                  : variant == 0 ? plan_bww_memo<8, 8, 2>(q, &l, EE, &c) : variant == 1 ? plan_bww_memo<16, 16, 2>(q, &l, EE, &c)
                   : variant == 2 ? plan_bww_memo<8, 16, 2>(q, &l, EE, &c) : variant == 3 ? plan_bww_memo<16, 32, 2>(q, &l, EE, &c)
                   : variant == 4 ? plan_bww_memo<32, 16, 2>(q, &l, EE, &c) : plan_bww_memo<32, 32, 2>(q, &l, EE, &c);
       if (r == TEM_OK && c < cbest) { best = q; cbest = c; lds_bytes = l; rc = TEM_OK; }
@@ -519,6 +524,7 @@ static int run_bww(const tem_bww_args *a, hipStream_t st, int mode, int *nslab, 
   if (rc != TEM_OK) return rc;
   const int nblocks = p.N * p.nby * p.nbx * p.zsegs;
   if (nblocks > (a->nslab > 0 ? a->nslab : 1024)) return TEM_EUNSUPPORTED;
+  tem_plan_note(TEM_PLAN_WINO_BWW, p.E, p.BY, p.BX, p.zsegs, p.zper, p.nby, p.nbx, p.ndma);
   if (mode == 1) { *nslab = nblocks; return TEM_OK; }
   if (mode == 2) { if (name) snprintf(name, name_len, "wino_bww_k<%d, %d, 2, %s, %d>", CI, CO, pair ? "true" : "false", p.E); return TEM_OK; }
   if (!a->slabs || a->nslab != nblocks || a->accumulate) return TEM_EINVAL;
