@@ -453,6 +453,37 @@ int tem_u8_ssim(const uint8_t *a, int32_t Da, int32_t Ha, int32_t Wa, int32_t az
                 int32_t nz, int32_t ny, int32_t nx, int32_t win, int32_t flat, int64_t *sums, uint8_t *map,
                 tem_stream_t stream);
 
+/* A uint8 volume brought onto a grid of another voxel size: intensities only (labels need nearest or majority).  Each
+ * axis has a step p / q in lowest terms, the output voxel's edge in source voxels: 1 <= p, q <= 64, 1/8 <= p / q <= 8.
+ * An axis of n source voxels gives ceil(n q / p) output voxels, the grid anchored at the volume's voxel 0.  Output j
+ * of an axis has integer taps (i, w) and a denominator W:
+ *   p >= q, the area average: in units of 1 / q source voxel, j covers [j p, (j + 1) p) and source voxel i covers
+ *     [i q, (i + 1) q); w is the length of the overlap, for i from floor(j p / q) while i q < (j + 1) p and i <= n - 1;
+ *     W is the sum of the weights kept: p, or less at the far face where n q is not a multiple of p (a voxel that
+ *     does not exist never enters a mean: tem_u8_pool2's rule).  At most ceil(p / q) + 1 taps.
+ *   p < q, linear between voxel centres: C = (2 j + 1) p - q, i0 = floor(C / (2 q)), f = C - 2 q i0; the taps are
+ *     (clamp(i0), 2 q - f) and (clamp(i0 + 1), f), clamp to [0, n - 1]; W = 2 q  (scipy.ndimage.zoom(order=1,
+ *     mode="nearest", grid_mode=True) before rounding).
+ *   the voxel: S = sum of wz wy wx v over the tap product, Den = Wz Wy Wx, out = (2 S + Den) / (2 Den)  (integers)
+ * -- one rounding, half up, at the very end; no pass rounds an intermediate.  2 S + Den <= 511 x 128^3 < 2^31.
+ * src[D][H][W] is a dense block of the volume [VZ][VY][VX] with its voxel 0 at (sz0, sy0, sx0); dst[OD][OH][OW] is a
+ * dense block of the output grid with its voxel 0 at (oz0, oy0, ox0).  Taps and the far faces are computed in volume
+ * coordinates, so a block's bytes do not depend on how the volume was cut.  Every byte of dst is written exactly once
+ * and nothing else is written; no source byte outside the hull of the block's taps is read, and a tap of weight 0
+ * (f == 0) is no tap: it need not lie in the source block and is not read.  Any alignment of src, dst, W and OW;
+ * every byte offset is 64 bits.
+ * TEM_EINVAL, without a launch: a null pointer, a dimension below 1, p or q outside 1...64, a step outside [1/8, 8]
+ * or not in lowest terms, a negative origin, a source block that leaves the volume, an output block that leaves the
+ * grid, an output block one of whose taps lies outside the source block, and an output block of more workgroups than
+ * one launch holds: a workgroup takes 8 x 32 outputs over (y, x) and a run of 32 output planes, and
+ *   ceil(OH / 8) x ceil(OW / 32) x ceil(OD / 32)  must stay below 2^24
+ * (its 256 threads then stay below 2^32 per launch).  A block of fewer than 2^34 voxels with no extent below 32
+ * always passes. */
+int tem_u8_rescale(const uint8_t *src, int32_t D, int32_t H, int32_t W, int32_t sz0, int32_t sy0, int32_t sx0,
+                   int32_t VZ, int32_t VY, int32_t VX, int32_t pz, int32_t qz, int32_t py, int32_t qy, int32_t px,
+                   int32_t qx, uint8_t *dst, int32_t OD, int32_t OH, int32_t OW, int32_t oz0, int32_t oy0, int32_t ox0,
+                   tem_stream_t stream);
+
 /* Intensity remapping of a dense uint8 block in place (tiled inference: the uploaded bytes, ahead of the gather).
  *   per_section = 0:  buf[z][y][x] = lut[buf[z][y][x]]                          lut: 256 bytes
  *   per_section = 1:  buf[z][y][x] = lut[(zsec0 + z) * 256 + buf[z][y][x]]      lut: at least zsec0 + D rows of 256

@@ -34,12 +34,17 @@ it for a prediction against its ground truth while the prediction is still on th
 `volume_ssim` is the structural half of that comparison: the windowed structural similarity (SSIM) of two uint8 volumes
 out of core, in integers (tem_u8_ssim), as per-section sums that `ssim_from_sums` turns into the index, and optionally
 as a uint8 map of where the two volumes differ in structure.
+
+`volume_rescale` brings a uint8 volume onto the voxel grid of the other domain out of core (tem_u8_rescale): one step
+p / q per axis, the area average where an axis shrinks and linear interpolation where it grows, in integers with one
+rounding per voxel; `rescale_step`, `rescale_shape`, `rescale_taps` and `rescale_chunks` are its host side.
 """
 import contextlib
 import json
 import os
 import time
 from concurrent.futures import ThreadPoolExecutor
+from fractions import Fraction
 from typing import NamedTuple
 
 import numpy as np
@@ -1134,6 +1139,237 @@ def ssim_from_sums(s):
     total = [sum(row[i] for row in rows) / (n * SSIM_Q) for i in range(3)]
     per = np.array([[v / (windows * SSIM_Q) for v in row] for row in rows], np.float64)
     return {"n": n, "ssim": total[0], "luminance": total[1], "contrast_structure": total[2], "per_section": per}
+
+
+RESCALE_MAX_PQ = 64              # tem_u8_rescale: 1 <= p, q <= 64 and 1/8 <= p / q <= 8 keep 2 S + Den below 2^31
+RESCALE_MAX_STEP = 8
+
+
+def _rescale_fraction(s):
+    """One axis' step as a reduced Fraction p / q: an int, a Fraction or a (p, q) pair; ValueError otherwise, and for
+    p or q outside 1...RESCALE_MAX_PQ or a step outside [1 / RESCALE_MAX_STEP, RESCALE_MAX_STEP]."""
+    try:
+        if isinstance(s, (bool, np.bool_, float, np.floating, str, bytes)):
+            raise TypeError
+        if isinstance(s, (tuple, list)):
+            if len(s) != 2 or any(isinstance(v, (bool, float)) for v in s):
+                raise TypeError
+            f = Fraction(int(s[0]), int(s[1]))
+        else:
+            f = Fraction(s)
+    except (TypeError, ValueError, ZeroDivisionError):
+        raise ValueError(f"a step must be an int, a Fraction or a (p, q) pair of positive integers, got {s!r}")
+    p, q = f.numerator, f.denominator
+    if not (1 <= p <= RESCALE_MAX_PQ and 1 <= q <= RESCALE_MAX_PQ and q <= RESCALE_MAX_STEP * p and
+            p <= RESCALE_MAX_STEP * q):
+        raise ValueError(f"a step p / q needs 1 <= p, q <= {RESCALE_MAX_PQ} in lowest terms and 1/{RESCALE_MAX_STEP} <= "
+                         f"p / q <= {RESCALE_MAX_STEP}, got {s!r}")
+    return f
+
+
+def _rescale_steps(step, nd):
+    """`step` as `nd` reduced Fractions in (x, y[, z]) order: one step per axis, or one int or Fraction for all."""
+    if isinstance(step, (int, np.integer, Fraction)) and not isinstance(step, (bool, np.bool_)):
+        return (_rescale_fraction(step),) * nd
+    if not isinstance(step, (tuple, list)) or len(step) != nd:
+        raise ValueError(f"step must have {nd} elements in (x, y, z) order, or be one int or Fraction, got {step!r}")
+    return tuple(_rescale_fraction(s) for s in step)
+
+
+def rescale_step(src_size, dst_size):
+    """The steps that bring a volume of voxel size `src_size` onto a grid of voxel size `dst_size`, both (x, y, z)
+    (or (x, y)) in one unit, e.g. (4, 4, 40) and (8, 8, 8) nm: the tuple of reduced Fractions dst / src, the output
+    voxel's edge in source voxels -- (2, 2, 1/5) there.  ValueError for a step volume_rescale does not take."""
+    src, dst = tuple(src_size), tuple(dst_size)
+    if len(src) != len(dst) or len(src) not in (2, 3):
+        raise ValueError(f"voxel sizes must both be (x, y, z) or (x, y), got {src_size!r}, {dst_size!r}")
+    try:
+        steps = tuple(Fraction(d) / Fraction(s) for s, d in zip(src, dst))
+    except (TypeError, ValueError, ZeroDivisionError):
+        raise ValueError(f"voxel sizes must be positive integers or Fractions, got {src_size!r}, {dst_size!r}")
+    return tuple(_rescale_fraction(f) for f in steps)
+
+
+def rescale_shape(vol_shape, step):
+    """The shape [z, y, x] (or [y, x]) of the output grid of a volume of shape `vol_shape` at `step` ((x, y, z) order,
+    each an int, a Fraction or a (p, q) pair): ceil(n q / p) per axis."""
+    shape = tuple(int(v) for v in vol_shape)
+    if len(shape) not in (2, 3) or min(shape) < 1:
+        raise ValueError(f"volume must be a non-empty [z, y, x] or one image [y, x], got shape {shape}")
+    steps = _rescale_steps(step, len(shape))
+    return tuple(-(-n * f.denominator // f.numerator) for n, f in zip(shape, reversed(steps)))
+
+
+def _rescale_tap(j, n, p, q):
+    """(first tap, weights, W) of output j of an axis of n source voxels at step p / q: the rule of rescale_taps."""
+    if p >= q:
+        lo, hi = j * p, min((j + 1) * p, n * q)
+        first = lo // q
+        return first, tuple(min((i + 1) * q, hi) - max(i * q, lo) for i in range(first, (hi - 1) // q + 1)), hi - lo
+    C = (2 * j + 1) * p - q
+    i0 = C // (2 * q)
+    f = C - 2 * q * i0
+    a, b = min(max(i0, 0), n - 1), min(max(i0 + 1, 0), n - 1)
+    return (a, (2 * q,), 2 * q) if a == b or f == 0 else (a, (2 * q - f, f), 2 * q)
+
+
+def rescale_taps(n, p, q):
+    """The one host copy of tem_u8_rescale's rule for one axis of `n` source voxels at step p / q (reduced): a list
+    with, per output voxel j < ceil(n q / p), (first, weights, W) -- the taps are source voxels first, first + 1, ...
+    with those integer weights, and W is their sum.
+      p >= q, the area average: in units of 1 / q source voxel j covers [j p, (j + 1) p) and voxel i [i q, (i + 1) q);
+        a weight is the length of the overlap, over the voxels that exist; W = p, or less at the far face.
+      p < q, linear between voxel centres: C = (2 j + 1) p - q, i0 = floor(C / 2 q), f = C - 2 q i0, taps
+        (clamp(i0), 2 q - f) and (clamp(i0 + 1), f); W = 2 q.  Taps that clamp onto one voxel are given as one tap of
+        weight 2 q, and a tap of weight 0 (f == 0) is dropped: every weight returned is positive.
+    The voxel is (2 S + Den) // (2 Den) with S the sum over the tap product of the three axes and Den = Wz Wy Wx."""
+    f = _rescale_fraction((p, q))
+    if (f.numerator, f.denominator) != (p, q):
+        raise ValueError(f"the step {p} / {q} is not in lowest terms")
+    if n < 1:
+        raise ValueError(f"an axis has at least one voxel, got {n}")
+    return [_rescale_tap(j, n, p, q) for j in range(-(-n * q // p))]
+
+
+def _rescale_hull(lo, hi, n, f):
+    """The (lo, hi) source voxels that outputs [lo, hi) of an axis of n voxels at step f read."""
+    first = _rescale_tap(lo, n, f.numerator, f.denominator)
+    last = _rescale_tap(hi - 1, n, f.numerator, f.denominator)
+    return first[0], last[0] + len(last[1])
+
+
+def rescale_chunks(out_box, vol_shape, step, chunk_bytes=None, rank=0, world_size=1):
+    """Cut the (z, y, x) (lo, hi) box `out_box` of the output grid of a volume of shape `vol_shape` [z, y, x] at `step`
+    ((x, y, z) order) into slabs for volume_rescale.  Returns this rank's list of (output slab, read slab), (z, y, x)
+    (lo, hi) boxes of the output grid and of the volume: the output slabs are disjoint and their union is the box; a
+    read slab is the tight hull of its output slab's taps along z and y, over the volume's whole x extent -- x is never
+    cut -- so neighbouring read slabs overlap by the taps they share.  Both slabs hold at most `chunk_bytes` bytes
+    (HIST_CHUNK_BYTES when None): runs of whole output planes of the box, as many as fit, or, where one output plane or
+    its hull is larger than the budget, runs of whole output rows of that plane (one row at the least).  Slabs are in
+    (z, y) order and go round-robin to the ranks.  Pure host function; ValueError as hist_chunks, for a bad step and
+    for a box outside the grid."""
+    budget = HIST_CHUNK_BYTES if chunk_bytes is None else int(chunk_bytes)
+    if budget < 1:
+        raise ValueError(f"chunk_bytes must be positive, got {chunk_bytes}")
+    if not 0 <= rank < world_size:
+        raise ValueError(f"rank {rank} is outside [0, {world_size})")
+    vol_shape = tuple(int(v) for v in vol_shape)
+    if len(vol_shape) != 3:
+        raise ValueError(f"rescale_chunks takes a volume shape [z, y, x], got {vol_shape}")
+    grid = rescale_shape(vol_shape, step)
+    fx, fy, fz = _rescale_steps(step, 3)
+    (z0, z1), (y0, y1), (x0, x1) = out_box
+    if any(lo < 0 or hi > n for (lo, hi), n in zip(out_box, grid)):
+        raise ValueError(f"the box {tuple(out_box)} reaches outside the output grid of shape {grid}")
+    VZ, VY, VX = vol_shape
+    ny, nx = y1 - y0, x1 - x0
+    if z1 <= z0 or ny <= 0 or nx <= 0:
+        return []
+
+    def fits(nz, rz, rows, ry):         # an output slab of nz planes of `rows` rows and its hull of rz planes of ry rows
+        return nz * rows * nx <= budget and rz * ry * VX <= budget
+
+    whole_y = _rescale_hull(y0, y1, VY, fy)
+    slabs, z = [], z0
+    while z < z1:
+        lo, hi = _rescale_hull(z, z + 1, VZ, fz)
+        if fits(1, hi - lo, ny, whole_y[1] - whole_y[0]):
+            k = 1
+            while z + k < z1:
+                more = _rescale_hull(z, z + k + 1, VZ, fz)[1]
+                if not fits(k + 1, more - lo, ny, whole_y[1] - whole_y[0]):
+                    break
+                k, hi = k + 1, more
+            slabs.append((((z, z + k), (y0, y1), (x0, x1)), ((lo, hi), whole_y, (0, VX))))
+            z += k
+            continue
+        y = y0
+        while y < y1:
+            ylo, yhi = _rescale_hull(y, y + 1, VY, fy)
+            k = 1
+            while y + k < y1:
+                more = _rescale_hull(y, y + k + 1, VY, fy)[1]
+                if not fits(1, hi - lo, k + 1, more - ylo):
+                    break
+                k, yhi = k + 1, more
+            slabs.append((((z, z + 1), (y, y + k), (x0, x1)), ((lo, hi), (ylo, yhi), (0, VX))))
+            y += k
+        z += 1
+    return slabs[rank::world_size]
+
+
+def volume_rescale(volume, step, out=None, start=None, size=None, chunk_bytes=None, rank=0, world_size=1, device=None,
+                   stats=None):
+    """A uint8 array-like `volume` indexed [z, y, x] (ndarray, np.memmap, h5py / zarr dataset), or one image [y, x] with
+    a 2-element step, brought onto a grid of another voxel size: the step between two EM domains that seldom share one
+    (4 nm against 8 nm FIB-SEM; 4 x 4 x 40 nm ssTEM against 8 nm isotropic) -- once over a training volume ahead of
+    volume3d_ng, over the input ahead of predict_volume, and the inverse step on the way back.  Intensities only: a
+    label volume needs nearest or majority, which this is not.
+
+    `step` holds one step per axis in (x, y, z) order, each an int, a Fraction or a (p, q) pair (or is one int or
+    Fraction for every axis; rescale_step derives it from two voxel sizes): the output voxel's edge in source voxels,
+    p / q in lowest terms with 1 <= p, q <= 64 and 1/8 <= p / q <= 8.  An axis of n voxels gives ceil(n q / p), anchored
+    at voxel 0 (rescale_shape).  Where an axis shrinks the output is the area average over the source voxels it covers,
+    those that exist (tem_u8_pool2's rule at step 2); where it grows, linear interpolation between voxel centres,
+    clamped at the faces (scipy.ndimage.zoom(order=1, mode="nearest", grid_mode=True)).  The three axes' integer
+    weights multiply, and the voxel is rounded once, half up: (2 S + Den) // (2 Den) -- rescale_taps has the rule,
+    numpy reproduces it bit for bit, and a voxel does not depend on the slab, ROI or rank it was computed in.
+
+    `start` / `size` are an ROI of the OUTPUT grid in (x, y, z) order (default: the whole grid); `out` is a writable
+    uint8 array-like of the ROI's shape (allocated when None) and is returned.  Out of core as clahe_volume: the ROI is
+    cut into output slabs and the read slabs that hold their taps (rescale_chunks), both at most `chunk_bytes`; host
+    thread -> pinned -> H2D -> one tem_u8_rescale launch per slab -> D2H -> host write, on double buffers, in the order
+    write(k), read(k + 2) on the one host thread.  Ranks (rank / world_size) take slabs round-robin and write disjoint
+    boxes of a shared `out`.  `stats` receives `read_s`, `write_s` and `chunks`.
+
+    There is no rescale= keyword on predict_cube / predict_volume: a rescaled chunk's footprint would need hull logic
+    of its own inside chunk_plan.  Rescale, then predict.
+
+    ValueError, before any GPU work: a volume that is not uint8, a bad step, an ROI outside the output grid, an `out` of
+    another shape or dtype."""
+    _check_u8(volume)
+    vshape = tuple(int(v) for v in volume.shape)
+    one = len(vshape) == 2
+    grid = rescale_shape(vshape, step)
+    steps = _rescale_steps(step, len(vshape)) + ((Fraction(1),) if one else ())      # (x, y, z)
+    try:
+        box = hist_box(grid, start, size)
+    except ValueError as e:
+        raise ValueError(f"volume_rescale: start / size are an ROI of the output grid of shape {grid}: {e}")
+    shape = tuple(hi - lo for lo, hi in box)
+    want = shape[1:] if one else shape
+    if out is None:
+        out = np.zeros(want, np.uint8)
+    elif tuple(out.shape) != want or getattr(out, "dtype", None) != np.uint8:
+        raise ValueError(f"out must be uint8 of the ROI's shape {want}, got {getattr(out, 'dtype', None)} "
+                         f"{tuple(out.shape)}")
+    vol3 = (1,) + vshape if one else vshape
+    chunks = rescale_chunks(box, vol3, steps, chunk_bytes, rank, world_size)
+    p = _SlabPass([volume], [hist_box(vshape)], chunk_bytes, rank, world_size, device, slabs=[r for _, r in chunks])
+    lib = H.require_gpu()
+    oslabs = [o for o, _ in chunks]
+    odims = [tuple(hi - lo for lo, hi in o) for o in oslabs]
+    pq = [v for f in reversed(steps) for v in (f.numerator, f.denominator)]          # pz, qz, py, qy, px, qx
+    dst_vol = _OneSection(out) if one else out
+    (oz, _), (oy, _), (ox, _) = box
+    p.st["write_s"] = 0.0
+
+    def write_from(k, flat):            # host thread: the slab's box of `out`
+        (z0, z1), (y0, y1), (x0, x1) = oslabs[k]
+        dst_vol[z0 - oz:z1 - oz, y0 - oy:y1 - oy, x0 - ox:x1 - ox] = flat.reshape(odims[k])
+
+    with p.streaming():
+        with _OutputStream([int(np.prod(d)) for d in odims], write_from, p.dev, p.pool, p.st,
+                           own_buffers=True) as outp:                    # the reader's thread: write(k), read(k + 2)
+            for k, slab, d, (src,) in p:
+                _lib.check(lib.tem_u8_rescale(src.data_ptr(), *d, *(lo for lo, _ in slab), *vol3, *pq,
+                                              outp.device(k).data_ptr(), *odims[k], *(lo for lo, _ in oslabs[k]),
+                                              p.compute.cuda_stream), "tem_u8_rescale")
+                p.release_on = p.compute.record_event()                  # behind the kernel: the input is free too
+                outp.put(k, p.release_on)
+    if stats is not None:
+        stats.update(p.st)
+    return out
 
 
 def _check_compare(compare, vol_shape, stats):
