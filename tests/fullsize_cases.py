@@ -15,8 +15,11 @@ planes the shorter input no longer produces -- while k / s / p, offsets and orig
 import numpy as np
 import torch
 
+import bf16_exact
 from util import rel_err
 
+# bf16 outputs: the max-norm bar below and, for the rows exact_checked names, every stored element against the rounded
+# float64 reference (bf16_exact.py: 4 x the sequential float32 sum's error plus four epilogue roundings, <= 10 % undecided)
 TOL_BF16 = 6e-3           # test_gpu_bf16.TOL: one bf16 ulp at the top of the range is 2^-8 = 3.9e-3
 TOL_BF16_SLAB = 2e-5      # fp32 slabs from bf16 operands: exact products, fp32 summation order (test_gpu_bf16.py)
 TOL_FP32 = 3e-5           # test_gpu_fullsize_oracle.py: the direct fp32 forms
@@ -306,10 +309,14 @@ def build_conv(H, c, N, is3d, bf16, rng=None, device="cuda", plant=False):
     return launch, d
 
 
-def conv_reference(T, oracle_lib, d):
-    """float64 result of the row on the operands build_conv drew: (N, ..., co0 + co1)."""
+def conv_reference(T, oracle_lib, d, mag=False, act=True):
+    """float64 result of the row on the operands build_conv drew: (N, ..., co0 + co1).  mag: the same operation on the
+    magnitudes of inputs, kernel, bias and add, with the gate's and the dropout's factors as the row applies them (the S
+    of bf16_exact.store_interval).  act=False leaves out the final LeakyReLU."""
     c, X = d["c"], d["X"]
     k, s, p, m = c["k"], c["s"], c["p"], c["m"]
+    if mag:
+        d = dict(d, **{key: np.abs(d[key]) for key in ("x0", "x1", "w", "bias", "add") if d.get(key) is not None})
     x = d["x0"] if d["x1"] is None else np.concatenate([d["x0"], d["x1"]], -1)
     w = d["w"]
     if c["T"]:
@@ -331,34 +338,62 @@ def conv_reference(T, oracle_lib, d):
         y0 = np.where(d["saved"] > 0, y0, np.float32(c["gate"]) * y0)
     if c["drop"] is not None:
         org, full, mode = c["drop"]
-        if mode == 2:
-            keep = d["bits"]
-        else:
-            keep = oracle_lib.dropout_mask(X.shape(full, co0, out=True), SEED, SITE, STEP)
-        d["keep"] = X.win(keep, org, m, out=True)
+        if "keep" not in d:
+            if mode == 2:
+                keep = d["bits"]
+            else:
+                keep = oracle_lib.dropout_mask(X.shape(full, co0, out=True), SEED, SITE, STEP)
+            d["keep"] = X.win(keep, org, m, out=True)
         y0 = np.where(d["keep"] > 0, 2.0 * y0, 0.0)
     y = np.concatenate([y0, y[..., co0:]], -1) if c["co1"] else y0
-    if c["slope"] != 1.0:
+    if act and c["slope"] != 1.0:
         y = np.where(y > 0, y, np.float32(c["slope"]) * y)
     return y
 
 
-def check_conv(H, T, oracle_lib, c, N, is3d, bf16, seed, plant=False):
-    """Build, check the kernel symbol, run, compare; returns the measured errors of out0 (and out1)."""
+EXACT_MAX = 1 << 22       # full-depth bf16 rows with more output elements keep the max-norm bar only (see exact_checked)
+
+
+def exact_checked(c, N, is3d):
+    """Whether check_conv holds the bf16 row's stores element by element to the rounded float64 reference
+    (bf16_exact.py), which takes a second float64 pass of the oracle on magnitudes: every thin row, and every full-depth
+    row of at most EXACT_MAX output elements -- at 132^3 a second pass takes longer than a test here should."""
+    elems = N * c["m"] ** (3 if is3d else 2) * (c["co0"] + c["co1"])
+    return c.get("depth") is not None or elems <= EXACT_MAX
+
+
+def check_conv(H, T, oracle_lib, c, N, is3d, bf16, seed, plant=False, report=None):
+    """Build, check the kernel symbol, run, compare; returns the measured errors of out0 (and out1).  report: a dict
+    that receives the figures (errs, tol, and the exact check's counts) before anything is asserted."""
     launch, d = build_conv(H, c, N, is3d, bf16, np.random.default_rng(seed), plant=plant)
     assert launch.meta["kernel"] == c["kernel"], (c["name"], launch.meta["kernel"])
     H.run([launch]); torch.cuda.synchronize()
     if c.get("depth") is not None:
         for big in d["big"]:                                   # nothing written outside the window
             assert torch.isnan(big[:, :GUARD]).all() and torch.isnan(big[:, -GUARD:]).all(), (c["name"], "guard planes written")
-    ref = conv_reference(T, oracle_lib, d)
+    pre = conv_reference(T, oracle_lib, d, act=False)
+    ref = np.where(pre > 0, pre, np.float32(c["slope"]) * pre) if c["slope"] != 1.0 else pre
     tol = TOL_BF16 if bf16 else (TOL_FP32_WINO if launch.meta["kernel"].startswith("wino_conv_k") else TOL_FP32)
     co0 = c["co0"]
-    errs = [rel_err(d["out0"].float().cpu().numpy(), ref[..., :co0])]
+    got = [d["out0"].float().cpu().numpy()] + ([d["out1"].float().cpu().numpy()] if c["co1"] else [])
+    errs = [rel_err(got[0], ref[..., :co0])]
     if c["co1"]:
-        errs.append(rel_err(d["out1"].float().cpu().numpy(), ref[..., co0:]))
+        errs.append(rel_err(got[1], ref[..., co0:]))
     print(f"{c['name']} {launch.meta['kernel']}: rel_err", *(f"{e:.2e}" for e in errs))
+    exact = None
+    if bf16 and exact_checked(c, N, is3d):
+        # the stores element by element: S from a second pass on magnitudes, the LeakyReLU slope where the reference is
+        # clear of 0 (bf16_exact.epilogue64); K = k^dims (ci0 + ci1), an upper bound for the transposed forms
+        K = c["k"] ** (3 if is3d else 2) * (c["ci0"] + c["ci1"])
+        r64, S = bf16_exact.epilogue64(pre, conv_reference(T, oracle_lib, d, mag=True, act=False), K, slope=c["slope"])
+        exact = bf16_exact.check_bf16_stores(np.concatenate(got, -1), r64, S, K, f"{c['name']} {launch.meta['kernel']}")
+    if report is not None:
+        report.update(errs=errs, tol=tol, exact=exact)
     assert all(e < tol for e in errs), (c["name"], launch.meta["kernel"], errs)     # (NaN: an output voxel not written)
+    if exact is not None:
+        assert exact["undecided"] <= bf16_exact.UNDECIDED_CAP, (c["name"], "undecided share", exact["undecided"])
+        assert exact["fails"] == 0, (c["name"], launch.meta["kernel"], f"{exact['fails']} of {exact['total']} stored bf16 "
+                                     "values outside the rounded reference", exact["first"])
     if c["drop"] is not None and c["drop"][2] == 1:
         # the launch drew the keep bits itself and wrote them into the frame's mask: inside its window the oracle's bits
         org, full, _ = c["drop"]

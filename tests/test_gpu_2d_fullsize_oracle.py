@@ -11,7 +11,8 @@ decode of conv2d_bf16_k / convT2d_bf16_k sees grids 32 x larger than the batch-2
 The coverage guards hold each table to its step.
 
 Bars (fullsize_cases.py): bf16 outputs 6e-3, fp32 slabs from bf16 operands 2e-5 (test_gpu_bf16.py); fp32: 3e-5 for the
-direct forms, 1e-5 (3e-6 in the L2 norm) for the kernel gradients (test_gpu_fullsize_oracle.py)."""
+direct forms, 1e-5 (3e-6 in the L2 norm) for the kernel gradients (test_gpu_fullsize_oracle.py).  bf16 rows of at most
+2^22 output elements also hold every stored element to the rounded float64 reference (fullsize_cases.exact_checked)."""
 import pytest
 import torch
 

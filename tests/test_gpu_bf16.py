@@ -4,11 +4,19 @@ v_mfma_f32_16x16x32_bf16, fp32 master weights / slabs / Adam.
 The reference is fp32 only (cgan.py:13-14), so this mode is a build extension; its oracle is the same CPU
 restatement evaluated on the bf16-ROUNDED operands (inputs, kernels, every stored activation), compared at a
 tolerance set by bf16's 8-bit significand: outputs are rounded to bf16 on store (relative error up to 2^-9 per
-value) and the fp32 accumulation order differs from the oracle's double sums.  PARITY UNPINNED, as for fp32."""
+value) and the fp32 accumulation order differs from the oracle's double sums.  PARITY UNPINNED, as for fp32.
+
+TOL is a max-norm bar: 1.5 bf16 ulp of the tensor's LARGEST value, under which a small element may be far off and a
+truncating store passes.  Next to it every convolution case holds each stored element to the round-to-nearest-even
+bf16 of the float64 reference (`stores`, bf16_exact.py): the interval around the reference is 4 x the sequential
+float32 sum's own error against float64 (gamma(K), measured from the reference alone, table in bf16_exact.py) plus
+four fp32 roundings of the epilogue, both relative to the same operation on magnitudes; where that interval holds a
+rounding tie either neighbour passes, and at most 10 % of a case's elements may be undecided in that way."""
 import numpy as np
 import pytest
 import torch
 
+import bf16_exact
 from util import rel_err
 
 pytestmark = pytest.mark.gpu
@@ -42,6 +50,36 @@ def rnd(rng, *shape):
     return rng.standard_normal(shape).astype(np.float32)
 
 
+def pm(fn, arrays, *rest):
+    """(float64 result, the same operation on magnitudes) of an operator of oracle/torch_ops.py (float64 throughout;
+    oracle.ops returns float32) on the arrays (None passes through): the pair bf16_exact.store_interval starts from."""
+    return (np.array(fn(*arrays, *rest), np.float64),
+            np.array(fn(*[None if a is None else np.abs(a) for a in arrays], *rest), np.float64))
+
+
+def add_window(pair, addw, crop):
+    """The skip-gradient window added to the interior of (reference, magnitudes), as the kernels add it before the gate."""
+    pair[0][crop] += addw
+    pair[1][crop] += np.abs(addw)
+    return pair
+
+
+def stores(name, out, pair, K, **epilogue):
+    """Hold the bf16 tensor `out` element by element to the rounded float64 reference (bf16_exact.py): pair = (result
+    before gate / dropout / slope, its magnitudes), K = k^dims * C_in products per output (an upper bound for the
+    transposed forms), epilogue = saved / gate_slope / keep / slope of bf16_exact.epilogue64."""
+    ref, S = bf16_exact.epilogue64(pair[0], pair[1], K, **epilogue)
+    got = out.float().cpu().numpy() if torch.is_tensor(out) else out
+    return bf16_exact.assert_bf16_stores(got, ref, S, K, name)
+
+
+@pytest.fixture(scope="module")
+def T64():
+    from oracle import torch_ops
+    torch.set_num_threads(min(16, len(__import__("os").sched_getaffinity(0))))
+    return torch_ops
+
+
 FWD = [(1, 8, 3, 1, 0, 21), (8, 8, 3, 1, 0, 18), (8, 16, 3, 1, 0, 14), (16, 16, 3, 1, 0, 17), (16, 32, 3, 1, 0, 11),
        (32, 32, 3, 1, 0, 10), (32, 16, 3, 1, 0, 10), (16, 1, 3, 1, 0, 19), (8, 8, 4, 2, 0, 20), (16, 16, 4, 2, 0, 15),
        (32, 32, 4, 2, 0, 12), (8, 16, 4, 2, 1, 14), (16, 32, 4, 2, 1, 10), (32, 32, 1, 1, 0, 6), (32, 1, 1, 1, 0, 6),
@@ -49,7 +87,7 @@ FWD = [(1, 8, 3, 1, 0, 21), (8, 8, 3, 1, 0, 18), (8, 16, 3, 1, 0, 14), (16, 16, 
 
 
 @pytest.mark.parametrize("CI,CO,k,s,pad,n", FWD)
-def test_conv_bf16_forward(H, oracle_lib, CI, CO, k, s, pad, n):
+def test_conv_bf16_forward(H, oracle_lib, T64, CI, CO, k, s, pad, n):
     rng = np.random.default_rng(CI * 1000 + CO * 10 + k)
     x = rb(rnd(rng, 2, n, n, n + 1, CI))
     w = rb(rnd(rng, k, k, k, CI, CO) * 0.2)
@@ -64,10 +102,12 @@ def test_conv_bf16_forward(H, oracle_lib, CI, CO, k, s, pad, n):
     c1out = CO == 1 and k == 3 and CI in (8, 16)
     assert launch.meta["kernel"].startswith("c1out_h_k" if c1out else "conv3_bf16_k" if marching else "conv_bf16_k")
     assert rel_err(out.float().cpu().numpy(), ref) < TOL
+    stores(f"forward {CI}->{CO} k{k} s{s} p{pad} {launch.meta['kernel']}", out,
+           pm(T64.conv_fwd, (xin, w), s, max(pad, 0), bias), k ** 3 * CI, slope=0.3)
 
 
 @pytest.mark.parametrize("CI", [8, 16])
-def test_conv_bf16_one_output_channel(H, oracle_lib, CI):
+def test_conv_bf16_one_output_channel(H, oracle_lib, T64, CI):
     """c1out_h_k: the one-output-channel 3x3x3 layers with bf16 tensors (fragments straight from global memory, one bf16
     MFMA per 16 voxels and n-tile, fp32 shifted sum through LDS): forward with bias + LeakyReLU on a ragged batch-2 volume
     (patches of 16 x 16 columns with partial edges, two z-runs), and the input-gradient form of a 1 -> CI layer (flipped
@@ -82,6 +122,7 @@ def test_conv_bf16_one_output_channel(H, oracle_lib, CI):
     H.run([launch])
     assert launch.meta["kernel"].startswith("c1out_h_k"), launch.meta["kernel"]
     assert rel_err(out.float().cpu().numpy(), ref) < TOL
+    stores(f"c1out forward {CI}->1", out, pm(T64.conv_fwd, (x, w), 1, 0, bias), 27 * CI, slope=0.3)
     g = rb(rnd(rng, 2, 9, 18, 31, CI))
     wf = rb(rnd(rng, 3, 3, 3, 1, CI) * 0.3)
     shape = (2, 11, 20, 33, 1)
@@ -92,10 +133,11 @@ def test_conv_bf16_one_output_channel(H, oracle_lib, CI):
     H.run([launch])
     assert launch.meta["kernel"].startswith("c1out_h_k"), launch.meta["kernel"]
     assert rel_err(out.float().cpu().numpy(), ref) < TOL
+    stores(f"c1out input gradient {CI}->1", out, pm(T64.conv_bwd_data, (g, wf), shape), 27 * CI, saved=saved)
 
 
 @pytest.mark.parametrize("CO", [8, 16])
-def test_conv_bf16_one_input_channel(H, oracle_lib, CO):
+def test_conv_bf16_one_input_channel(H, oracle_lib, T64, CO):
     """c1_mfma_h_k: the one-input-channel 3x3x3 layers with bf16 tensors (fp32 LDS patch widened by the loader, fp32 MFMAs,
     8-byte bf16 stores): forward with LeakyReLU, and the input-gradient form (flipped taps, padding 2, gate), batch 2."""
     rng = np.random.default_rng(CO)
@@ -107,6 +149,7 @@ def test_conv_bf16_one_input_channel(H, oracle_lib, CO):
     H.run([launch])
     assert launch.meta["kernel"].startswith("c1_mfma_h_k"), launch.meta["kernel"]
     assert rel_err(out.float().cpu().numpy(), ref) < TOL
+    stores(f"c1 forward 1->{CO}", out, pm(T64.conv_fwd, (x, w), 1, 0), 27, slope=0.3)
     # input-gradient of a CO -> 1 forward layer: operator 1 -> CO with the forward kernel (tap, CO, 1), gate = the saved input
     g = rb(rnd(rng, 2, 7, 10, 20, 1))
     wf = rb(rnd(rng, 3, 3, 3, CO, 1) * 0.3)
@@ -118,10 +161,11 @@ def test_conv_bf16_one_input_channel(H, oracle_lib, CO):
     H.run([launch])
     assert launch.meta["kernel"].startswith("c1_mfma_h_k"), launch.meta["kernel"]
     assert rel_err(out.float().cpu().numpy(), ref) < TOL
+    stores(f"c1 input gradient 1->{CO}", out, pm(T64.conv_bwd_data, (g, wf), shape), 27, saved=saved)
 
 
 @pytest.mark.parametrize("CI,CO", [(8, 8), (8, 16), (16, 8), (16, 16), (16, 32), (32, 16), (32, 32)])
-def test_conv3_bf16_marching_kernel(H, oracle_lib, CI, CO):
+def test_conv3_bf16_marching_kernel(H, oracle_lib, T64, CI, CO):
     """conv3_bf16_k (z-marching 3x3x3 kernel, LDS-DMA ring with permuted channel chunks): forward on a ragged non-cubic
     batch-2 volume, and the input-gradient form (flipped taps, padding 2, LeakyReLU' gate + skip-gradient window)."""
     rng = np.random.default_rng(CI * 100 + CO)
@@ -133,6 +177,7 @@ def test_conv3_bf16_marching_kernel(H, oracle_lib, CI, CO):
     H.run([launch])
     assert launch.meta["kernel"].startswith("conv3_bf16_k")
     assert rel_err(out.float().cpu().numpy(), ref) < TOL
+    stores(f"conv3 forward {CI}->{CO}", out, pm(T64.conv_fwd, (x, w), 1, 0), 27 * CI, slope=0.3)
     # input-gradient of a CO -> CI forward layer: operator CI -> CO with the forward kernel (tap, ci_f = CO, co_f = CI)
     g = rb(rnd(rng, 2, 7, 12, 29, CI))
     wf = rb(rnd(rng, 3, 3, 3, CO, CI) * 0.2)
@@ -149,10 +194,13 @@ def test_conv3_bf16_marching_kernel(H, oracle_lib, CI, CO):
     H.run([launch])
     assert launch.meta["kernel"].startswith("conv3_bf16_k")
     assert rel_err(out.float().cpu().numpy(), ref) < TOL
+    inner = np.s_[:, 1:-1, 1:-1, 1:-1, :]
+    stores(f"conv3 input gradient {CI}->{CO}", out, add_window(pm(T64.conv_bwd_data, (g, wf), shape), addw, inner), 27 * CI,
+           saved=saved)
 
 
 @pytest.mark.parametrize("CI,CO", [(8, 8), (8, 16), (16, 16), (16, 32)])
-def test_conv3_bf16_marching_kernel_k4s2(H, oracle_lib, CI, CO):
+def test_conv3_bf16_marching_kernel_k4s2(H, oracle_lib, T64, CI, CO):
     """conv3_bf16_k<.., 4, 2, ..>: the 4x4x4 stride-2 form (6-slot ring, two new planes per step, tile pairs inside an output
     row): padded forward on a ragged batch-2 volume, and an un-padded launch with gate + skip-gradient window."""
     rng = np.random.default_rng(CI * 10 + CO)
@@ -164,6 +212,7 @@ def test_conv3_bf16_marching_kernel_k4s2(H, oracle_lib, CI, CO):
     H.run([launch])
     assert launch.meta["kernel"].startswith("conv3_bf16_k"), launch.meta["kernel"]
     assert rel_err(out.float().cpu().numpy(), ref) < TOL
+    stores(f"conv3 k4 s2 p1 {CI}->{CO}", out, pm(T64.conv_fwd, (x, w), 2, 1), 64 * CI, slope=0.3)
     x = rb(rnd(rng, 1, 10, 16, 36, CI))
     full = oracle_lib.conv_fwd(x, w, 2, 0, None)
     saved = rb(rnd(rng, *full.shape))
@@ -176,9 +225,11 @@ def test_conv3_bf16_marching_kernel_k4s2(H, oracle_lib, CI, CO):
     H.run([launch])
     assert launch.meta["kernel"].startswith("conv3_bf16_k"), launch.meta["kernel"]
     assert rel_err(out.float().cpu().numpy(), ref) < TOL
+    stores(f"conv3 k4 s2 p0 gate + add {CI}->{CO}", out,
+           add_window(pm(T64.conv_fwd, (x, w), 2, 0), addw, np.s_[:, 1:-1, 1:-1, 1:-1, :]), 64 * CI, saved=saved)
 
 
-def test_conv3_bf16_columns_segments_concat_split(H, oracle_lib):
+def test_conv3_bf16_columns_segments_concat_split(H, oracle_lib, T64):
     """conv3_bf16_k across several output columns and z segments (a volume wider than one ring row allows at 32
     channels), a concat input (two tensors behind one buffer descriptor) and split outputs without dropout."""
     rng = np.random.default_rng(5)
@@ -190,6 +241,7 @@ def test_conv3_bf16_columns_segments_concat_split(H, oracle_lib):
     H.run([launch])
     assert launch.meta["kernel"].startswith("conv3_bf16_k")
     assert rel_err(out.float().cpu().numpy(), ref) < TOL
+    stores("conv3 columns 32->16", out, pm(T64.conv_fwd, (x, w), 1, 0), 27 * 32, slope=0.3)
     x = rb(rnd(rng, 1, 44, 38, 41, 16))
     w = rb(rnd(rng, 3, 3, 3, 16, 16) * 0.1)
     ref = oracle_lib.leaky_relu(oracle_lib.conv_fwd(x, w, 1, 0, None))
@@ -197,6 +249,7 @@ def test_conv3_bf16_columns_segments_concat_split(H, oracle_lib):
     launch = H.conv_launch("t", devb(x), pack(w), out, 3, 1, 0, slope=0.3)
     H.run([launch])
     assert rel_err(out.float().cpu().numpy(), ref) < TOL
+    stores("conv3 z segments 16->16", out, pm(T64.conv_fwd, (x, w), 1, 0), 27 * 16, slope=0.3)
     # concat [a | crop(b)] in, then the input-gradient split 8 | 8 (gate on the first half only)
     a = rb(rnd(rng, 1, 12, 13, 22, 8))
     bb = rb(rnd(rng, 1, 15, 16, 25, 8))
@@ -209,6 +262,7 @@ def test_conv3_bf16_columns_segments_concat_split(H, oracle_lib):
     H.run([launch])
     assert launch.meta["kernel"].startswith("conv3_bf16_k")
     assert rel_err(o2.float().cpu().numpy(), ref) < TOL
+    stores("conv3 concat 8|8->16", o2, pm(T64.conv_fwd, (cat, wf), 1, 0), 27 * 16, slope=0.3)
     g = rb(rnd(rng, *ref.shape))
     full = oracle_lib.conv_bwd_data(g, wf, cat.shape)
     ref0 = oracle_lib.leaky_relu_grad_from_out(full[..., :8], a)
@@ -219,10 +273,13 @@ def test_conv3_bf16_columns_segments_concat_split(H, oracle_lib):
     H.run([launch])
     assert launch.meta["kernel"].startswith("conv3_bf16_k")
     assert rel_err(d0.float().cpu().numpy(), ref0) < TOL and rel_err(d1.float().cpu().numpy(), ref1) < TOL
+    pre, mag = pm(T64.conv_bwd_data, (g, wf), cat.shape)
+    stores("conv3 split 16->8|8, gated half", d0, (pre[..., :8], mag[..., :8]), 27 * 16, saved=a)
+    stores("conv3 split 16->8|8, plain half", d1, (pre[..., 8:], mag[..., 8:]), 27 * 16)
 
 
 @pytest.mark.parametrize("CI,CO", [(16, 8), (32, 16), (8, 8), (16, 16), (32, 32)])
-def test_conv_transpose_bf16(H, oracle_lib, CI, CO):
+def test_conv_transpose_bf16(H, oracle_lib, T64, CI, CO):
     """k4 s2 transposed convolution (parity-class GEMM) in bf16: shifted windows, gate + add, batch 2."""
     rng = np.random.default_rng(CI * 3 + CO)
     w = rb(rnd(rng, 4, 4, 4, CO, CI) * 0.1)
@@ -241,9 +298,13 @@ def test_conv_transpose_bf16(H, oracle_lib, CI, CO):
         H.run([launch])
         assert launch.meta["kernel"].startswith("convT_bf16_k")
         assert rel_err(out.float().cpu().numpy(), ref) < TOL, (n, pad, lo, osz)
+        pre, mag = pm(T64.convT_fwd, (x, w), 2, pad, (2 * n + 2 - 2 * pad,) * 3)
+        cut = np.s_[:, lo:lo + osz, lo:lo + osz, lo:lo + osz, :]
+        stores(f"convT {CI}->{CO} n{n} p{pad} window {lo}+{osz}", out,
+               add_window((pre[cut].copy(), mag[cut].copy()), addw, np.s_[:, 1:-1, 1:-1, 1:-1, :]), 64 * CI, saved=saved)
 
 
-def test_conv_bf16_dropout_mask_concat_split(H, oracle_lib):
+def test_conv_bf16_dropout_mask_concat_split(H, oracle_lib, T64):
     """Dropout keep mask written by the bf16 transposed convolution (forward) and read by the bf16 input-gradient
     through a concat (split 8|8 outputs, gate on the first half only) -- the same Philox bits as the oracle's."""
     rng = np.random.default_rng(11)
@@ -261,6 +322,7 @@ def test_conv_bf16_dropout_mask_concat_split(H, oracle_lib):
                          keep_mask=(mask, 1))])
     assert np.array_equal(np.unpackbits(mask.cpu().numpy(), bitorder="little").astype(bool), keep.reshape(-1))
     assert rel_err(out.float().cpu().numpy(), ref_fwd) < TOL
+    stores("convT 16->8 dropout + LeakyReLU", out, pm(T64.convT_fwd, (x, w), 2, 1), 64 * 16, keep=keep, slope=0.3)
     # input-gradient of a 16 -> 16 k3 conv whose input was concat([up (dropout+lrelu), skip]): split outputs
     g = rb(rnd(rng, 1, 2 * n - 2, 2 * n - 2, 2 * n - 2, 16))
     wf = rb(rnd(rng, 3, 3, 3, 16, 16) * 0.1)                 # Keras forward kernel (tap, ci, co)
@@ -280,6 +342,10 @@ def test_conv_bf16_dropout_mask_concat_split(H, oracle_lib):
     assert np.array_equal(res[0][0] == 0, res[1][0] == 0)
     assert rel_err(res[0][0], res[1][0]) < TOL and rel_err(res[0][1], res[1][1]) < TOL
     assert rel_err(res[0][0], ref0) < TOL and rel_err(res[0][1], ref1) < TOL
+    pre, mag = pm(T64.conv_bwd_data, (g, wf), (1, 2 * n, 2 * n, 2 * n, 16))
+    for (d0, d1), how in zip(res, ("bits drawn again (conv_bf16_k)", "mask read (conv3_bf16_k)")):
+        stores(f"split 16->8|8 gate + dropout, {how}", d0, (pre[..., :8], mag[..., :8]), 27 * 16, saved=up, keep=keep)
+        stores(f"split 16->8|8 plain half, {how}", d1, (pre[..., 8:], mag[..., 8:]), 27 * 16)
     # concat on the input side: conv over [up | crop(skip)]
     skip = rb(rnd(rng, 1, 2 * n + 3, 2 * n + 3, 2 * n + 3, 8))
     cat = np.concatenate([up, skip[:, 1:-2, 1:-2, 1:-2, :]], -1)
@@ -288,6 +354,7 @@ def test_conv_bf16_dropout_mask_concat_split(H, oracle_lib):
     sk = devb(skip)
     H.run([H.conv_launch("t", out, pack(wf), o2, 3, in1=H.crop(sk, 1, 2), slope=0.3)])
     assert rel_err(o2.float().cpu().numpy(), ref) < TOL
+    stores("concat [up | crop(skip)] 16->16", o2, pm(T64.conv_fwd, (cat, wf), 1, 0), 27 * 16, slope=0.3)
 
 
 class _P:          # minimal stand-in for a ParamSet: one layer "w"

@@ -3,7 +3,9 @@ and the 2-D train step / inference built on them.
 
 The bars are those of test_gpu_bf16.py (3-D): the oracle evaluated on bf16-rounded operands, TOL for outputs rounded
 to bf16 on store, 2e-5 for the fp32 kernel-gradient slabs, and the step thresholds of
-test_train_step_bf16_matches_oracle.  Every operator case also checks that the 2-D kernel, not a fallback, ran."""
+test_train_step_bf16_matches_oracle.  Every operator case also checks that the 2-D kernel, not a fallback, ran, and
+holds every stored bf16 element to the rounded float64 reference (test_gpu_bf16.stores / bf16_exact.py: 4 x the
+sequential float32 sum's error plus four epilogue roundings; at most 10 % of a case's elements next to a tie)."""
 import re
 
 import numpy as np
@@ -11,7 +13,7 @@ import pytest
 import torch
 
 from util import rel_err
-from test_gpu_bf16 import TOL, rb, devb, rnd, _inputs, _l2
+from test_gpu_bf16 import TOL, rb, devb, rnd, _inputs, _l2, pm, add_window, stores, T64  # noqa: F401 (T64: a fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -44,8 +46,13 @@ FWD2 = [(1, 8, 3, 1, 0, 37, 45), (1, 16, 3, 1, 0, 33, 29), (8, 8, 3, 1, 0, 31, 4
         (1, 8, 3, 1, 5, 13, 17), (16, 8, 3, 1, -1, 21, 24)]
 
 
+def fwd2_launch(H, x, wk, out, k, s, pad, bias=None):
+    """The launch of test_conv2d_bf16_forward (test_bf16_exact.py builds it on uninitialised host tensors for its symbol)."""
+    return H.conv_launch("t", x, wk, out, k, s, pad, is3d=False, slope=0.3, bias=bias)
+
+
 @pytest.mark.parametrize("CI,CO,k,s,pad,h,w", FWD2)
-def test_conv2d_bf16_forward(H, oracle_lib, CI, CO, k, s, pad, h, w):
+def test_conv2d_bf16_forward(H, oracle_lib, T64, CI, CO, k, s, pad, h, w):
     rng = np.random.default_rng(CI * 1000 + CO * 10 + k + h)
     x = img(rng, 2, h, w, CI)
     wk = rb(rnd(rng, 1, k, k, CI, CO) * 0.2)
@@ -53,11 +60,12 @@ def test_conv2d_bf16_forward(H, oracle_lib, CI, CO, k, s, pad, h, w):
     xin = x[:, :, -pad:pad, -pad:pad, :] if pad < 0 else x
     ref = oracle_lib.leaky_relu(oracle_lib.conv_fwd(xin, wk, (1, s, s), (0, max(pad, 0), max(pad, 0)), bias))
     out = torch.empty(ref.shape, dtype=torch.bfloat16, device="cuda")
-    launch = H.conv_launch("t", devb(x), pack2(wk), out, k, s, pad, is3d=False, slope=0.3,
-                           bias=torch.from_numpy(bias).cuda() if bias is not None else None)
+    launch = fwd2_launch(H, devb(x), pack2(wk), out, k, s, pad, torch.from_numpy(bias).cuda() if bias is not None else None)
     H.run([launch])
     _expect(launch, "conv2d_bf16_k")
     assert rel_err(out.float().cpu().numpy(), ref) < TOL
+    stores(f"2-D forward {CI}->{CO} k{k} s{s} p{pad} {h}x{w}", out,
+           pm(T64.conv_fwd, (xin, wk), (1, s, s), (0, max(pad, 0), max(pad, 0)), bias), k * k * CI, slope=0.3)
 
 
 # input-gradients of the k3 s1 layers (flipped taps, pad 2), gated unless they produce the one-channel image gradient
@@ -67,7 +75,7 @@ BWD2 = [(1, 8, 35, 41), (1, 16, 31, 27), (16, 1, 33, 29), (8, 8, 29, 36), (8, 16
 
 
 @pytest.mark.parametrize("FCI,FCO,h,w", BWD2)
-def test_conv2d_bf16_input_gradient(H, oracle_lib, FCI, FCO, h, w):
+def test_conv2d_bf16_input_gradient(H, oracle_lib, T64, FCI, FCO, h, w):
     rng = np.random.default_rng(FCI * 100 + FCO + h)
     g = img(rng, 2, h, w, FCO)
     wf = rb(rnd(rng, 1, 3, 3, FCI, FCO) * 0.2)                # Keras forward kernel (tap, ci, co)
@@ -81,10 +89,11 @@ def test_conv2d_bf16_input_gradient(H, oracle_lib, FCI, FCO, h, w):
     H.run([launch])
     _expect(launch, "conv2d_bf16_k")
     assert rel_err(out.float().cpu().numpy(), ref) < TOL
+    stores(f"2-D input gradient of {FCI}->{FCO} {h}x{w}", out, pm(T64.conv_bwd_data, (g, wf), shape, 1, 0), 9 * FCO, saved=saved)
 
 
 @pytest.mark.parametrize("CI,CO", [(8, 16), (16, 32)])
-def test_conv2d_bf16_k4s2_over_convT_gradient(H, oracle_lib, CI, CO):
+def test_conv2d_bf16_k4s2_over_convT_gradient(H, oracle_lib, T64, CI, CO):
     """Input-gradient of the Conv2DTranspose layers u1b (16 -> 8) and u2b (32 -> 16): a k4 s2 pad-1 convolution
     CI -> CO over the output gradient, gated by the saved input of the layer."""
     rng = np.random.default_rng(CI + CO)
@@ -99,15 +108,25 @@ def test_conv2d_bf16_k4s2_over_convT_gradient(H, oracle_lib, CI, CO):
         H.run([launch])
         _expect(launch, "conv2d_bf16_k")
         assert rel_err(out.float().cpu().numpy(), ref) < TOL, n_in
+        stores(f"2-D k4 s2 p1 gated {CI}->{CO} n{n_in}", out, pm(T64.conv_fwd, (g, wT), (1, 2, 2), (0, 1, 1)), 16 * CI, saved=saved)
 
 
-@pytest.mark.parametrize("CI,CO", [(8, 8), (16, 16), (32, 32)])
-def test_conv_transpose2d_bf16_add_gate(H, oracle_lib, CI, CO):
+CONVT2 = [(8, 8), (16, 16), (32, 32)]
+CONVT2_WINDOWS = ((9, 11, 1, 0, 18), (7, 8, 1, 3, 9), (6, 9, 0, 2, 11))       # (h, w, pad, window origin, window edge)
+
+
+def convT2_launch(H, x, w, out, pad, gate, add):
+    """The launch of test_conv_transpose2d_bf16_add_gate (and of test_bf16_exact.py, on host tensors, for its symbol)."""
+    return H.conv_launch("t", x, w, out, 4, 2, pad, is3d=False, transposed=True, gate=gate, add=add, add_off=1)
+
+
+@pytest.mark.parametrize("CI,CO", CONVT2)
+def test_conv_transpose2d_bf16_add_gate(H, oracle_lib, T64, CI, CO):
     """k4 s2 transposed convolution on convT2d_bf16_k: shifted windows, skip-gradient add + gate (the input-gradients of
     the k4 s2 layers), batch 2."""
     rng = np.random.default_rng(CI * 3 + CO)
     w = rb(rnd(rng, 1, 4, 4, CO, CI) * 0.1)
-    for h, wd, pad, lo, osz in ((9, 11, 1, 0, 18), (7, 8, 1, 3, 9), (6, 9, 0, 2, 11)):
+    for h, wd, pad, lo, osz in CONVT2_WINDOWS:
         x = img(rng, 2, h, wd, CI)
         full = oracle_lib.convT_fwd(x, w, (1, 2, 2), (0, pad, pad), out_dims=(1, 2 * h + 2 - 2 * pad, 2 * wd + 2 - 2 * pad))
         win = full[:, :, lo:lo + osz, lo:lo + osz, :]
@@ -117,15 +136,18 @@ def test_conv_transpose2d_bf16_add_gate(H, oracle_lib, CI, CO):
         ref[:, :, 1:-1, 1:-1, :] += addw
         ref = oracle_lib.leaky_relu_grad_from_out(ref, saved)
         out = torch.empty(ref.shape, dtype=torch.bfloat16, device="cuda")
-        launch = H.conv_launch("t", devb(x), devb(w.reshape(-1)), out, 4, 2, pad + lo, is3d=False, transposed=True,
-                               gate=devb(saved), add=devb(addw), add_off=1)
+        launch = convT2_launch(H, devb(x), devb(w.reshape(-1)), out, pad + lo, devb(saved), devb(addw))
         H.run([launch])
         _expect(launch, "convT2d_bf16_k")
         assert rel_err(out.float().cpu().numpy(), ref) < TOL, (h, wd, pad, lo, osz)
+        pre, mag = pm(T64.convT_fwd, (x, w), (1, 2, 2), (0, pad, pad), (1, 2 * h + 2 - 2 * pad, 2 * wd + 2 - 2 * pad))
+        cut = np.s_[:, :, lo:lo + osz, lo:lo + osz, :]
+        stores(f"2-D convT {CI}->{CO} {h}x{wd} p{pad} window {lo}+{osz}", out,
+               add_window((pre[cut].copy(), mag[cut].copy()), addw, np.s_[:, :, 1:-1, 1:-1, :]), 16 * CI, saved=saved)
 
 
 @pytest.mark.parametrize("CI,CO", [(32, 16), (16, 8)])
-def test_conv_transpose2d_bf16_dropout_then_concat_split(H, oracle_lib, CI, CO):
+def test_conv_transpose2d_bf16_dropout_then_concat_split(H, oracle_lib, T64, CI, CO):
     """u2b / u1b in 2-D: the transposed convolution draws the Dropout keep bits in its epilogue and writes the mask
     (keep_mode 1, the oracle's Philox bits); the input-gradient of the consuming conv over concat([up, crop(skip)])
     splits its output CO | CO, gates and drops the first half reading that mask (keep_mode 2) or drawing it again --
@@ -147,6 +169,8 @@ def test_conv_transpose2d_bf16_dropout_then_concat_split(H, oracle_lib, CI, CO):
     _expect(launch, "convT2d_bf16_k")
     assert np.array_equal(np.unpackbits(mask.cpu().numpy(), bitorder="little").astype(bool), keep.reshape(-1))
     assert rel_err(out.float().cpu().numpy(), ref_fwd) < TOL
+    stores(f"2-D convT {CI}->{CO} dropout + LeakyReLU", out, pm(T64.convT_fwd, (x, w), (1, 2, 2), (0, 1, 1), shape[1:4]),
+           16 * CI, keep=keep, slope=0.3)
     # input-gradient of the 2 CO -> CC k3 conv over concat([up, skip])
     CC = 2 * CO
     g = img(rng, 2, 2 * h - 2, 2 * wd - 2, CC)
@@ -167,6 +191,9 @@ def test_conv_transpose2d_bf16_dropout_then_concat_split(H, oracle_lib, CI, CO):
     assert np.array_equal(res[0][0] == 0, res[1][0] == 0)
     assert np.array_equal(res[0][0], res[1][0]) and np.array_equal(res[0][1], res[1][1])
     assert rel_err(res[0][0], ref0) < TOL and rel_err(res[0][1], ref1) < TOL
+    pre, mag = pm(T64.conv_bwd_data, (g, wf), (2, 1, 2 * h, 2 * wd, 2 * CO), 1, 0)
+    stores(f"2-D split {CC}->{CO}|{CO} gate + dropout", res[0][0], (pre[..., :CO], mag[..., :CO]), 9 * CC, saved=up, keep=keep)
+    stores(f"2-D split {CC}->{CO}|{CO} plain half", res[0][1], (pre[..., CO:], mag[..., CO:]), 9 * CC)
     # forward conv over [up | crop(skip)]
     skip = img(rng, 2, 2 * h + 3, 2 * wd + 3, CO)
     cat = np.concatenate([up, skip[:, :, 1:-2, 1:-2, :]], -1)
@@ -177,6 +204,7 @@ def test_conv_transpose2d_bf16_dropout_then_concat_split(H, oracle_lib, CI, CO):
     H.run([launch])
     _expect(launch, "conv2d_bf16_k")
     assert rel_err(o2.float().cpu().numpy(), ref) < TOL
+    stores(f"2-D concat [up | crop(skip)] {CC}->{CC}", o2, pm(T64.conv_fwd, (cat, wf), 1, 0), 9 * CC, slope=0.3)
 
 
 # kernel gradients (CI, CO, k, s, pad, H, W of the input)

@@ -10,7 +10,10 @@ test_tables_cover_the_step holds the tables to the step: a launch the step gains
 
 Bars (fullsize_cases.py): 6e-3 of the output's largest value for bf16 outputs (test_gpu_bf16.TOL: one bf16 ulp at the top
 of the range, independent of the tensor's size), 2e-5 for the fp32 kernel-gradient slabs (exact products of bf16 values;
-the error is the fp32 summation order, which grows like the entries themselves).  Parity unpinned (oracle/README.md)."""
+the error is the fp32 summation order, which grows like the entries themselves).  Rows of at most 2^22 output elements
+also hold every stored bf16 element to the rounded float64 reference (fullsize_cases.exact_checked, bf16_exact.py); the
+larger ones keep the max-norm bar only, and test_bf16_exact.py checks that each of their kernels runs in a case that
+gets the element-by-element check.  Parity unpinned (oracle/README.md)."""
 import pytest
 import torch
 

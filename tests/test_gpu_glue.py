@@ -5,8 +5,9 @@ weight pack, the flip-transpose and the uint8 boundaries.
 Operands are crops (strided views) of larger tensors wherever the entry point takes a view; the surrounding frame is
 pre-filled with a sentinel and asserted untouched.  Every bar that is not exact is (a) a standing bar of
 test_gpu_ops.py / test_gpu_bf16.py, (b) a bound derived in the comment next to it, or (c) 4x the error of a float32
-NumPy restatement (util.inorm_f32) against the float64 oracle, with the measured figure beside it -- none is taken from
-a kernel's output.  Each test prints its figures before it asserts.
+NumPy restatement (util.inorm_f32, util.focal_*_grad_f32) against the float64 oracle, with the measured figure beside
+it -- none is taken from a kernel's output.  Each test prints its figures before it asserts.  The bf16 focal gradients
+are held element by element, next to TOL_BF16 of the largest gradient: bf16_gradient_stores.
 """
 import ctypes as C
 import functools
@@ -15,7 +16,8 @@ import numpy as np
 import pytest
 import torch
 
-from util import rel_err, inorm_f32
+import bf16_exact
+from util import rel_err, inorm_f32, focal_logits_grad_f32, focal_match_grad_f32
 
 pytestmark = pytest.mark.gpu
 
@@ -151,6 +153,30 @@ def match_input(shape, bf16):
     return a, b, planted
 
 
+def bf16_gradient_stores(name, got, ref, f32, rest, cond=1.0):
+    """The bf16 focal gradients element by element: each stored value within rne_bf16 of an interval around its own
+    float64 reference `ref`.  The relative half-width is 4 x the per-element relative error of the float32 restatement
+    `f32` (util.focal_*_grad_f32: the kernels' formula in NumPy float32, no HIP code) against the float64 oracle, the
+    worst over the elements `rest` -- measured, printed, and for these inputs 3.1e-7 .. 7.1e-7 (focal_match) and
+    1.2e-7 .. 1.7e-6 (focal_logits, per unit of `cond`).
+    cond: the conditioning of the formula itself, where it is not 1.  For target == 1 the base of the modulating factor
+    is 1 - p, and float32 has p only to 2^-24: 1 - p is known to 2^-24 p / (1 - p) = 2^-24 e^z relative, whatever computes
+    it, and mod, dmod and dbase are powers of it.  Un-normalised, the restatement is 9.6e-3 off at z = 11.6 -- a uniform
+    4 x that would be ten bf16 ulps for every element -- so the error is measured per unit of cond = 1 + e^z and the
+    half-width of an element is 4 x that figure x its own cond.  The planted elements keep their separate comparison."""
+    ref = np.asarray(ref, np.float64)
+    cond = np.broadcast_to(np.asarray(cond, np.float64), ref.shape)
+    assert (ref[rest] != 0).all()
+    e = np.abs(f32.astype(np.float64) - ref)[rest] / np.abs(ref[rest]) / cond[rest]
+    rho = float(e.max())
+    lo, hi = bf16_exact.interval(ref[rest], 4 * rho * cond[rest] * np.abs(ref[rest]))
+    r = bf16_exact.check_bounds(got[rest], ref[rest], lo, hi, f"{name}: float32 restatement {rho:.2e}, half-width 4 x that", rho=rho)
+    assert rho < 4e-6, (name, rho)                        # the restatement itself: a few float32 roundings
+    assert r["undecided"] <= bf16_exact.UNDECIDED_CAP, (name, r["undecided"])
+    assert r["fails"] == 0, (name, r["fails"], r["total"], r["first"])
+    return r
+
+
 def _check_loss_slots(got, mask, want, bar):
     on = [k for k in range(8) if mask >> k & 1]
     off = [k for k in range(8) if not mask >> k & 1]
@@ -187,6 +213,10 @@ def test_focal_logits(H, oracle_lib, bf16, gamma):
             e_p = rel_err(dz[planted], 3 * g_ref[planted]) if planted.any() else 0.0
             print(f"focal_logits bf16={bf16} gamma={gamma} {shape} t={target}: loss {e_l:.2e} grad {e_g:.2e} planted {e_p:.2e}")
             assert e_g < tol and e_p < tol, (shape, target, e_g, e_p)
+            if bf16:
+                bf16_gradient_stores(f"focal_logits gamma={gamma} {shape} t={target}", dz, 3 * g_ref,
+                                     focal_logits_grad_f32(z, target, gamma, 3.0), ~planted,
+                                     cond=1 + target * np.exp(z.astype(np.float64)))
             assert dzf.frame_ok()
         assert same_bits(host(zv.contiguous()), z)                       # the input is only read
 
@@ -214,6 +244,9 @@ def test_focal_match(H, oracle_lib, bf16, gamma):
             e_p = rel_err(db[planted], 4 * g_ref[planted])
             print(f"focal_match bf16={bf16} gamma={gamma} {shape} mask={mask:#b}: loss {e_l:.2e} grad {e_g:.2e} planted {e_p:.2e}")
             assert e_g < tol and e_p < tol, (shape, mask, e_g, e_p)
+            if bf16:
+                bf16_gradient_stores(f"focal_match gamma={gamma} {shape} mask={mask:#b}", db, 4 * g_ref,
+                                     focal_match_grad_f32(a, b, gamma, 4.0), ~planted)
             assert dbf.frame_ok()
         assert af.frame_ok() and bf.frame_ok() and same_bits(af.get(), a) and same_bits(bf.get(), b)
 

@@ -14,8 +14,9 @@ and test_gpu_model260.py (the 260^3 forward) stand for those.
 
 Each case runs through oracle/torch_ops.py (float64) on the same -- for bf16 tensors bf16-rounded -- operands under the
 standing bars of fullsize_cases.py: 3e-5 (fp32 direct forms), 1e-5 (Winograd forms), 1e-5 and 3e-6 in L2 (fp32 kernel
-gradients), 6e-3 (bf16 outputs), 2e-5 (bf16 kernel gradients).  Outputs are windows of NaN-filled tensors: a voxel left
-out fails the comparison, a plane written outside the window fails the guard check."""
+gradients), 6e-3 (bf16 outputs), 2e-5 (bf16 kernel gradients); every bf16 convolution row also holds each stored element
+to the rounded float64 reference (fullsize_cases.exact_checked, bf16_exact.py).  Outputs are windows of NaN-filled
+tensors: a voxel left out fails the comparison, a plane written outside the window fails the guard check."""
 import time
 
 import numpy as np
@@ -280,10 +281,15 @@ def test_kernel_gradient_260_step_shapes_bf16(H, T, case):
 @gpu
 @pytest.mark.parametrize("bf16", [False, True], ids=["fp32", "bf16"])
 def test_a_planted_error_fails_its_row(H, T, oracle_lib, bf16):
-    """One tap of g.d1a's kernel scaled by 1.05 on the device, the true kernel in the reference: the row must fail."""
+    """One tap of g.d1a's kernel scaled by 1.05 on the device, the true kernel in the reference: the row must fail --
+    on the max-norm bar and, for bf16 tensors, on the element-by-element check of the stores as well."""
     case = next(c for c in TABLES["bf16" if bf16 else "fp32"][0] if c["name"] == "g.d1a")
+    figures = {}
     with pytest.raises(AssertionError, match="g.d1a"):
-        F.check_conv(H, T, oracle_lib, case, N, IS3D, bf16, seed=1, plant=True)
+        F.check_conv(H, T, oracle_lib, case, N, IS3D, bf16, seed=1, plant=True, report=figures)
+    assert not all(e < figures["tol"] for e in figures["errs"])
+    if bf16:
+        assert figures["exact"]["fails"] > 0.10 * figures["exact"]["total"], figures["exact"]
 
 
 # ------------------------------------------------------------------------------------------------ host: the tables and the step

@@ -33,6 +33,52 @@ def inorm_f32(x, dy, scale, offset, eps=1e-5):
             s2.sum(axis=0).reshape(-1).astype(f), s1.sum(axis=0).reshape(-1).astype(f))
 
 
+def _pow_f32(base, gamma):
+    """(base ** gamma, d / d base) in float32, as the focal kernels' pow_gamma: the multiply path for gamma == 2, a
+    non-finite derivative (0 ** negative) -> 0."""
+    f = np.float32
+    if gamma == 2:
+        return base * base, f(2) * base
+    with np.errstate(all="ignore"):
+        val = np.power(base, f(gamma))
+        grd = f(gamma) * np.power(base, f(gamma) - f(1))
+    return val, np.where(np.isfinite(grd), grd, f(0)).astype(f)
+
+
+def focal_logits_grad_f32(z, target, gamma, grad_scale):
+    """d/dz of oracle.ops.focal_logits times grad_scale, restated in float32 op for op as csrc/elementwise*.hip computes
+    it (every intermediate rounded to float32).  Pure NumPy: the yardstick of what float32 costs against float64."""
+    f = np.float32
+    z = np.asarray(z, f)
+    with np.errstate(over="ignore"):
+        ce = np.maximum(z, f(0)) - z * f(target) + np.log1p(np.exp(-np.abs(z)))
+        pr = f(1) / (f(1) + np.exp(-z))
+    dce = pr - f(target)
+    base = f(1) - pr if target else pr
+    dbase = -pr * (f(1) - pr) if target else pr * (f(1) - pr)
+    mod, dmod = _pow_f32(base, gamma)
+    out = (f(grad_scale) / f(z.size)) * f(0.5) * (dmod * dbase * ce + mod * dce)
+    assert out.dtype == f
+    return out
+
+
+def focal_match_grad_f32(a, b, gamma, grad_scale):
+    """d/db of oracle.ops.focal_prob_match times grad_scale in float32, op for op as the kernels compute it."""
+    f = np.float32
+    a, b = np.asarray(a, f), np.asarray(b, f)
+    eps, hi = f(1e-7), f(1) - f(1e-7)
+    diff = a - b
+    t = f(1) - np.abs(diff) * f(0.5)
+    tc = np.minimum(np.maximum(t, eps), hi)
+    ce = -np.log(tc + eps)
+    dce = np.where((t >= eps) & (t <= hi), f(-1) / (tc + eps), f(0)).astype(f)
+    mod, dmod = _pow_f32(f(1) - t, gamma)
+    dper = f(0.5) * (-dmod * ce + mod * dce)
+    out = (f(grad_scale) / f(a.size)) * dper * f(0.5) * np.sign(diff).astype(f)
+    assert out.dtype == f
+    return out
+
+
 def scaled_params(shapes, seed, gain=1.0):
     """Kernels with variance-preserving scale (so that every layer carries signal and gradient:
     the reference's N(0, 0.02) init makes the inner layers' gradients ~1e-10 of the outer ones,
