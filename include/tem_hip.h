@@ -692,11 +692,27 @@ int tem_instance_norm_bwd(const tem_view *x, const tem_view *dy, const float *sc
  *   TEM_PLAN_WINO        {E, BY, BX, zsegs}       {E, BY, BX, zsegs, zper, nby, nbx, ndma}      (z in tiles of 2 planes)
  *   TEM_PLAN_WINO_BWW    {E, BY, BX, zsegs}       {E, BY, BX, zsegs, zper, nby, nbx, ndma}
  *   TEM_PLAN_CONV_LDS    {MTW, R, patch, zsegs}   {MTW, R, patch, zsegs, zper, nych, ntiles, 0}
- *   TEM_PLAN_CONV3_BF16  {nbx, TY, zsegs, -1}     {nbx, TY, zsegs, zper, nby, RD, ndma, 0} */
+ *   TEM_PLAN_CONV3_BF16  {nbx, TY, zsegs, -1}     {nbx, TY, zsegs, zper, nby, RD, ndma, 0}
+ * The k4 s2 kernels take their launch geometry from closed-form rules, one number each; a pin replaces the number the rule
+ * would have computed and every validity check of the host code applies unchanged.  Outside the range the kernel covers the
+ * family answers TEM_EUNSUPPORTED (and tem_conv / tem_conv_transpose / tem_conv_bwd_weight go on to their next kernel); the
+ * slab-count and *_is_tiled queries answer under a pin what the launch will do.  A pin takes precedence over the knob builds'
+ * TEM_S2_WGS, TEM_BWW_S2_R and TEM_BWW_S2_TBR.
+ *   family               pin v4            valid under a pin                          last v8
+ *   TEM_PLAN_CONV_S2     {nblocks, -1..}   1 <= nblocks <= min(iters, resident)       {nblocks, ny, T, iters, total, tiles_pp, TB, resident}
+ *   TEM_PLAN_CONVT_MFMA  {TY, -1..}        1 <= TY <= min(nQy, 32), the patch within  {TY, nband, nQz, nQy, nQx, NCLS, EPM, 0}
+ *                                          the loader's registers and 56 KB of LDS
+ *   TEM_PLAN_BWW_S2      {R, -1..}         1 <= R <= min(rows, max slabs)             {R, rows, tb (1: bww_s2tb_k), KS, OW, 0, 0, 0}
+ * (conv_s2_k: workgroups along x, along y, tiles per iteration, iterations, tiles, tiles per plane, two-block form, resident
+ * slots.  convT_mfma_k: Q_y rows per band, bands, Q extents, classes per patch, compiled epilogue.  bww_s2_k / bww_s2tb_k: row
+ * ranges = slabs, output rows N OD OH, kernel extent, row length.) */
 #define TEM_PLAN_WINO       1
 #define TEM_PLAN_WINO_BWW   2
 #define TEM_PLAN_CONV_LDS   3
 #define TEM_PLAN_CONV3_BF16 4
+#define TEM_PLAN_CONV_S2    5
+#define TEM_PLAN_CONVT_MFMA 6
+#define TEM_PLAN_BWW_S2     7
 int tem_plan_pin(int32_t family, const int32_t *v4);
 int tem_plan_last(int32_t family, int32_t *v8);
 

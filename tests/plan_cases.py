@@ -18,18 +18,27 @@ Class signature of a plan ("Plan space") -- the coordinates along whi
   tcap   the tile count of a workgroup is at its cap
   dcap   Winograd: the LDS-DMA count of a plane is at its cap.  conv3_bf16_k: one more tile row is refused (LDS-DMA budget or LDS
          bytes) although the row count is in range.  conv_lds_k stages through registers: False
+The k4 s2 kernels (conv_s2_k, convT_mfma_k, bww_s2_k / bww_s2tb_k) have no cost model: one number each comes from a closed-form
+rule, and the same seam pins it.  Their cases, shapes and class coordinates stand in the section "the k4 s2 kernels" below.
 tests/test_plan_space.py holds the tables to these definitions on the CPU, tests/test_gpu_plan_space.py runs them."""
 import contextlib
 import ctypes as C
 
 from span_cases import MAX_SLABS, Case, _g, dense, extents, out_dims
 
-WINO, WINO_BWW, CONV_LDS, CONV3_BF16 = 1, 2, 3, 4
-FAMILIES = (WINO, WINO_BWW, CONV_LDS, CONV3_BF16)
-KERNEL = {WINO: "wino_conv_k", WINO_BWW: "wino_bww_k", CONV_LDS: "conv_lds_k", CONV3_BF16: "conv3_bf16_k"}
+WINO, WINO_BWW, CONV_LDS, CONV3_BF16, CONV_S2, CONVT_MFMA, BWW_S2 = 1, 2, 3, 4, 5, 6, 7
+PLANNED = (WINO, WINO_BWW, CONV_LDS, CONV3_BF16)        # the plan comes from a cost model's search
+S2 = (CONV_S2, CONVT_MFMA, BWW_S2)                      # the k4 s2 kernels: one number from a closed-form rule (further down)
+FAMILIES = PLANNED + S2
+KERNEL = {WINO: "wino_conv_k", WINO_BWW: "wino_bww_k", CONV_LDS: "conv_lds_k", CONV3_BF16: "conv3_bf16_k",
+          CONV_S2: "conv_s2_k", CONVT_MFMA: "convT_mfma_k", BWW_S2: "bww_s2_k"}
+SYMBOLS = {f: (k + "<",) for f, k in KERNEL.items()}
+SYMBOLS[BWW_S2] += ("bww_s2tb_k<",)                     # 8 -> 8: the two-block form, same rule and the same family
 FIELDS = {WINO: "E BY BX zsegs zper nby nbx ndma".split(), WINO_BWW: "E BY BX zsegs zper nby nbx ndma".split(),
-          CONV_LDS: "MTW R patch zsegs zper nych ntiles -".split(), CONV3_BF16: "nbx TY zsegs zper nby RD ndma -".split()}
-NPIN = {WINO: 4, WINO_BWW: 4, CONV_LDS: 4, CONV3_BF16: 3}
+          CONV_LDS: "MTW R patch zsegs zper nych ntiles -".split(), CONV3_BF16: "nbx TY zsegs zper nby RD ndma -".split(),
+          CONV_S2: "nblocks ny T iters total tiles_pp TB resident".split(), CONVT_MFMA: "TY nband nQz nQy nQx NCLS EPM -".split(),
+          BWW_S2: "R rows tb KS OW - - -".split()}
+NPIN = {WINO: 4, WINO_BWW: 4, CONV_LDS: 4, CONV3_BF16: 3, CONV_S2: 1, CONVT_MFMA: 1, BWW_S2: 1}
 EUNSUPPORTED, EINVAL = -2, -1
 
 
@@ -37,10 +46,25 @@ class PlanCase(Case):
     """span_cases.Case without a limit row: geometry `g` at batch N, every operand dense (the dry queries and the plan
     depend on extents alone; the GPU test places the operands itself)"""
 
-    def __init__(self, name, family, g, N):
-        self.name, self.family, self.geom, self.N = name, family, g, N
+    def __init__(self, name, family, g, N, add_off=None):
+        self.name, self.family, self.geom, self.N, self.add_off = name, family, g, N, add_off
         self.row = self.side = self.frame = None
-        self.views = {o: dense(e, N) for o, e in extents(g).items()}
+        self.views = {o: dense(e, N) for o, e in self.extents().items()}
+
+    def extents(self):
+        """span_cases.extents; with `add_off` the skip-gradient is a window of the output that starts there and stops one voxel
+        short of the far faces (tem_epilogue.add_off: voxels outside the window get no skip-gradient)"""
+        e = extents(self.geom)
+        if self.add_off:
+            self.add_off = tuple(min(o, d - 1) for d, o in zip(e["add"][:3], self.add_off))        # (an axis of one voxel: the whole of it)
+            e["add"] = tuple(max(1, d - o - 1) for d, o in zip(e["add"][:3], self.add_off)) + e["add"][3:]
+        return e
+
+    def args(self, ptr, w, **kw):
+        a = super().args(ptr, w, **kw)
+        if self.add_off:
+            a.ep.add_off[0], a.ep.add_off[1], a.ep.add_off[2] = self.add_off
+        return a
 
     @property
     def id(self):
@@ -56,7 +80,10 @@ class PlanCase(Case):
         """what a plan depends on: the kernel instance's channels and geometry, the batch, the output extents and (conv3_bf16_k)
         whether there are two inputs"""
         g = self.geom
-        return (self.family,) + self.channels + (g["k"], g["s"], self.N) + out_dims(g) + (bool(g["ci1"]),)
+        key = (self.family,) + self.channels + (g["k"], g["s"], self.N) + out_dims(g) + (bool(g["ci1"]),)
+        if self.family in S2:               # convT_mfma_k: the Q ranges follow the padding, the readback names the compiled epilogue
+            key += (g["p"], g["gate"], g["keep"])
+        return key
 
 
 # ------------------------------------------------------------------------------------------------ the seam
@@ -106,6 +133,17 @@ def describe(lib, case, a):
         ok = lib.tem_conv_is_tiled(C.byref(a), 0, name, 96) == 1
     elif f == CONV3_BF16:
         ok = lib.tem_conv_bf16_describe(C.byref(a), name, 96) == 0
+    elif f == CONV_S2:
+        ok = lib.tem_conv_is_tiled(C.byref(a), 0, name, 96) == 1
+    elif f == CONVT_MFMA:
+        ok = lib.tem_conv_is_tiled(C.byref(a), 1, name, 96) == 1
+    elif f == BWW_S2:                      # the slab count is the plan's R; asked with it, tem_bww_is_tiled names the launch's kernel
+        a.nslab = MAX_SLABS
+        n = lib.tem_conv_bwd_weight_nslab(C.byref(a))
+        ok = n > 0
+        if ok:
+            a.nslab = n
+            ok = lib.tem_bww_is_tiled(C.byref(a), name, 96) == 1
     else:
         a.nslab = MAX_SLABS
         n = lib.tem_conv_bwd_weight_winograd_nslab(C.byref(a), name, 96)
@@ -113,7 +151,7 @@ def describe(lib, case, a):
         if ok:
             a.nslab = n
     sym = name.value.decode()
-    return ok and sym.startswith(KERNEL[f] + "<"), sym
+    return ok and sym.startswith(SYMBOLS[f]), sym
 
 
 def decide(lib, case, v4=None, a=None):
@@ -156,11 +194,21 @@ def tile_grid(case):
 _PLANS = {}
 
 
+def pin_range(lib, case):
+    """the values a k4 s2 family's one pinned number is asked at: 0 .. one past the extent it counts (iterations, Q_y rows,
+    output rows), which the unpinned readback names.  The library's answers, not this range, are the feasible list."""
+    d = default_plan(lib, case)
+    return range(0, d[{CONV_S2: 3, CONVT_MFMA: 3, BWW_S2: 1}[case.family]] + 2)
+
+
 def enumerate_plans(lib, case):
     """every feasible plan of the case, as v8 tuples in grid order.  A tile triple is asked once with the z split free;
     only where that is feasible, once per z split."""
     if case.key in _PLANS:
         return _PLANS[case.key]
+    if case.family in S2:
+        _PLANS[case.key] = plans = [v for v in (decide(lib, case, (x,)) for x in pin_range(lib, case)) if v is not None]
+        return plans
     a, n, plans = dry_args(case), zaxis(case), []
     for t in tile_grid(case):
         if decide(lib, case, t + (-1,) * (NPIN[case.family] - len(t)), a) is None:
@@ -196,6 +244,8 @@ def dma_cap(case):
 def signature(case, v, feasible=None):
     """class signature of plan v (a v8 tuple) of `case`; `feasible`: the case's feasible list (conv3_bf16_k's dcap is
     read off it: the plan with one more row is refused although the row count is inside the planner's range)"""
+    if case.family in S2:
+        return s2_signature(case, v)
     f, n, e1 = case.family, zaxis(case), extent1(case)
     _, OH, OW = out_dims(case.geom)
     if f in (WINO, WINO_BWW):
@@ -276,7 +326,7 @@ SHAPES = {
     CONV3_BF16: [("small", (5, 6, 17), 2), ("8x25x33", (8, 25, 33), 1), ("9x24x33", (9, 24, 33), 1), ("8x24x127", (8, 24, 127), 1),
                  ("9x6x62", (9, 6, 62), 1)],
 }
-LARGE = {f: SHAPES[f][1][0] for f in FAMILIES}          # tag of the family's first large shape
+LARGE = {f: SHAPES[f][1][0] for f in PLANNED}          # tag of the family's first large shape
 ENTRY = {WINO: "conv", WINO_BWW: "bww_wino", CONV_LDS: "conv", CONV3_BF16: "conv_h"}
 
 
@@ -332,6 +382,164 @@ CASES[CONV3_BF16] += _cases(CONV3_BF16, "plain", 8, 8, 4, 2, 0)
 CASES[CONV3_BF16] += _cases(CONV3_BF16, "gated", 8, 16, 4, 2, 1, **H_GATED)
 CASES[CONV3_BF16] += _cases(CONV3_BF16, "plain", 16, 16, 4, 2, 0)
 CASES[CONV3_BF16] += _cases(CONV3_BF16, "plain", 16, 32, 4, 2, 1)
+
+
+# ------------------------------------------------------------------------------------------------ the k4 s2 kernels
+# conv_s2_k, convT_mfma_k and bww_s2_k / bww_s2tb_k take one number each from a closed-form rule (workgroups; Q_y rows per band;
+# row ranges).  Their class coordinates name what that number changes in the kernel, computed from the readback and the case's
+# extents -- the kernels' own index arithmetic is restated where a coordinate is that arithmetic (conv_s2_k's two walks, the row
+# ranges of bww_s2_k), next to the line it quotes:
+#   conv_s2_k     walk   "one" interleaved walk (fewer workgroups than XCDs) / "xcd": per XCD over contiguous eighths
+#                 ipw    the most iterations a workgroup owns: "1" / "2" / "3+odd" (the ping-pong ends on the first fragment
+#                        set) / "4+even"
+#                 dead   some workgroup owns no iteration
+#                 tail   total % T != 0: the last iteration carries dead tiles (T = 1: never)
+#                 prag   plane_vox % VPT != 0: a plane's last tile is partial
+#   convT_mfma_k  bands  "1" / "div" (TY divides nQy) / "rag" (a shorter last band)
+#                 ty     "1" / ">1"
+#                 wtiles a full band's 16-voxel tiles ceil(TY nQx / 16) against the WPN = 4 / NT waves of an n-tile:
+#                        "<WPN" (idle waves) / "div" / "rag" (C_out = 32: one wave per n-tile, "div" alone)
+#                 zpar   OD "even" / "odd", with the padding: "/p0", "/p1" (odd OD: a class group has no plane at one end)
+#   bww_s2_k      rows   rows per wave in the shortest range: "0" (a wave without a row; not with 32 input channels, where a
+#                        wave takes one ky of every row) / "1" / "2+"
+#                 even   rows % R == 0: all ranges have one length
+#                 cross  a range spans two planes (or samples)
+#                 ring   k-steps of the longest wave share against the ring of 8 fragment sets: "<8" (the steady-state loop is
+#                        never entered) / ">=8"
+#                 xtail  OW % 4 != 0: a row's last k-step is partial
+S2_COORDS = {CONV_S2: ("walk", "ipw", "dead", "tail", "prag"), CONVT_MFMA: ("bands", "ty", "wtiles", "zpar"),
+             BWW_S2: ("rows", "even", "cross", "ring", "xtail")}
+
+
+def s2_owned(nblocks, iters):
+    """iterations each workgroup of conv_s2_k owns (conv_s2.hip, conv_s2_k: `one`, `step`, `x0`, `it1`, `it0`)"""
+    if nblocks < 8:
+        return [len(range(b, iters, nblocks)) for b in range(nblocks)]
+    own = []
+    for b in range(nblocks):
+        xcd = b & 7
+        step, x0, it1 = (nblocks - xcd + 7) >> 3, (xcd * iters) >> 3, ((xcd + 1) * iters) >> 3
+        own.append(len(range(x0 + (b >> 3), it1, step)))
+    return own
+
+
+def bww_ranges(R, rows):
+    """[ra, rb) of every row range (bww_s2.hip, bww_s2_k: `ra`, `rb`)"""
+    return [(i * rows // R, (i + 1) * rows // R) for i in range(R)]
+
+
+def s2_signature(case, v):
+    f = case.family
+    OD, OH, OW = out_dims(case.geom)
+    ci, co = case.channels
+    if f == CONV_S2:
+        nblocks, _, T, iters, total, tiles_pp, tb, _ = v
+        own = s2_owned(nblocks, iters)
+        assert sum(own) == iters, (case.id, v)                    # every iteration has exactly one owner
+        m = max(own)
+        plane_vox, vpt = OH * (OW + tb), 16 - tb                  # conv_s2.hip run(): RL = TB ? OW + 1 : OW; VPT = TB ? 15 : 16
+        assert tiles_pp == -(-plane_vox // vpt) and iters == -(-total // T), (case.id, v)
+        return ("one" if nblocks < 8 else "xcd", "1" if m == 1 else "2" if m == 2 else "3+odd" if m % 2 else "4+even",
+                min(own) == 0, total % T != 0, plane_vox % vpt != 0)
+    if f == CONVT_MFMA:
+        TY, nband, _, nQy, nQx, _, _, _ = v
+        assert nband == -(-nQy // TY), (case.id, v)
+        wpn, ntiles = 4 // (2 * co // 16), -(-TY * nQx // 16)     # convT_mfma.hip: NT = 2 CO / 16, WPN = 4 / NT
+        return ("1" if nband == 1 else "div" if nQy % TY == 0 else "rag", "1" if TY == 1 else ">1",
+                "<WPN" if ntiles < wpn else "div" if ntiles % wpn == 0 else "rag", f"{'odd' if OD % 2 else 'even'}/p{case.geom['p']}")
+    R, rows, tb, _, ow, _, _, _ = v
+    assert rows == case.N * OD * OH and ow == OW, (case.id, v)
+    ranges = bww_ranges(R, rows)
+    lens = [b - a for a, b in ranges]
+    wky = ci == 32                                                # bww_s2.hip: WKY, a wave takes one ky of every row of the range
+    per_wave = (lambda n: n) if wky else (lambda n: n // 4)       # the fourth wave's rows: (n - 3 + 3) >> 2
+    ksteps = (OW + 4) // 4 if tb else -(-OW // 4)                 # (bww_s2tb_k: slots 0 .. OW)
+    longest = max(lens) if wky else -(-max(lens) // 4)            # the first wave's rows
+    lo = per_wave(min(lens))
+    return ("0" if lo == 0 else "1" if lo == 1 else "2+", rows % R == 0, any(a // OH != (b - 1) // OH for a, b in ranges),
+            "<8" if longest * ksteps < 8 else ">=8", OW % 4 != 0)
+
+
+def s2_values(case):
+    """the values each coordinate must take in the sweep of the case's kernel instance: every one, but for the three an
+    instance cannot have (named above)"""
+    f, (ci, co) = case.family, case.channels
+    if f == CONV_S2:
+        return dict(walk={"one", "xcd"}, ipw={"1", "2", "3+odd", "4+even"}, dead={False, True},
+                    tail={False} if ci == 32 else {False, True}, prag={False, True})
+    if f == CONVT_MFMA:
+        return dict(bands={"1", "div", "rag"}, ty={"1", ">1"}, wtiles={"div"} if co == 32 else {"<WPN", "div", "rag"},
+                    zpar={"even/p0", "even/p1", "odd/p0", "odd/p1"})
+    return dict(rows={"1", "2+"} if ci == 32 else {"0", "1", "2+"}, even={False, True}, cross={False, True},
+                ring={"<8", ">=8"}, xtail={False, True})
+
+
+# Shapes (OUTPUT extents of conv_s2_k and bww_s2_k, INPUT extents of convT_mfma_k; batch).  A tag that starts with "small": the whole
+# feasible list runs; of the others one plan per class signature.  The lists are a greedy cover, over a few thousand candidate
+# extents, of the two conditions tests/test_plan_space.py asserts per kernel instance: every value of every coordinate, and the
+# class signature of every k4 s2 launch of the 74, 132 and 260 train steps.
+#   conv_s2_k     (3, 5, 7) x 2: iters 5 / 9 / 18 for T = 4 (two-block form) / 2 / 1 -- the one walk through ipw 1 .. 4+, the XCD
+#                 walk with and without dead workgroups; a plane's last tile is partial; the two-block form has a tail.
+#                 (1, 3, 4) x 2 and (5, 3, 4) x 3: a tile per plane, fewer iterations than XCDs (the step's 32 -> 32 layer at 74
+#                 is one iteration).  The batches of three make odd tile counts, which T = 2 needs for a tail (a batch of two
+#                 makes every count even); 8 must divide the iterations for the XCD walk to give every workgroup exactly one, and
+#                 ipw 3+odd / 4+even without a dead workgroup, as the full-size launches have it, needs 17 .. 32 iterations or
+#                 more: (3, 7, 16), (4, 6, 19), (3, 9, 22), (4, 8, 16), (6, 10, 8) x 3 bring these together with each
+#                 (tail, prag) pair the step has (planes of 128 = 8 x 16 voxels: whole tiles)
+#   convT_mfma_k  input (3, 5, 6): nQy = 6, nQx = 7 (8 with pad 0), TY = 1 .. 6 gives bands 6, 3, 2, 2 ragged, 2 ragged, 1; its twin
+#                 with the output one plane short (odd OD); input (3, 11, 14): nQy = 12, rows of 15 (16 with pad 0; 13 with
+#                 pad 3) voxels, so a band's tile count runs through every remainder of the waves of an n-tile, with whole and
+#                 ragged bands
+#   bww_s2_k      rows = N OD OH of 30, 8 and 28 with OW = 7 (partial last k-step, 2 k-steps a row), 12 (whole k-steps) and 33
+#                 (9 k-steps: one row fills the ring; rows = 28 has R = 3 with ranges of 9, 9, 10 rows -- unequal, two rows a
+#                 wave and more -- which is what every full-size launch looks like): every R = 1 .. rows runs
+S2_SHAPES = {
+    CONV_S2: [("small", (3, 5, 7), 2), ("small-1x3x4", (1, 3, 4), 2), ("small-5x3x4", (5, 3, 4), 3), ("3x7x16", (3, 7, 16), 3),
+              ("4x6x19", (4, 6, 19), 3), ("3x9x22", (3, 9, 22), 3), ("4x8x16", (4, 8, 16), 3), ("6x10x8", (6, 10, 8), 3)],
+    CONVT_MFMA: [("small", (3, 5, 6), 2), ("small-odd", (3, 5, 6), 2), ("small-3x11x14", (3, 11, 14), 2)],
+    BWW_S2: [("small", (3, 5, 7), 2), ("small-1x4x12", (1, 4, 12), 2), ("small-2x7x33", (2, 7, 33), 2)],
+}
+ENTRY.update({CONV_S2: "conv", CONVT_MFMA: "convT", BWW_S2: "bww"})
+ADD_OFF = (1, 1, 2)
+
+
+def _s2_cases(family, variant, ci, co, k, s, p, add_off=None, **kw):
+    out = []
+    for tag, dims, N in S2_SHAPES[family]:
+        if family == CONVT_MFMA:
+            g = _g("convT", ci, co, k, s, p, dims, **kw)
+            if tag.endswith("odd"):
+                od = out_dims(g)
+                g["out"] = (od[0] - 1,) + od[1:]
+        else:
+            g = _g(ENTRY[family], ci, co, k, s, p, tuple((d - 1) * s + k - 2 * p for d in dims), **kw)
+            assert out_dims(g) == dims, (variant, dims, out_dims(g))
+        c = PlanCase(f"{ci}to{co}-k{k}s{s}-{variant}-{tag}", family, g, N, add_off)
+        c.small, c.variant = tag.startswith("small"), variant
+        out.append(c)
+    return out
+
+
+S2_PAIRS = [(8, 8), (8, 16), (16, 16), (16, 32), (32, 32)]          # conv_s2.hip dispatch(): <8,1,4,true> <8,1,2> <16,1,2> <16,2,2> <32,1,1>
+CONVT_PAIRS = [(16, 8), (32, 16), (8, 8), (16, 16), (32, 32)]       # convT_mfma.hip CT_CASE
+BWW_S2_PAIRS = [(8, 16), (16, 16), (16, 32), (32, 32), (8, 8)]       # bww_s2.hip dispatch(); 8 -> 8: bww_s2tb_k
+CASES.update({f: [] for f in S2})
+for _ci, _co in S2_PAIRS:
+    CASES[CONV_S2] += _s2_cases(CONV_S2, "fwd", _ci, _co, 4, 2, 0)                                        # LeakyReLU 0.3
+    CASES[CONV_S2] += _s2_cases(CONV_S2, "bd", _ci, _co, 4, 2, 1, ADD_OFF, slope=1.0, gate=True, add=True)   # input-gradient of a transposed layer
+for _ci, _co in CONVT_PAIRS:
+    CASES[CONVT_MFMA] += _s2_cases(CONVT_MFMA, "keepw", _ci, _co, 4, 2, 1, keep=1)                         # EPM 0: Philox, keep bits written
+    CASES[CONVT_MFMA] += _s2_cases(CONVT_MFMA, "keepr", _ci, _co, 4, 2, 1, keep=2)                         # EPM 1: keep bits read
+    CASES[CONVT_MFMA] += _s2_cases(CONVT_MFMA, "plain", _ci, _co, 4, 2, 1)                                 # EPM 0, no Dropout
+    CASES[CONVT_MFMA] += _s2_cases(CONVT_MFMA, "bd", _ci, _co, 4, 2, 0, ADD_OFF, slope=1.0, gate=True, add=True)   # EPM 2
+for _ci, _co in CONVT_PAIRS[:2]:                                     # the generator's two: pad 1 and a crop of one (two) voxels a side
+    CASES[CONVT_MFMA] += _s2_cases(CONVT_MFMA, "keepr2", _ci, _co, 4, 2, 2, keep=2)
+    CASES[CONVT_MFMA] += _s2_cases(CONVT_MFMA, "keepr3", _ci, _co, 4, 2, 3, keep=2)
+for _ci, _co in BWW_S2_PAIRS:
+    CASES[BWW_S2] += _s2_cases(BWW_S2, "p0", _ci, _co, 4, 2, 0)
+    CASES[BWW_S2] += _s2_cases(BWW_S2, "p1", _ci, _co, 4, 2, 1)                                           # 8 -> 16: a transposed layer's, operands swapped
+CASES[BWW_S2] += _s2_cases(BWW_S2, "p0", 16, 32, 3, 1, 0)                                                 # the small k3 s1 layers routed here
+CASES[BWW_S2] += _s2_cases(BWW_S2, "p0", 32, 32, 3, 1, 0)
 ALL_CASES = [c for f in FAMILIES for c in CASES[f]]
 
 

@@ -323,6 +323,8 @@ OPERANDS = {
 
 # ------------------------------------------------------------------------------------------------ building a case
 def out_dims(g):
+    if g.get("out"):                        # an output view that stops short of the natural extents (plan_cases: odd OD of a transposed layer)
+        return g["out"]
     k, s, p = g["k"], g["s"], g["p"]
     f = (lambda d: (d - 1) * s + k - 2 * p) if g["entry"].startswith("convT") else (lambda d: (d + 2 * p - k) // s + 1)
     D, H, W = g["dims"]

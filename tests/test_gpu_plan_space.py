@@ -10,6 +10,11 @@ bit: a plan deals output voxels to workgroups, waves and z steps and leaves each
 split reorders the sums: every plan goes against the oracle's kernel gradient at test_gpu_wino's bar, twice, and must
 reproduce itself bit for bit.
 
+conv_s2_k and convT_mfma_k (one pinned number: workgroups, Q_y rows per band) ride the same forward test at test_gpu_ops.TOL,
+every pinned plan bit-equal to the default one; bww_s2_k / bww_s2tb_k (row ranges R, which regroup the sum) go against the
+oracle's kernel gradient per R after tem_reduce_slabs, twice, with the slabs behind the R-th left untouched.  Three planted
+errors at the end lie on paths only a pin opens at these shapes.
+
 Operands are strided windows of larger allocations that start as a NaN sentinel (span_cases), a plane, a row and a voxel
 of head room on every side; after each launch the output is finite, the allocation outside the window untouched, and the
 window is back to the sentinel for the next plan.  Comparisons run on the device."""
@@ -20,11 +25,11 @@ import pytest
 import torch
 
 import plan_cases as P
-from plan_cases import CASES, CONV3_BF16, CONV_LDS, WINO, WINO_BWW
+from plan_cases import BWW_S2, CASES, CONV3_BF16, CONVT_MFMA, CONV_LDS, CONV_S2, WINO, WINO_BWW
 from span_cases import SENTINEL, View, _bits, extents, frame_intact, out_dims, span
 
 pytestmark = pytest.mark.gpu
-TOL = {CONV_LDS: 2e-5, CONV3_BF16: 6e-3}            # test_gpu_ops.TOL, test_gpu_bf16.TOL (max error over the largest |ref|)
+TOL = {CONV_LDS: 2e-5, CONV3_BF16: 6e-3, CONV_S2: 2e-5, CONVT_MFMA: 2e-5, BWW_S2: 2e-5}   # test_gpu_ops.TOL, test_gpu_bf16.TOL (max error over the largest |ref|)
 
 
 @pytest.fixture(scope="module")
@@ -65,13 +70,16 @@ def operands(case):
     rng = np.random.default_rng(sum(map(ord, case.id)))
     bf = g["esz"] == 2                  # bf16: the oracle gets the values the bf16 tensors hold
     rb = (lambda a: torch.from_numpy(a).to(torch.bfloat16).to(torch.float32).numpy()) if bf else (lambda a: a)
-    d = {o: rb(rng.standard_normal((N,) + e).astype(np.float32)) for o, e in extents(g).items() if not o.startswith("out")}
+    d = {o: rb(rng.standard_normal((N,) + e).astype(np.float32)) for o, e in case.extents().items() if not o.startswith("out")}
     k, s, p = g["k"], g["s"], g["p"]
     ci, co = case.channels
     x = np.concatenate([d["in0"], d["in1"]], -1) if g["ci1"] else d["in0"]
-    if case.family == WINO_BWW:
+    if case.family in (WINO_BWW, BWW_S2):
         return d, None, O.conv_bwd_weight(x, d["dout"], (k, k, k), s, p)
-    if g["flip"]:          # the input-gradient of a co -> ci layer, whose kernel (tap, co, ci) is read flipped / transposed
+    if g["entry"] == "convT":             # the kernel in Keras' layout (tap, co, ci)
+        w = (rng.standard_normal((k, k, k, co, ci)) * 0.1).astype(np.float32)
+        raw = O.convT_fwd(x, w, s, p, out_dims=out_dims(g))
+    elif g["flip"]:          # the input-gradient of a co -> ci layer, whose kernel (tap, co, ci) is read flipped / transposed
         w = (rng.standard_normal((k, k, k, co, ci)) * 0.1).astype(np.float32)
         raw = O.conv_fwd(x, np.ascontiguousarray(np.flip(w, (0, 1, 2)).transpose(0, 1, 2, 4, 3)), s, p)
     else:
@@ -79,6 +87,10 @@ def operands(case):
         raw = O.conv_fwd(x, w, s, p)
     assert raw.shape == (N,) + out_dims(g) + (co,)
     ref, c0 = np.array(raw, np.float64), g["co"]
+    if g["add"]:                          # tem_epilogue's order: skip-gradient (inside its window), gate, keep bits, slope
+        oz, oy, ox = case.add_off or (0, 0, 0)
+        _, aD, aH, aW, _ = d["add"].shape
+        ref[:, oz:oz + aD, oy:oy + aH, ox:ox + aW, :c0] += d["add"]
     if g["gate"]:
         ref[..., :c0] = np.where(d["gate"] > 0, ref[..., :c0], 0.3 * ref[..., :c0])
     if g["keep"]:
@@ -101,25 +113,29 @@ class Launcher:
         self.ref = torch.from_numpy(ref).cuda()
         dtype = torch.bfloat16 if g["esz"] == 2 else torch.float32
         self.bufs, self.t, views = {}, {}, {}
-        for o, e in extents(g).items():
+        for o, e in case.extents().items():
             views[o], head = window(e, case.N)
             self.bufs[o], self.t[o] = framed(views[o], head, dtype)
             if o in d:
                 self.t[o].copy_(torch.from_numpy(d[o]).cuda())
-        placed = P.PlanCase(case.name, f, g, case.N)
+        placed = P.PlanCase(case.name, f, g, case.N, case.add_off)
         placed.views = views
         self.keep = torch.from_numpy(d["keep"]).cuda() if g["keep"] else None
+        self.mask = None
+        if g["keep"] == 1:                 # the launch draws the bits itself and writes them: a mask of its own inside a frame of bytes
+            self.mask_ref, self.keep = self.keep, torch.full((self.keep.numel() + 64,), 0xA5, dtype=torch.uint8, device="cuda")
+            self.mask = self.keep
         ptr = {o: t.data_ptr() for o, t in self.t.items()}
         self.outs = [o for o in ("out0", "out1") if o in views]
-        if f == WINO_BWW:
+        if f in (WINO_BWW, BWW_S2):
             self.a = placed.args(ptr, 0)
-            self.fn = lib.tem_conv_bwd_weight_winograd
+            self.fn = lib.tem_conv_bwd_weight_winograd if f == WINO_BWW else lib.tem_conv_bwd_weight
             return
         if f == CONV3_BF16:                               # the packed bf16 kernel [tap][co][ci] (test_gpu_bf16.pack)
             w = np.ascontiguousarray(w.reshape(-1, w.shape[3], w.shape[4]).transpose(0, 2, 1))
         self.w = torch.from_numpy(w.reshape(-1)).cuda().to(dtype)
         self.a = placed.args(ptr, self.w.data_ptr(), keep_mask=self.keep.data_ptr() if self.keep is not None else 0)
-        self.fn = lib.tem_conv_bf16 if f == CONV3_BF16 else lib.tem_conv
+        self.fn = lib.tem_conv_bf16 if f == CONV3_BF16 else lib.tem_conv_transpose if f == CONVT_MFMA else lib.tem_conv
         if f == WINO:
             ci, co = case.channels
             self.u = torch.zeros(H.wino_u_floats(ci, co), device="cuda")
@@ -148,6 +164,10 @@ class Launcher:
                 inside, b = frame_intact(self.bufs[o], self.t[o])           # (leaves the window NaN-filled for the next launch)
                 got.append(inside)
                 bad += b
+            if self.mask is not None:      # the keep bits are the oracle's Philox mask, the bytes behind them untouched; reset for the next plan
+                n = self.mask_ref.numel()
+                bad += int((self.mask[:n] != self.mask_ref).sum()) + int((self.mask[n:] != 0xA5).sum())
+                self.mask.fill_(0xA5)
             return torch.cat(got, -1), bad, plan
         return self._guard(v4, go)
 
@@ -171,6 +191,34 @@ class Launcher:
             return runs[0].double().sum(0).reshape(self.ref.shape), torch.equal(runs[0], runs[1]), plan
         return self._guard(v4, go)
 
+    def ranges(self, v4=None):
+        """bww_s2_k / bww_s2tb_k under pin v4: slab-count query, launch and tem_reduce_slabs, twice, each into a fresh workspace
+        of R + 2 sentinel slabs -> (reduced gradient fp32, the two runs equal bit for bit in slabs and sum, sentinel elements
+        lost in the slabs behind the R-th, plan)"""
+        ci, co = self.case.channels
+        n = self.case.geom["k"] ** 3 * ci * co
+
+        def go():
+            P.pin(self.lib, BWW_S2, v4)
+            taken, sym = P.describe(self.lib, self.case, self.a)              # sets a.nslab to the plan's R
+            assert taken, (self.case.id, v4, sym)
+            plan, R, runs, lost = P.last(self.lib, BWW_S2), self.a.nslab, [], 0
+            for _ in range(2):
+                slabs, out = torch.empty((R + 2, n), device="cuda"), torch.empty(n, device="cuda")
+                _bits(slabs).fill_(SENTINEL[4])
+                self.a.slabs, self.a.accumulate = slabs.data_ptr(), 0
+                rc = self.fn(C.byref(self.a), self.H.current_stream())
+                assert rc == 0 and P.last(self.lib, BWW_S2) == plan, (self.case.id, v4, rc)
+                rc = self.lib.tem_reduce_slabs(slabs.data_ptr(), R, n, 0, out.data_ptr(), 0, 1.0, self.H.current_stream())
+                assert rc == 0, (self.case.id, v4, rc)
+                torch.cuda.synchronize()
+                lost += int((_bits(slabs[R:]) != SENTINEL[4]).sum())
+                runs.append((slabs[:R], out))
+            P.pin(self.lib, BWW_S2, None)
+            same = torch.equal(_bits(runs[0][0]), _bits(runs[1][0])) and torch.equal(runs[0][1], runs[1][1])
+            return runs[0][1].reshape(self.ref.shape), same, lost, plan
+        return self._guard(v4, go)
+
     def error(self, got):
         """(error, bound) in the family's own measure, computed on the device"""
         f, ref = self.case.family, self.ref
@@ -188,7 +236,7 @@ def _npin(case):
 
 
 # ------------------------------------------------------------------------------------------------ the sweep
-FORWARD = [c for f in (WINO, CONV_LDS, CONV3_BF16) for c in CASES[f]]
+FORWARD = [c for f in (WINO, CONV_LDS, CONV3_BF16, CONV_S2, CONVT_MFMA) for c in CASES[f]]
 
 
 @pytest.mark.parametrize("case", FORWARD, ids=lambda c: c.id)
@@ -233,6 +281,39 @@ def test_every_kernel_gradient_plan_matches_the_oracle(lib, case):
             wrong.append((v, "two runs differ"))
         elif not (err <= bound and l2 <= 3e-6 * nref):            # (a NaN fails both)
             wrong.append((v, "oracle", err, bound, l2 / nref))
+    print(f"{case.id}: {len(run)} plans, worst error / bar {worst:.3g}")
+    assert not wrong, (case.id, len(wrong), len(run), wrong[:8])
+
+
+@pytest.mark.parametrize("case", CASES[BWW_S2], ids=lambda c: c.id)
+def test_every_row_range_count_matches_the_oracle_and_reproduces_itself(lib, case):
+    """R regroups the sum over the output rows, so the plans differ in their bits: each goes against the float64 oracle at
+    test_gpu_ops.TOL after tem_reduce_slabs, twice, and must reproduce itself; the slabs behind the R-th stay untouched.  A
+    pad-1 8 -> 16 case is a transposed layer's kernel gradient with input and gradient swapped: oracle.ops.convT_bwd_weight of
+    the swapped operands is held to the same numbers."""
+    from oracle import ops as O
+    run = P.sweep_list(lib, case)
+    L = Launcher(lib, case)
+    if case.geom["p"] == 1 and case.channels == (8, 16):
+        refT = O.convT_bwd_weight(L.t["dout"].cpu().numpy(), L.t["in0"].cpu().numpy(), (4, 4, 4), 2, 1)
+        assert refT.shape == tuple(L.ref.shape)
+        assert float(np.abs(refT - L.ref.cpu().numpy()).max()) <= 1e-9 * float(L.ref.abs().max())
+    wrong, worst = [], 0.0
+    for v in [None] + run:
+        got, same, lost, plan = L.ranges(None if v is None else v[:1])
+        err, bound = L.error(got)
+        worst = max(worst, err / bound)
+        if v is None:
+            assert plan == P.default_plan(lib, case) and plan in run
+            v = plan
+        if plan != v:
+            wrong.append((v, "read back", plan))
+        elif not same:
+            wrong.append((v, "two runs differ"))
+        elif lost:
+            wrong.append((v, "slabs behind the last range written", lost))
+        elif not err <= bound:                                     # (a NaN fails)
+            wrong.append((v, "oracle", err, bound))
     print(f"{case.id}: {len(run)} plans, worst error / bar {worst:.3g}")
     assert not wrong, (case.id, len(wrong), len(run), wrong[:8])
 
@@ -310,3 +391,70 @@ def test_bit_equality_tells_two_kernels_apart(lib):
     assert rel <= TOL[CONV_LDS], rel                                   # the direct forms' bar (test_gpu_ops.TOL)
     assert not torch.equal(wino, direct)
     assert _lib.TEM_PLAN_WINO == WINO and _lib.TEM_PLAN_CONV3_BF16 == CONV3_BF16
+
+
+# ---- the k4 s2 kernels: an error on a path only the pin opens
+def _s2_case(family, tag, variant, channels):
+    return next(c for c in CASES[family] if c.name.split("-", 3)[3] == tag and c.variant == variant and c.channels == channels)
+
+
+def test_the_comparison_sees_an_error_only_a_second_iteration_makes(lib):
+    """conv_s2_k 16 -> 16 at (3, 5, 7) x 2: 9 iterations of two tiles.  The default plan gives every iteration a workgroup of
+    its own.  With 5 workgroups pinned (one walk: workgroup b owns b and b + 5) iterations 5 .. 8 -- tiles 10 .. 17, which hold the
+    last output plane of the last sample, tiles 15 .. 17 -- run as second iterations, on the second fragment set and LDS buffer.
+    The last two input planes of that sample are read by that output plane alone (pad 0: plane 2 reads planes 4 .. 7)."""
+    case = _s2_case(CONV_S2, "small", "fwd", (16, 16))
+    assert case.geom["p"] == 0 and P.default_plan(lib, case)[:4] == (9, 1, 2, 9)
+    assert P.s2_owned(5, 9) == [2, 2, 2, 2, 1] and P.s2_owned(9, 9).count(0) == 1
+    L = Launcher(lib, case)
+    clean, _, plan = L.forward((5,))
+    assert plan[0] == 5
+    err, bound = L.error(clean)
+    assert err <= bound
+    L.t["in0"][-1, -2:] += BUMP
+    got, bad, plan = L.forward((5,))
+    assert plan[0] == 5 and bad == 0
+    bar = bound * float(L.ref.abs().max())
+    per_plane = (got.double() - L.ref).abs().amax(dim=(2, 3, 4)).reshape(-1)            # (sample, output plane)
+    assert float(per_plane[:-1].max()) <= bar and float(per_plane[-1]) > 10 * bar, (bar, per_plane.tolist())
+    assert torch.equal(got.reshape(-1, *got.shape[2:])[:-1], clean.reshape(-1, *clean.shape[2:])[:-1])
+
+
+def test_the_comparison_sees_an_error_only_a_second_band_makes(lib):
+    """convT_mfma_k 16 -> 8, input (3, 5, 6), pad 1: nQy = 6, one band by default.  TY = 3 pinned makes two; the second holds
+    Q_y = 3 .. 5, output rows 5 .. 9.  The last input row j_y = 4 reaches the output rows 2 j_y + t - 1 = 7 .. 9 alone, through
+    Q_y = 4 and 5: the second band's patch."""
+    case = _s2_case(CONVT_MFMA, "small", "plain", (16, 8))
+    assert P.default_plan(lib, case)[:2] == (6, 1)
+    L = Launcher(lib, case)
+    clean, _, plan = L.forward((3,))
+    assert plan[:2] == (3, 2)
+    err, bound = L.error(clean)
+    assert err <= bound
+    L.t["in0"][:, :, -1] += BUMP
+    got, bad, plan = L.forward((3,))
+    assert plan[:2] == (3, 2) and bad == 0
+    bar = bound * float(L.ref.abs().max())
+    per_row = (got.double() - L.ref).abs().amax(dim=(0, 1, 3, 4))
+    assert per_row.numel() == 10 and float(per_row[:7].max()) <= bar and float(per_row[7:].min()) > 10 * bar, (bar, per_row.tolist())
+    assert torch.equal(got[:, :, :7], clean[:, :, :7])
+
+
+def test_the_gradient_comparison_sees_an_error_only_a_ranges_last_wave_makes(lib):
+    """bww_s2_k 16 -> 16 at (3, 5, 7) x 2: 30 output rows, two ranges by default.  In the second range [15, 30) the fourth wave
+    takes rows 18, 22 and 26.  With the gradient's row 18 = (sample 1, plane 0, row 3) changed on the device, the result must
+    leave the reference and meet the oracle's kernel gradient of the changed operand."""
+    from oracle import ops as O
+    case = _s2_case(BWW_S2, "small", "p0", (16, 16))
+    assert P.default_plan(lib, case)[:2] == (2, 30) and P.bww_ranges(2, 30)[1] == (15, 30)
+    L = Launcher(lib, case)
+    clean, same, lost, plan = L.ranges((2,))
+    err, bound = L.error(clean)
+    assert plan[0] == 2 and same and not lost and err <= bound
+    L.t["dout"][1, 0, 3] += BUMP
+    got, same, lost, plan = L.ranges((2,))
+    assert plan[0] == 2 and same and not lost
+    err, bound = L.error(got)
+    assert err > 10 * bound, (err, bound)
+    ref2 = torch.from_numpy(O.conv_bwd_weight(L.t["in0"].cpu().numpy(), L.t["dout"].cpu().numpy(), (4, 4, 4), 2, 0)).cuda()
+    assert float((got.double() - ref2).abs().max() / ref2.abs().max()) <= bound

@@ -8,14 +8,17 @@
 * every launch of the workload that one of the four kernels takes -- the step-shape tables of
   test_gpu_fullsize_oracle.py and test_gpu_bf16_fullsize_oracle.py, utils.plan_routes of the 132 and 260 models -- has a
   default plan whose class signature the GPU sweep (tests/test_gpu_plan_space.py) executes for the same kernel instance.
-  A cost-model change that moves a layer onto a plan class no oracle-checked test has run fails here."""
+  A cost-model change that moves a layer onto a plan class no oracle-checked test has run fails here;
+* the same for the one pinned number of conv_s2_k, convT_mfma_k and bww_s2_k / bww_s2tb_k (section "the k4 s2 kernels"): the seam,
+  the unpinned geometry held to a restatement of the three rules, every class value in every kernel
+  instance's sweep, and the class signature of every k4 s2 launch of the 74, 132 and 260 train steps inside it."""
 import ctypes as C
 
 import pytest
 import torch
 
 import plan_cases as P
-from plan_cases import CASES, CONV3_BF16, CONV_LDS, FAMILIES, KERNEL, WINO, WINO_BWW
+from plan_cases import BWW_S2, CASES, CONV3_BF16, CONVT_MFMA, CONV_LDS, CONV_S2, FAMILIES, KERNEL, PLANNED, S2, WINO, WINO_BWW
 from span_cases import _g, out_dims
 
 
@@ -50,20 +53,21 @@ def test_readback_before_any_decision_and_unknown_family():
     def ask():
         v = (C.c_int32 * 8)()
         seen["last"] = [lib.tem_plan_last(f, v) for f in FAMILIES]
-        seen["unknown"] = [lib.tem_plan_last(0, v), lib.tem_plan_last(5, v), lib.tem_plan_pin(0, None), lib.tem_plan_pin(5, None)]
+        past = max(FAMILIES) + 1                                        # the first number past the last family
+        seen["unknown"] = [lib.tem_plan_last(0, v), lib.tem_plan_last(past, v), lib.tem_plan_pin(0, None), lib.tem_plan_pin(past, None)]
         seen["null"] = lib.tem_plan_last(WINO, None)
         c = _case(WINO, "small", "ep0", (16, 16))
         seen["plan"] = P.decide(lib, c, (17, 2, 3, 1))
     P.decide(lib, _case(WINO, "small", "ep0", (16, 16)))                # this thread has decided; the other has not
     t = threading.Thread(target=ask)
     t.start(); t.join()
-    assert seen["last"] == [P.EINVAL] * 4 and seen["unknown"] == [P.EINVAL] * 4 and seen["null"] == P.EINVAL
+    assert seen["last"] == [P.EINVAL] * len(FAMILIES) and seen["unknown"] == [P.EINVAL] * 4 and seen["null"] == P.EINVAL
     assert seen["plan"][:4] == (17, 2, 3, 1)
     c = _case(WINO, "small", "ep0", (16, 16))
     assert P.decide(lib, c) == P.default_plan(lib, c) and P.decide(lib, c)[:4] != (17, 2, 3, 1)      # the other thread's pin is not ours
 
 
-@pytest.mark.parametrize("family", FAMILIES, ids=lambda f: KERNEL[f])
+@pytest.mark.parametrize("family", PLANNED, ids=lambda f: KERNEL[f])
 def test_pin_in_pin_out(lib, family):
     """every feasible plan of the family's first large case: the pinned fields come back, the derived ones follow from them,
     and a partial pin leaves the planner its choice among the rest"""
@@ -132,7 +136,7 @@ def _fresh(family, od, N=3):
     return P.PlanCase(f"fresh-{od}", family, g, N)
 
 
-@pytest.mark.parametrize("family", FAMILIES, ids=lambda f: KERNEL[f])
+@pytest.mark.parametrize("family", PLANNED, ids=lambda f: KERNEL[f])
 def test_a_pinned_query_neither_reads_nor_writes_the_memo(lib, family):
     """the other plan: one run over the whole z axis with the smallest tile block -- never the cost model's choice for a
     batch of three at these sizes, so a memo that had kept it would answer the unpinned query with it"""
@@ -165,7 +169,7 @@ def test_case_is_the_familys_and_its_default_plan_is_in_the_list(lib, case):
     assert (len(run) == len(plans)) if case.small else (len(run) <= 170), (case.id, len(run), len(plans))
 
 
-@pytest.mark.parametrize("family", FAMILIES, ids=lambda f: KERNEL[f])
+@pytest.mark.parametrize("family", PLANNED, ids=lambda f: KERNEL[f])
 def test_every_value_of_every_class_coordinate_is_swept(lib, family):
     """the condition the sweep shapes were chosen by (plan_cases.SHAPES): over the family's cases, every coordinate takes
     every one of its values; and every kernel instance sees every z-run class and both pitches / all MTW"""
@@ -205,7 +209,7 @@ def _swept(lib):
 
 
 def _family_of(sym):
-    return next((f for f in FAMILIES if sym.startswith(KERNEL[f] + "<")), None)
+    return next((f for f in PLANNED if sym.startswith(KERNEL[f] + "<")), None)
 
 
 def _case_of_args(family, a, name):
@@ -297,3 +301,246 @@ def test_the_workloads_default_plans_stay_inside_the_sweep(lib, monkeypatch):
         if sig not in swept.get(P.instance(case), ()):
             outside.append((name, plan, sig))
     assert not outside, "\n".join(map(str, outside))
+
+
+# ------------------------------------------------------------------------------------------------ the k4 s2 kernels
+# conv_s2_k, convT_mfma_k, bww_s2_k / bww_s2tb_k: one pinned number each, in place of the closed-form rule's
+@pytest.fixture(scope="module")
+def s2_plans(lib):
+    """{case id: (default plan, feasible list)} of every k4 s2 case"""
+    return {c.id: (P.default_plan(lib, c), P.enumerate_plans(lib, c)) for f in S2 for c in CASES[f]}
+
+
+def _refused(lib, case, x):
+    """a pin outside the family's range: the family declines (the C ABI shows it by what answers instead) -> the symbol the
+    dry query names"""
+    a = P.dry_args(case)
+    with P.pinned(lib, case.family, (x,)):
+        taken, sym = P.describe(lib, case, a)
+        assert not taken and not sym.startswith(P.SYMBOLS[case.family]), (case.id, x, sym)
+    return sym
+
+
+@pytest.mark.parametrize("family", S2, ids=lambda f: KERNEL[f])
+def test_s2_pin_in_pin_out(lib, s2_plans, family):
+    """every case: the accepted pins are 1 .. K without a gap, K the valid range of include/tem_hip.h's table; the pinned number
+    comes back and nothing else moves but what follows from it; 0 and K + 1 are refused by the family (TEM_EUNSUPPORTED inside
+    the library: tem_conv_is_tiled / tem_bww_is_tiled go on and name the next kernel, or none for a transposed layer, whose direct
+    form has no dry query), and the refusal leaves the last decision alone"""
+    nxt = {CONV_S2: lambda sym: sym.startswith(("conv_lds_k<", "conv_direct_k<")), CONVT_MFMA: lambda sym: sym == "",
+           BWW_S2: lambda sym: sym == "" or sym.startswith("bww_lds_k<")}[family]
+    for case in CASES[family]:
+        d, plans = s2_plans[case.id]
+        K = len(plans)
+        assert [v[0] for v in plans] == list(range(1, K + 1)) and d in plans, (case.id, d, plans)
+        if family == CONV_S2:
+            assert K == min(d[3], d[7]) and all(v[1:] == d[1:] for v in plans), case.id            # min(iters, resident)
+        elif family == CONVT_MFMA:
+            assert d[0] <= K <= min(d[3], 32), case.id                                            # the hard bounds may stop short of nQy
+            assert all(v[1] == ceil(v[3], v[0]) and v[2:] == d[2:] for v in plans), case.id
+        else:
+            assert K == min(d[1], P.MAX_SLABS) and all(v[1:] == d[1:] for v in plans), case.id     # min(rows, max slabs)
+        assert P.decide(lib, case, (-1, -1, -1, -1)) == d
+        for x in (0, K + 1, 1 << 20):
+            want = P.default_plan(lib, case)
+            sym = _refused(lib, case, x)
+            assert nxt(sym), (case.id, x, sym)
+            assert P.last(lib, family) == want, (case.id, x)
+        assert P.default_plan(lib, case) == d                                                      # set and clear: nothing moved
+
+
+def test_s2_slab_count_is_the_pinned_R_and_the_budget_still_binds(lib):
+    case = _case(BWW_S2, "small", "p0", (16, 16))
+    a = P.dry_args(case)
+    for R in (1, 7, 30):
+        with P.pinned(lib, BWW_S2, (R,)):
+            a.nslab = P.MAX_SLABS
+            assert lib.tem_conv_bwd_weight_nslab(C.byref(a)) == R
+            a.nslab = R
+            name = C.create_string_buffer(96)
+            assert lib.tem_bww_is_tiled(C.byref(a), name, 96) == 1 and name.value.startswith(b"bww_s2_k<"), name.value
+            assert P.last(lib, BWW_S2)[0] == R
+    with P.pinned(lib, BWW_S2, (7,)):                    # a pin above the caller's slab budget: max_slabs applies unchanged
+        a.nslab = 6
+        assert lib.tem_conv_bwd_weight_nslab(C.byref(a)) != 7
+
+
+@pytest.mark.parametrize("family", S2, ids=lambda f: KERNEL[f])
+def test_s2_pins_are_per_thread(lib, family):
+    import threading
+    case = CASES[family][0]
+    d, seen = P.default_plan(lib, case), {}
+    P.pin(lib, family, (1,))                             # stays set in this thread while the other one asks
+
+    def ask():
+        seen["before"] = P.last(lib, family)
+        seen["plan"] = P.decide(lib, case)
+    t = threading.Thread(target=ask)
+    t.start(); t.join()
+    assert seen["before"] is None and seen["plan"] == d and d[0] != 1
+    assert P.last(lib, family) == d and P.decide(lib, case, None, P.dry_args(case))[0] == 1      # ours is still pinned
+    P.pin(lib, family, None)
+    assert P.decide(lib, case) == d
+
+
+# The three closed-form rules, restated: unpinned, the seam must not move any launch's geometry.
+S2_INSTANCE = {(8, 8): (4, 1, 1), (8, 16): (2, 1, 0), (16, 16): (2, 1, 0), (16, 32): (2, 2, 0), (32, 32): (1, 1, 0)}     # conv_s2_k: T, NT, TB
+
+
+def _rule(case, v, max_slabs=P.MAX_SLABS):
+    (ci, co), g, N = case.channels, case.geom, case.N
+    OD, OH, OW = out_dims(g)
+    if case.family == CONV_S2:
+        T, NT, TB = S2_INSTANCE[(ci, co)]
+        tiles_pp = ceil(OH * (OW + TB), 16 - TB)
+        total = N * OD * tiles_pp
+        iters, ny = ceil(total, T), ceil(co, 16 * NT)
+        resident = 256 * (2 if ci == 8 else 1) // ny
+        return (min(iters, resident), ny, T, iters, total, tiles_pp, TB, resident)
+    if case.family == CONVT_MFMA:
+        p = g["p"]
+        nQz, nQy, nQx = ((o - 1 + p) // 2 - p // 2 + 1 for o in (OD, OH, OW))
+        TY = 0
+        for ty in range(1, min(nQy, 32) + 1):
+            if 2 * (ty + 1) * (nQx + 1) * (ci // 4) > 12 * 256 or (2 * (ty + 1) * (nQx + 1) * (ci + 2) + 4 * 16 * 20 + 4) * 4 > 56 * 1024:
+                break
+            TY = ty
+            if ceil(ty * nQx, 16) >= 16:
+                break
+        return (TY, ceil(nQy, TY), nQz, nQy, nQx, 1, v[6], 0)
+    k, rows = g["k"], N * OD * OH
+    tb = int(k == 4 and (ci, co) == (8, 8))
+    if tb:
+        R, least = 512, 8
+    else:
+        lds = 0 if ci == 32 else 4 * k * (ci // 4) * ceil(co, 16) * 64 * 16
+        R, least = (128 if lds <= 80 * 1024 and ci != 32 else 64), (2 if ci == 32 else 8)
+    while R > 1 and rows // R < least:
+        R >>= 1
+    return (min(R, max_slabs), rows, tb, k, OW, 0, 0, 0)
+
+
+def _s2_family_of(sym):
+    return next((f for f in S2 if sym.startswith(P.SYMBOLS[f])), None)
+
+
+_STEP_LAUNCHES = []
+
+
+def _step_launches(lib, monkeypatch):
+    """(name, case, default plan, slab budget) of every launch of the 3-D fp32 train steps at 74, 132 and 260 that one of the k4 s2
+    kernels takes: the launch lists tests/test_step_admission.py builds, each asked again from its finished struct"""
+    if _STEP_LAUNCHES:
+        return _STEP_LAUNCHES
+    import test_step_admission as SA
+    from fullsize_cases import launch_struct
+    from transfer_em_amd import _lib
+    for n, is3d, prec, b in SA.CONFIGS:
+        if not is3d or prec != "fp32":
+            continue
+        with SA.dry_step(monkeypatch, n, is3d, prec, b) as st:
+            for l in st.compute + st.update:
+                a, f = launch_struct(l), _s2_family_of(l.meta.get("kernel") or "")
+                if a is None or f is None:
+                    continue
+                name, buf = f"{n} b{b} {l.name}", C.create_string_buffer(96)
+                if f == BWW_S2:
+                    assert lib.tem_conv_bwd_weight_nslab(C.byref(a)) == a.nslab, name
+                    g = _g("bww", a.in0.C, a.dout.C, a.kd, a.sd, a.pd, (a.in0.D, a.in0.H, a.in0.W))
+                    g["out"], budget = (a.dout.D, a.dout.H, a.dout.W), a.nslab
+                else:
+                    assert lib.tem_conv_is_tiled(C.byref(a), int(f == CONVT_MFMA), buf, 96) == 1 and buf.value.decode() == l.meta["kernel"], name
+                    g = _g(P.ENTRY[f], a.in0.C, a.out0.C, a.kd, a.sd, a.pd, (a.in0.D, a.in0.H, a.in0.W))
+                    g["out"], budget = (a.out0.D, a.out0.H, a.out0.W), 0
+                _STEP_LAUNCHES.append((name, P.PlanCase(name, f, g, a.in0.N), P.last(lib, f), budget))
+    return _STEP_LAUNCHES
+
+
+def test_s2_unpinned_geometry_is_the_closed_form_rule(lib, s2_plans, monkeypatch):
+    for f in S2:
+        for case in CASES[f]:
+            d = s2_plans[case.id][0]
+            assert d == _rule(case, d), (case.id, d)
+    launches = _step_launches(lib, monkeypatch)
+    assert len(launches) > 100 and {c.family for _, c, _, _ in launches} == set(S2)
+    for name, case, plan, budget in launches:
+        assert plan == _rule(case, plan, budget or P.MAX_SLABS), (name, plan)
+
+
+@pytest.mark.parametrize("family", S2, ids=lambda f: KERNEL[f])
+def test_every_value_of_every_s2_coordinate_is_swept_in_every_instance(lib, family):
+    """no class is waived: what an instance lacks is what it cannot have (plan_cases.s2_values)"""
+    per, want = {}, {}
+    for case in CASES[family]:
+        have = per.setdefault(P.instance(case), {c: set() for c in P.S2_COORDS[family]})
+        want[P.instance(case)] = P.s2_values(case)
+        for v in P.sweep_list(lib, case):
+            for c, x in zip(P.S2_COORDS[family], P.signature(case, v)):
+                have[c].add(x)
+    assert len(per) == {CONV_S2: 5, CONVT_MFMA: 5, BWW_S2: 7}[family]
+    for inst, have in per.items():
+        assert all(have[c] >= want[inst][c] for c in have), (inst, {c: want[inst][c] - have[c] for c in have})
+        assert all(have[c] == want[inst][c] for c in have if c != "zpar"), (inst, have)      # (the generator's pairs also run pad 2 and 3)
+    if family == CONVT_MFMA:                               # the three compiled epilogues of every pair, the Philox form as well
+        assert {(P.instance(c), P.default_plan(lib, c)[6], c.geom["keep"]) for c in CASES[family]} == \
+            {(i, e, k) for i in per for e, k in ((0, 0), (0, 1), (1, 2), (2, 0))}
+        assert all(P.default_plan(lib, c)[5] == 1 for c in CASES[family])                   # NCLS: every CT_CASE compiles 1 today
+
+
+def test_the_steps_stride2_default_plans_stay_inside_the_sweep(lib, monkeypatch):
+    swept = _swept(lib)
+    outside, seen = [], set()
+    for name, case, plan, _ in _step_launches(lib, monkeypatch):
+        sig = P.signature(case, plan)
+        if (P.instance(case), plan, case.N) + out_dims(case.geom) not in seen:
+            seen.add((P.instance(case), plan, case.N) + out_dims(case.geom))
+            print(f"{name}: {case.channels} {case.N} x {out_dims(case.geom)} {dict(zip(P.FIELDS[case.family], plan))} {sig}")
+        if sig not in swept.get(P.instance(case), ()):
+            outside.append((name, plan, sig))
+    assert not outside, "\n".join(map(str, sorted(set(map(str, outside)))))
+
+
+# (feasible, run) per shape of plan_cases.S2_SHAPES, by (kernel, C_in, C_out, k[, pad of a transposed layer])
+S2_COUNTS = {
+    ('conv_s2_k', 8, 8, 4): [(5, 5), (1, 1), (4, 4), (18, 6), (24, 5), (32, 5), (30, 6), (27, 6)],
+    ('conv_s2_k', 8, 16, 4): [(9, 9), (1, 1), (8, 8), (32, 5), (48, 6), (59, 7), (48, 6), (45, 7)],
+    ('conv_s2_k', 16, 16, 4): [(9, 9), (1, 1), (8, 8), (32, 5), (48, 6), (59, 7), (48, 6), (45, 7)],
+    ('conv_s2_k', 16, 32, 4): [(9, 9), (1, 1), (8, 8), (32, 5), (48, 6), (59, 7), (48, 6), (45, 7)],
+    ('conv_s2_k', 32, 32, 4): [(18, 18), (2, 2), (15, 15), (63, 7), (96, 5), (117, 7), (96, 5), (90, 7)],
+    ('convT_mfma_k', 16, 8, 4, 1): [(6, 6), (6, 6), (12, 12)],
+    ('convT_mfma_k', 16, 8, 4, 0): [(6, 6), (6, 6), (12, 12)],
+    ('convT_mfma_k', 32, 16, 4, 1): [(6, 6), (6, 6), (10, 10)],          # TY = 11 would pass 56 KB of LDS: the hard bound, not nQy, ends the list
+    ('convT_mfma_k', 32, 16, 4, 0): [(6, 6), (6, 6), (10, 10)],
+    ('convT_mfma_k', 8, 8, 4, 1): [(6, 6), (6, 6), (12, 12)],
+    ('convT_mfma_k', 8, 8, 4, 0): [(6, 6), (6, 6), (12, 12)],
+    ('convT_mfma_k', 16, 16, 4, 1): [(6, 6), (6, 6), (12, 12)],
+    ('convT_mfma_k', 16, 16, 4, 0): [(6, 6), (6, 6), (12, 12)],
+    ('convT_mfma_k', 32, 32, 4, 1): [(6, 6), (6, 6), (10, 10)],
+    ('convT_mfma_k', 32, 32, 4, 0): [(6, 6), (6, 6), (10, 10)],
+    ('convT_mfma_k', 16, 8, 4, 2): [(4, 4), (4, 4), (10, 10)],
+    ('convT_mfma_k', 16, 8, 4, 3): [(4, 4), (4, 4), (10, 10)],
+    ('convT_mfma_k', 32, 16, 4, 2): [(4, 4), (4, 4), (10, 10)],
+    ('convT_mfma_k', 32, 16, 4, 3): [(4, 4), (4, 4), (10, 10)],
+    ('bww_s2_k', 8, 16, 4): [(30, 30), (8, 8), (28, 28)],
+    ('bww_s2_k', 16, 16, 4): [(30, 30), (8, 8), (28, 28)],
+    ('bww_s2_k', 16, 32, 4): [(30, 30), (8, 8), (28, 28)],
+    ('bww_s2_k', 32, 32, 4): [(30, 30), (8, 8), (28, 28)],
+    ('bww_s2_k', 8, 8, 4): [(30, 30), (8, 8), (28, 28)],
+    ('bww_s2_k', 16, 32, 3): [(30, 30), (8, 8), (28, 28)],
+    ('bww_s2_k', 32, 32, 3): [(30, 30), (8, 8), (28, 28)],
+}
+
+
+def test_s2_feasible_plan_counts(lib, s2_plans):
+    """the numbers of DESIGN.md's table for the k4 s2 kernels: feasible plans / plans run, per instance and shape (the variants of
+    an instance at one padding agree; convT_mfma_k's Q ranges follow the padding)"""
+    table = {}
+    for f in S2:
+        for case in CASES[f]:
+            tag = case.name.split("-", 3)[3]
+            key = (KERNEL[f],) + case.channels + (case.geom["k"],) + ((case.geom["p"],) if f == CONVT_MFMA else ())
+            table.setdefault(key, {}).setdefault(tag, set()).add((len(s2_plans[case.id][1]), len(P.sweep_list(lib, case))))
+    assert all(len(v) == 1 for row in table.values() for v in row.values()), table
+    family = {KERNEL[f]: f for f in S2}
+    got = {k: [next(iter(row[tag])) for tag, _, _ in P.S2_SHAPES[family[k[0]]]] for k, row in table.items()}
+    assert got == S2_COUNTS, got

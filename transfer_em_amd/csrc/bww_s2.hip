@@ -386,6 +386,17 @@ __global__ __launch_bounds__(256) void bww_s2tb_k(Dev p) {
 
 // ------------------------------------------------------------------------------------------ host
 
+// pin: the {R} of tem_plan_pin -- a pinned count of row ranges replaces the rule's (and the TEM_BWW_S2_R / _TBR knobs') inside the
+// range the kernels cover: every range holds a row (blockIdx.x rows / R is then strictly increasing) and has a slab.  -> false
+// where the pin lies outside it
+static bool pinned_ranges(int rows, int max_slabs, int &R) {
+  const int32_t *const pin = tem_plan_pinned(TEM_PLAN_BWW_S2);
+  if (!pin || pin[0] < 0) return true;
+  if (pin[0] < 1 || pin[0] > rows || pin[0] > max_slabs) return false;
+  R = pin[0];
+  return true;
+}
+
 template <int CI, int CO, int KS = 4, int S = 2>
 static int run(Dev p, int max_slabs, hipStream_t st, bool dry, int *nslab_out, char *name, int name_len) {
   constexpr int MT = (CO + 15) / 16, J = CI / 4, NACC = KS * J * MT;
@@ -399,8 +410,10 @@ static int run(Dev p, int max_slabs, hipStream_t st, bool dry, int *nslab_out, c
   if (rr > 0) R = rr;
   while (R > 1 && p.rows / R < (CI == 32 ? 2 : 8)) R >>= 1;     // (32 input channels: every wave walks all rows of the range)
   if (R > max_slabs) R = max_slabs;
+  if (!pinned_ranges(p.rows, max_slabs, R)) return TEM_EUNSUPPORTED;
   if (R < 1) return TEM_EUNSUPPORTED;
   p.R = R;
+  tem_plan_note(TEM_PLAN_BWW_S2, R, p.rows, 0, KS, p.OW, 0, 0, 0);
   if (nslab_out) *nslab_out = R;
   if (name) snprintf(name, name_len, "bww_s2_k<%d, %d, %d, %d>", CI, CO, KS, S);
   if (dry) return TEM_OK;
@@ -425,8 +438,10 @@ static int run_tb(Dev p, int max_slabs, hipStream_t st, bool dry, int *nslab_out
   if (rr > 0) R = rr;
   else while (R > 1 && p.rows / R < 8) R >>= 1;                      // at least two rows per wave
   if (R > max_slabs) R = max_slabs;
+  if (!pinned_ranges(p.rows, max_slabs, R)) return TEM_EUNSUPPORTED;
   if (R < 1) return TEM_EUNSUPPORTED;
   p.R = R;
+  tem_plan_note(TEM_PLAN_BWW_S2, R, p.rows, 1, 4, p.OW, 0, 0, 0);
   if (nslab_out) *nslab_out = R;
   if (name) snprintf(name, name_len, "bww_s2tb_k<%d>", nb == 6 ? 6 : 8);
   if (dry) return TEM_OK;

@@ -301,12 +301,7 @@ static int run(Dev p, hipStream_t st, bool dry, char *name, int name_len) {
   p.tiles_pp = (p.plane_vox + VPT - 1) / VPT;
   const int64_t total = (int64_t)p.oN_count * p.OD * p.tiles_pp;
   if (total > (1 << 22) || p.tiles_pp > 1024 || p.OW > 1024) return TEM_EUNSUPPORTED;    // range of the magic divisions
-  if (dry) {
-    if (name) snprintf(name, name_len, "conv_s2_k<%d, %d, %d, %s>", CI, NT, T, TB ? "true" : "false");
-    return TEM_OK;
-  }
   p.total = (int)total;
-  p.magicOW = magic_for(p.RL); p.magicTpp = magic_for(p.tiles_pp); p.magicOD = magic_for(p.OD);
   p.iters = (p.total + T - 1) / T;
   // as many workgroups as are resident at once (each keeps its B fragment for its whole contiguous range of tiles: the
   // ~3 us prologue -- B loads, first A loads -- is paid once per CU slot; more, shorter workgroups measured 15-25 % slower)
@@ -314,7 +309,19 @@ static int run(Dev p, hipStream_t st, bool dry, char *name, int name_len) {
   if (mult < 0) mult = tem_env_int("TEM_S2_WGS", 1);
   const int ny = (p.CO + 16 * NT - 1) / (16 * NT);
   const int resident = 256 * (CI == 8 ? 2 : 1) * mult / ny;
-  const int nblocks = p.iters < resident ? p.iters : resident;
+  int nblocks = p.iters < resident ? p.iters : resident;
+  // pin: the {nblocks} of tem_plan_pin or null -- a pinned count replaces the rule's inside the range the kernel's two walks
+  // cover (every iteration has a workgroup: 1 .. the rule's own count), nothing else changes
+  if (const int32_t *const pin = tem_plan_pinned(TEM_PLAN_CONV_S2); pin && pin[0] >= 0) {
+    if (pin[0] < 1 || pin[0] > nblocks) return TEM_EUNSUPPORTED;
+    nblocks = pin[0];
+  }
+  tem_plan_note(TEM_PLAN_CONV_S2, nblocks, ny, T, p.iters, p.total, p.tiles_pp, TB ? 1 : 0, resident);
+  if (dry) {
+    if (name) snprintf(name, name_len, "conv_s2_k<%d, %d, %d, %s>", CI, NT, T, TB ? "true" : "false");
+    return TEM_OK;
+  }
+  p.magicOW = magic_for(p.RL); p.magicTpp = magic_for(p.tiles_pp); p.magicOD = magic_for(p.OD);
   const size_t lds_bytes = (size_t)2 * NWAVE * T * NT * 16 * PITCH * 4;
   static bool attr = false;
   if (!attr && lds_bytes > 64 * 1024) {
