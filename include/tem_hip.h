@@ -705,7 +705,27 @@ int tem_instance_norm_bwd(const tem_view *x, const tem_view *dy, const float *sc
  *   TEM_PLAN_BWW_S2      {R, -1..}         1 <= R <= min(rows, max slabs)             {R, rows, tb (1: bww_s2tb_k), KS, OW, 0, 0, 0}
  * (conv_s2_k: workgroups along x, along y, tiles per iteration, iterations, tiles, tiles per plane, two-block form, resident
  * slots.  convT_mfma_k: Q_y rows per band, bands, Q extents, classes per patch, compiled epilogue.  bww_s2_k / bww_s2tb_k: row
- * ranges = slabs, output rows N OD OH, kernel extent, row length.) */
+ * ranges = slabs, output rows N OD OH, kernel extent, row length.)
+ * The 3-D kernels of bf16 mode take their launch geometry from the host as well: conv_bf16_k an output patch from a score search
+ * over TY 1..16 x nbx 1..8, convT_bf16_k the Q_y rows of a band and bww_bf16_k band rows, z-runs and column segments from closed
+ * forms.  The same semantics: a pin replaces the searched or computed number, every validity check of the host code applies
+ * unchanged, outside the valid range the family answers TEM_EUNSUPPORTED (the route goes on; these kernels are its last), and
+ * tem_conv_bf16_describe / tem_conv_transpose_bf16_describe / tem_conv_bwd_weight_bf16_nslab answer under a pin what the launch
+ * will do.  A pin takes precedence over the knob builds' TEM_BWWH_*.
+ *   family               pin v4               valid under a pin                            last v8
+ *   TEM_PLAN_CONV_BF16   {TY, nbx, -1, -1}    the search's own feasibility (loader chunks, {TY, nbx, TX, nby, rows, cols, tiles, LDS bytes}
+ *                                             64 KB) and nbx == ceil(OW / TX): no empty
+ *                                             last column
+ *   TEM_PLAN_CONVT_BF16  {TY, -1..}           1 <= TY <= min(nQy, 32), the patch within    {TY, nband, nQz, nQy, nQx, NCLS, EPM, 0}
+ *                                             the loader's registers and 56 KB of LDS
+ *   TEM_PLAN_BWW_BF16    {TY, zsegs, seg, -1} TY: 1 .. the rule's own bound for the row;   {TY, nband, zsegs, zper, nseg, seg, NGRP, slabs}
+ *                                             zsegs: 1 .. OD and canonical (zsegs ==
+ *                                             ceil(OD / ceil(OD / zsegs))); seg: a multiple
+ *                                             of 16 whose one-row band fits, pad 0 (seg >=
+ *                                             OW: the single launch); workgroups <= nslab
+ * (conv_bf16_k: patch rows, column blocks, patch columns, row blocks, input patch rows and columns, 16-voxel tiles of a full
+ * patch, dynamic LDS.  bww_bf16_k: rows per band, bands, z-runs, planes per run, column segments, segment width (OW: one
+ * launch), row groups = grid.y, slabs of the whole launch; TY, nband, zsegs, zper are the first segment's.) */
 #define TEM_PLAN_WINO       1
 #define TEM_PLAN_WINO_BWW   2
 #define TEM_PLAN_CONV_LDS   3
@@ -713,6 +733,9 @@ int tem_instance_norm_bwd(const tem_view *x, const tem_view *dy, const float *sc
 #define TEM_PLAN_CONV_S2    5
 #define TEM_PLAN_CONVT_MFMA 6
 #define TEM_PLAN_BWW_S2     7
+#define TEM_PLAN_CONV_BF16  8
+#define TEM_PLAN_CONVT_BF16 9
+#define TEM_PLAN_BWW_BF16   10
 int tem_plan_pin(int32_t family, const int32_t *v4);
 int tem_plan_last(int32_t family, int32_t *v8);
 

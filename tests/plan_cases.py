@@ -20,7 +20,9 @@ Class signature of a plan ("Plan space") -- the coordinates along whi
          bytes) although the row count is in range.  conv_lds_k stages through registers: False
 The k4 s2 kernels (conv_s2_k, convT_mfma_k, bww_s2_k / bww_s2tb_k) have no cost model: one number each comes from a closed-form
 rule, and the same seam pins it.  Their cases, shapes and class coordinates stand in the section "the k4 s2 kernels" below.
-tests/test_plan_space.py holds the tables to these definitions on the CPU, tests/test_gpu_plan_space.py runs them."""
+tests/test_plan_space.py holds the tables to these definitions on the CPU, tests/test_gpu_plan_space.py runs them.
+Families 8 .. 10 (conv_bf16_k, convT_bf16_k, bww_bf16_k) have their constants and dry queries here, so that one `clear_pins`
+serves every test; their cases, coordinates and restated rules stand in tests/bf16_plan_cases.py."""
 import contextlib
 import ctypes as C
 
@@ -29,16 +31,21 @@ from span_cases import MAX_SLABS, Case, _g, dense, extents, out_dims
 WINO, WINO_BWW, CONV_LDS, CONV3_BF16, CONV_S2, CONVT_MFMA, BWW_S2 = 1, 2, 3, 4, 5, 6, 7
 PLANNED = (WINO, WINO_BWW, CONV_LDS, CONV3_BF16)        # the plan comes from a cost model's search
 S2 = (CONV_S2, CONVT_MFMA, BWW_S2)                      # the k4 s2 kernels: one number from a closed-form rule (further down)
-FAMILIES = PLANNED + S2
+CONV_BF16, CONVT_BF16, BWW_BF16 = 8, 9, 10                 # the other 3-D kernels of bf16 mode: tests/bf16_plan_cases.py
+BF16 = (CONV_BF16, CONVT_BF16, BWW_BF16)
+FAMILIES = PLANNED + S2 + BF16
 KERNEL = {WINO: "wino_conv_k", WINO_BWW: "wino_bww_k", CONV_LDS: "conv_lds_k", CONV3_BF16: "conv3_bf16_k",
-          CONV_S2: "conv_s2_k", CONVT_MFMA: "convT_mfma_k", BWW_S2: "bww_s2_k"}
+          CONV_S2: "conv_s2_k", CONVT_MFMA: "convT_mfma_k", BWW_S2: "bww_s2_k",
+          CONV_BF16: "conv_bf16_k", CONVT_BF16: "convT_bf16_k", BWW_BF16: "bww_bf16_k"}
 SYMBOLS = {f: (k + "<",) for f, k in KERNEL.items()}
 SYMBOLS[BWW_S2] += ("bww_s2tb_k<",)                     # 8 -> 8: the two-block form, same rule and the same family
 FIELDS = {WINO: "E BY BX zsegs zper nby nbx ndma".split(), WINO_BWW: "E BY BX zsegs zper nby nbx ndma".split(),
           CONV_LDS: "MTW R patch zsegs zper nych ntiles -".split(), CONV3_BF16: "nbx TY zsegs zper nby RD ndma -".split(),
           CONV_S2: "nblocks ny T iters total tiles_pp TB resident".split(), CONVT_MFMA: "TY nband nQz nQy nQx NCLS EPM -".split(),
-          BWW_S2: "R rows tb KS OW - - -".split()}
-NPIN = {WINO: 4, WINO_BWW: 4, CONV_LDS: 4, CONV3_BF16: 3, CONV_S2: 1, CONVT_MFMA: 1, BWW_S2: 1}
+          BWW_S2: "R rows tb KS OW - - -".split(), CONV_BF16: "TY nbx TX nby rows cols tiles lds".split(),
+          CONVT_BF16: "TY nband nQz nQy nQx NCLS EPM -".split(), BWW_BF16: "TY nband zsegs zper nseg seg NGRP slabs".split()}
+NPIN = {WINO: 4, WINO_BWW: 4, CONV_LDS: 4, CONV3_BF16: 3, CONV_S2: 1, CONVT_MFMA: 1, BWW_S2: 1, CONV_BF16: 2, CONVT_BF16: 1,
+        BWW_BF16: 3}
 EUNSUPPORTED, EINVAL = -2, -1
 
 
@@ -137,6 +144,17 @@ def describe(lib, case, a):
         ok = lib.tem_conv_is_tiled(C.byref(a), 0, name, 96) == 1
     elif f == CONVT_MFMA:
         ok = lib.tem_conv_is_tiled(C.byref(a), 1, name, 96) == 1
+    elif f == CONV_BF16:
+        ok = lib.tem_conv_bf16_describe(C.byref(a), name, 96) == 0
+    elif f == CONVT_BF16:
+        ok = lib.tem_conv_transpose_bf16_describe(C.byref(a), name, 96) == 0
+    elif f == BWW_BF16:                    # the slab count follows the plan; asked again with it, the query repeats it (the launch's check)
+        a.nslab = MAX_SLABS if not getattr(case, "budget", 0) else case.budget
+        n = lib.tem_conv_bwd_weight_bf16_nslab(C.byref(a), name, 96)
+        ok = n > 0
+        if ok:
+            a.nslab = n
+            ok = lib.tem_conv_bwd_weight_bf16_nslab(C.byref(a), name, 96) == n
     elif f == BWW_S2:                      # the slab count is the plan's R; asked with it, tem_bww_is_tiled names the launch's kernel
         a.nslab = MAX_SLABS
         n = lib.tem_conv_bwd_weight_nslab(C.byref(a))
@@ -540,7 +558,7 @@ for _ci, _co in BWW_S2_PAIRS:
     CASES[BWW_S2] += _s2_cases(BWW_S2, "p1", _ci, _co, 4, 2, 1)                                           # 8 -> 16: a transposed layer's, operands swapped
 CASES[BWW_S2] += _s2_cases(BWW_S2, "p0", 16, 32, 3, 1, 0)                                                 # the small k3 s1 layers routed here
 CASES[BWW_S2] += _s2_cases(BWW_S2, "p0", 32, 32, 3, 1, 0)
-ALL_CASES = [c for f in FAMILIES for c in CASES[f]]
+ALL_CASES = [c for f in PLANNED + S2 for c in CASES[f]]
 
 
 def instance(case):

@@ -265,9 +265,10 @@ __global__ __launch_bounds__(256) void bww_bf16_k(Dev p) {
 
 // ------------------------------------------------------------------------------------------ host
 // Rows per band for output rows of OW voxels: the largest band (<= 8 rows) whose patch fits the loaders' prefetch registers
-// and the LDS; 0 when not even a band of one row fits.
+// and the LDS; 0 when not even a band of one row fits.  want >= 0: the pinned {TY} of tem_plan_pin -- that band height under the
+// same conditions (they tighten with ty, so every height up to the rule's own passes them), 0 where it lies outside them.
 template <int CI, int CO, int K, int S, int PFX, int PFG>
-int band_rows(int OW, int OH, size_t *lds_bytes) {
+int band_rows(int OW, int OH, size_t *lds_bytes, int want = -1) {
   constexpr int PITCH = CI >= 8 ? (CI <= 16 ? CI : CI + 4) : 1, GP = CO <= 16 ? CO : CO + 4, CPX = CI >= 8 ? CI / 8 : 1, CPG = CO / 8;
   const int OWp = (OW + 15) & ~15, colsR = (OW - 1) * S + K, colsA = (OWp - 1) * S + K + 4;
   int TY = 0;
@@ -279,20 +280,26 @@ int band_rows(int OW, int OH, size_t *lds_bytes) {
     if ((size_t)rows * colsR * CPX > (size_t)((PFX + 2) / 3) * 256 || (size_t)ty * OW * CPG > (size_t)PFG * 256 ||
         bytes > (ty == 1 ? 120 : 72) * 1024) break;
     TY = ty; *lds_bytes = bytes;
+    if (ty == want) break;
   }
-  return TY;
+  return want >= 0 && TY != want ? 0 : TY;
 }
 
 // One launch over output rows of p.OW voxels.  nseg: the number of column segments the row was cut into (run(), below);
-// the segments share the workgroup budget.
+// the segments share the workgroup budget.  plan (or null): receives this launch's {TY, nband, zsegs, zper, slabs}; run() notes the
+// row's plan from its first segment once every segment has been admitted, so that a refusal leaves the last decision alone.
+// pin: the {TY, zsegs, seg} of tem_plan_pin or null -- a pinned band height or z split replaces the rule's (and the TEM_BWWH_*
+// knobs') inside the range the kernel covers: the band within band_rows' conditions, every z-run with a plane (zsegs the
+// count its own run length gives back), and as many workgroups as the caller has slabs.
 template <int CI, int CO, int K, int S, int PFX, int PFG, int MTG>
-int run_seg(Dev p, int N, int max_slabs, int nseg, hipStream_t st, bool dry, int *nslab_out, char *name, int name_len) {
+int run_seg(Dev p, int N, int max_slabs, int nseg, int32_t *plan, const int32_t *pin, hipStream_t st, bool dry, int *nslab_out,
+            char *name, int name_len) {
   constexpr int NTAP = K * K * K, MT = (NTAP * CI + 15) / 16;
   p.OWp = (p.OW + 15) & ~15;
   p.colsR = (p.OW - 1) * S + K;
   p.colsA = (p.OWp - 1) * S + K + 4;                      // the last k-block reads up to OWp voxels (+ C_in == 1: 4-voxel reads)
   size_t lds_bytes = 0;
-  const int TY = band_rows<CI, CO, K, S, PFX, PFG>(p.OW, p.OH, &lds_bytes);
+  const int TY = band_rows<CI, CO, K, S, PFX, PFG>(p.OW, p.OH, &lds_bytes, pin ? pin[0] : -1);
   if (TY < 1) return TEM_EUNSUPPORTED;
   p.TY = TY; p.rows = (TY - 1) * S + K;
   p.nband = (p.OH + TY - 1) / TY;
@@ -310,11 +317,17 @@ int run_seg(Dev p, int N, int max_slabs, int nseg, hipStream_t st, bool dry, int
   int zsegs = want / cols;
   if (zsegs < 1) zsegs = 1;
   if (zsegs > p.OD) zsegs = p.OD;
+  if (pin && pin[1] >= 0) {
+    if (pin[1] < 1 || pin[1] > p.OD) return TEM_EUNSUPPORTED;
+    zsegs = pin[1];
+  }
   p.zper = (p.OD + zsegs - 1) / zsegs;
   p.zsegs = (p.OD + p.zper - 1) / p.zper;
+  if (pin && pin[1] >= 0 && p.zsegs != pin[1]) return TEM_EUNSUPPORTED;
   const int nblocks = cols * p.zsegs;
   if (nblocks > max_slabs) return TEM_EUNSUPPORTED;
   if (nslab_out) *nslab_out = nblocks;
+  if (plan) { plan[0] = p.TY; plan[1] = p.nband; plan[2] = p.zsegs; plan[3] = p.zper; plan[4] = nblocks; }
   p.magicColsR = magic_for(p.colsR);
   p.magicPlaneR = magic_for(p.rows * p.colsR);
   p.magicOW = magic_for(p.OW);
@@ -337,17 +350,27 @@ int run_seg(Dev p, int N, int max_slabs, int nseg, hipStream_t st, bool dry, int
 // A row that fits one band is one launch.  A wider row (pad 0 only: the 260 model's layers) is cut into column segments of a
 // multiple of 16 output voxels (whole k-blocks; the last segment takes the rest), chosen so that a band of one row fits: the same
 // kernel runs once per segment on the offset views -- in0 / in1 at x0 * S, dout at x0 -- and writes its own slab range.
+// pin: a pinned {seg} is the segment width itself -- a multiple of 16 whose one-row band fits, pad 0 -- and cuts a row that would
+// fit one band as well; a width that covers the row is the single launch.
 template <int CI, int CO, int K, int S, int PFX, int PFG, int MTG>
 int run(Dev p, int N, int max_slabs, hipStream_t st, bool dry, int *nslab_out, char *name, int name_len) {
   size_t unused = 0;
-  if (p.OW < 1 || band_rows<CI, CO, K, S, PFX, PFG>(p.OW, 1, &unused) >= 1)
-    return run_seg<CI, CO, K, S, PFX, PFG, MTG>(p, N, max_slabs, 1, st, dry, nslab_out, name, name_len);
+  constexpr int NGRP = ((K * K * K * CI + 15) / 16 + MTG - 1) / MTG;
+  int32_t plan[5] = {};
+  const int32_t *const pin = tem_plan_pinned(TEM_PLAN_BWW_BF16);
+  const int pseg = pin ? pin[2] : -1;
+  if (pseg >= 0 && (pseg < 16 || pseg % 16)) return TEM_EUNSUPPORTED;
+  if (p.OW < 1 || (pseg < 0 ? band_rows<CI, CO, K, S, PFX, PFG>(p.OW, 1, &unused) >= 1 : pseg >= p.OW)) {
+    const int rc = run_seg<CI, CO, K, S, PFX, PFG, MTG>(p, N, max_slabs, 1, plan, pin, st, dry, nslab_out, name, name_len);
+    if (rc == TEM_OK) tem_plan_note(TEM_PLAN_BWW_BF16, plan[0], plan[1], plan[2], plan[3], 1, p.OW, NGRP, plan[4]);
+    return rc;
+  }
   if (p.P != 0) return TEM_EUNSUPPORTED;                   // the zero frame of a padded row belongs to its first and last segment only
-  int seg = p.OW & ~15;
-  while (seg >= 16 && band_rows<CI, CO, K, S, PFX, PFG>(seg, 1, &unused) < 1) seg -= 16;
-  if (seg < 16) return TEM_EUNSUPPORTED;
+  int seg = pseg >= 0 ? pseg : p.OW & ~15;
+  while (pseg < 0 && seg >= 16 && band_rows<CI, CO, K, S, PFX, PFG>(seg, 1, &unused) < 1) seg -= 16;
+  if (seg < 16 || (pseg >= 0 && band_rows<CI, CO, K, S, PFX, PFG>(seg, 1, &unused) < 1)) return TEM_EUNSUPPORTED;
   const int nseg = (p.OW + seg - 1) / seg;
-  seg = ((p.OW + nseg - 1) / nseg + 15) & ~15;             // equal segments, not one sliver at the end
+  if (pseg < 0) seg = ((p.OW + nseg - 1) / nseg + 15) & ~15;   // equal segments, not one sliver at the end
   int total = 0;
   for (int x0 = 0; x0 < p.OW; x0 += seg) {
     Dev q = p;
@@ -357,10 +380,11 @@ int run(Dev p, int N, int max_slabs, hipStream_t st, bool dry, int *nslab_out, c
     if (p.slabs) q.slabs = p.slabs + (int64_t)total * p.slab_stride;
     if (max_slabs - total < 1) return TEM_EUNSUPPORTED;
     int n = 0;
-    const int rc = run_seg<CI, CO, K, S, PFX, PFG, MTG>(q, N, max_slabs - total, nseg, st, dry, &n, name, name_len);
+    const int rc = run_seg<CI, CO, K, S, PFX, PFG, MTG>(q, N, max_slabs - total, nseg, x0 == 0 ? plan : nullptr, pin, st, dry, &n, name, name_len);
     if (rc != TEM_OK) return rc;
     total += n;
   }
+  tem_plan_note(TEM_PLAN_BWW_BF16, plan[0], plan[1], plan[2], plan[3], nseg, seg, NGRP, total);      // (slabs: the whole launch's)
   if (nslab_out) *nslab_out = total;
   return TEM_OK;
 }

@@ -273,20 +273,25 @@ int run(Dev p, int N, const u16 *w, hipStream_t st, bool dry, int epm, char *nam
   p.Qlo_y = floordiv2(p.P); p.nQy = floordiv2(p.OH - 1 + p.P) - p.Qlo_y + 1;
   p.Qlo_z = floordiv2(p.P); p.nQz = floordiv2(p.OD - 1 + p.P) - p.Qlo_z + 1;
   p.cols = p.nQx + 1;
-  // rows per band: as many as the loader's registers and ~48 KB of LDS allow, but at least ~8 tiles per workgroup
+  // rows per band: as many as the loader's registers and ~48 KB of LDS allow, but at least ~8 tiles per workgroup.
+  // pin: the {TY} of tem_plan_pin or null -- a pinned band height replaces the rule's; the two hard bounds of the loop (the
+  // loader's registers, the LDS bytes) hold for it as for any other, the stop at 16 tiles is a preference and does not
+  const int32_t *const pin = tem_plan_pinned(TEM_PLAN_CONVT_BF16);
+  const int want = pin ? pin[0] : -1;
   int TY = 0;
   for (int ty = 1; ty <= p.nQy && ty <= 32; ++ty) {
     const size_t chunks = (size_t)2 * (ty + 1) * p.cols * CPV;
     const size_t bytes = (size_t)2 * (ty + 1) * p.cols * CIP * 2 + 16 + 4 * 16 * 20 * 4;
     if (chunks > (size_t)PF * 256 || bytes > 56 * 1024) break;
     TY = ty;
-    if ((ty * p.nQx + 15) / 16 >= 16) break;
+    if (want >= 0 ? ty == want : (ty * p.nQx + 15) / 16 >= 16) break;
   }
-  if (TY < 1) return TEM_EUNSUPPORTED;
+  if (TY < 1 || (want >= 0 && TY != want)) return TEM_EUNSUPPORTED;
   p.TY = TY; p.rows = TY + 1;
   p.nband = (p.nQy + TY - 1) / TY;
   p.magicQx = magic_for(p.nQx);
   p.magicCols = magic_for(p.cols);
+  tem_plan_note(TEM_PLAN_CONVT_BF16, p.TY, p.nband, p.nQz, p.nQy, p.nQx, NCLS, epm, 0);
   if (dry) {
     if (name) snprintf(name, name_len, "convT_bf16_k<%d, %d, %d, %d, %d>", CI, CO, PF, NCLS, epm);
     return TEM_OK;

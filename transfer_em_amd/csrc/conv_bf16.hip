@@ -378,12 +378,19 @@ int run(Dev p, int N, hipStream_t st, bool dry, char *name, int name_len) {
   constexpr size_t TAB_BYTES = (CI == 1 ? 32 : (BLDS ? 1 : 2) * ((NSTEP * 4 + 3) & ~3)) * 4;
   constexpr size_t FIXED = B_BYTES + TAB_BYTES + 4 * 16 * 20 * 4;
   // output patch (TX x TY): the largest that fits ~64 KB of LDS and the loader's registers, preferring wide patches
-  // (halo share) and few wasted lanes in the last tile
+  // (halo share) and few wasted lanes in the last tile.
+  // pin: the {TY, nbx} of tem_plan_pin or null -- the search skips the candidates whose pinned fields differ; every feasibility
+  // condition holds for the pinned patch as for any other.  An nbx that gives the TX of a smaller nbx would leave its last
+  // column of patches empty (OW = 6, nbx = 4: TX = 2, a fourth column at ox0 = OW): its score ties with the smaller nbx, which
+  // comes first and stays, so skipping it changes no choice -- and keeps a pin from launching workgroups without a voxel
+  const int32_t *const pin = tem_plan_pinned(TEM_PLAN_CONV_BF16);
   double best = -1.0;
   size_t best_bytes = 0;
   for (int TY = 1; TY <= 16 && TY <= p.OH; ++TY) {
+    if (!tem_pin_ok(pin, 0, TY)) continue;
     for (int nbx = 1; nbx <= 8; ++nbx) {
       const int TX = (p.OW + nbx - 1) / nbx;
+      if (!tem_pin_ok(pin, 1, nbx) || (p.OW + TX - 1) / TX != nbx) continue;
       const int cols = (TX - 1) * S + K, rows = (TY - 1) * S + K;
       const size_t chunks = (size_t)K * rows * cols * CPV;
       const size_t bytes = ((((size_t)K * rows * cols * PITCH * 2) + 15) & ~(size_t)15) + FIXED;
@@ -401,6 +408,7 @@ int run(Dev p, int N, hipStream_t st, bool dry, char *name, int name_len) {
   p.magicCols = magic_for(p.cols);
   p.magicPlane = magic_for(p.rows * p.cols);
   p.magicTX = magic_for(p.TX);
+  tem_plan_note(TEM_PLAN_CONV_BF16, p.TY, p.nbx, p.TX, p.nby, p.rows, p.cols, (p.TX * p.TY + 15) / 16, (int)best_bytes);
   if (dry) {
     if (name) snprintf(name, name_len, "conv_bf16_k<%d, %d, %d, %d, %d, %s>", CI, CO, K, S, PF, BLDS ? "true" : "false");
     return TEM_OK;

@@ -67,9 +67,9 @@ extern "C" int tem_bww_is_tiled(const tem_bww_args *a, char *name, int32_t name_
 }
 
 // ---- plan pins: storage and helpers in tem_common.h, read by the planners of wino.hip, wino_bww.hip, conv_lds.hip, conv3_bf16.hip
-// and by the closed-form geometry rules of conv_s2.hip, convT_mfma.hip, bww_s2.hip
+// and by the host geometry rules of conv_s2.hip, convT_mfma.hip, bww_s2.hip, conv_bf16.hip, convT_bf16.hip, bww_bf16.hip
 extern "C" int tem_plan_pin(int32_t family, const int32_t *v4) {
-  if (family < TEM_PLAN_WINO || family > TEM_PLAN_BWW_S2) return TEM_EINVAL;
+  if (family < TEM_PLAN_WINO || family > TEM_PLAN_BWW_BF16) return TEM_EINVAL;
   tem_plan_slot &s = tem_plan_slots()[family];
   s.pinned = v4 != nullptr;
   for (int i = 0; i < 4; ++i) s.pin[i] = v4 ? v4[i] : -1;
@@ -77,7 +77,7 @@ extern "C" int tem_plan_pin(int32_t family, const int32_t *v4) {
 }
 
 extern "C" int tem_plan_last(int32_t family, int32_t *v8) {
-  if (family < TEM_PLAN_WINO || family > TEM_PLAN_BWW_S2 || !v8) return TEM_EINVAL;
+  if (family < TEM_PLAN_WINO || family > TEM_PLAN_BWW_BF16 || !v8) return TEM_EINVAL;
   const tem_plan_slot &s = tem_plan_slots()[family];
   if (!s.have) return TEM_EINVAL;
   for (int i = 0; i < 8; ++i) v8[i] = s.last[i];

@@ -226,7 +226,7 @@ template <size_t NK, typename R> struct tem_plan_cache {
 // neither read nor written then.  Unpinned, a planner pays one thread-local read (tem_plan_pinned) and the note of its plan.
 struct tem_plan_slot { bool pinned, have; int32_t pin[4], last[8]; };
 inline tem_plan_slot *tem_plan_slots() {            // one array per thread for the whole library (inline: one definition)
-  static thread_local tem_plan_slot s[TEM_PLAN_BWW_S2 + 1] = {};            // (the last family)
+  static thread_local tem_plan_slot s[TEM_PLAN_BWW_BF16 + 1] = {};          // (the last family)
   return s;
 }
 static inline const int32_t *tem_plan_pinned(int family) {
