@@ -494,6 +494,32 @@ int tem_u8_rescale(const uint8_t *src, int32_t D, int32_t H, int32_t W, int32_t 
 int tem_u8_lut(uint8_t *buf, int32_t D, int32_t H, int32_t W, const uint8_t *lut, int32_t per_section, int32_t zsec0,
                tem_stream_t stream);
 
+/* Repair of damaged sections and voxels of a dense uint8 block along z, in place (tiled inference and
+ * utils.volume_repair: the uploaded bytes, ahead of everything else).  buf[D][H][W] holds the sections zsec0 ...
+ * zsec0 + D - 1 of the caller's volume.  A voxel (d, y, x) is BAD if any source that is given says so:
+ *   mask      (dense [D][H][W], or NULL):           mask[d][y][x] != 0
+ *   sections  (one flag per section of the volume, or NULL):  sections[zsec0 + d] != 0
+ *   missing   (-1: none, or 0 ... 255):             buf[d][y][x] == missing
+ * With R = max_gap (1 ... 32), for a bad voxel at plane d of its column (y, x):
+ *   d0 = the smallest k in 1 ... R with d - k >= 0 and voxel d - k good,      a = buf[d - d0]
+ *   d1 = the smallest k in 1 ... R with d + k <= D - 1 and voxel d + k good,  b = buf[d + d1]
+ *   both exist:  out = (2 (a d1 + b d0) + n) / (2 n),  n = d0 + d1     (integers: linear between the two, half up)
+ *   one exists:  out = that value;      neither: the voxel stays as it is.
+ * Good voxels are never changed and a bad voxel is never a source, so a voxel's result depends on the planes
+ * [d - R, d + R] of its own column only.  Only the core planes [c0, c1) are written; the planes around them are the
+ * halo that the core's voxels read, and the caller lets the block reach R planes past the core on each side or to the
+ * volume's face -- then the core's bytes do not depend on how the volume was cut.  Nothing outside buf is written,
+ * nothing outside buf, mask and sections[zsec0 ... zsec0 + D) is read.  Any alignment of buf, mask and W (a plane
+ * stride H W that is a multiple of 4, with mask congruent to buf mod 4, takes dword loads and stores).
+ * counts (8-byte aligned, or NULL): counts[0] += bad core voxels that were repaired, counts[1] += bad core voxels
+ * left as they are (one 64-bit global atomic add each per workgroup at most; the caller clears them).
+ * TEM_EINVAL, without a launch: a null buf, a dimension below 1, a negative zsec0, max_gap outside 1 ... 32, a core
+ * that is not 0 <= c0 <= c1 <= D, missing outside -1 ... 255, no source at all, counts off 8-byte alignment.
+ * TEM_EUNSUPPORTED: D above 2^21, or more than 2^31 - 1 workgroups per plane.  An empty core launches nothing. */
+int tem_u8_repair_z(uint8_t *buf, int32_t D, int32_t H, int32_t W, int32_t zsec0, int32_t c0, int32_t c1,
+                    const uint8_t *mask, const uint8_t *sections, int32_t missing, int32_t max_gap, uint64_t *counts,
+                    tem_stream_t stream);
+
 /* Contrast-limited adaptive histogram equalisation (CLAHE) of uint8 sections, the two device passes; the tables
  * between them are host work (utils.clahe_tables).  The tile is (th, tw) pixels over (y, x), and the grid of gy x gx
  * tiles is anchored at (0, 0) of the caller's volume.  Both calls cover a dense block [D][H][W] of it whose voxel

@@ -38,6 +38,11 @@ as a uint8 map of where the two volumes differ in structure.
 `volume_rescale` brings a uint8 volume onto the voxel grid of the other domain out of core (tem_u8_rescale): one step
 p / q per axis, the area average where an axis shrinks and linear interpolation where it grows, in integers with one
 rounding per voxel; `rescale_step`, `rescale_shape`, `rescale_taps` and `rescale_chunks` are its host side.
+
+`volume_repair` fills lost sections and bad voxels along z from the nearest good sections below and above, out of core
+(tem_u8_repair_z); `Repair` names what is bad, `flat_sections` finds blank sections in a per-section histogram,
+`repair_chunks` is its slab plan, and `repair=` of `predict_cube` / `predict_volume` does the same to the uploaded bytes
+ahead of `clahe` and `lut`, without a repaired copy of the volume.
 """
 import contextlib
 import json
@@ -439,12 +444,24 @@ class _Prepare:
     """What predict_cube and predict_volume do to uploaded bytes ahead of the gather, made once per call: `clahe`
     (_check_clahe's tuple) and `lut` (_check_lut's table), either may be None, are uploaded here, once.  apply() remaps
     a block in place on `stream`: tem_u8_clahe first, then tem_u8_lut on the equalised bytes.  clahe_volume uses the
-    first half alone."""
+    first half alone.  `repair` (_check_repair's spec, or None) comes ahead of both: its section flags are uploaded here,
+    once, and repair_block() fills a block's core planes in place (tem_u8_repair_z); volume_repair uses that alone."""
 
-    def __init__(self, lib, clahe, lut, dev, stream):
-        self.lib, self.clahe, self.lut, self.stream = lib, clahe, lut, stream
+    def __init__(self, lib, clahe, lut, dev, stream, repair=None):
+        self.lib, self.clahe, self.lut, self.stream, self.rp = lib, clahe, lut, stream, repair
         self.tab_dev = None if clahe is None else torch.from_numpy(clahe[0]).to(dev)    # every section's tables
         self.lut_dev = None if lut is None else torch.from_numpy(lut).to(dev)
+        self.flags_dev = None if repair is None or repair.flags is None else torch.from_numpy(repair.flags).to(dev)
+
+    def repair_block(self, ptr, block, zsec0, c0, c1, mask_ptr, counts_ptr=None):
+        """Repair the core planes [c0, c1) of the dense uint8 block of shape `block` at `ptr`, whose plane 0 is the
+        volume's section zsec0 and which reaches max_gap planes past the core or to the volume's face; `mask_ptr` is the
+        mask's same block (None without a mask).  A block with an empty side is not there and nothing is launched."""
+        if self.rp is None or min(block) < 1 or c1 <= c0:
+            return
+        _lib.check(self.lib.tem_u8_repair_z(ptr, *block, zsec0, c0, c1, mask_ptr,
+                                            None if self.flags_dev is None else self.flags_dev.data_ptr(),
+                                            self.rp.missing, self.rp.max_gap, counts_ptr, self.stream), "tem_u8_repair_z")
 
     def apply(self, ptr, block, lo):
         """Remap the dense uint8 block of shape `block` at `ptr` that holds the volume's box at `lo`: the tile grid and
@@ -1372,6 +1389,219 @@ def volume_rescale(volume, step, out=None, start=None, size=None, chunk_bytes=No
     return out
 
 
+REPAIR_MAX_GAP = 32              # tem_u8_repair_z: 1 <= max_gap <= 32
+
+
+class Repair(NamedTuple):
+    """What the `repair=` keyword and volume_repair take: which voxels of a uint8 volume [z, y, x] are bad, and how far
+    along z a good voxel may lie to fill them.  A voxel is bad if any source that is given says so:
+      sections       an iterable of whole bad sections z (lost, black, folded, charged; flat_sections finds the blank ones)
+      mask           a uint8 array-like of the volume's shape: bad where mask[z, y, x] != 0
+      missing_value  one grey level in 0...255 that stands for "no data"
+    and takes, with R = max_gap (1...32), the nearest good voxel of its own column (y, x) at most R sections below
+    (value a, distance d0) and above (b, d1):
+      both exist: (2 (a d1 + b d0) + n) // (2 n), n = d0 + d1 -- linear between the two, the nearer one weighted more,
+      rounded half up; one exists: that value; neither: the voxel stays as it is.
+    Good voxels are never changed and a bad voxel is never a source, so a voxel's result depends only on the sections
+    [z - R, z + R] of its own column: not on the slab, chunk, ROI or rank it was computed in.  A run of up to R bad
+    voxels between two good ones is interpolated throughout; a run longer than 2 R keeps an untouched middle
+    (volume_repair counts those voxels)."""
+    sections: object = None
+    mask: object = None
+    missing_value: object = None
+    max_gap: int = 8
+
+
+class _RepairSpec(NamedTuple):
+    """_check_repair's result: `flags` np.uint8[Z] (1: a bad section) or None, `mask` the array-like or None, `missing`
+    -1 or the grey level, `max_gap`."""
+    flags: object
+    mask: object
+    missing: int
+    max_gap: int
+
+
+def _index(v, what):
+    import operator
+    try:
+        if isinstance(v, (bool, np.bool_)):
+            raise TypeError
+        return operator.index(v)
+    except TypeError:
+        raise ValueError(f"{what} must be an integer, got {v!r}")
+
+
+def _check_repair(repair, vol_shape):
+    """None, or the _RepairSpec of `repair` (a Repair, or any (sections, mask, missing_value, max_gap) tuple) for a
+    volume of shape `vol_shape` [z, y, x].  ValueError for: no source at all, max_gap outside 1...32, a section outside
+    [0, Z), a mask of another shape or dtype, a missing_value outside 0...255, and a single image [y, x], which has no z
+    to repair along."""
+    if repair is None:
+        return None
+    if isinstance(repair, _RepairSpec):
+        return repair
+    try:
+        sections, mask, missing, max_gap = repair
+    except (TypeError, ValueError):
+        raise ValueError(f"repair must be None or a Repair (sections, mask, missing_value, max_gap), got "
+                         f"{type(repair).__name__}")
+    shape = tuple(int(v) for v in vol_shape)
+    if len(shape) != 3:
+        raise ValueError(f"repair fills along z: it needs a volume [z, y, x], got shape {shape}")
+    R = _index(max_gap, "max_gap")
+    if not 1 <= R <= REPAIR_MAX_GAP:
+        raise ValueError(f"max_gap must lie in 1...{REPAIR_MAX_GAP}, got {R}")
+    if sections is None and mask is None and missing is None:
+        raise ValueError("repair names no bad voxel: give sections, mask or missing_value")
+    flags = None
+    if sections is not None:
+        try:
+            zs = [_index(z, "a section") for z in sections]
+        except TypeError:
+            raise ValueError(f"sections must be an iterable of section indices, got {sections!r}")
+        flags = np.zeros(shape[0], np.uint8)
+        for z in zs:
+            if not 0 <= z < shape[0]:
+                raise ValueError(f"section {z} is outside [0, {shape[0]})")
+            flags[z] = 1
+    if mask is not None:
+        mshape, dtype = getattr(mask, "shape", None), getattr(mask, "dtype", None)
+        if mshape is None or dtype is None or dtype != np.uint8:
+            raise ValueError(f"mask must be a uint8 array-like, got {type(mask).__name__} of dtype {dtype}")
+        if tuple(int(v) for v in mshape) != shape:
+            raise ValueError(f"mask must have the volume's shape {shape}, got {tuple(mshape)}")
+    m = -1
+    if missing is not None:
+        m = _index(missing, "missing_value")
+        if not 0 <= m <= 255:
+            raise ValueError(f"missing_value must lie in 0...255, got {m}")
+    return _RepairSpec(flags, mask, m, R)
+
+
+def repair_chunks(box, vol_shape, max_gap, chunk_bytes=None, rank=0, world_size=1):
+    """Cut the (z, y, x) (lo, hi) `box` of a volume of shape `vol_shape` [z, y, x] into slabs for volume_repair.  Returns
+    this rank's list of (core slab, read slab), both (z, y, x) (lo, hi) boxes of the volume: the cores are disjoint and
+    their union is the box (hist_chunks' cuts: runs of whole sections of the box, or runs of whole rows of one section;
+    x is never cut); a read slab is its core extended by `max_gap` sections along z on each side and clipped to the
+    volume, so neighbouring read slabs overlap.  A read slab holds at most `chunk_bytes` bytes (HIST_CHUNK_BYTES when
+    None) wherever one core plane allows it: as many whole sections per core as fit next to the 2 max_gap around them,
+    or, where 2 max_gap + 1 sections of the box are larger than the budget, one section's rows, as many as fit (one row
+    at the least).  Slabs are in (z, y) order and go round-robin to the ranks.  Pure host function; ValueError as
+    hist_chunks, and for a max_gap outside 1...32."""
+    budget = HIST_CHUNK_BYTES if chunk_bytes is None else int(chunk_bytes)
+    if budget < 1:
+        raise ValueError(f"chunk_bytes must be positive, got {chunk_bytes}")
+    if not 0 <= rank < world_size:
+        raise ValueError(f"rank {rank} is outside [0, {world_size})")
+    R = _index(max_gap, "max_gap")
+    if not 1 <= R <= REPAIR_MAX_GAP:
+        raise ValueError(f"max_gap must lie in 1...{REPAIR_MAX_GAP}, got {R}")
+    Z = int(vol_shape[0])
+    (z0, z1), (y0, y1), (x0, x1) = box
+    ny, nx = y1 - y0, x1 - x0
+    if z1 <= z0 or ny <= 0 or nx <= 0:
+        return []
+    if (2 * R + 1) * ny * nx <= budget:
+        kz = budget // (ny * nx) - 2 * R
+        cores = [((z, min(z + kz, z1)), (y0, y1)) for z in range(z0, z1, kz)]
+    else:
+        ky = max(1, budget // ((2 * R + 1) * nx))
+        cores = [((z, z + 1), (y, min(y + ky, y1))) for z in range(z0, z1) for y in range(y0, y1, ky)]
+    slabs = [((cz, cy, (x0, x1)), ((max(cz[0] - R, 0), min(cz[1] + R, Z)), cy, (x0, x1))) for cz, cy in cores]
+    return slabs[rank::world_size]
+
+
+def volume_repair(volume, repair, out=None, start=None, size=None, chunk_bytes=None, stats=None, rank=0, world_size=1,
+                  device=None):
+    """The ROI [start, start + size) ((x, y, z) order; default: the whole volume) of a uint8 array-like `volume` [z, y, x]
+    (ndarray, np.memmap, h5py / zarr dataset) with its damaged sections and voxels filled along z from the nearest good
+    sections below and above, by the rule of `Repair` (a Repair of the WHOLE volume: its mask has the volume's shape),
+    written into `out`: a writable uint8 array-like of the ROI's shape (allocated when None), which is returned.  This
+    is how training volumes are prepared, ahead of clahe_fit and volume3d_ng, so that no crop teaches a loss to
+    reproduce a defect; predict_*(repair=...) sees the same bytes without the copy.  Everything is integers and numpy
+    reproduces it byte for byte; a voxel depends only on the sections [z - max_gap, z + max_gap] of its own column, so
+    the result of an ROI is the ROI of the whole result, however it is cut.
+
+    Out of core exactly like clahe_volume, over read slabs that overlap by max_gap sections (repair_chunks): one host
+    thread reads each read slab -- and the mask's same box, through a second input stream, when there is a mask --
+    into double-buffered pinned memory -> H2D -> one tem_u8_repair_z launch per slab, in place -> D2H of the core
+    planes only, one contiguous range of the block -> host write, in the order write(k), read(k + 2) on the one host
+    thread.  The section flags are uploaded once.  Ranks take slabs round-robin and write disjoint boxes of a shared
+    `out`.  `stats` receives `read_s`, `write_s`, `chunks`, and `repaired` / `unrepaired`: the bad voxels of this
+    rank's cores that were filled, and those left as they are because no good voxel lies within max_gap (the middle of
+    a run longer than 2 max_gap); cores are disjoint, so the ranks' counts add.
+    ValueError, before any GPU work: _check_repair's, an ROI outside the volume, a non-uint8 volume, an `out` of another
+    shape or dtype."""
+    _check_u8(volume)
+    vshape = tuple(int(v) for v in volume.shape)
+    rp = _check_repair(repair, vshape)
+    if rp is None:
+        raise ValueError("volume_repair needs a Repair")
+    box = hist_box(vshape, start, size)
+    shape = tuple(hi - lo for lo, hi in box)
+    if out is None:
+        out = np.zeros(shape, np.uint8)
+    elif tuple(out.shape) != shape or getattr(out, "dtype", None) != np.uint8:
+        raise ValueError(f"out must be uint8 of the ROI's shape {shape}, got {getattr(out, 'dtype', None)} "
+                         f"{tuple(out.shape)}")
+    chunks = repair_chunks(box, vshape, rp.max_gap, chunk_bytes, rank, world_size)
+    whole = hist_box(vshape)
+    vols = [volume] + ([rp.mask] if rp.mask is not None else [])
+    p = _SlabPass(vols, [whole] * len(vols), chunk_bytes, rank, world_size, device, slabs=[r for _, r in chunks])
+    lib = H.require_gpu()
+    cores = [c for c, _ in chunks]
+    cdims = [tuple(hi - lo for lo, hi in c) for c in cores]
+    (oz, _), (oy, _), (ox, _) = box
+    p.st["write_s"] = 0.0
+
+    def write_from(k, flat):            # host thread: the core's box of `out`
+        (z0, z1), (y0, y1), (x0, x1) = cores[k]
+        out[z0 - oz:z1 - oz, y0 - oy:y1 - oy, x0 - ox:x1 - ox] = flat.reshape(cdims[k])
+
+    with p.streaming():
+        prepare = _Prepare(lib, None, None, p.dev, p.compute.cuda_stream, repair=rp)     # the section flags, once
+        counts = torch.zeros(2, dtype=torch.int64, device=p.dev)
+        with _OutputStream([int(np.prod(d)) for d in cdims], write_from, p.dev, p.pool, p.st) as outp:
+            for k, slab, d, bufs in p:
+                c0 = cores[k][0][0] - slab[0][0]
+                prepare.repair_block(bufs[0].data_ptr(), d, slab[0][0], c0, c0 + cdims[k][0],
+                                     bufs[1].data_ptr() if rp.mask is not None else None, counts.data_ptr())
+                # the core planes: one contiguous range of the block; the inputs are free once it is copied out
+                p.release_on = outp.put(k, p.compute.record_event(), bufs[0][c0 * d[1] * d[2]:])
+        p.st["repaired"], p.st["unrepaired"] = (int(v) for v in counts.cpu().numpy())    # the one read-back
+    if stats is not None:
+        stats.update(p.st)
+    return out
+
+
+def flat_sections(h, fraction=Fraction(1, 2)):
+    """A first detector of lost sections, host only: the sorted list of the sections z of a per-section histogram `h`
+    (np integer [Z, 256]: volume_histogram(..., per_section=True)) whose most frequent grey level holds at least
+    `fraction` (an int, a Fraction or a (num, den) pair in (0, 1]) of their pixels, decided in integers:
+    max(h[z]) den >= num sum(h[z]).  An empty section is not flagged.  Blank and saturated sections are what this
+    finds -- the list is what Repair takes as `sections` --; anything subtler is the user's mask."""
+    h = np.asarray(h)
+    if h.ndim != 2 or h.shape[1] != 256 or h.dtype.kind not in "iu":
+        raise ValueError(f"flat_sections: h must be integer counts of shape [Z, 256], got {h.dtype} {h.shape}")
+    if h.size and int(h.min()) < 0:
+        raise ValueError("flat_sections: h has negative counts")
+    try:
+        if isinstance(fraction, (bool, np.bool_, float, np.floating, str, bytes)):
+            raise TypeError
+        f = Fraction(int(fraction[0]), int(fraction[1])) if isinstance(fraction, (tuple, list)) else Fraction(fraction)
+    except (TypeError, ValueError, ZeroDivisionError, IndexError):
+        raise ValueError(f"fraction must be an int, a Fraction or a (num, den) pair, got {fraction!r}")
+    if not 0 < f <= 1:
+        raise ValueError(f"fraction must lie in (0, 1], got {fraction!r}")
+    num, den = f.numerator, f.denominator
+    out = []
+    for z, row in enumerate(h):
+        top, total = int(row.max()), sum(int(c) for c in row)
+        if total > 0 and top * den >= num * total:
+            out.append(z)
+    return out
+
+
 def _check_compare(compare, vol_shape, stats):
     """None, or `compare` itself: a uint8 array-like of the volume's shape, reported in a dict `stats`.  A _OneSection
     is the image that the single-image form has checked already and passes on as a one-section stack."""
@@ -1711,7 +1941,7 @@ def clahe_volume(volume, clahe, out=None, start=None, size=None, chunk_bytes=Non
 
 def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=False, outdimsize=None, buffer=None,
                  rank=0, world_size=1, tile_batch=None, boundary="zeros", ensemble=None, mips=None, lut=None,
-                 histogram=False, stats=None, clahe=None, compare=None, spread=None, spread_gain=8.0):
+                 histogram=False, stats=None, clahe=None, compare=None, repair=None, spread=None, spread_gain=8.0):
     """Predict the subvolume [start, start+size) (x,y,z order as in the reference) of a uint8
     array `volume` indexed [z, y, x].  Voxels outside the array read as 0 (the reference fetches
     them from the store) or, with boundary="reflect" / "edge", the voxel that `fold` names on every axis: the result
@@ -1785,6 +2015,18 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
     the cropped result against gt's ROI-within-the-volume box, uploaded once; after the all-reduce of a multi-rank
     call.  Anything else raises ValueError before any GPU work.
 
+    repair=None reads the volume as it is and runs the launches above.  repair = a Repair (bad sections, a bad-voxel
+    mask of the volume's shape, a missing grey level; max_gap) fills the volume's bad voxels along z first, each from
+    the nearest good voxels of its column at most max_gap sections below and above (the rule is Repair's): one
+    tem_u8_repair_z launch over the whole uploaded volume, in place, ahead of `clahe` and `lut`, with the mask uploaded
+    next to it.  The result is, bit for bit, that of the same call on volume_repair(volume, repair), for 3-D and 2-D
+    models and every boundary, ensemble, mips, lut, clahe, compare, spread, tile_batch and rank split.  Repair belongs
+    to the volume, not to its padding: a voxel outside the volume reads the repaired voxel it folds to under the
+    mirrored modes, and 0 under "zeros", which is not "missing" -- the same rule as `lut`.  fetch_input returns what the
+    network saw, the repaired bytes.  _check_repair's ValueErrors (no source, max_gap outside 1...32, a section outside
+    the volume, a mask of another shape or dtype, a missing_value outside 0...255, a single image, which has no z) come
+    before any GPU work.
+
     spread=None measures nothing and runs the launches above.  spread = S, a writable np.uint8 ndarray of the result's
     shape -- (size[2], size[1], size[0]), or (size[1], size[0]) for one image -- needs an `ensemble` and receives how
     much its members disagree at every voxel, the test-time-augmentation uncertainty of the translation where there is
@@ -1809,6 +2051,9 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
     if clahe is not None:
         _check_u8(volume)
     cl = _check_clahe(clahe, np.shape(volume))
+    if repair is not None:
+        _check_u8(volume)
+    rp = _check_repair(repair, np.shape(volume))
     histogram = _check_histogram(histogram, stats)
     compare = _check_compare(compare, np.shape(volume), stats)
     if outdimsize is None:
@@ -1822,7 +2067,7 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
                            meanstd_y, fetch_input=fetch_input, outdimsize=outdimsize, buffer=buffer, rank=rank,
                            world_size=world_size, tile_batch=tile_batch, boundary=boundary, ensemble=ensemble,
                            mips=mips, lut=lut, histogram=histogram, stats=stats, clahe=clahe,
-                           compare=None if compare is None else np.asarray(compare)[None],
+                           compare=None if compare is None else np.asarray(compare)[None], repair=repair,
                            spread=None if spread is None else spread[None], spread_gain=spread_gain)
         one = lambda r: [v[0] for v in r] if isinstance(r, list) else r[0]
         return tuple(one(r) for r in res) if fetch_input else one(res)
@@ -1836,7 +2081,10 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
     vol = torch.from_numpy(vol_host).to(dev, non_blocking=True)          # ONE upload of the whole volume
     Z, Y, X = vol_host.shape
     stream = H.current_stream()
-    prepare = _Prepare(lib, cl, lut, dev, stream)
+    prepare = _Prepare(lib, cl, lut, dev, stream, repair=rp)
+    if rp is not None:                                                   # first: one launch, the core is the whole volume
+        mask_dev = None if rp.mask is None else torch.from_numpy(np.ascontiguousarray(rp.mask, dtype=np.uint8)).to(dev)
+        prepare.repair_block(vol.data_ptr(), (Z, Y, X), 0, 0, Z, None if mask_dev is None else mask_dev.data_ptr())
     prepare.apply(vol.data_ptr(), (Z, Y, X), (0, 0, 0))                  # in place, once, behind the upload
     out_buffer = torch.zeros((rnd(z) if is3d else z, rnd(y), rnd(x)), dtype=torch.uint8, device=dev)
     OZ, OY, OX = out_buffer.shape
@@ -1884,7 +2132,7 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
         # the reference returns the RAW uint8 block here after a detour (utils.py:122-125: the standardized float
         # tile is un-standardized, rescaled and truncated into a uint8 buffer -- the original bytes up to float
         # rounding); the bytes themselves are returned instead
-        if cl is not None:                       # ... as the network saw them: the bytes the kernels left
+        if cl is not None or rp is not None:     # ... as the network saw them: the bytes the kernels left
             vol_host = vol.cpu().numpy()
         elif lut is not None:                    # ... remapped
             vol_host = _lut_host(vol_host, lut)
@@ -2034,7 +2282,8 @@ def chunk_plan(start, size, outdimsize, buffer, vol_shape, chunk_tiles, rank=0, 
 
 def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, chunk_tiles=None, tile_batch=None,
                    outdimsize=None, buffer=None, rank=0, world_size=1, stats=None, boundary="zeros", ensemble=None,
-                   mips=None, lut=None, histogram=False, clahe=None, compare=None, spread=None, spread_gain=8.0):
+                   mips=None, lut=None, histogram=False, clahe=None, compare=None, repair=None, spread=None,
+                   spread_gain=8.0):
     """Out-of-core predict_cube: the subvolume [start, start+size) (x,y,z order) of a uint8 array-like `volume`
     indexed [z, y, x] (ndarray, np.memmap, h5py / zarr dataset: `.shape` and basic slicing are all it needs) is
     predicted chunk by chunk (chunk_plan) into `out`, a writable uint8 array-like of shape (size[2], size[1], size[0])
@@ -2100,6 +2349,17 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
     misses the volume launches nothing.  The table does not depend on chunk_tiles or tile_batch; each rank reports its
     own chunks, and the ranks' tables add up to that of the whole result.
 
+    `repair` is predict_cube's (a Repair of the whole volume; its mask may be a memmap): the chunk plan and its
+    footprints stay as they are, but the host thread reads each footprint with max_gap more sections on each side of z,
+    clipped to the volume -- and the mask's same box through a second input stream, as `compare` reads its ground truth
+    -- and one tem_u8_repair_z launch, ahead of `clahe` and `lut`, fills the footprint's planes in place as the core of
+    that block (the section flags are uploaded once per call).  Everything behind it, clahe, lut and every gather, is
+    given the pointer to the footprint's first plane and sees the block it sees without `repair`.  A voxel's result
+    needs only the sections [z - max_gap, z + max_gap] of its column, which the block holds, so it does not depend on
+    the chunk it arrives in: the result equals predict_cube(repair=...)'s, i.e. that of the same call on
+    volume_repair(volume, repair), which is never made.  A chunk with an empty footprint launches nothing, and nothing
+    is counted: footprints overlap, so counts would mean nothing (volume_repair reports them).
+
     `spread` / `spread_gain` are predict_cube's: spread = S, a writable uint8 array-like of `out`'s level-0 shape
     (ndarray, memmap, h5py, zarr), receives the map of the ensemble members' disagreement, equal to predict_cube's bit
     for bit.  A chunk's device and pinned output block grows by one block of its `dims`, behind the pyramid levels if
@@ -2119,6 +2379,9 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
     if clahe is not None:
         _check_u8(volume)
     cl = _check_clahe(clahe, tuple(volume.shape))
+    if repair is not None:
+        _check_u8(volume)
+    rp = _check_repair(repair, tuple(volume.shape))
     histogram = _check_histogram(histogram, stats)
     compare = _check_compare(compare, tuple(volume.shape), stats)
     lib = H.require_gpu()
@@ -2134,7 +2397,7 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
                        out=[_OneSection(o) for o in out] if L else _OneSection(out), chunk_tiles=chunk_tiles,
                        tile_batch=tile_batch, outdimsize=outdimsize, buffer=buffer, rank=rank, world_size=world_size,
                        stats=stats, boundary=boundary, ensemble=ensemble, mips=mips, lut=lut, histogram=histogram,
-                       clahe=clahe, compare=None if compare is None else _OneSection(compare),
+                       clahe=clahe, compare=None if compare is None else _OneSection(compare), repair=repair,
                        spread=None if spread is None else _OneSection(spread), spread_gain=spread_gain)
         return out
     vol_shape = tuple(int(v) for v in volume.shape)
@@ -2165,7 +2428,13 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
     # a chunk wholly outside the volume has an empty footprint: it gathers from one zero byte (all voxels read 0);
     # with a mirrored boundary no footprint is empty
     gdims = [c.block if min(c.block) > 0 else (1, 1, 1) for c in chunks]
-    in_bytes = [int(np.prod(g)) for g in gdims]
+    # with `repair` a footprint is read with max_gap more sections on each side of z, clipped to the volume: rz[k] is
+    # that z range, and the footprint itself -- the repair's core, what everything downstream sees -- its planes
+    # [c.read[0][0] - rz[k][0], ...) of the block that is read
+    R = 0 if rp is None else rp.max_gap
+    rz = [(max(c.read[0][0] - R, 0), min(c.read[0][1] + R, vol_shape[0])) if min(c.block) > 0 else (0, 1) for c in chunks]
+    rdims = [(z1 - z0,) + tuple(g[1:]) for (z0, z1), g in zip(rz, gdims)]
+    in_bytes = [int(np.prod(g)) for g in rdims]
     # a chunk's output block on the device and in pinned memory: its L + 1 levels back to back, level l at
     # lvl_off[k][l] with the dense dims lvl_dims[k][l] = c.dims divided by 2^l on the pooled axes (exact: dims are
     # whole tiles and outdimsize % 2^L == 0)
@@ -2180,7 +2449,7 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
     first = np.cumsum([0] + [len(c.tiles) for c in chunks])
     org = torch.tensor([o for c in chunks for o in c.origins], dtype=torch.int32).to(dev)     # every chunk's, once
     idx = torch.tensor([o for c in chunks for o in c.offsets], dtype=torch.int32).to(dev)
-    prepare = _Prepare(lib, cl, lut, dev, compute.cuda_stream)
+    prepare = _Prepare(lib, cl, lut, dev, compute.cuda_stream, repair=rp)
     measure = _Measure(lib, histogram, compare is not None, dev, compute.cuda_stream, spread=gain is not None)
     runner = _TileRunner(lib, model, is3d, edge, tpad, od, boundary, syms, meanstd_x, meanstd_y, vol_shape,
                          compute.cuda_stream, gain)
@@ -2196,13 +2465,18 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
             (z0, z1), (y0, y1), (x0, x1) = gt_box[k]
             flat.reshape(gt_dims[k])[...] = compare[z0:z1, y0:y1, x0:x1]
 
-    def read_into(k, flat):             # host thread: footprint of chunk k
-        c, dst = chunks[k], flat.reshape(gdims[k])
-        if min(c.block) > 0:
-            (z0, z1), (y0, y1), (x0, x1) = c.read
-            dst[...] = volume[z0:z1, y0:y1, x0:x1]
-        else:
-            dst[...] = 0
+    def read_box(src):                  # host thread: footprint of chunk k (with `repair`: and its halo along z)
+        def read_into(k, flat):
+            c, dst = chunks[k], flat.reshape(rdims[k])
+            if min(c.block) > 0:
+                (z0, z1), (_, (y0, y1), (x0, x1)) = rz[k], c.read
+                dst[...] = src[z0:z1, y0:y1, x0:x1]
+            else:
+                dst[...] = 0
+        return read_into
+
+    read_into = read_box(volume)
+    with_mask = rp is not None and rp.mask is not None
 
     def write_from(k, buf):             # host thread: the chunk's box of `out` (and of `spread`)
         c = chunks[k]
@@ -2221,10 +2495,21 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
     outp = _OutputStream(out_bytes, write_from, dev, pool, st, own_buffers=True)
     with _InputStream(in_bytes, read_into, dev, pool, st) as inp, \
             (contextlib.nullcontext() if compare is None else _InputStream(gt_bytes, read_gt, dev, pool, st)) as gt_inp, \
+            (_InputStream(in_bytes, read_box(rp.mask), dev, pool, st) if with_mask else
+             contextlib.nullcontext()) as mask_inp, \
             outp:
         for k, c in enumerate(chunks):
             src, dst = inp.get(k).data_ptr(), outp.device(k).data_ptr()
             lo = tuple(r[0] for r in c.read)
+            if with_mask:
+                mask_buf = mask_inp.get(k)
+            if rp is not None and min(c.block) > 0:          # first: the footprint is the core of the block that was read
+                c0 = lo[0] - rz[k][0]
+                prepare.repair_block(src, (rdims[k][0],) + tuple(c.block[1:]), rz[k][0], c0, c0 + c.block[0],
+                                     mask_buf.data_ptr() if with_mask else None)
+                src += c0 * c.block[1] * c.block[2]          # ... and what everything behind it sees
+            if with_mask:
+                mask_inp.release(k, compute.record_event())
             prepare.apply(src, c.block, lo)                  # the footprint; never the stand-in zero byte
             t = 12 * int(first[k])
             # the staging buffer is free for the next upload once the chunk's last gather is enqueued
@@ -2251,6 +2536,8 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
             inp.prefetch(k + 2)
             if compare is not None:
                 gt_inp.prefetch(k + 2)
+            if with_mask:
+                mask_inp.prefetch(k + 2)
     measure.report(st)                                       # the one read-back of each
     if stats is not None:
         stats.update(st)
@@ -2297,7 +2584,7 @@ def predict_ng_cube(location, start, size, model, meanstd_x, meanstd_y, cloudrun
     instead of a cloud path; `cloudrun` is accepted and ignored.  The signature is the reference's, so voxels outside
     the array always read 0 here: predict_cube(..., boundary="reflect" | "edge") mirrors or clamps at the faces.
     It takes no `mips` either: predict_cube(..., mips=L) returns the mip pyramid of the prediction; nor `lut`, `clahe`,
-    `compare` or `spread`."""
+    `compare`, `repair` or `spread`."""
     return predict_cube(_local_volume(location), start, size, model, meanstd_x, meanstd_y, fetch_input=fetch_input,
                         outdimsize=outdimsize, buffer=buffer)
 
@@ -2324,8 +2611,9 @@ def predict_volume_from_saved_model(volume, start, size, model_dir, out=None, **
     histogram (True: stats["histogram"] receives the 256-bin histogram of the result), clahe (None, or the
     ClaheTables of the volume, clahe_fit: the volume is equalised on the device, ahead of lut) and compare (None, or
     the ground truth as a uint8 array-like of the volume's shape: stats["joint_histogram"] receives the 256 x 256
-    joint histogram of (ground truth, result), see compare_from_joint), and spread / spread_gain (None, or a writable
-    uint8 array-like of the result's shape that receives the map of the ensemble members' disagreement, see
+    joint histogram of (ground truth, result), see compare_from_joint), repair (None, or a Repair: the volume's bad
+    sections and voxels are filled along z on the device, ahead of clahe and lut) and spread / spread_gain (None, or a
+    writable uint8 array-like of the result's shape that receives the map of the ensemble members' disagreement, see
     predict_cube).
     The reference's signatures, predict_ng_cube and predict_cube_from_saved_model, take none of these keywords; they
     run unensembled and return the full-resolution array alone."""
