@@ -549,6 +549,31 @@ int tem_u8_hist_tiles(const uint8_t *src, int32_t D, int32_t H, int32_t W, int32
 int tem_u8_clahe(uint8_t *buf, int32_t D, int32_t H, int32_t W, int32_t zsec0, int32_t y_org, int32_t x_org,
                  const uint8_t *tables, int32_t gy, int32_t gx, int32_t th, int32_t tw, tem_stream_t stream);
 
+/* The sums behind the correlation of every tile of a section with the same tile one section up (utils.section_sums ->
+ * section_scores -> find_defects: sections and regions that resemble neither neighbour).  src[D][H][W] is a dense
+ * block of a uint8 volume on tem_u8_hist_tiles' tile grid: (th, tw) pixels, gy x gx tiles anchored at the volume's
+ * (0, 0), the block's voxel (d, y, x) at in-plane volume coordinates (y_org + y, x_org + x).  Only the core planes
+ * [c0, c1) are counted; sums (8-byte aligned) points at the rows of plane c0.  For every core plane d and every voxel
+ * of value v in tile (i, j) = ((y_org + y) / th, (x_org + x) / tw), with v+ the voxel at (d + 1, y, x):
+ *   q = sums + (((d - c0) * gy + i) * gx + j) * 4
+ *   q[0] += v     q[1] += v v     q[2] += v v+  (only if d + 1 < D)     q[3] += 1
+ * Plane D - 1 has no pair term: the caller lets the block reach one plane past the core, or the core end at the
+ * volume's last section.  The kernel ADDS (64-bit global atomic adds, one per workgroup, plane and quantity): the
+ * caller clears sums once, and blocks that cut a tile along y, x or z between them accumulate into it; the adds are
+ * integers, so the result does not depend on how the volume was cut or launched.  Nothing but sums is written.  A load
+ * touches only naturally aligned words (up to 16 bytes) that hold at least one byte of the block.  Any alignment of
+ * src, W and the origins.  No partial can overflow at 255 x 255 = 65025 per voxel: a thread sums at most 64 voxels
+ * of a plane in 32 bits (64 x 65025 < 2^23), a wave 64 such partials in 32 bits (< 2^29), a workgroup is given at
+ * most 16384 voxels of a plane -- a 2048 x 2048 tile goes to 256 of them -- and adds its four wave sums in 64 bits
+ * (16384 x 65025 < 2^31); the 64-bit counter takes a whole such tile per plane (2^22 x 65025 < 2^38) 2^25 times over.
+ * TEM_EINVAL, without a launch: a null pointer, sums off 8-byte alignment, a dimension, gy or gx below 1, th or tw
+ * outside [1, 2048], a negative origin, a block that reaches past the grid (y_org + H > gy th, x_org + W > gx tw), a
+ * core that is not 0 <= c0 <= c1 <= D.  TEM_EUNSUPPORTED: more than 2^31 - 1 workgroups (one per tile of the block,
+ * run of rows of about 1024 16-byte pieces, and run of up to 16 core planes).  An empty core launches nothing. */
+int tem_u8_zcorr_tiles(const uint8_t *src, int32_t D, int32_t H, int32_t W, int32_t c0, int32_t c1, int32_t y_org,
+                       int32_t x_org, int32_t th, int32_t tw, int32_t gy, int32_t gx, uint64_t *sums,
+                       tem_stream_t stream);
+
 /* Random augmentation of one cached sample (datasets.py:123-155) with host-drawn parameters:
  *   dst = reverse(transpose(src, perm = (p0,p1,p2)), dims with f_k != 0) * scale + shift
  * src is a dense single-channel (D,H,W) volume (2-D: D == 1, p0 must be 0); dst has extents

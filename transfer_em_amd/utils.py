@@ -43,6 +43,11 @@ rounding per voxel; `rescale_step`, `rescale_shape`, `rescale_taps` and `rescale
 (tem_u8_repair_z); `Repair` names what is bad, `flat_sections` finds blank sections in a per-section histogram,
 `repair_chunks` is its slab plan, and `repair=` of `predict_cube` / `predict_volume` does the same to the uploaded bytes
 ahead of `clahe` and `lut`, without a repaired copy of the volume.
+
+`section_sums` measures out of core how much every tile of a section resembles the same tile one section up
+(tem_u8_zcorr_tiles: exact integer sums); `section_scores` turns the sums into correlations, `find_defects` into the
+sections and regions that resemble neither neighbour, and `defect_mask` / `defects_repair` into the `Repair` that
+`volume_repair` and `repair=` take; `zcorr_chunks` is its slab plan.
 """
 import contextlib
 import json
@@ -678,7 +683,7 @@ def hist_chunks(box, chunk_bytes=None, rank=0, world_size=1):
     ny, nx = y1 - y0, x1 - x0
     if z1 <= z0 or ny <= 0 or nx <= 0:
         return []
-    slabs = []
+    slabs = []                          # zcorr_chunks restates these cuts with one section of halo: keep the two in step
     if ny * nx <= budget:
         kz = budget // (ny * nx)
         slabs = [((z, min(z + kz, z1)), (y0, y1), (x0, x1)) for z in range(z0, z1, kz)]
@@ -1579,7 +1584,7 @@ def flat_sections(h, fraction=Fraction(1, 2)):
     (np integer [Z, 256]: volume_histogram(..., per_section=True)) whose most frequent grey level holds at least
     `fraction` (an int, a Fraction or a (num, den) pair in (0, 1]) of their pixels, decided in integers:
     max(h[z]) den >= num sum(h[z]).  An empty section is not flagged.  Blank and saturated sections are what this
-    finds -- the list is what Repair takes as `sections` --; anything subtler is the user's mask."""
+    finds -- the list is what Repair takes as `sections` --; find_defects finds what is subtler."""
     h = np.asarray(h)
     if h.ndim != 2 or h.shape[1] != 256 or h.dtype.kind not in "iu":
         raise ValueError(f"flat_sections: h must be integer counts of shape [Z, 256], got {h.dtype} {h.shape}")
@@ -1600,6 +1605,210 @@ def flat_sections(h, fraction=Fraction(1, 2)):
         if total > 0 and top * den >= num * total:
             out.append(z)
     return out
+
+
+def zcorr_chunks(vol_shape, chunk_bytes=None, rank=0, world_size=1):
+    """Cut a volume of shape `vol_shape` [z, y, x] (one image [y, x]: one section) into slabs for section_sums.  Returns
+    this rank's list of (core slab, read slab), both (z, y, x) (lo, hi) boxes: the cores are disjoint and their union is
+    the volume (hist_chunks' cuts: runs of whole sections, or runs of whole rows of one section; x is never cut); a read
+    slab is its core plus the same rows of the next section where the volume has one -- the plane its last core plane
+    is correlated with.  A read slab holds at most `chunk_bytes` bytes (HIST_CHUNK_BYTES when None) wherever one row
+    allows it: as many whole sections per core as fit next to the one above them, or, where two sections are larger
+    than the budget, one section's rows, as many as fit twice (one row at the least).  Slabs are in (z, y) order and go
+    round-robin to the ranks.  Pure host function; ValueError as hist_box and hist_chunks."""
+    budget = HIST_CHUNK_BYTES if chunk_bytes is None else int(chunk_bytes)
+    if budget < 1:
+        raise ValueError(f"chunk_bytes must be positive, got {chunk_bytes}")
+    if not 0 <= rank < world_size:
+        raise ValueError(f"rank {rank} is outside [0, {world_size})")
+    (_, Z), (_, ny), (_, nx) = hist_box(vol_shape)
+    if Z <= 0 or ny <= 0 or nx <= 0:
+        return []
+    halo = 1 if Z > 1 else 0
+    if (1 + halo) * ny * nx <= budget:
+        kz = budget // (ny * nx) - halo
+        cores = [((z, min(z + kz, Z)), (0, ny)) for z in range(0, Z, kz)]
+    else:
+        ky = max(1, budget // ((1 + halo) * nx))
+        cores = [((z, z + 1), (y, min(y + ky, ny))) for z in range(Z) for y in range(0, ny, ky)]
+    slabs = [((cz, cy, (0, nx)), ((cz[0], min(cz[1] + 1, Z)), cy, (0, nx))) for cz, cy in cores]
+    return slabs[rank::world_size]
+
+
+def section_sums(volume, tile=128, chunk_bytes=None, rank=0, world_size=1, device=None, stats=None):
+    """The sums behind the correlation of every tile of a section with the same tile one section up: np.int64
+    [Z, gy, gx, 4] over the WHOLE uint8 `volume` [z, y, x] (ndarray, np.memmap, h5py / zarr dataset; one image [y, x]:
+    Z = 1) on clahe_grid's tiles of `tile` pixels (an int or (th, tw) in [1, 2048]).  With v the voxels of tile (i, j) of
+    section z and v+ those one section up:
+      s[z, i, j] = (sum v, sum v v, sum v v+, the number of voxels);   the last section's sum v v+ is 0.
+    Exact integers that numpy reproduces bit for bit, whatever the slabs, ranks and launches.  section_scores turns
+    them into correlations, find_defects into the sections and regions that resemble neither neighbour.
+
+    Out of core exactly as clahe_histograms, over read slabs that reach one section past their core (zcorr_chunks): one
+    host thread -> pinned -> H2D -> one tem_u8_zcorr_tiles launch per slab, adding into a device accumulator.  The
+    accumulator holds the whole volume's Z*gy*gx*32 bytes and is read back once where that is at most CLAHE_ACC_BYTES;
+    else it holds one slab's core sections and is read back, and added on the host, per slab.  Ranks take slabs
+    round-robin and their results add up to the whole.  `stats` receives `read_s` and `chunks`.  ValueError, before any
+    GPU work: a non-uint8 volume, a bad tile, shape, chunk_bytes or rank."""
+    _check_u8(volume)
+    th, tw = _clahe_tile(tile)
+    gy, gx = clahe_grid(volume.shape, (th, tw))
+    box = hist_box(volume.shape)
+    chunks = zcorr_chunks(volume.shape, chunk_bytes, rank, world_size)
+    p = _SlabPass([volume], [box], chunk_bytes, rank, world_size, device, slabs=[r for _, r in chunks])
+    lib = H.require_gpu()
+    Z, sec = box[0][1], gy * gx * 4
+    whole = Z * sec * 8 <= CLAHE_ACC_BYTES
+    out = None if whole else np.zeros((Z, gy, gx, 4), np.int64)
+    with p.streaming():
+        most = max((c[0][1] - c[0][0] for c, _ in chunks), default=1)
+        acc = torch.zeros((Z if whole else most, sec), dtype=torch.int64, device=p.dev)
+        for k, ((r0, _), (y0, _), (x0, _)), d, (src,) in p:
+            z0, z1 = chunks[k][0][0]
+            if not whole:
+                acc[:z1 - z0].zero_()
+            _lib.check(lib.tem_u8_zcorr_tiles(src.data_ptr(), *d, z0 - r0, z1 - r0, y0, x0, th, tw, gy, gx,
+                                              acc.data_ptr() + 8 * sec * (z0 if whole else 0), p.compute.cuda_stream),
+                       "tem_u8_zcorr_tiles")
+            if not whole:                                        # this slab's core sections, added on the host
+                out[z0:z1] += acc[:z1 - z0].cpu().numpy().reshape(z1 - z0, gy, gx, 4)
+        if whole:
+            out = acc.cpu().numpy().reshape(Z, gy, gx, 4)        # the one read-back
+    if stats is not None:
+        stats.update(p.st)
+    return out
+
+
+def _check_sums(s, who):
+    s = np.asarray(s)
+    if s.ndim != 4 or s.shape[3] != 4 or s.dtype.kind not in "iu":
+        raise ValueError(f"{who}: s must be section_sums' integer array [Z, gy, gx, 4], got {s.dtype} {s.shape}")
+    return s.astype(np.int64, copy=False)
+
+
+def section_scores(s):
+    """float64 c[Z - 1, gy, gx]: the Pearson correlation of every tile of section z with the same tile of section z + 1,
+    from section_sums' `s`.  Host only.  Per tile, with n = s[..., 3], S1 = s[..., 0], S2 = s[..., 1], S12 = s[..., 2]:
+      A = n S2[z] - S1[z]^2,   B = the same at z + 1,   N = n S12[z] - S1[z] S1[z + 1]
+    -- exact in int64: a tile holds at most 2^22 voxels of at most 255, so every term stays below 2^61 -- and
+    c = N / (sqrt(A) sqrt(B)) where A > 0 and B > 0, else 0.0: a constant tile correlates with nothing."""
+    s = _check_sums(s, "section_scores")
+    Z = s.shape[0]
+    c = np.zeros((max(Z - 1, 0),) + s.shape[1:3], np.float64)
+    if Z < 2:
+        return c
+    n, S1, S2, S12 = (s[..., q] for q in (3, 0, 1, 2))
+    var = n * S2 - S1 * S1
+    A, B = var[:-1], var[1:]
+    N = n[:-1] * S12[:-1] - S1[:-1] * S1[1:]
+    ok = (A > 0) & (B > 0)
+    c[ok] = N[ok] / (np.sqrt(A[ok].astype(np.float64)) * np.sqrt(B[ok].astype(np.float64)))
+    return c
+
+
+class Defects(NamedTuple):
+    """find_defects' verdict: `sections` the sorted list of bad sections, `tiles` bool[Z, gy, gx] the bad tiles of the
+    other sections, `undecided` bool[gy, gx] the tile columns without a verdict, `scores` float64[Z, gy, gx] what it was
+    decided on."""
+    sections: list
+    tiles: np.ndarray
+    undecided: np.ndarray
+    scores: np.ndarray
+
+
+def _unit(v, what, closed):
+    try:
+        if isinstance(v, (bool, np.bool_, str, bytes)):
+            raise TypeError
+        f = float(v)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what} must be a number, got {v!r}")
+    if not (0 < f <= 1 if closed else 0 < f < 1):
+        raise ValueError(f"{what} must lie in (0, 1{']' if closed else ')'}, got {v!r}")
+    return f
+
+
+def find_defects(s, ratio=0.5, min_corr=0.1, section_fraction=0.5):
+    """The sections and regions of a volume that resemble neither the section below nor the section above -- charging
+    noise, a fold or a tear, a section from the wrong place, a blank one -- from section_sums' `s`.  Host only.  With
+    c = section_scores(s):
+      scores     t[z, i, j] = the larger of c[z - 1, i, j] and c[z, i, j] that exist: a tile is suspect only if it
+                 resembles NEITHER neighbour, so a clean cut in the data (two good halves) flags nothing
+      med[i, j]  = np.median(c[:, i, j]): what "resembles" means for this column of tiles
+      undecided  med <= min_corr: resin, or nothing to correlate -- no verdict for this column
+      bad        decided and t < ratio med
+      sections   the sorted list of sections whose bad tiles are at least `section_fraction` of the decided tiles
+      tiles      bool[Z, gy, gx]: the bad tiles of the other sections
+    Z < 2 gives no verdict anywhere (every column undecided).  `ratio` and `section_fraction` lie in (0, 1], `min_corr`
+    in (0, 1): ValueError otherwise.  The limit of the rule: a run of two or more bad sections that resemble EACH OTHER
+    (a block from the wrong place) is seen only at its two ends, as the two low correlations of section_scores across
+    its cuts -- every section of the run, the end ones included, still resembles a neighbour inside the run, so none is
+    flagged; that is what a clean cut looks like, too.  Blank or saturated sections in a row are still found, since a
+    constant tile correlates with nothing.  defects_repair turns the verdict into a Repair."""
+    s = _check_sums(s, "find_defects")
+    ratio, frac = _unit(ratio, "ratio", True), _unit(section_fraction, "section_fraction", True)
+    min_corr = _unit(min_corr, "min_corr", False)
+    Z, grid = s.shape[0], s.shape[1:3]
+    t = np.zeros((Z,) + grid, np.float64)
+    if Z < 2:
+        return Defects([], np.zeros((Z,) + grid, bool), np.ones(grid, bool), t)
+    c = section_scores(s)
+    t[0], t[-1] = c[0], c[-1]
+    t[1:-1] = np.maximum(c[:-1], c[1:])
+    med = np.median(c, axis=0)
+    undecided = med <= min_corr
+    bad = ~undecided[None] & (t < ratio * med[None])
+    decided = int((~undecided).sum())
+    nbad = bad.reshape(Z, -1).sum(axis=1)
+    sections = [z for z in range(Z) if nbad[z] > 0 and nbad[z] >= frac * decided]
+    tiles = bad.copy()
+    tiles[sections] = False
+    return Defects(sections, tiles, undecided, t)
+
+
+def defect_mask(tiles, tile, vol_shape, out=None):
+    """The uint8 mask [Z, Y, X] of a volume of shape `vol_shape` that is 1 in the voxels of the tiles (i, j) of section z
+    with tiles[z, i, j] and 0 elsewhere, on clahe_grid's tiles of `tile` pixels: what Repair takes as `mask`.  Written
+    into `out` (ndarray, np.memmap, h5py / zarr dataset of the volume's shape, uint8) section by section -- every
+    section, so `out` need not be cleared --, or into a new ndarray; returned.  Host only.  ValueError for a shape that
+    is not [z, y, x], tiles of another shape than (Z, gy, gx), a bad tile or `out`."""
+    th, tw = _clahe_tile(tile)
+    shape = tuple(int(v) for v in vol_shape)
+    if len(shape) != 3:
+        raise ValueError(f"defect_mask needs a volume [z, y, x], got shape {shape}")
+    gy, gx = clahe_grid(shape, (th, tw))
+    tiles = np.asarray(tiles)
+    if tiles.shape != (shape[0], gy, gx):
+        raise ValueError(f"tiles must have the shape {(shape[0], gy, gx)} of the volume's tile grid, got {tiles.shape}")
+    tiles = tiles != 0
+    if out is None:
+        out = np.zeros(shape, np.uint8)
+    elif tuple(out.shape) != shape or getattr(out, "dtype", None) != np.uint8:
+        raise ValueError(f"out must be uint8 of the volume's shape {shape}, got {getattr(out, 'dtype', None)} "
+                         f"{tuple(out.shape)}")
+    clear = np.zeros(shape[1:], np.uint8)
+    for z in range(shape[0]):
+        if tiles[z].any():
+            out[z] = np.repeat(np.repeat(tiles[z], th, axis=0), tw, axis=1)[:shape[1], :shape[2]].astype(np.uint8)
+        else:
+            out[z] = clear
+    return out
+
+
+def defects_repair(d, tile, vol_shape, mask_out=None, max_gap=8):
+    """The Repair of find_defects' verdict `d` for a volume of shape `vol_shape` [z, y, x] on tiles of `tile` pixels: its
+    `sections` are d.sections, its mask defect_mask(d.tiles, ...) -- written into `mask_out` where that is given -- when
+    any tile is bad, otherwise it has no mask (and `mask_out` is left as it is).  volume_repair and `repair=` take it
+    unchanged; a verdict without any defect gives a Repair that changes nothing."""
+    R = _index(max_gap, "max_gap")
+    if not 1 <= R <= REPAIR_MAX_GAP:
+        raise ValueError(f"max_gap must lie in 1...{REPAIR_MAX_GAP}, got {R}")
+    try:
+        sections, tiles = [_index(z, "a section") for z in d.sections], np.asarray(d.tiles)
+    except (AttributeError, TypeError):
+        raise ValueError(f"defects_repair needs find_defects' Defects, got {type(d).__name__}")
+    mask = defect_mask(tiles, tile, vol_shape, mask_out) if tiles.any() else None
+    return Repair(sections, mask, None, R)
 
 
 def _check_compare(compare, vol_shape, stats):
