@@ -574,6 +574,39 @@ int tem_u8_zcorr_tiles(const uint8_t *src, int32_t D, int32_t H, int32_t W, int3
                        int32_t x_org, int32_t th, int32_t tw, int32_t gy, int32_t gx, uint64_t *sums,
                        tem_stream_t stream);
 
+/* The sums behind the correlation of every tile of a section with the NEXT SECTION DISPLACED by every integer offset
+ * within a radius (utils.section_shift_sums -> shift_scores -> section_shifts: how far consecutive sections sit apart
+ * in y and x).  The definition: the volume is V[Z][Y][X], uint8; tiles of (th, tw) pixels on tem_u8_hist_tiles' grid,
+ * gy x gx of them anchored at the volume's (0, 0); the radius r lies in 1...8 and R = 2 r + 1.  For a section
+ * z < Z - 1, a tile (i, j) and an offset (dy, dx) in [-r, r]^2, over the tile's voxels (y, x) whose partner
+ * (y + dy, x + dx) lies inside the section -- 0 <= y + dy < Y and 0 <= x + dx < X; it may lie outside the tile --, with
+ * v = V[z][y][x] and w = V[z + 1][y + dy][x + dx]:
+ *   q[z][i][j][dy + r][dx + r][0..4] = (sum v, sum v v, sum w, sum w w, sum v w)
+ * int64; the last section's are all zero.  The number of terms n[i][j][dy + r][dx + r] is geometry only
+ * (utils.shift_counts); the kernel does not count.  A full tile of 255s stays below 2^38 per entry.
+ *
+ * tem_u8_zshift_tiles follows tem_u8_zcorr_tiles' contract, except: src[D][H][W] is a dense block of WHOLE rows
+ * (W == X, no x_org) whose row 0 sits at volume row y_org of a section of Y rows.  The voxels counted as v are the core
+ * planes [c0, c1) and core rows [r0, r1); the block must hold every partner row of the core that the volume has --
+ * [0, H) contains [r0 - radius, r1 + radius) cut to [-y_org, Y - y_org) -- and plane d + 1 for every core plane d,
+ * except that a core plane d = D - 1 gets no sums at all.  sums (8-byte aligned) points at the rows of plane c0:
+ *   sums[((((d - c0) * gy + i) * gx + j) * R + dy + r) * R + dx + r) * 5 + 0..4] += the five sums above
+ * The kernel ADDS (64-bit global atomic adds, ordinary vector atomics: one per workgroup, offset and quantity): the
+ * caller clears sums once, and blocks that cut a tile along y or z between them accumulate into it.  Nothing but sums
+ * is written.  A load touches only naturally aligned 4-byte words that hold at least one byte of the block.  Any
+ * alignment of src and W.  No partial can overflow at 255 x 255 = 65025 per term: a workgroup is given one plane of a
+ * part of a tile of at most 4096 voxels (64 rows, 128 columns), so a lane's sums, and the sums of its four waves in
+ * LDS, stay below 4096 x 65025 < 2^28 in 32 bits; they are widened to 64 bits for the global add, and the 64-bit
+ * counter takes a whole 2048 x 2048 tile per plane (2^22 x 65025 < 2^38) 2^25 times over.
+ * TEM_EINVAL, without a launch: a null pointer, sums off 8-byte alignment, a dimension, Y, gy or gx below 1, th or tw
+ * outside [1, 2048], a radius outside [1, 8], a negative y_org, a block that reaches past the section or the section
+ * past the grid (y_org + H > Y, Y > gy th, W > gx tw), a core that is not 0 <= c0 <= c1 <= D and 0 <= r0 <= r1 <= H, a
+ * block without a partner row that the volume has.  TEM_EUNSUPPORTED: more than 2^31 - 1 workgroups (one per core
+ * plane with a partner plane, tile and part of it).  An empty core launches nothing. */
+int tem_u8_zshift_tiles(const uint8_t *src, int32_t D, int32_t H, int32_t W, int32_t c0, int32_t c1, int32_t r0,
+                        int32_t r1, int32_t y_org, int32_t Y, int32_t th, int32_t tw, int32_t gy, int32_t gx,
+                        int32_t radius, uint64_t *sums, tem_stream_t stream);
+
 /* Random augmentation of one cached sample (datasets.py:123-155) with host-drawn parameters:
  *   dst = reverse(transpose(src, perm = (p0,p1,p2)), dims with f_k != 0) * scale + shift
  * src is a dense single-channel (D,H,W) volume (2-D: D == 1, p0 must be 0); dst has extents

@@ -48,6 +48,11 @@ ahead of `clahe` and `lut`, without a repaired copy of the volume.
 (tem_u8_zcorr_tiles: exact integer sums); `section_scores` turns the sums into correlations, `find_defects` into the
 sections and regions that resemble neither neighbour, and `defect_mask` / `defects_repair` into the `Repair` that
 `volume_repair` and `repair=` take; `zcorr_chunks` is its slab plan.
+
+`section_shift_sums` is the same measurement against the next section displaced by every integer offset within a
+radius (tem_u8_zshift_tiles); `shift_counts` and `shift_scores` turn the sums into correlations, `section_shifts` into
+the displacement of every section against the one below it, `shift_positions` into a position per section, and
+`volume_shift` moves the sections (or a mask) there on the host; `zshift_chunks` is the slab plan.
 """
 import contextlib
 import json
@@ -1809,6 +1814,259 @@ def defects_repair(d, tile, vol_shape, mask_out=None, max_gap=8):
         raise ValueError(f"defects_repair needs find_defects' Defects, got {type(d).__name__}")
     mask = defect_mask(tiles, tile, vol_shape, mask_out) if tiles.any() else None
     return Repair(sections, mask, None, R)
+
+
+SHIFT_MAX_RADIUS = 8             # offsets of section_shift_sums: [-r, r]^2, r in 1...8
+
+
+def _shift_radius(radius):
+    r = _index(radius, "radius")
+    if not 1 <= r <= SHIFT_MAX_RADIUS:
+        raise ValueError(f"radius must lie in 1...{SHIFT_MAX_RADIUS}, got {r}")
+    return r
+
+
+def zshift_chunks(vol_shape, radius, chunk_bytes=None, rank=0, world_size=1):
+    """Cut a volume of shape `vol_shape` [z, y, x] (one image [y, x]: one section) into slabs for section_shift_sums.
+    Returns this rank's list of (core slab, read slab), both (z, y, x) (lo, hi) boxes: the cores are disjoint and their
+    union is the volume (hist_chunks' cuts: runs of whole sections, or runs of whole rows of one section; x is never
+    cut); a read slab is its core plus `radius` rows on each side, clipped to the volume, and the same rows of the next
+    section where the volume has one -- where the partners of its last core plane lie.  A read slab holds at most
+    `chunk_bytes` bytes (HIST_CHUNK_BYTES when None) wherever one core row allows it: as many whole sections per core as
+    fit next to the one above them, or, where two sections are larger than the budget, one section's rows, as many as
+    fit twice next to their 2 radius rows of halo (one row at the least).  Slabs are in (z, y) order and go round-robin
+    to the ranks.  Pure host function; ValueError as zcorr_chunks, and for a radius outside 1...8."""
+    r = _shift_radius(radius)
+    budget = HIST_CHUNK_BYTES if chunk_bytes is None else int(chunk_bytes)
+    if budget < 1:
+        raise ValueError(f"chunk_bytes must be positive, got {chunk_bytes}")
+    if not 0 <= rank < world_size:
+        raise ValueError(f"rank {rank} is outside [0, {world_size})")
+    (_, Z), (_, ny), (_, nx) = hist_box(vol_shape)
+    if Z <= 0 or ny <= 0 or nx <= 0:
+        return []
+    halo = 1 if Z > 1 else 0
+    if (1 + halo) * ny * nx <= budget:
+        kz = budget // (ny * nx) - halo
+        cores = [((z, min(z + kz, Z)), (0, ny)) for z in range(0, Z, kz)]
+    else:
+        ky = max(1, budget // ((1 + halo) * nx) - 2 * r)
+        cores = [((z, z + 1), (y, min(y + ky, ny))) for z in range(Z) for y in range(0, ny, ky)]
+    slabs = [((cz, cy, (0, nx)), ((cz[0], min(cz[1] + 1, Z)), (max(cy[0] - r, 0), min(cy[1] + r, ny)), (0, nx)))
+             for cz, cy in cores]
+    return slabs[rank::world_size]
+
+
+def shift_counts(vol_shape, tile, radius):
+    """np.int64 n[gy, gx, R, R], R = 2 radius + 1: the number of voxels (y, x) of tile (i, j) of a section of a volume of
+    shape `vol_shape` ([z, y, x] or [y, x]) whose partner (y + dy, x + dx) lies inside the section -- the number of
+    terms of section_shift_sums' q[z, i, j, dy + radius, dx + radius].  Geometry only, in closed form: rows times
+    columns, each the length of the tile's interval cut to [-d, extent - d).  Pure host function."""
+    r = _shift_radius(radius)
+    th, tw = _clahe_tile(tile)
+    _, (_, Y), (_, X) = hist_box(vol_shape)
+    gy, gx = clahe_grid(vol_shape, (th, tw))
+    d = np.arange(-r, r + 1, dtype=np.int64)[None]
+
+    def along(t, g, n):
+        lo = (np.arange(g, dtype=np.int64) * t)[:, None]
+        return np.maximum(np.minimum(np.minimum(lo + t, n), n - d) - np.maximum(lo, -d), 0)
+    return along(th, gy, Y)[:, None, :, None] * along(tw, gx, X)[None, :, None, :]
+
+
+def section_shift_sums(volume, tile=128, radius=4, chunk_bytes=None, rank=0, world_size=1, device=None, stats=None):
+    """The sums behind the correlation of every tile of a section with the next section displaced by every integer
+    offset (dy, dx) in [-radius, radius]^2: np.int64 q[Z, gy, gx, R, R, 5], R = 2 radius + 1, over the WHOLE uint8
+    `volume` [z, y, x] (ndarray, np.memmap, h5py / zarr dataset; one image [y, x]: Z = 1) on clahe_grid's tiles of `tile`
+    pixels (an int or (th, tw) in [1, 2048]).  Over the voxels (y, x) of tile (i, j) whose partner (y + dy, x + dx) lies
+    inside the section -- it may lie outside the tile --, with v = volume[z, y, x], w = volume[z + 1, y + dy, x + dx]:
+      q[z, i, j, dy + radius, dx + radius] = (sum v, sum v v, sum w, sum w w, sum v w);   the last section's are 0.
+    The number of terms is shift_counts'.  Exact integers that numpy reproduces bit for bit, whatever the slabs, ranks
+    and launches.  shift_scores turns them into correlations, section_shifts into the displacement of every section
+    against the one below it.
+
+    Out of core exactly as section_sums, over read slabs that reach `radius` rows and one section past their core
+    (zshift_chunks): one host thread -> pinned -> H2D -> one tem_u8_zshift_tiles launch per slab, adding into a device
+    accumulator.  The accumulator holds the whole volume's Z*gy*gx*R*R*40 bytes and is read back once where that is at
+    most CLAHE_ACC_BYTES; else it holds one slab's core sections and is read back, and added on the host, per slab.
+    Ranks take slabs round-robin and their results add up to the whole.  `stats` receives `read_s` and `chunks`.
+    ValueError, before any GPU work: a non-uint8 volume, a bad tile, radius, shape, chunk_bytes or rank."""
+    _check_u8(volume)
+    th, tw = _clahe_tile(tile)
+    r = _shift_radius(radius)
+    gy, gx = clahe_grid(volume.shape, (th, tw))
+    box = hist_box(volume.shape)
+    chunks = zshift_chunks(volume.shape, r, chunk_bytes, rank, world_size)
+    p = _SlabPass([volume], [box], chunk_bytes, rank, world_size, device, slabs=[s for _, s in chunks])
+    lib = H.require_gpu()
+    R = 2 * r + 1
+    Z, Y, sec = box[0][1], box[1][1], gy * gx * R * R * 5
+    shape = (gy, gx, R, R, 5)
+    whole = Z * sec * 8 <= CLAHE_ACC_BYTES
+    out = None if whole else np.zeros((Z,) + shape, np.int64)
+    with p.streaming():
+        most = max((c[0][1] - c[0][0] for c, _ in chunks), default=1)
+        acc = torch.zeros((Z if whole else most, sec), dtype=torch.int64, device=p.dev)
+        for k, ((s0, _), (y0, _), _), d, (src,) in p:
+            (z0, z1), (c0, c1), _ = chunks[k][0]
+            if not whole:
+                acc[:z1 - z0].zero_()
+            _lib.check(lib.tem_u8_zshift_tiles(src.data_ptr(), *d, z0 - s0, z1 - s0, c0 - y0, c1 - y0, y0, Y, th, tw,
+                                               gy, gx, r, acc.data_ptr() + 8 * sec * (z0 if whole else 0),
+                                               p.compute.cuda_stream), "tem_u8_zshift_tiles")
+            if not whole:                                        # this slab's core sections, added on the host
+                out[z0:z1] += acc[:z1 - z0].cpu().numpy().reshape((z1 - z0,) + shape)
+        if whole:
+            out = acc.cpu().numpy().reshape((Z,) + shape)        # the one read-back
+    if stats is not None:
+        stats.update(p.st)
+    return out
+
+
+def _check_shift_sums(q, n, who):
+    q, n = np.asarray(q), np.asarray(n)
+    if q.ndim != 6 or q.shape[5] != 5 or q.dtype.kind not in "iu" or q.shape[3] != q.shape[4] or \
+            q.shape[3] % 2 != 1 or not 3 <= q.shape[3] <= 2 * SHIFT_MAX_RADIUS + 1:
+        raise ValueError(f"{who}: q must be section_shift_sums' integer array [Z, gy, gx, R, R, 5], got {q.dtype} "
+                         f"{q.shape}")
+    if n.shape != q.shape[1:5] or n.dtype.kind not in "iu":
+        raise ValueError(f"{who}: n must be shift_counts' integer array {q.shape[1:5]}, got {n.dtype} {n.shape}")
+    return q.astype(np.int64, copy=False), n.astype(np.int64, copy=False)
+
+
+def shift_scores(q, n):
+    """float64 c[Z - 1, gy, gx, R, R]: the Pearson correlation of every tile of section z with section z + 1 displaced
+    by (dy, dx), from section_shift_sums' `q` and shift_counts' `n`.  Host only.  Per entry, with
+    (S1, S2, T1, T2, P) = q[z, i, j, dy + r, dx + r]:
+      A = n S2 - S1^2,   B = n T2 - T1^2,   N = n P - S1 T1
+    -- exact in int64: a tile holds at most 2^22 voxels of at most 255, so every term stays below 2^61 -- and
+    c = N / (sqrt(A) sqrt(B)) where A > 0 and B > 0, else 0.0: a constant tile correlates with nothing."""
+    q, n = _check_shift_sums(q, n, "shift_scores")
+    Z = q.shape[0]
+    c = np.zeros((max(Z - 1, 0),) + q.shape[1:5], np.float64)
+    if Z < 2:
+        return c
+    S1, S2, T1, T2, P = (q[:-1, ..., k] for k in range(5))
+    A, B, N = n * S2 - S1 * S1, n * T2 - T1 * T1, n * P - S1 * T1
+    ok = (A > 0) & (B > 0)
+    c[ok] = N[ok] / (np.sqrt(A[ok].astype(np.float64)) * np.sqrt(B[ok].astype(np.float64)))
+    return c
+
+
+class Shifts(NamedTuple):
+    """section_shifts' verdict: `pairs` int64[Z - 1, 2] the (dy, dx) by which section z + 1 is displaced against section
+    z, `tiles` int64[Z - 1, gy, gx, 2] the offset of every tile's largest score, `peak` float64[Z - 1, gy, gx] that
+    score, `decided` bool[Z - 1, gy, gx] the tiles that were counted, `unresolved` the sorted list of the pairs z without
+    a decided tile."""
+    pairs: np.ndarray
+    tiles: np.ndarray
+    peak: np.ndarray
+    decided: np.ndarray
+    unresolved: list
+
+
+def section_shifts(q, n, min_corr=0.1):
+    """How far consecutive sections sit apart, from section_shift_sums' `q` and shift_counts' `n`.  Host only.  With
+    c = shift_scores(q, n) and r the radius:
+      tiles[z, i, j]  = the offset (dy, dx) of the largest c[z, i, j]; the offsets are searched in the order
+                        (dy^2 + dx^2, dy, dx), so ties go to the smaller displacement
+      peak[z, i, j]   = the score at that offset
+      decided         peak > min_corr, and the offset not on the rim of the search (|dy| < r and |dx| < r): a maximum
+                      on the rim says only "at least this far"
+      pairs[z]        per axis the lower median, sorted[(k - 1) // 2], of the k decided tiles' offsets: section z + 1
+                      shows at (y + dy, x + dx) what section z shows at (y, x)
+      unresolved      the pairs without a decided tile; they get (0, 0)
+    `min_corr` lies in (0, 1): ValueError otherwise.  shift_positions adds the pairs up into a position per section,
+    volume_shift moves the sections there."""
+    q, n = _check_shift_sums(q, n, "section_shifts")
+    min_corr = _unit(min_corr, "min_corr", False)
+    c = shift_scores(q, n)
+    R = q.shape[3]
+    r = R // 2
+    order = sorted(((dy, dx) for dy in range(-r, r + 1) for dx in range(-r, r + 1)),
+                   key=lambda o: (o[0] * o[0] + o[1] * o[1], o[0], o[1]))
+    offs = np.array(order, np.int64)                                             # [R R, 2]
+    flat = c.reshape(c.shape[:3] + (R * R,))[..., (offs[:, 0] + r) * R + offs[:, 1] + r]
+    best = flat.argmax(axis=-1)                                                  # the first of equal maxima
+    tiles = offs[best]
+    peak = np.take_along_axis(flat, best[..., None], axis=-1)[..., 0]
+    decided = (peak > min_corr) & (np.abs(tiles) < r).all(axis=-1)
+    pairs, unresolved = np.zeros((c.shape[0], 2), np.int64), []
+    for z in range(c.shape[0]):
+        k = int(decided[z].sum())
+        if k == 0:
+            unresolved.append(z)
+            continue
+        pairs[z] = np.sort(tiles[z][decided[z]], axis=0)[(k - 1) // 2]
+    return Shifts(pairs, tiles, peak, decided, unresolved)
+
+
+def shift_positions(pairs, window=None):
+    """np.int64 P[Z, 2]: the (y, x) position of every section in the frame of section 0, from section_shifts' pairs
+    [Z - 1, 2]: P[0] = 0, P[z + 1] = P[z] + pairs[z].  With `window` (an odd int >= 3) the lower median of P over the
+    sections [z - window // 2, z + window // 2], clipped to the stack, is subtracted per axis: that removes the jitter
+    and keeps a real oblique trend, which a cut through tilted tissue shows.  Integers throughout.  Host only;
+    ValueError for pairs of another shape or dtype, or a bad window."""
+    pairs = np.asarray(pairs)
+    if pairs.ndim != 2 or pairs.shape[1] != 2 or pairs.dtype.kind not in "iu":
+        raise ValueError(f"pairs must be integers of shape [Z - 1, 2], got {pairs.dtype} {pairs.shape}")
+    P = np.zeros((pairs.shape[0] + 1, 2), np.int64)
+    np.cumsum(pairs.astype(np.int64), axis=0, out=P[1:])
+    if window is None:
+        return P
+    w = _index(window, "window")
+    if w < 3 or w % 2 != 1:
+        raise ValueError(f"window must be an odd integer >= 3, got {w}")
+    h, Z = w // 2, P.shape[0]
+    trend = np.empty_like(P)
+    for z in range(Z):
+        run = np.sort(P[max(z - h, 0):min(z + h + 1, Z)], axis=0)
+        trend[z] = run[(run.shape[0] - 1) // 2]
+    return P - trend
+
+
+def volume_shift(volume, positions, out=None, start=None, size=None, fill=0):
+    """The ROI [start, start + size) ((x, y, z) order; default: the whole volume) of an array-like `volume` [z, y, x]
+    (ndarray, np.memmap, h5py / zarr dataset) with every section moved back by its position:
+      out[z, y, x] = volume[z, y + P[z, 0], x + P[z, 1]]   where that voxel exists, else `fill`
+    with P = `positions`, integers [Z, 2] (shift_positions'), written into `out`: a writable array-like of the ROI's
+    shape and the volume's dtype (allocated when None), which is returned.  The same call moves a mask.
+    Host only, section by section like defect_mask: it is a copy, and the out-of-core passes next to it are bound by
+    their one host thread's read and write, so a device leg would add two transfers and no speed.  ValueError for a
+    volume that is not [z, y, x], positions of another shape or dtype, an ROI outside the volume, an `out` of another
+    shape or dtype, a fill that the dtype does not hold."""
+    vshape = tuple(int(v) for v in volume.shape)
+    if len(vshape) != 3:
+        raise ValueError(f"volume_shift needs a volume [z, y, x], got shape {vshape}")
+    dtype = np.dtype(getattr(volume, "dtype", np.uint8))
+    P = np.asarray(positions)
+    if P.shape != (vshape[0], 2) or P.dtype.kind not in "iu":
+        raise ValueError(f"positions must be integers of shape {(vshape[0], 2)}, got {P.dtype} {P.shape}")
+    try:
+        if isinstance(fill, (bool, np.bool_)) and dtype.kind != "b":
+            raise TypeError
+        f = np.array(fill).astype(dtype)
+        if f.ndim or f != fill:
+            raise TypeError
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(f"fill must be one value that {dtype} holds, got {fill!r}")
+    (z0, z1), (y0, y1), (x0, x1) = hist_box(vshape, start, size)
+    shape = (z1 - z0, y1 - y0, x1 - x0)
+    if out is None:
+        out = np.zeros(shape, dtype)
+    elif tuple(out.shape) != shape or getattr(out, "dtype", None) != dtype:
+        raise ValueError(f"out must be {dtype} of the ROI's shape {shape}, got {getattr(out, 'dtype', None)} "
+                         f"{tuple(out.shape)}")
+    Y, X = vshape[1:]
+    sec = np.empty(shape[1:], dtype)
+    for z in range(z0, z1):
+        dy, dx = int(P[z, 0]), int(P[z, 1])
+        ya, yb, xa, xb = max(y0 + dy, 0), min(y1 + dy, Y), max(x0 + dx, 0), min(x1 + dx, X)    # what exists, in the volume
+        sec[...] = f
+        if ya < yb and xa < xb:
+            sec[ya - dy - y0:yb - dy - y0, xa - dx - x0:xb - dx - x0] = volume[z, ya:yb, xa:xb]
+        out[z - z0] = sec
+    return out
 
 
 def _check_compare(compare, vol_shape, stats):
