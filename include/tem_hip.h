@@ -607,6 +607,44 @@ int tem_u8_zshift_tiles(const uint8_t *src, int32_t D, int32_t H, int32_t W, int
                         int32_t r1, int32_t y_org, int32_t Y, int32_t th, int32_t tw, int32_t gy, int32_t gx,
                         int32_t radius, uint64_t *sums, tem_stream_t stream);
 
+/* Every section of a uint8 volume V[Z][Y][X] resampled through its own affine map (utils.volume_warp: sections aligned
+ * by the maps that utils.fit_section_maps fits to the tile offsets of tem_u8_zshift_tiles).  The definition, once: a
+ * section's map is six int64 in units of 2^-16, (a_yy, a_yx, b_y, a_xy, a_xx, b_x).  For the output voxel (y, x) of the
+ * section, in volume coordinates, in 64-bit integers:
+ *   sy = a_yy y + a_yx x + b_y,   sx = a_xy y + a_xx x + b_x
+ *   fy = (sy + 128) >> 8,  fx = (sx + 128) >> 8         (arithmetic shifts: the position in 1/256 px, rounded half up)
+ *   inside  iff  0 <= fy <= 256 (Y - 1)  and  0 <= fx <= 256 (X - 1);  a voxel that is not inside is `fill` -- no tap
+ *           is ever blended with fill
+ *   iy = fy >> 8, ty = fy & 255: the taps are rows iy and min(iy + 1, Y - 1) (the clamp is reached only with ty = 0);
+ *           ix, tx likewise
+ *   out = ((256 - ty) ((256 - tx) v00 + tx v01) + ty ((256 - tx) v10 + tx v11) + 2^15) >> 16      (at most 2^24: one
+ *           rounding, half up, at the very end)
+ *   nearest = 1 (masks):  out = V[(fy + 128) >> 8][(fx + 128) >> 8]
+ * The limits |a_yy - 2^16|, |a_yx|, |a_xy|, |a_xx - 2^16| <= 2^13 (one eighth: seven degrees, or 12 % of scale) and
+ * |b| < 2^47 keep every product inside 64 bits and bound the source hull of a 16 x 64 output tile by 27 rows of 75
+ * bytes, which is what the kernel stages.
+ * src[D][H][W] is a dense block of whole rows [sy0, sy0 + H) of D sections of VY rows and W columns (x is never cut);
+ * dst[OD][OH][OW], OD == D, is the output box with its voxel 0 at (oy0, ox0) of the same sections.  maps_host points at
+ * the D rows of six on the host, which are validated without a launch; maps_dev at the same rows on the device, which
+ * the kernel reads.  The kernel clamps the coefficients it reads to the limits and every load to the block, so a
+ * device table that disagrees with the host's gives wrong bytes, never a fault.  Every byte of dst is written exactly
+ * once and nothing else is written; a load touches only naturally aligned 4-byte words that hold at least one byte of
+ * the block.  Any alignment of src, dst, W and OW; every byte offset is 64 bits.  A voxel depends on its section and
+ * its map alone, not on how the volume was cut.
+ * TEM_EINVAL, without a launch: a null pointer, a dimension below 1, OD != D, a negative origin, a block that leaves
+ * the section (sy0 + H > VY, oy0 + OH > VY, ox0 + OW > W), fill outside 0...255, nearest outside {0, 1}, a coefficient
+ * outside the limits, an output block one of whose taps of weight above 0 lies outside the source block -- decided
+ * per plane from the block's four corners, where the affine sy takes its extremes: with fy cut to [0, 256 (VY - 1)]
+ * the rows fy_min >> 8 ... (fy_max >> 8) + (fy_max & 255 ? 1 : 0), for nearest (fy_min + 128) >> 8 ... (fy_max + 128)
+ * >> 8; none where the plane is wholly outside -- and an output block of more workgroups than one launch holds: a
+ * workgroup takes 16 x 64 outputs of one plane, and
+ *   ceil(OH / 16) x ceil(OW / 64) x D  must stay below 2^24
+ * (its 256 threads then stay below 2^32 per launch).  A block of fewer than 2^32 voxels with OH >= 16 and OW >= 64
+ * always passes. */
+int tem_u8_warp_affine(const uint8_t *src, int32_t D, int32_t H, int32_t W, int32_t sy0, int32_t VY, uint8_t *dst,
+                       int32_t OD, int32_t OH, int32_t OW, int32_t oy0, int32_t ox0, const int64_t *maps_host,
+                       const int64_t *maps_dev, int32_t fill, int32_t nearest, tem_stream_t stream);
+
 /* Random augmentation of one cached sample (datasets.py:123-155) with host-drawn parameters:
  *   dst = reverse(transpose(src, perm = (p0,p1,p2)), dims with f_k != 0) * scale + shift
  * src is a dense single-channel (D,H,W) volume (2-D: D == 1, p0 must be 0); dst has extents

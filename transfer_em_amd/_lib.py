@@ -157,6 +157,8 @@ _SIGS = {
     "tem_u8_hist_tiles":[C.c_void_p] + [C.c_int32] * 9 + [C.c_void_p, C.c_void_p],
     "tem_u8_zcorr_tiles": [C.c_void_p] + [C.c_int32] * 11 + [C.c_void_p, C.c_void_p],
     "tem_u8_zshift_tiles": [C.c_void_p] + [C.c_int32] * 14 + [C.c_void_p, C.c_void_p],
+    "tem_u8_warp_affine": [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_void_p,
+                           C.c_int32, C.c_int32, C.c_void_p],
     "tem_u8_clahe": [C.c_void_p] + [C.c_int32] * 6 + [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p],
     "tem_augment_f32": [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                         C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p],

@@ -53,6 +53,11 @@ sections and regions that resemble neither neighbour, and `defect_mask` / `defec
 radius (tem_u8_zshift_tiles); `shift_counts` and `shift_scores` turn the sums into correlations, `section_shifts` into
 the displacement of every section against the one below it, `shift_positions` into a position per section, and
 `volume_shift` moves the sections (or a mask) there on the host; `zshift_chunks` is the slab plan.
+
+`shift_subpixel` refines the same tile offsets below a pixel, `fit_section_maps` fits one affine map (or translation)
+per pair of sections to them, `section_maps` composes the pair maps into one map per section, `quantize_maps` brings
+them to the 2^-16 fixed point of the device, and `volume_warp` resamples every section through its map out of core
+(tem_u8_warp_affine: bilinear or nearest, in integers with one rounding per voxel); `warp_chunks` is the slab plan.
 """
 import contextlib
 import json
@@ -2032,7 +2037,8 @@ def volume_shift(volume, positions, out=None, start=None, size=None, fill=0):
     with P = `positions`, integers [Z, 2] (shift_positions'), written into `out`: a writable array-like of the ROI's
     shape and the volume's dtype (allocated when None), which is returned.  The same call moves a mask.
     Host only, section by section like defect_mask: it is a copy, and the out-of-core passes next to it are bound by
-    their one host thread's read and write, so a device leg would add two transfers and no speed.  ValueError for a
+    their one host thread's read and write, so a device leg would add two transfers and no speed.  Shifts below a pixel,
+    rotation, scale and shear need resampling: that is volume_warp, on the device.  ValueError for a
     volume that is not [z, y, x], positions of another shape or dtype, an ROI outside the volume, an `out` of another
     shape or dtype, a fill that the dtype does not hold."""
     vshape = tuple(int(v) for v in volume.shape)
@@ -2066,6 +2072,345 @@ def volume_shift(volume, positions, out=None, start=None, size=None, fill=0):
         if ya < yb and xa < xb:
             sec[ya - dy - y0:yb - dy - y0, xa - dx - x0:xb - dx - x0] = volume[z, ya:yb, xa:xb]
         out[z - z0] = sec
+    return out
+
+
+class SubShifts(NamedTuple):
+    """shift_subpixel's verdict: `offsets` float64[Z - 1, gy, gx, 2] the (dy, dx) of every tile, refined below a pixel
+    where the tile is decided, `decided` and `peak` those of section_shifts, unchanged."""
+    offsets: np.ndarray
+    decided: np.ndarray
+    peak: np.ndarray
+
+
+def shift_subpixel(q, n, min_corr=0.1):
+    """section_shifts' tile offsets refined below a pixel, from section_shift_sums' `q` and shift_counts' `n`.  Host
+    only.  It starts from section_shifts' `tiles`, `decided` and `peak`, unchanged.  A decided tile is never on the rim
+    of the search, so both neighbours of its peak exist along each axis; per axis, with c0 the peak of shift_scores and
+    m, p the scores one offset below and above it along that axis, the vertex of the parabola through the three,
+      delta = (m - p) / (2 (m - 2 c0 + p)),   clipped to [-1/2, 1/2],
+    is added where the denominator is below 0 (a true maximum).  Undecided tiles keep their integer offset and stay
+    undecided.  fit_section_maps turns the offsets into one map per pair."""
+    s = section_shifts(q, n, min_corr)
+    c = shift_scores(q, n)
+    r = c.shape[-1] // 2
+    offsets = s.tiles.astype(np.float64)
+    for z, i, j in zip(*np.nonzero(s.decided)):
+        dy, dx = (int(v) for v in s.tiles[z, i, j])
+        c0 = c[z, i, j, dy + r, dx + r]
+        for axis, (m, p) in enumerate(((c[z, i, j, dy + r - 1, dx + r], c[z, i, j, dy + r + 1, dx + r]),
+                                       (c[z, i, j, dy + r, dx + r - 1], c[z, i, j, dy + r, dx + r + 1]))):
+            den = m - 2.0 * c0 + p
+            if den < 0:
+                offsets[z, i, j, axis] += min(max((m - p) / (2.0 * den), -0.5), 0.5)
+    return SubShifts(offsets, s.decided, s.peak)
+
+
+class SectionFits(NamedTuple):
+    """fit_section_maps' verdict: `maps` float64[Z - 1, 2, 3] the map T_z of every pair (rows (y, x); columns: from y,
+    from x, constant), `kept` bool[Z - 1, gy, gx] the tiles the final fit rests on, `residual` float64[Z - 1] the
+    largest max-norm residual among them in pixels, `unresolved` the sorted list of the pairs without a decided tile."""
+    maps: np.ndarray
+    kept: np.ndarray
+    residual: np.ndarray
+    unresolved: list
+
+
+def _fit_map(pts, target, affine):
+    """The least-squares map of `pts` [k, 2] onto `target` [k, 2] as [2, 3], and whether it is affine: L = I where
+    `affine` is False or the points do not span the plane."""
+    mean = pts.mean(axis=0)
+    A = np.concatenate([pts - mean, np.ones((pts.shape[0], 1))], axis=1)
+    if affine and np.linalg.matrix_rank(A) == 3:
+        coef = np.linalg.lstsq(A, target, rcond=None)[0]                 # [3, 2]: target = (p - mean) L^T + c
+        L = coef[:2].T
+        return np.concatenate([L, (coef[2] - L @ mean)[:, None]], axis=1)
+    return np.concatenate([np.eye(2), (target - pts).mean(axis=0)[:, None]], axis=1)
+
+
+def fit_section_maps(sub, tile, vol_shape, model="affine", max_residual=1.0):
+    """One map per pair of sections from the tile offsets of shift_subpixel (or any (offsets, decided, ...) tuple) on
+    clahe_grid's tiles of `tile` pixels over a volume of shape `vol_shape`.  Host only.  The pair map is
+    T_z(p) = L p + b with p = (y, x) in voxel indices: section z + 1 shows at T_z(p) what section z shows at p.  A
+    tile's point is the mean index of its existing voxels, (lo + hi - 1) / 2 per axis; the fit is ordinary least squares
+    of point + offset on (point, 1) over the kept tiles, which start as the decided ones.  Robust and deterministic:
+    fit; if the worst max-norm residual exceeds `max_residual` pixels, drop that one tile (ties: the lowest index) and
+    refit; stop when none exceeds it or half of the decided tiles are gone.  model="translation" fixes L = I;
+    "affine" falls back to it for a pair whose kept points do not span the plane.  A pair without a decided tile gets
+    the identity and a place in `unresolved`.  section_maps composes the pair maps into one map per section.
+    Per-tile (elastic) maps are out of scope.  ValueError for offsets or decided of another shape, an unknown model, a
+    max_residual that is not a positive number."""
+    th, tw = _clahe_tile(tile)
+    gy, gx = clahe_grid(vol_shape, (th, tw))
+    _, (_, Y), (_, X) = hist_box(vol_shape)
+    offsets, decided = np.asarray(sub[0]), np.asarray(sub[1])
+    if offsets.ndim != 4 or offsets.shape[1:] != (gy, gx, 2) or offsets.dtype.kind not in "fiu":
+        raise ValueError(f"offsets must be numbers of shape [Z - 1, {gy}, {gx}, 2], got {offsets.dtype} {offsets.shape}")
+    if decided.shape != offsets.shape[:3] or decided.dtype != np.bool_:
+        raise ValueError(f"decided must be bool of shape {offsets.shape[:3]}, got {decided.dtype} {decided.shape}")
+    if model not in ("affine", "translation"):
+        raise ValueError(f"model must be 'affine' or 'translation', got {model!r}")
+    if isinstance(max_residual, (bool, np.bool_)) or not isinstance(max_residual, (int, float, np.integer, np.floating)) \
+            or not (max_residual > 0 and np.isfinite(max_residual)):
+        raise ValueError(f"max_residual must be a positive number, got {max_residual!r}")
+    offsets = offsets.astype(np.float64)
+    centre = lambda t, g, n: np.array([(k * t + min((k + 1) * t, n) - 1) / 2 for k in range(g)])
+    points = np.stack(np.meshgrid(centre(th, gy, Y), centre(tw, gx, X), indexing="ij"), axis=-1)     # [gy, gx, 2]
+    P = offsets.shape[0]
+    maps = np.tile(np.concatenate([np.eye(2), np.zeros((2, 1))], axis=1), (P, 1, 1))
+    kept, residual, unresolved = decided.copy(), np.zeros(P, np.float64), []
+    for z in range(P):
+        nd, gone = int(decided[z].sum()), 0
+        if nd == 0:
+            unresolved.append(z)
+            continue
+        while True:
+            idx = np.flatnonzero(kept[z])
+            pts = points.reshape(-1, 2)[idx]
+            target = pts + offsets[z].reshape(-1, 2)[idx]
+            m = _fit_map(pts, target, model == "affine")
+            res = np.abs(pts @ m[:, :2].T + m[:, 2] - target).max(axis=1)
+            worst = int(res.argmax())                                    # the first of equal maxima: the lowest index
+            if res[worst] <= max_residual or 2 * gone >= nd or idx.size == 1:
+                break
+            kept[z].reshape(-1)[idx[worst]] = False
+            gone += 1
+        maps[z], residual[z] = m, res.max()
+    return SectionFits(maps, kept, residual, unresolved)
+
+
+def _map_compose(a, b):
+    """a o b of two [2, 3] maps."""
+    return np.concatenate([a[:, :2] @ b[:, :2], (a[:, :2] @ b[:, 2] + a[:, 2])[:, None]], axis=1)
+
+
+def section_maps(pair_maps, window=None):
+    """float64 B[Z, 2, 3]: one map per section from fit_section_maps' pair maps [Z - 1, 2, 3]: B_0 = I and
+    B_{z + 1} = T_z o B_z, so that out[z](p) = volume[z](B_z p) shows what section 0 shows at p -- what volume_warp
+    computes.  With `window` (an odd int >= 3) the trend, the element-wise running lower median of the six coefficients
+    over the sections [z - window // 2, z + window // 2], clipped to the stack, is taken out: the result is
+    B_z o trend_z^-1, which removes the jitter and keeps a real drift.  For integer translations this equals
+    shift_positions(pairs, window) exactly.  Host only; ValueError for maps of another shape or dtype, values that are
+    not finite, a bad window."""
+    T = np.asarray(pair_maps)
+    if T.ndim != 3 or T.shape[1:] != (2, 3) or T.dtype.kind != "f" or not np.isfinite(T).all():
+        raise ValueError(f"pair_maps must be finite floats of shape [Z - 1, 2, 3], got {T.dtype} {T.shape}")
+    T = T.astype(np.float64)
+    B = np.empty((T.shape[0] + 1, 2, 3), np.float64)
+    B[0] = [[1, 0, 0], [0, 1, 0]]
+    for z in range(T.shape[0]):
+        B[z + 1] = _map_compose(T[z], B[z])
+    if window is None:
+        return B
+    w = _index(window, "window")
+    if w < 3 or w % 2 != 1:
+        raise ValueError(f"window must be an odd integer >= 3, got {w}")
+    h, Z = w // 2, B.shape[0]
+    out = np.empty_like(B)
+    for z in range(Z):
+        run = np.sort(B[max(z - h, 0):min(z + h + 1, Z)].reshape(-1, 6), axis=0)
+        (a, b, ty), (c, d, tx) = run[(run.shape[0] - 1) // 2].reshape(2, 3)
+        det = a * d - b * c
+        if det == 0:
+            raise ValueError(f"the trend of section {z} cannot be inverted")
+        Li = np.array([[d, -b], [-c, a]]) / det
+        inv = np.concatenate([Li, (-Li @ np.array([ty, tx]))[:, None]], axis=1)
+        out[z] = _map_compose(B[z], inv)
+    return out
+
+
+WARP_UNIT = 1 << 16              # tem_u8_warp_affine: coefficients in 2^-16, a matrix coefficient within 2^13 of I,
+WARP_MAX_DEV = 1 << 13           # |b| below 2^47
+WARP_MAX_B = 1 << 47
+
+
+def _check_qmaps(M, what):
+    """int64 [Z, 6] `M` inside tem_u8_warp_affine's limits, or ValueError."""
+    dev = np.abs(M - np.array([WARP_UNIT, 0, 0, 0, WARP_UNIT, 0], np.int64))
+    if (dev[:, [0, 1, 3, 4]] > WARP_MAX_DEV).any() or (dev[:, [2, 5]] >= WARP_MAX_B).any():
+        z = int(np.flatnonzero((dev[:, [0, 1, 3, 4]] > WARP_MAX_DEV).any(axis=1) | (dev[:, [2, 5]] >= WARP_MAX_B).any(axis=1))[0])
+        raise ValueError(f"{what}: the map of section {z}, {M[z].tolist()} in 2^-16, is outside the limits: a matrix "
+                         f"coefficient within 1/8 of the identity's, |b| below 2^31 pixels")
+    return M
+
+
+def quantize_maps(maps):
+    """np.int64[Z, 6] = (a_yy, a_yx, b_y, a_xy, a_xx, b_x) in units of 2^-16, rounded with rint, of float maps [Z, 2, 3]
+    (section_maps'): what tem_u8_warp_affine and volume_warp compute with.  ValueError for another shape or dtype,
+    values that are not finite, and outside the limits |a_yy - 2^16|, |a_yx|, |a_xy|, |a_xx - 2^16| <= 2^13 and
+    |b| < 2^47: one eighth -- seven degrees, or 12 % of scale -- which is what bounds the kernel's staging hull."""
+    m = np.asarray(maps)
+    if m.ndim != 3 or m.shape[1:] != (2, 3) or m.dtype.kind != "f":
+        raise ValueError(f"maps must be floats of shape [Z, 2, 3], got {m.dtype} {m.shape}")
+    if not np.isfinite(m).all():
+        raise ValueError("maps must be finite")
+    m = m.astype(np.float64) * WARP_UNIT
+    if (np.abs(m) >= 2.0 ** 62).any():
+        raise ValueError("maps: a coefficient is outside the limits")
+    return _check_qmaps(np.rint(m).astype(np.int64).reshape(-1, 6), "maps")
+
+
+def _warp_table(maps, Z, one):
+    """volume_warp's `maps` as the int64[Z, 6] table: float [Z, 2, 3] is quantised, int64 [Z, 6] is checked; one image
+    also takes one map [2, 3] or [6]."""
+    m = np.asarray(maps)
+    if one and m.ndim == (2 if m.dtype.kind == "f" else 1):
+        m = m[None]
+    if m.dtype.kind == "f" and m.shape == (Z, 2, 3):
+        return quantize_maps(m)
+    if m.dtype == np.int64 and m.shape == (Z, 6):
+        return _check_qmaps(np.array(m), "maps")                          # a writable copy
+    raise ValueError(f"maps must be floats of shape {(Z, 2, 3)} or int64 of shape {(Z, 6)}, got {m.dtype} {m.shape}")
+
+
+def _warp_rows(M, z0, z1, y0, y1, x0, x1, Y):
+    """The rows [lo, hi) of the section that the outputs [y0, y1) x [x0, x1) of sections [z0, z1) can read: [min iy,
+    max iy + 2) over the box's corners -- where the affine sy takes its extremes --, unioned over the sections and
+    clipped to the section; one row at the least."""
+    a, b, c = M[z0:z1, 0], M[z0:z1, 1], M[z0:z1, 2]
+    s, ey, ex = a * y0 + b * x0 + c, a * (y1 - 1 - y0), b * (x1 - 1 - x0)
+    lo = int(((s + np.minimum(ey, 0) + np.minimum(ex, 0) + 128) >> 16).min())
+    hi = int(((s + np.maximum(ey, 0) + np.maximum(ex, 0) + 128) >> 16).max()) + 2
+    lo = min(max(lo, 0), Y - 1)
+    return lo, max(min(hi, Y), lo + 1)
+
+
+def warp_chunks(out_box, vol_shape, M, chunk_bytes=None, rank=0, world_size=1):
+    """Cut the (z, y, x) (lo, hi) box `out_box` of a volume of shape `vol_shape` [z, y, x] into slabs for volume_warp
+    under the maps `M`, quantize_maps' int64[Z, 6].  Returns this rank's list of (output slab, read slab), (z, y, x)
+    (lo, hi) boxes of the volume: the output slabs are disjoint and their union is the box -- runs of whole sections of
+    the box, as many as fit, or, where one section or its hull is larger than the budget, runs of whole rows of that
+    section (one row at the least).  A read slab is the same sections with the rows [min iy, max iy + 2) over its
+    output slab's corners, unioned over its sections and clipped to the section (one row at the least, when everything
+    is outside), over the volume's whole x extent: x is never cut.  Both slabs hold at most `chunk_bytes` bytes
+    (HIST_CHUNK_BYTES when None).  Slabs are in (z, y) order and go round-robin to the ranks.  Pure host function;
+    ValueError as rescale_chunks, and for maps of another shape or dtype or outside the limits."""
+    budget = HIST_CHUNK_BYTES if chunk_bytes is None else int(chunk_bytes)
+    if budget < 1:
+        raise ValueError(f"chunk_bytes must be positive, got {chunk_bytes}")
+    if not 0 <= rank < world_size:
+        raise ValueError(f"rank {rank} is outside [0, {world_size})")
+    vol_shape = tuple(int(v) for v in vol_shape)
+    if len(vol_shape) != 3 or min(vol_shape) < 1:
+        raise ValueError(f"warp_chunks takes a non-empty volume shape [z, y, x], got {vol_shape}")
+    Z, Y, X = vol_shape
+    M = np.asarray(M)
+    if M.dtype != np.int64 or M.shape != (Z, 6):
+        raise ValueError(f"M must be int64 of shape {(Z, 6)}, got {M.dtype} {M.shape}")
+    _check_qmaps(M, "M")
+    (z0, z1), (y0, y1), (x0, x1) = out_box
+    if any(lo < 0 or hi > n for (lo, hi), n in zip(out_box, vol_shape)):
+        raise ValueError(f"the box {tuple(out_box)} reaches outside the volume of shape {vol_shape}")
+    ny, nx = y1 - y0, x1 - x0
+    if z1 <= z0 or ny <= 0 or nx <= 0:
+        return []
+
+    def fits(nz, rows, ry):             # an output slab of nz sections of `rows` rows and its read slab of ry rows
+        return nz * rows * nx <= budget and nz * ry * X <= budget
+
+    slabs, z = [], z0
+    while z < z1:
+        lo, hi = _warp_rows(M, z, z + 1, y0, y1, x0, x1, Y)
+        if fits(1, ny, hi - lo):
+            k = 1
+            while z + k < z1:
+                more = _warp_rows(M, z, z + k + 1, y0, y1, x0, x1, Y)
+                if not fits(k + 1, ny, more[1] - more[0]):
+                    break
+                k, (lo, hi) = k + 1, more
+            slabs.append((((z, z + k), (y0, y1), (x0, x1)), ((z, z + k), (lo, hi), (0, X))))
+            z += k
+            continue
+        y = y0
+        while y < y1:
+            rows = _warp_rows(M, z, z + 1, y, y + 1, x0, x1, Y)
+            k = 1
+            while y + k < y1:
+                more = _warp_rows(M, z, z + 1, y, y + k + 1, x0, x1, Y)
+                if not fits(1, k + 1, more[1] - more[0]):
+                    break
+                k, rows = k + 1, more
+            slabs.append((((z, z + 1), (y, y + k), (x0, x1)), ((z, z + 1), rows, (0, X))))
+            y += k
+        z += 1
+    return slabs[rank::world_size]
+
+
+def volume_warp(volume, maps, out=None, start=None, size=None, fill=0, nearest=False, chunk_bytes=None, rank=0,
+                world_size=1, device=None, stats=None):
+    """A uint8 array-like `volume` indexed [z, y, x] (ndarray, np.memmap, h5py / zarr dataset), or one image [y, x], with
+    every section resampled through its own affine map, on the device: out[z](p) = volume[z](B_z p) with B = `maps`,
+    float [Z, 2, 3] (section_maps': rows (y, x); columns from y, from x, constant; quantised inside with
+    quantize_maps) or quantize_maps' int64 [Z, 6]; one image takes one map.  This is the sub-pixel, rotating, scaling
+    and shearing form of volume_shift -- section_shift_sums -> shift_subpixel -> fit_section_maps -> section_maps ->
+    volume_warp aligns a stack -- and with the identity matrix and integer translations it reproduces volume_shift byte
+    for byte.
+
+    The position is computed in 64-bit integers in units of 2^-16, rounded half up to 1/256 px; a voxel whose position
+    lies outside [0, Y - 1] x [0, X - 1] is `fill` (0...255) -- no tap is ever blended with fill; otherwise it is the
+    bilinear blend of the 2 x 2 voxels around it in integers, rounded once, half up (tem_u8_warp_affine; include/
+    tem_hip.h has the definition, numpy reproduces it bit for bit), or with `nearest`, for masks, the voxel nearest to
+    it.  A voxel depends on its section and its map alone, not on the slab, ROI or rank it was computed in.  A matrix
+    coefficient must lie within 1/8 of the identity's (seven degrees, or 12 % of scale).
+
+    The output grid is the volume's own; `start` / `size` are an ROI of it in (x, y, z) order (default: all of it),
+    `out` a writable uint8 array-like of the ROI's shape (allocated when None), which is returned.  Out of core as
+    volume_rescale: the ROI is cut into output slabs and the read slabs that hold their taps (warp_chunks), both at most
+    `chunk_bytes`; host thread -> pinned -> H2D -> one tem_u8_warp_affine launch per slab -> D2H -> host write, on
+    double buffers, in the order write(k), read(k + 2) on the one host thread; the table of maps is uploaded once.
+    Ranks (rank / world_size) take slabs round-robin and write disjoint boxes of a shared `out`.  `stats` receives
+    `read_s`, `write_s` and `chunks`.
+
+    Out of scope: per-tile (elastic) warps, resampling along z, a warp= keyword on predict_cube / predict_volume (warp,
+    then predict), and majority resampling of labels (nearest is what masks get).
+
+    ValueError, before any GPU work: a volume that is not uint8 or not [z, y, x] (or one image), maps of a wrong shape
+    or dtype or outside the limits, an ROI outside the volume, an `out` of another shape or dtype, a fill outside
+    0...255."""
+    _check_u8(volume)
+    vshape = tuple(int(v) for v in volume.shape)
+    if len(vshape) not in (2, 3) or min(vshape) < 1:
+        raise ValueError(f"volume_warp needs a non-empty volume [z, y, x] or one image [y, x], got shape {vshape}")
+    one = len(vshape) == 2
+    vol3 = (1,) + vshape if one else vshape
+    M = _warp_table(maps, vol3[0], one)
+    fill = _index(fill, "fill")
+    if not 0 <= fill <= 255:
+        raise ValueError(f"fill must lie in 0...255, got {fill}")
+    box = hist_box(vshape, start, size)
+    shape = tuple(hi - lo for lo, hi in box)
+    want = shape[1:] if one else shape
+    if out is None:
+        out = np.zeros(want, np.uint8)
+    elif tuple(out.shape) != want or getattr(out, "dtype", None) != np.uint8:
+        raise ValueError(f"out must be uint8 of the ROI's shape {want}, got {getattr(out, 'dtype', None)} "
+                         f"{tuple(out.shape)}")
+    chunks = warp_chunks(box, vol3, M, chunk_bytes, rank, world_size)
+    p = _SlabPass([volume], [hist_box(vshape)], chunk_bytes, rank, world_size, device, slabs=[r for _, r in chunks])
+    lib = H.require_gpu()
+    oslabs = [o for o, _ in chunks]
+    odims = [tuple(hi - lo for lo, hi in o) for o in oslabs]
+    dst_vol = _OneSection(out) if one else out
+    (oz, _), (oy, _), (ox, _) = box
+    p.st["write_s"] = 0.0
+
+    def write_from(k, flat):            # host thread: the slab's box of `out`
+        (z0, z1), (y0, y1), (x0, x1) = oslabs[k]
+        dst_vol[z0 - oz:z1 - oz, y0 - oy:y1 - oy, x0 - ox:x1 - ox] = flat.reshape(odims[k])
+
+    with p.streaming():
+        table = torch.from_numpy(M).to(p.dev)                            # the whole table, once
+        with _OutputStream([int(np.prod(d)) for d in odims], write_from, p.dev, p.pool, p.st,
+                           own_buffers=True) as outp:                    # the reader's thread: write(k), read(k + 2)
+            for k, ((z0, _), (y0, _), _), d, (src,) in p:
+                _lib.check(lib.tem_u8_warp_affine(src.data_ptr(), *d, y0, vol3[1], outp.device(k).data_ptr(), *odims[k],
+                                                  oslabs[k][1][0], oslabs[k][2][0], M.ctypes.data + 48 * z0,
+                                                  table.data_ptr() + 48 * z0, fill, int(bool(nearest)),
+                                                  p.compute.cuda_stream), "tem_u8_warp_affine")
+                p.release_on = p.compute.record_event()                  # behind the kernel: the input is free too
+                outp.put(k, p.release_on)
+    if stats is not None:
+        stats.update(p.st)
     return out
 
 
