@@ -645,6 +645,54 @@ int tem_u8_warp_affine(const uint8_t *src, int32_t D, int32_t H, int32_t W, int3
                        int32_t OD, int32_t OH, int32_t OW, int32_t oy0, int32_t ox0, const int64_t *maps_host,
                        const int64_t *maps_dev, int32_t fill, int32_t nearest, tem_stream_t stream);
 
+/* tem_u8_warp_affine with a smooth displacement field added to every section's map (utils.volume_warp_field: sections
+ * aligned elastically by the fields that utils.fit_section_fields fits to what the affine fit leaves over).  The
+ * definition, once: the lattice has the spacings Sy = 2^ky and Sx = 2^kx pixels, ky and kx in 4...10; node (i, j) sits
+ * at pixel (i Sy, j Sx); there are ny = ((Y - 1) >> ky) + 2 by nx = ((X - 1) >> kx) + 2 nodes, so that every pixel of
+ * the section lies in a cell with four nodes; the node values are U[i][j][0..1] = (u_y, u_x), int32 in units of 2^-16
+ * px.  For the output voxel (y, x), in 64-bit integers:
+ *   i = y >> ky,  ry = y & (Sy - 1);   j = x >> kx,  rx = x & (Sx - 1)
+ *   uy = ((Sy - ry) ((Sx - rx) U[i][j][0] + rx U[i][j+1][0])
+ *         + ry ((Sx - rx) U[i+1][j][0] + rx U[i+1][j+1][0])) >> (ky + kx)       (arithmetic shift; ux from [..][1])
+ *   sy = a_yy y + a_yx x + b_y + uy,   sx = a_xy y + a_xx x + b_x + ux
+ * and from sy and sx on everything is tem_u8_warp_affine's definition: fy, inside, the taps, the one rounding, nearest.
+ * Consequences, exact: U = 0 gives tem_u8_warp_affine's bytes; a constant U those of the map with b moved by it; a ramp
+ * U[i][j][0] = i Sy g those of the map with a_yy + g (the interpolation of a linear lattice is exact and the shift
+ * divides an exact multiple), likewise for the other three coefficients.
+ * The limits: the affine ones, |U| <= 2^21 (32 px), and two nodes adjacent along y differ by at most Sy 2^13 per
+ * component, two adjacent along x by at most Sx 2^13: a gradient of one eighth, the size of the matrix limit.  Inside
+ * a cell the exact bilinear value then changes by at most 2^13 per pixel along either axis, it is continuous across
+ * cells, and the shift moves it by less than 1, so over a 16 x 64 tile u stays within (8 + 32) 2^13 + 1 of its value
+ * at the tile's middle voxel: a range of 10 px on top of the matrix's 15 (1 + 1/8) + 63 / 8 = 24.75 px in sy and 72.75
+ * px in sx.  34.75 px span at most 36 rows and the tap below the last makes 37; 82.75 px make 85 columns: the source
+ * hull of a tile is at most 37 rows of 85 bytes, which is what the kernel stages (3,256 B of LDS).
+ * src, dst, the blocks, maps_host / maps_dev, fill and nearest are tem_u8_warp_affine's; field_host points at the D
+ * sections' [ny][nx][2] rows on the host, which are validated without a launch, field_dev at the same rows on the
+ * device, which the kernel reads.  The kernel clamps coefficients and node values to the limits and every load to the
+ * block, so a device table that disagrees with the host's gives wrong bytes, never a fault.  Every byte of dst is
+ * written exactly once and nothing else is written; a load from src touches only naturally aligned 4-byte words that
+ * hold at least one byte of the block; any alignment of src, dst, W and OW; every byte offset is 64 bits.
+ * TEM_EINVAL, without a launch: everything tem_u8_warp_affine refuses (a null field pointer included); ky or kx
+ * outside 4...10; ny or nx that are not the lattice of (VY, W); a node value or a difference of adjacent nodes outside
+ * the limits; an output block whose required rows are not in the source block -- decided per plane from a superset of
+ * every tap: the extremes of the affine sy at the block's four corners plus the least and the largest U[..][0] over the
+ * nodes [oy0 >> ky, ((oy0 + OH - 1) >> ky) + 1] x [ox0 >> kx, ((ox0 + OW - 1) >> kx) + 1] (the interpolated value lies
+ * between its nodes, and every shift is monotone), fy cut to the section, the rows fy_min >> 8 ... (fy_max >> 8) +
+ * (fy_max & 255 ? 1 : 0), for nearest (fy + 128) >> 8; none where the plane is wholly outside in y or in x by the same
+ * bounds -- and more workgroups than one launch holds, as tem_u8_warp_affine. */
+int tem_u8_warp_field(const uint8_t *src, int32_t D, int32_t H, int32_t W, int32_t sy0, int32_t VY, uint8_t *dst,
+                      int32_t OD, int32_t OH, int32_t OW, int32_t oy0, int32_t ox0, const int64_t *maps_host,
+                      const int64_t *maps_dev, const int32_t *field_host, const int32_t *field_dev, int32_t ny,
+                      int32_t nx, int32_t ky, int32_t kx, int32_t fill, int32_t nearest, tem_stream_t stream);
+
+/* tem_u8_warp_field's baseline for measurements (tests/tools/volume_field_time.py): the same arguments, checks and
+ * bytes, computed without LDS -- every output's position from the definition in 64 bits, its taps and nodes as loads
+ * from global memory, clamped to the block and the lattice.  Its loads from src are single bytes. */
+int tem_u8_warp_field_direct(const uint8_t *src, int32_t D, int32_t H, int32_t W, int32_t sy0, int32_t VY, uint8_t *dst,
+                             int32_t OD, int32_t OH, int32_t OW, int32_t oy0, int32_t ox0, const int64_t *maps_host,
+                             const int64_t *maps_dev, const int32_t *field_host, const int32_t *field_dev, int32_t ny,
+                             int32_t nx, int32_t ky, int32_t kx, int32_t fill, int32_t nearest, tem_stream_t stream);
+
 /* Random augmentation of one cached sample (datasets.py:123-155) with host-drawn parameters:
  *   dst = reverse(transpose(src, perm = (p0,p1,p2)), dims with f_k != 0) * scale + shift
  * src is a dense single-channel (D,H,W) volume (2-D: D == 1, p0 must be 0); dst has extents

@@ -159,6 +159,10 @@ _SIGS = {
     "tem_u8_zshift_tiles": [C.c_void_p] + [C.c_int32] * 14 + [C.c_void_p, C.c_void_p],
     "tem_u8_warp_affine": [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_void_p,
                            C.c_int32, C.c_int32, C.c_void_p],
+    "tem_u8_warp_field": [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p] * 4 +
+                         [C.c_int32] * 6 + [C.c_void_p],
+    "tem_u8_warp_field_direct": [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p] * 4 +
+                                [C.c_int32] * 6 + [C.c_void_p],
     "tem_u8_clahe": [C.c_void_p] + [C.c_int32] * 6 + [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p],
     "tem_augment_f32": [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                         C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p],

@@ -58,6 +58,11 @@ the displacement of every section against the one below it, `shift_positions` in
 per pair of sections to them, `section_maps` composes the pair maps into one map per section, `quantize_maps` brings
 them to the 2^-16 fixed point of the device, and `volume_warp` resamples every section through its map out of core
 (tem_u8_warp_affine: bilinear or nearest, in integers with one rounding per voxel); `warp_chunks` is the slab plan.
+
+`fit_section_fields` turns what the affine fit leaves over in the tile offsets into one smooth displacement field per
+pair on a lattice (`field_grid`), `section_fields` composes the pairs into one map and one field per section,
+`quantize_field` brings the fields to the device's fixed point, and `volume_warp_field` resamples every section through
+"affine map + field" out of core (tem_u8_warp_field); `field_chunks` is the slab plan.
 """
 import contextlib
 import json
@@ -2138,7 +2143,8 @@ def fit_section_maps(sub, tile, vol_shape, model="affine", max_residual=1.0):
     refit; stop when none exceeds it or half of the decided tiles are gone.  model="translation" fixes L = I;
     "affine" falls back to it for a pair whose kept points do not span the plane.  A pair without a decided tile gets
     the identity and a place in `unresolved`.  section_maps composes the pair maps into one map per section.
-    Per-tile (elastic) maps are out of scope.  ValueError for offsets or decided of another shape, an unknown model, a
+    What the maps leave over tile by tile (`residual`) is what fit_section_fields turns into a smooth displacement
+    field per pair.  ValueError for offsets or decided of another shape, an unknown model, a
     max_residual that is not a positive number."""
     th, tw = _clahe_tile(tile)
     gy, gx = clahe_grid(vol_shape, (th, tw))
@@ -2305,16 +2311,26 @@ def warp_chunks(out_box, vol_shape, M, chunk_bytes=None, rank=0, world_size=1):
     if z1 <= z0 or ny <= 0 or nx <= 0:
         return []
 
-    def fits(nz, rows, ry):             # an output slab of nz sections of `rows` rows and its read slab of ry rows
-        return nz * rows * nx <= budget and nz * ry * X <= budget
+    rows = lambda za, zb, ya, yb: _warp_rows(M, za, zb, ya, yb, x0, x1, Y)
+    return _row_cut_slabs(rows, out_box, X, budget)[rank::world_size]
+
+
+def _row_cut_slabs(rows, out_box, X, budget):
+    """warp_chunks' cut of a non-empty `out_box`: (output slab, read slab) in (z, y) order, where rows(z0, z1, y0, y1)
+    gives the rows [lo, hi) that the outputs [y0, y1) of the sections [z0, z1) read, over a volume of X columns."""
+    (z0, z1), (y0, y1), (x0, x1) = out_box
+    ny, nx = y1 - y0, x1 - x0
+
+    def fits(nz, nrows, ry):            # an output slab of nz sections of `nrows` rows and its read slab of ry rows
+        return nz * nrows * nx <= budget and nz * ry * X <= budget
 
     slabs, z = [], z0
     while z < z1:
-        lo, hi = _warp_rows(M, z, z + 1, y0, y1, x0, x1, Y)
+        lo, hi = rows(z, z + 1, y0, y1)
         if fits(1, ny, hi - lo):
             k = 1
             while z + k < z1:
-                more = _warp_rows(M, z, z + k + 1, y0, y1, x0, x1, Y)
+                more = rows(z, z + k + 1, y0, y1)
                 if not fits(k + 1, ny, more[1] - more[0]):
                     break
                 k, (lo, hi) = k + 1, more
@@ -2323,17 +2339,17 @@ def warp_chunks(out_box, vol_shape, M, chunk_bytes=None, rank=0, world_size=1):
             continue
         y = y0
         while y < y1:
-            rows = _warp_rows(M, z, z + 1, y, y + 1, x0, x1, Y)
+            rd = rows(z, z + 1, y, y + 1)
             k = 1
             while y + k < y1:
-                more = _warp_rows(M, z, z + 1, y, y + k + 1, x0, x1, Y)
+                more = rows(z, z + 1, y, y + k + 1)
                 if not fits(1, k + 1, more[1] - more[0]):
                     break
-                k, rows = k + 1, more
-            slabs.append((((z, z + 1), (y, y + k), (x0, x1)), ((z, z + 1), rows, (0, X))))
+                k, rd = k + 1, more
+            slabs.append((((z, z + 1), (y, y + k), (x0, x1)), ((z, z + 1), rd, (0, X))))
             y += k
         z += 1
-    return slabs[rank::world_size]
+    return slabs
 
 
 def volume_warp(volume, maps, out=None, start=None, size=None, fill=0, nearest=False, chunk_bytes=None, rank=0,
@@ -2361,8 +2377,9 @@ def volume_warp(volume, maps, out=None, start=None, size=None, fill=0, nearest=F
     Ranks (rank / world_size) take slabs round-robin and write disjoint boxes of a shared `out`.  `stats` receives
     `read_s`, `write_s` and `chunks`.
 
-    Out of scope: per-tile (elastic) warps, resampling along z, a warp= keyword on predict_cube / predict_volume (warp,
-    then predict), and majority resampling of labels (nearest is what masks get).
+    Elastic warps -- the map plus a smooth displacement field -- are volume_warp_field's.  Out of scope: resampling
+    along z, a warp= keyword on predict_cube / predict_volume (warp, then predict), and majority resampling of labels
+    (nearest is what masks get).
 
     ValueError, before any GPU work: a volume that is not uint8 or not [z, y, x] (or one image), maps of a wrong shape
     or dtype or outside the limits, an ROI outside the volume, an `out` of another shape or dtype, a fill outside
@@ -2407,6 +2424,363 @@ def volume_warp(volume, maps, out=None, start=None, size=None, fill=0, nearest=F
                                                   oslabs[k][1][0], oslabs[k][2][0], M.ctypes.data + 48 * z0,
                                                   table.data_ptr() + 48 * z0, fill, int(bool(nearest)),
                                                   p.compute.cuda_stream), "tem_u8_warp_affine")
+                p.release_on = p.compute.record_event()                  # behind the kernel: the input is free too
+                outp.put(k, p.release_on)
+    if stats is not None:
+        stats.update(p.st)
+    return out
+
+
+FIELD_MAX = 1 << 21              # tem_u8_warp_field: |U| <= 2^21 (32 px); adjacent nodes differ by at most S 2^13
+
+
+def _field_spacing(spacing):
+    """(ky, kx) of `spacing`, an int or (Sy, Sx): powers of two in 16...1024."""
+    try:
+        sy, sx = (spacing, spacing) if not hasattr(spacing, "__len__") else spacing
+        sy, sx = _index(sy, "spacing"), _index(sx, "spacing")
+    except (TypeError, ValueError):
+        raise ValueError(f"spacing must be an int or (Sy, Sx), got {spacing!r}")
+    for v in (sy, sx):
+        if not 16 <= v <= 1024 or v & (v - 1):
+            raise ValueError(f"spacing must be a power of two in 16...1024 per axis, got {(sy, sx)}")
+    return sy.bit_length() - 1, sx.bit_length() - 1
+
+
+def field_grid(vol_shape, spacing):
+    """(ny, nx) = (((Y - 1) >> ky) + 2, ((X - 1) >> kx) + 2): the nodes of the displacement lattice with the spacings
+    (Sy, Sx) = (2^ky, 2^kx) -- `spacing`, an int or (Sy, Sx), powers of two in 16...1024 -- over a section of a volume of
+    shape [Z, Y, X] or an image [Y, X].  Node (i, j) sits at pixel (i Sy, j Sx); every pixel of the section lies in a cell
+    with four nodes.  Pure host function."""
+    ky, kx = _field_spacing(spacing)
+    shape = tuple(int(v) for v in vol_shape)
+    if len(shape) not in (2, 3) or min(shape) < 1:
+        raise ValueError(f"volume must be a non-empty [z, y, x] or one image [y, x], got shape {shape}")
+    return ((shape[-2] - 1) >> ky) + 2, ((shape[-1] - 1) >> kx) + 2
+
+
+def _field_interp(F, ky, kx, p):
+    """The lattice function F [ny, nx, c] interpolated bilinearly at the points p [..., 2] = (y, x) in pixels, clamped to
+    the lattice."""
+    ny, nx = F.shape[:2]
+    gy, gx = np.clip(p[..., 0] / (1 << ky), 0, ny - 1), np.clip(p[..., 1] / (1 << kx), 0, nx - 1)
+    i, j = np.minimum(np.floor(gy).astype(np.int64), ny - 2), np.minimum(np.floor(gx).astype(np.int64), nx - 2)
+    ty, tx = (gy - i)[..., None], (gx - j)[..., None]
+    return (1 - ty) * ((1 - tx) * F[i, j] + tx * F[i, j + 1]) + ty * ((1 - tx) * F[i + 1, j] + tx * F[i + 1, j + 1])
+
+
+def _field_nodes(ny, nx, ky, kx):
+    """float64 [ny, nx, 2]: the nodes' pixels (y, x)."""
+    return np.stack(np.meshgrid(np.arange(ny, dtype=np.float64) * (1 << ky), np.arange(nx, dtype=np.float64) * (1 << kx),
+                                indexing="ij"), axis=-1)
+
+
+class FieldFits(NamedTuple):
+    """fit_section_fields' verdict: `fields` float64[Z - 1, ny, nx, 2] the displacement (u_y, u_x) in pixels of every
+    pair at the lattice's nodes, on top of the pair's map; `used` bool[Z - 1, gy, gx] the tiles it rests on; `residual`
+    float64[Z - 1] the largest max-norm misfit of a used tile against the field at its point, in pixels."""
+    fields: np.ndarray
+    used: np.ndarray
+    residual: np.ndarray
+
+
+_BINOMIAL = np.array([[1.0, 2.0, 1.0], [2.0, 4.0, 2.0], [1.0, 2.0, 1.0]])
+
+
+def fit_section_fields(sub, fits, tile, vol_shape, spacing, smooth=1, max_residual=1.0):
+    """One smooth displacement field per pair of sections from what fit_section_maps' maps leave over: `sub` are
+    shift_subpixel's tile offsets (or any (offsets, decided, ...) tuple), `fits` fit_section_maps' verdict on them (or
+    any (maps, kept, residual, unresolved) tuple), `tile` and `vol_shape` those of the fit, `spacing` the lattice's
+    (field_grid).  Host only.  With T_z = fits.maps[z], the pair function becomes F_z(p) = T_z p + r_z(p), r_z the field
+    interpolated bilinearly on the lattice.
+
+    Per pair: the residual of a decided tile is e = point + offset - T_z(point) at fit_section_maps' tile points.  A
+    tile is dropped when e lies further, in max norm, than `max_residual` pixels from the per-axis lower median of the
+    decided tiles of its 3 x 3 neighbourhood (itself included); the rest are `used`.  `smooth` passes (an int >= 0) of a
+    3 x 3 binomial average, normalised over the tiles that have a value, smooth the used tiles and fill tiles without a
+    value from neighbours that have one; a tile that still has none gets 0.  The node values are the separable linear
+    interpolation of the tile values between the tile points (np.interp along y, then along x); outside the outermost
+    points the value is held.  A pair in fits.unresolved, or without a decided tile, gets a zero field.  Deterministic:
+    the same input gives the same bytes.  section_fields composes the pairs; finer fields than 16 px are out of scope.
+    ValueError for offsets, decided or maps of another shape, a bad spacing, a smooth that is not an integer >= 0, a
+    max_residual that is not a positive number."""
+    th, tw = _clahe_tile(tile)
+    gy, gx = clahe_grid(vol_shape, (th, tw))
+    ky, kx = _field_spacing(spacing)
+    ny, nx = field_grid(vol_shape, spacing)
+    _, (_, Y), (_, X) = hist_box(vol_shape)
+    offsets, decided = np.asarray(sub[0]), np.asarray(sub[1])
+    if offsets.ndim != 4 or offsets.shape[1:] != (gy, gx, 2) or offsets.dtype.kind not in "fiu":
+        raise ValueError(f"offsets must be numbers of shape [Z - 1, {gy}, {gx}, 2], got {offsets.dtype} {offsets.shape}")
+    if decided.shape != offsets.shape[:3] or decided.dtype != np.bool_:
+        raise ValueError(f"decided must be bool of shape {offsets.shape[:3]}, got {decided.dtype} {decided.shape}")
+    P = offsets.shape[0]
+    maps = np.asarray(fits[0])
+    if maps.shape != (P, 2, 3) or maps.dtype.kind != "f" or not np.isfinite(maps).all():
+        raise ValueError(f"fits.maps must be finite floats of shape {(P, 2, 3)}, got {maps.dtype} {maps.shape}")
+    unresolved = set(int(z) for z in fits[3])
+    smooth = _index(smooth, "smooth")
+    if smooth < 0:
+        raise ValueError(f"smooth must be an integer >= 0, got {smooth}")
+    if isinstance(max_residual, (bool, np.bool_)) or not isinstance(max_residual, (int, float, np.integer, np.floating)) \
+            or not (max_residual > 0 and np.isfinite(max_residual)):
+        raise ValueError(f"max_residual must be a positive number, got {max_residual!r}")
+    offsets, maps = offsets.astype(np.float64), maps.astype(np.float64)
+    centre = lambda t, g, n: np.array([(k * t + min((k + 1) * t, n) - 1) / 2 for k in range(g)])
+    py, px = centre(th, gy, Y), centre(tw, gx, X)
+    points = np.stack(np.meshgrid(py, px, indexing="ij"), axis=-1)                                    # [gy, gx, 2]
+    node_y, node_x = np.arange(ny, dtype=np.float64) * (1 << ky), np.arange(nx, dtype=np.float64) * (1 << kx)
+    fields, used, residual = np.zeros((P, ny, nx, 2), np.float64), np.zeros((P, gy, gx), bool), np.zeros(P, np.float64)
+    for z in range(P):
+        if z in unresolved or not decided[z].any():
+            continue
+        e = points + offsets[z] - (points @ maps[z][:, :2].T + maps[z][:, 2])
+        for i, j in zip(*np.nonzero(decided[z])):
+            hood = (slice(max(i - 1, 0), i + 2), slice(max(j - 1, 0), j + 2))
+            near = np.sort(e[hood][decided[z][hood]], axis=0)
+            used[z, i, j] = np.abs(e[i, j] - near[(near.shape[0] - 1) // 2]).max() <= max_residual
+        val, have = np.where(used[z][..., None], e, 0.0), used[z].copy()
+        for _ in range(smooth):
+            num, den = np.zeros((gy, gx, 2)), np.zeros((gy, gx))
+            v, h = np.pad(val, ((1, 1), (1, 1), (0, 0))), np.pad(have.astype(np.float64), 1)
+            for a in range(3):
+                for b in range(3):
+                    num += _BINOMIAL[a, b] * v[a:a + gy, b:b + gx]
+                    den += _BINOMIAL[a, b] * h[a:a + gy, b:b + gx]
+            have = den > 0
+            val = np.where(have[..., None], num / np.where(have, den, 1.0)[..., None], 0.0)
+        along_y = np.stack([[np.interp(node_y, py, val[:, j, c]) for c in range(2)] for j in range(gx)])   # [gx, 2, ny]
+        fields[z] = np.stack([[np.interp(node_x, px, along_y[:, c, i]) for c in range(2)] for i in range(ny)]) \
+            .transpose(0, 2, 1)                                                                       # [ny, nx, 2]
+        if used[z].any():
+            residual[z] = np.abs(e - _field_interp(fields[z], ky, kx, points)).max(axis=-1)[used[z]].max()
+    return FieldFits(fields, used, residual)
+
+
+def section_fields(pair_maps, pair_fields, spacing, vol_shape, window=None):
+    """(maps float64[Z, 2, 3], fields float64[Z, ny, nx, 2]): one map and one displacement field per section from
+    fit_section_maps' pair maps [Z - 1, 2, 3] and fit_section_fields' pair fields [Z - 1, ny, nx, 2] on the lattice of
+    `spacing` over `vol_shape` -- what volume_warp_field takes: out[z](p) = volume[z](maps[z] p + fields[z](p)) shows
+    what section 0 shows at p.  Host only.
+
+    With the pair function F_z(q) = T_z q + r_z(q), r_z the pair field interpolated bilinearly at q and clamped to the
+    lattice, the composition G_0 = id, G_{z + 1}(p) = F_z(G_z(p)) is followed at every node p.  `maps` is
+    section_maps(pair_maps, window), unchanged, and with B the composition of the maps without a window the field is
+    what the maps do not explain, D_z = G_z - B_z, computed as D_{z + 1}(p) = L_z D_z(p) + r_z(B_z p + D_z(p)) (L_z the
+    matrix of T_z), so that zero pair fields give zero fields exactly.  For window=None fields[z] = D_z.  With a window,
+    maps[z] = B_z o trend_z^-1, and the field is D_z interpolated at the node carried through the inverse trend,
+    p' = (B_z^-1 o maps[z])(p); then the element-wise running lower median of the field over the same sections is taken
+    out.  That treats the field's own trend to first order: the median field is subtracted, not inverted and composed
+    as the maps' trend is.  ValueError as section_maps, for fields of another shape or dtype or not finite, a bad
+    spacing."""
+    maps = section_maps(pair_maps, window)
+    ky, kx = _field_spacing(spacing)
+    ny, nx = field_grid(vol_shape, spacing)
+    Z = maps.shape[0]
+    R = np.asarray(pair_fields)
+    if R.shape != (Z - 1, ny, nx, 2) or R.dtype.kind != "f" or not np.isfinite(R).all():
+        raise ValueError(f"pair_fields must be finite floats of shape {(Z - 1, ny, nx, 2)}, got {R.dtype} {R.shape}")
+    R = R.astype(np.float64)
+    T = np.asarray(pair_maps, np.float64)
+    B = maps if window is None else section_maps(pair_maps)
+    nodes = _field_nodes(ny, nx, ky, kx)
+    D = np.zeros((Z, ny, nx, 2), np.float64)
+    for z in range(Z - 1):
+        at = nodes @ B[z][:, :2].T + B[z][:, 2] + D[z]
+        D[z + 1] = D[z] @ T[z][:, :2].T + _field_interp(R[z], ky, kx, at)
+    if window is None:
+        return maps, D
+    out = np.empty_like(D)
+    for z in range(Z):
+        L, b = B[z][:, :2], B[z][:, 2]
+        q = nodes @ maps[z][:, :2].T + maps[z][:, 2] - b
+        out[z] = _field_interp(D[z], ky, kx, q @ np.linalg.inv(L).T)
+    h, trend = window // 2, np.empty_like(out)
+    for z in range(Z):
+        run = np.sort(out[max(z - h, 0):min(z + h + 1, Z)], axis=0)
+        trend[z] = run[(run.shape[0] - 1) // 2]
+    return maps, out - trend
+
+
+def _check_qfield(U, ky, kx, what):
+    """int32 [Z, ny, nx, 2] `U` inside tem_u8_warp_field's limits, or ValueError naming the section, node and limit."""
+    V = U.astype(np.int64)
+    bad = np.argwhere(np.abs(V) > FIELD_MAX)
+    if bad.size:
+        z, i, j, c = (int(v) for v in bad[0])
+        raise ValueError(f"{what}: section {z}, node ({i}, {j}): the displacement {V[z, i, j, c] / WARP_UNIT:g} px is "
+                         f"outside the limit of {FIELD_MAX // WARP_UNIT} px")
+    for axis, k, name in ((1, ky, "y"), (2, kx, "x")):
+        bad = np.argwhere(np.abs(np.diff(V, axis=axis)) > WARP_MAX_DEV << k)
+        if bad.size:
+            z, i, j, c = (int(v) for v in bad[0])
+            raise ValueError(f"{what}: section {z}, node ({i}, {j}): the displacement changes by "
+                             f"{np.diff(V, axis=axis)[z, i, j, c] / WARP_UNIT:g} px to the next node along {name}, above "
+                             f"the limit of 1/8 of the spacing, {(1 << k) / 8:g} px")
+    return U
+
+
+def quantize_field(fields, spacing):
+    """np.int32[Z, ny, nx, 2] = (u_y, u_x) in units of 2^-16 px, rounded with rint, of float fields [Z, ny, nx, 2] in
+    pixels (section_fields'): what tem_u8_warp_field and volume_warp_field compute with.  ValueError for another shape
+    or dtype, values that are not finite, a bad spacing, a displacement above 32 px (|U| > 2^21), and two adjacent nodes
+    that differ by more than one eighth of the spacing (S 2^13) -- the gradient limit, the size of the matrix limit of
+    quantize_maps, which is what bounds the kernel's staging hull; the message names the section, the node and the
+    limit."""
+    ky, kx = _field_spacing(spacing)
+    f = np.asarray(fields)
+    if f.ndim != 4 or f.shape[3] != 2 or f.shape[1] < 2 or f.shape[2] < 2 or f.dtype.kind != "f":
+        raise ValueError(f"fields must be floats of shape [Z, ny, nx, 2], got {f.dtype} {f.shape}")
+    if not np.isfinite(f).all():
+        raise ValueError("fields must be finite")
+    f = np.rint(np.clip(f.astype(np.float64), -1024.0, 1024.0) * WARP_UNIT)         # far outside the limit either way
+    return _check_qfield(f.astype(np.int64), ky, kx, "fields").astype(np.int32)
+
+
+def _field_table(fields, shape, ky, kx, one):
+    """volume_warp_field's `fields` as the int32 table of `shape` [Z, ny, nx, 2]: float is quantised, int32 is checked;
+    one image also takes one field [ny, nx, 2]."""
+    f = np.asarray(fields)
+    if one and f.ndim == 3:
+        f = f[None]
+    if f.dtype.kind == "f" and f.shape == shape:
+        return np.ascontiguousarray(quantize_field(f, (1 << ky, 1 << kx)))
+    if f.dtype == np.int32 and f.shape == shape:
+        return _check_qfield(np.array(f), ky, kx, "fields")                          # a writable, dense copy
+    raise ValueError(f"fields must be floats or int32 of shape {shape}, got {f.dtype} {f.shape}")
+
+
+def _field_rows(M, U, ky, kx, x0, x1, Y):
+    """_warp_rows with the field, as a function rows(z0, z1, y0, y1): per section the affine extremes over the box's
+    corners plus the least and largest u_y over the nodes of the cells the box meets, [min iy, max iy + 2), unioned over
+    the sections and clipped.  Runs of sections over the same rows (how a slab grows) share one pass over all sections."""
+    memo = {}
+
+    def per_section(z0, z1, y0, y1):
+        u = U[z0:z1, y0 >> ky:((y1 - 1) >> ky) + 2, x0 >> kx:((x1 - 1) >> kx) + 2, 0].reshape(z1 - z0, -1).astype(np.int64)
+        a, b, c = M[z0:z1, 0], M[z0:z1, 1], M[z0:z1, 2]
+        s, ey, ex = a * y0 + b * x0 + c, a * (y1 - 1 - y0), b * (x1 - 1 - x0)
+        return ((s + np.minimum(ey, 0) + np.minimum(ex, 0) + u.min(axis=1) + 128) >> 16,
+                (s + np.maximum(ey, 0) + np.maximum(ex, 0) + u.max(axis=1) + 128) >> 16)
+
+    def rows(z0, z1, y0, y1):
+        if z1 - z0 == 1:
+            lo, hi = per_section(z0, z1, y0, y1)
+        else:
+            if (y0, y1) not in memo:
+                memo.clear()
+                memo[y0, y1] = per_section(0, M.shape[0], y0, y1)
+            lo, hi = (v[z0:z1] for v in memo[y0, y1])
+        lo = min(max(int(lo.min()), 0), Y - 1)
+        return lo, max(min(int(hi.max()) + 2, Y), lo + 1)
+    return rows
+
+
+def field_chunks(out_box, vol_shape, M, U, spacing, chunk_bytes=None, rank=0, world_size=1):
+    """warp_chunks for volume_warp_field: the same cut of the (z, y, x) (lo, hi) box `out_box` into (output slab, read
+    slab) under the maps `M`, quantize_maps' int64[Z, 6], and the fields `U`, quantize_field's int32[Z, ny, nx, 2] on the
+    lattice of `spacing` -- the same budget, order, round-robin and refusals.  A read slab's rows bound every tap by
+    tem_u8_warp_field's rule: per section the extremes of the affine sy over the output slab's corners plus the least
+    and the largest u_y over the nodes of the cells the slab meets, [min iy, max iy + 2), unioned over the slab's
+    sections and clipped to the section (one row at the least).  With U = 0 it is warp_chunks.  Pure host function;
+    ValueError as warp_chunks, and for a bad spacing or fields of another shape or dtype or outside the limits."""
+    budget = HIST_CHUNK_BYTES if chunk_bytes is None else int(chunk_bytes)
+    if budget < 1:
+        raise ValueError(f"chunk_bytes must be positive, got {chunk_bytes}")
+    if not 0 <= rank < world_size:
+        raise ValueError(f"rank {rank} is outside [0, {world_size})")
+    vol_shape = tuple(int(v) for v in vol_shape)
+    if len(vol_shape) != 3 or min(vol_shape) < 1:
+        raise ValueError(f"field_chunks takes a non-empty volume shape [z, y, x], got {vol_shape}")
+    Z, Y, X = vol_shape
+    ky, kx = _field_spacing(spacing)
+    M, U = np.asarray(M), np.asarray(U)
+    if M.dtype != np.int64 or M.shape != (Z, 6):
+        raise ValueError(f"M must be int64 of shape {(Z, 6)}, got {M.dtype} {M.shape}")
+    _check_qmaps(M, "M")
+    if U.dtype != np.int32 or U.shape != (Z,) + field_grid(vol_shape, spacing) + (2,):
+        raise ValueError(f"U must be int32 of shape {(Z,) + field_grid(vol_shape, spacing) + (2,)}, got {U.dtype} {U.shape}")
+    _check_qfield(U, ky, kx, "U")
+    (z0, z1), (y0, y1), (x0, x1) = out_box
+    if any(lo < 0 or hi > n for (lo, hi), n in zip(out_box, vol_shape)):
+        raise ValueError(f"the box {tuple(out_box)} reaches outside the volume of shape {vol_shape}")
+    if z1 <= z0 or y1 <= y0 or x1 <= x0:
+        return []
+    return _row_cut_slabs(_field_rows(M, U, ky, kx, x0, x1, Y), out_box, X, budget)[rank::world_size]
+
+
+def volume_warp_field(volume, maps, fields, spacing, out=None, start=None, size=None, fill=0, nearest=False,
+                      chunk_bytes=None, rank=0, world_size=1, device=None, stats=None):
+    """volume_warp with a smooth displacement field on top of every section's map, on the device: out[z](p) =
+    volume[z](B_z p + u_z(p)), B = `maps` as volume_warp takes them (float [Z, 2, 3] or quantize_maps' int64 [Z, 6]) and
+    u_z = `fields`[z] interpolated bilinearly on the lattice of `spacing` (field_grid): float [Z, ny, nx, 2] in pixels
+    (section_fields'; quantised inside with quantize_field) or quantize_field's int32 [Z, ny, nx, 2].  One image [y, x]
+    takes one map and one field [ny, nx, 2].  This is the elastic link of the chain: section_shift_sums ->
+    shift_subpixel -> fit_section_maps -> fit_section_fields -> section_fields -> volume_warp_field; with zero fields
+    it reproduces volume_warp byte for byte.
+
+    The field at a voxel is the bilinear blend of its cell's four nodes in integers, floored to 2^-16 px, added to the
+    affine position; from there on everything is volume_warp's: rounded half up to 1/256 px, `fill` outside and never
+    blended, one rounding of the blend, `nearest` for masks -- a defect mask moves through the same field
+    (tem_u8_warp_field; include/tem_hip.h has the definition, numpy reproduces it bit for bit).  A displacement is at
+    most 32 px and changes by at most one eighth of the spacing from node to node.  A voxel depends on its section, its
+    map and its field alone, not on the slab, ROI or rank it was computed in.
+
+    `out`, `start` / `size`, `fill`, `chunk_bytes`, `rank` / `world_size`, `device` and `stats` (`read_s`, `write_s`,
+    `chunks`) are volume_warp's, and so is the pass: the ROI is cut into output slabs and the read slabs that hold
+    their taps (field_chunks); host thread -> pinned -> H2D -> one tem_u8_warp_field launch per slab -> D2H -> host
+    write, on double buffers, in the order write(k), read(k + 2) on the one host thread; both tables are uploaded once.
+
+    Out of scope: resampling along z, a warp= keyword on predict_cube / predict_volume (warp, then predict), majority
+    resampling of labels (nearest is what masks get), and fields finer than 16 px.
+
+    ValueError, before any GPU work: everything volume_warp refuses, a bad spacing, fields of a wrong shape or dtype
+    or outside the limits."""
+    _check_u8(volume)
+    vshape = tuple(int(v) for v in volume.shape)
+    if len(vshape) not in (2, 3) or min(vshape) < 1:
+        raise ValueError(f"volume_warp_field needs a non-empty volume [z, y, x] or one image [y, x], got shape {vshape}")
+    one = len(vshape) == 2
+    vol3 = (1,) + vshape if one else vshape
+    ky, kx = _field_spacing(spacing)
+    ny, nx = field_grid(vshape, spacing)
+    M = _warp_table(maps, vol3[0], one)
+    U = _field_table(fields, (vol3[0], ny, nx, 2), ky, kx, one)
+    fill = _index(fill, "fill")
+    if not 0 <= fill <= 255:
+        raise ValueError(f"fill must lie in 0...255, got {fill}")
+    box = hist_box(vshape, start, size)
+    shape = tuple(hi - lo for lo, hi in box)
+    want = shape[1:] if one else shape
+    if out is None:
+        out = np.zeros(want, np.uint8)
+    elif tuple(out.shape) != want or getattr(out, "dtype", None) != np.uint8:
+        raise ValueError(f"out must be uint8 of the ROI's shape {want}, got {getattr(out, 'dtype', None)} "
+                         f"{tuple(out.shape)}")
+    chunks = field_chunks(box, vol3, M, U, (1 << ky, 1 << kx), chunk_bytes, rank, world_size)
+    p = _SlabPass([volume], [hist_box(vshape)], chunk_bytes, rank, world_size, device, slabs=[r for _, r in chunks])
+    lib = H.require_gpu()
+    oslabs = [o for o, _ in chunks]
+    odims = [tuple(hi - lo for lo, hi in o) for o in oslabs]
+    dst_vol = _OneSection(out) if one else out
+    (oz, _), (oy, _), (ox, _) = box
+    p.st["write_s"] = 0.0
+    per = ny * nx * 8                                                       # bytes of one section's field
+
+    def write_from(k, flat):            # host thread: the slab's box of `out`
+        (z0, z1), (y0, y1), (x0, x1) = oslabs[k]
+        dst_vol[z0 - oz:z1 - oz, y0 - oy:y1 - oy, x0 - ox:x1 - ox] = flat.reshape(odims[k])
+
+    with p.streaming():
+        table, ftable = torch.from_numpy(M).to(p.dev), torch.from_numpy(U).to(p.dev)   # both tables, once
+        with _OutputStream([int(np.prod(d)) for d in odims], write_from, p.dev, p.pool, p.st,
+                           own_buffers=True) as outp:                    # the reader's thread: write(k), read(k + 2)
+            for k, ((z0, _), (y0, _), _), d, (src,) in p:
+                _lib.check(lib.tem_u8_warp_field(src.data_ptr(), *d, y0, vol3[1], outp.device(k).data_ptr(), *odims[k],
+                                                 oslabs[k][1][0], oslabs[k][2][0], M.ctypes.data + 48 * z0,
+                                                 table.data_ptr() + 48 * z0, U.ctypes.data + per * z0,
+                                                 ftable.data_ptr() + per * z0, ny, nx, ky, kx, fill, int(bool(nearest)),
+                                                 p.compute.cuda_stream), "tem_u8_warp_field")
                 p.release_on = p.compute.record_event()                  # behind the kernel: the input is free too
                 outp.put(k, p.release_on)
     if stats is not None:
