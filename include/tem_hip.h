@@ -607,6 +607,30 @@ int tem_u8_zshift_tiles(const uint8_t *src, int32_t D, int32_t H, int32_t W, int
                         int32_t r1, int32_t y_org, int32_t Y, int32_t th, int32_t tw, int32_t gy, int32_t gx,
                         int32_t radius, uint64_t *sums, tem_stream_t stream);
 
+/* tem_u8_zshift_tiles with the search window of every section and tile CENTRED on an offset of its own instead of on
+ * zero (utils.section_shift_sums_at, the device leg of utils.section_shifts_coarse_to_fine: a coarse level's answer,
+ * doubled, is the centre of the next finer level's search, so displacements far past the radius are measured).
+ * Everything is as above, plus a device table `centers` of int32 (4-byte aligned) laid out [plane][gy][gx][2] =
+ * (cy, cx); like sums the pointer addresses the rows of core plane c0.  For a section z, a tile (i, j) with centre
+ * (cy, cx) and a local offset (dy, dx) in [-r, r]^2, the sums run over the tile's voxels (y, x) whose partner
+ * (y + cy + dy, x + cx + dx) lies inside the section, with v = V[z][y][x] and w = V[z + 1][y + cy + dy][x + cx + dx]:
+ *   sums[((((d - c0) * gy + i) * gx + j) * R + dy + r) * R + dx + r) * 5 + 0..4] += (sum v, sum v v, sum w, sum w w, sum v w)
+ * The layout, the 64-bit atomic adds, integer exactness and the overflow bounds are unchanged (a part still holds at
+ * most 4096 voxels); the number of terms is utils.shift_counts_at.  A tile whose whole window lies outside the section
+ * gets nothing added, and nothing is loaded for it.  Zero centres give tem_u8_zshift_tiles' sums, bit for bit.
+ * The host promises bounds on the table: cy_lo <= cy <= cy_hi and |cx| <= cx_max, with
+ * -1024 <= cy_lo <= 0 <= cy_hi <= 1024 and 0 <= cx_max <= 1024 (utils.SHIFT_MAX_CENTER).  The block must hold every
+ * partner row of the core that the volume has: [0, H) contains [r0 - radius + cy_lo, r1 + radius + cy_hi) cut to
+ * [-y_org, Y - y_org).  The kernel clamps every centre it reads to the promised bounds, and reads no byte outside the
+ * block's rows [0, H) and columns [0, W) whatever the table holds: a table that disagrees with the promise gives
+ * other sums (those of the clamped centres), never a read outside the block.
+ * TEM_EINVAL as tem_u8_zshift_tiles, and: a null centers or one off 4-byte alignment, bounds outside the ranges
+ * above, a block without a partner row of the core, within the bounds, that the volume has.  TEM_EUNSUPPORTED as above. */
+int tem_u8_zshift_tiles_at(const uint8_t *src, int32_t D, int32_t H, int32_t W, int32_t c0, int32_t c1, int32_t r0,
+                           int32_t r1, int32_t y_org, int32_t Y, int32_t th, int32_t tw, int32_t gy, int32_t gx,
+                           int32_t radius, const int32_t *centers, int32_t cy_lo, int32_t cy_hi, int32_t cx_max,
+                           uint64_t *sums, tem_stream_t stream);
+
 /* Every section of a uint8 volume V[Z][Y][X] resampled through its own affine map (utils.volume_warp: sections aligned
  * by the maps that utils.fit_section_maps fits to the tile offsets of tem_u8_zshift_tiles).  The definition, once: a
  * section's map is six int64 in units of 2^-16, (a_yy, a_yx, b_y, a_xy, a_xx, b_x).  For the output voxel (y, x) of the

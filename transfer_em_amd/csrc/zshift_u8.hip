@@ -3,6 +3,9 @@
 //   tem_u8_zshift_tiles   sums[d - c0][i][j][dy + r][dx + r][0..4] += sum v, sum v v, sum w, sum w w, sum v w over the
 //                         core voxels v = (d, y, x) of tile (i, j) whose partner w = (d + 1, y + dy, x + dx) lies in the
 //                         section (no sums at all for the block's last plane)
+//   tem_u8_zshift_tiles_at  the same with the offsets of every plane and tile centred on (cy, cx) of a device table:
+//                         the partner is w = (d + 1, y + cy + dy, x + cx + dx) (utils.section_shift_sums_at, the
+//                         device leg of section_shifts_coarse_to_fine); see u8_zshift_tiles_at_k
 // The tile grid is tem_u8_hist_tiles': anchored at (0, 0) of the caller's VOLUME; the block holds whole rows, its row 0
 // at volume row y_org.  Everything is integers and the adds are atomic, so the sums do not depend on how the volume
 // was cut into blocks or the block into workgroups.
@@ -43,6 +46,7 @@ constexpr int ZS_THREADS = 256;
 constexpr int ZS_WAVES = ZS_THREADS / 64;
 constexpr int ZS_MAX_TILE = 2048;
 constexpr int ZS_MAX_R = 8;
+constexpr int ZS_MAX_CENTER = 1024;              // tem_u8_zshift_tiles_at: |cy|, |cx| of a window's centre, at most
 constexpr int ZS_MAX_COLS = 128;                 // columns of a part, at most
 constexpr int ZS_MAX_ROWS = 64;                  // rows of a part, at most
 constexpr int ZS_MAX_WORDS = 1024;               // words of a part, at most: rows x ceil(columns / 4)
@@ -216,6 +220,150 @@ __global__ __launch_bounds__(ZS_THREADS) void u8_zshift_tiles_k(const uint8_t *s
   }
 }
 
+// u8_zshift_tiles_k with the search window of every plane and tile CENTRED on (cy, cx) of `centers`
+// ([plane][gy][gx][2], the rows of core plane c0): the offset of lane o is (cy + dy, cx + dx).  Blocks, parts, LDS
+// images and the walk are the sibling's; what differs:
+//   - the workgroup reads its tile's centre once, uniformly, and clamps it to the host's promise: cy to
+//     [cy_lo, cy_hi], cx to [-cx_max, cx_max] (all within 1024, so every sum of offsets below stays far inside 32 bits);
+//   - the window of plane d + 1 is staged from (ya - r + cy, xa - r + cx): zs_stage zeroes what lies outside the
+//     section's rows in the block and outside [0, W), and loads no word without a byte of the block, wherever the
+//     origin lies;
+//   - a part whose whole window lies outside the section has no voxel with a partner at any offset: the workgroup
+//     leaves before it stages, loads or adds anything;
+//   - `inner` and the edge sums of sum v, sum v v use the total offset.  The missing columns [e0, e1) of a row are
+//     still one run at the row's left end (dx_total < 0) or right end (dx_total > 0), but the run is now up to the
+//     WHOLE width of the part -- |dx_total| reaches 1032, a part has 128 columns at most --, so its words k0 ... k1
+//     run over up to all pw words of the row, not over the one to three that r <= 8 columns took.
+__global__ __launch_bounds__(ZS_THREADS) void u8_zshift_tiles_at_k(const uint8_t *src, int64_t H, int64_t W, int32_t c0,
+                                                                   int64_t r0, int64_t r1, int64_t y_org, int64_t Y,
+                                                                   int64_t th, int64_t tw, int64_t gy, int64_t gx,
+                                                                   int64_t ti0, uint32_t nty, uint32_t ntx,
+                                                                   uint32_t nrc, uint32_t ncc, int32_t prows, int32_t r,
+                                                                   const int32_t *centers, int32_t cy_lo, int32_t cy_hi,
+                                                                   int32_t cx_max, uint64_t *sums) {
+  __shared__ uint32_t vl[ZS_MAX_WORDS + ZS_MAX_ROWS];
+  __shared__ uint32_t wl[ZS_WIN_WORDS];
+  __shared__ uint32_t acc[ZS_MAX_OFFS * 5];
+  __shared__ uint32_t once[2];                                           // sum v, sum v v of an interior part
+  uint32_t b = blockIdx.x;
+  const uint32_t cc = b % ncc;
+  b /= ncc;
+  const uint32_t rc = b % nrc;
+  b /= nrc;
+  const uint32_t tj = b % ntx;
+  b /= ntx;
+  const uint32_t til = b % nty, plane = b / nty;
+  const int64_t ti = ti0 + til;
+  const int64_t ya = max(ti * th - y_org, r0) + (int64_t)rc * prows;
+  const int64_t yb = min(min((ti + 1) * th - y_org, r1), ya + prows);
+  const int64_t xa = (int64_t)tj * tw + (int64_t)cc * ZS_MAX_COLS;
+  const int64_t xb = min(min((int64_t)(tj + 1) * tw, W), xa + ZS_MAX_COLS);
+  if (ya >= yb || xa >= xb) return;                                      // the whole workgroup: the tail part of a cut tile
+  const int32_t *ctr = centers + (((int64_t)plane * gy + ti) * gx + tj) * 2;       // the same for the whole workgroup
+  const int cy = min(max(__builtin_amdgcn_readfirstlane(ctr[0]), cy_lo), cy_hi);
+  const int cx = min(max(__builtin_amdgcn_readfirstlane(ctr[1]), -cx_max), cx_max);
+  // the window's rows and columns in the volume: [wy0, wy1) x [wx0, wx1); nothing of it in the section: no partner
+  // exists at any offset, so there is nothing to add and nothing to load
+  const int64_t wy0 = y_org + ya - r + cy, wy1 = y_org + yb + r + cy, wx0 = xa - r + cx, wx1 = xb + r + cx;
+  if (wy0 >= Y || wy1 <= 0 || wx0 >= W || wx1 <= 0) return;             // the whole workgroup
+  const int rows = (int)(yb - ya), width = (int)(xb - xa);
+  const int R = 2 * r + 1, noffs = R * R;
+  const int pw = (width + 3) >> 2, pv = pw | 1;                          // words per row of v, and its odd row stride
+  const int nw = pw + (2 * r >> 2) + 1;                                  // words per row of the window that are read
+  int stride = nw;                                                       // 5, 13, 19 or 27 modulo 32
+  while ((stride & 31) != 5 && (stride & 31) != 13 && (stride & 31) != 19 && (stride & 31) != 27) ++stride;
+  const int64_t d = (int64_t)c0 + plane;
+  // a part whose every voxel has every partner: the whole window lies in the section
+  const bool inner = wy0 >= 0 && wy1 <= Y && wx0 >= 0 && wx1 <= W;
+
+  for (uint32_t i = threadIdx.x; i < (uint32_t)noffs * 5; i += ZS_THREADS) acc[i] = 0;
+  if (threadIdx.x < 2) once[threadIdx.x] = 0;
+  zs_stage(vl, rows, pw, pv, src, d, H, W, ya, xa, ya, yb, xa, xb);
+  zs_stage(wl, rows + 2 * r, nw, stride, src, d + 1, H, W, ya - r + cy, xa - r + cx, max((int64_t)0, -y_org),
+           min(H, Y - y_org), 0, W);
+  __syncthreads();
+
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int ra = rows * wave / ZS_WAVES, rb = rows * (wave + 1) / ZS_WAVES;      // this wave's rows of the part: <= 16
+  const uint32_t tail = zs_bytes(0, width - 4 * (pw - 1));               // the bytes of a row's last word that are voxels
+  if (ra < rb) {
+    // sum v and sum v v of row ra + lane, in lane `lane` (the odd row stride pv keeps the lanes on different banks)
+    uint32_t row1 = 0, row2 = 0;
+    if (lane < rb - ra) {
+      const uint32_t *vrow = vl + (ra + lane) * pv;
+      for (int k = 0; k < pw; ++k) {
+        const uint32_t v = vrow[k];
+        row1 = __builtin_amdgcn_udot4(v, 0x01010101u, row1, false);
+        row2 = __builtin_amdgcn_udot4(v, v, row2, false);
+      }
+    }
+    if (inner) {                                                         // every offset has every partner: once per wave
+      const uint32_t s1 = zs_wave_sum(row1), s2 = zs_wave_sum(row2);
+      if (lane == 0) atomicAdd(&once[0], s1), atomicAdd(&once[1], s2);
+    }
+    for (int o0 = 0; o0 < noffs; o0 += 64) {
+      const int o = min(o0 + lane, noffs - 1);
+      const int dyi = o / R, dxi = o - dyi * R;                          // dy + r, dx + r
+      uint32_t sv = 0, svv = 0, sw = 0, sww = 0, svw = 0;
+      if (!inner) {
+        // sum v, sum v v over the voxels with a partner: the rows whose partner row is in the section, of each the
+        // row's sums less those of the columns [e0, e1) of the part whose partner column is not: one run at the row's
+        // left end for dx < 0 or at its right end for dx > 0, of up to the whole width (k0 ... k1: up to pw words)
+        const int64_t dx = cx + dxi - r;
+        const int e0 = dx > 0 ? (int)max((int64_t)0, min((int64_t)width, W - dx - xa)) : 0;
+        const int e1 = dx > 0 ? width : (int)max((int64_t)0, min((int64_t)width, -dx - xa));
+        const int k0 = e0 >> 2, k1 = e0 < e1 ? (e1 + 3) >> 2 : k0;
+        for (int y = ra; y < rb; ++y) {
+          const uint32_t a1 = (uint32_t)__shfl((int)row1, y - ra, 64), a2 = (uint32_t)__shfl((int)row2, y - ra, 64);
+          const int64_t py = y_org + ya + y + cy + dyi - r;              // the partner's row in the volume
+          uint32_t m1 = 0, m2 = 0;
+          for (int k = k0; k < k1; ++k) {
+            const uint32_t v = vl[y * pv + k] & zs_bytes(e0 - 4 * k, e1 - 4 * k);
+            m1 = __builtin_amdgcn_udot4(v, 0x01010101u, m1, false);
+            m2 = __builtin_amdgcn_udot4(v, v, m2, false);
+          }
+          if (py >= 0 && py < Y) sv += a1 - m1, svv += a2 - m2;
+        }
+      }
+      const uint32_t sh = (uint32_t)dxi & 3u;
+      const uint32_t *wrow = wl + (ra + dyi) * stride + (dxi >> 2);
+      const uint32_t *vrow = vl + ra * pv;
+      for (int y = ra; y < rb; ++y, wrow += stride, vrow += pv) {
+        uint32_t prev = wrow[0];
+#pragma unroll 4
+        for (int k = 0; k < pw - 1; ++k) {
+          const uint32_t nxt = wrow[k + 1];
+          const uint32_t w = __builtin_amdgcn_alignbyte(nxt, prev, sh), v = vrow[k];
+          prev = nxt;
+          sw = __builtin_amdgcn_udot4(w, 0x01010101u, sw, false);
+          sww = __builtin_amdgcn_udot4(w, w, sww, false);
+          svw = __builtin_amdgcn_udot4(v, w, svw, false);
+        }
+        const uint32_t w = __builtin_amdgcn_alignbyte(wrow[pw], prev, sh) & tail, v = vrow[pw - 1];
+        sw = __builtin_amdgcn_udot4(w, 0x01010101u, sw, false);
+        sww = __builtin_amdgcn_udot4(w, w, sww, false);
+        svw = __builtin_amdgcn_udot4(v, w, svw, false);
+      }
+      if (o0 + lane < noffs) {
+        uint32_t *a = acc + 5 * o;
+        if (sv) atomicAdd(a + 0, sv);
+        if (svv) atomicAdd(a + 1, svv);
+        if (sw) atomicAdd(a + 2, sw);
+        if (sww) atomicAdd(a + 3, sww);
+        if (svw) atomicAdd(a + 4, svw);
+      }
+    }
+  }
+  __syncthreads();
+  uint64_t *out = sums + ((((int64_t)plane * gy + ti) * gx + tj) * noffs) * 5;
+  for (uint32_t i = threadIdx.x; i < (uint32_t)noffs * 5; i += ZS_THREADS) {
+    const uint32_t q = i % 5;
+    const uint32_t v = inner && q < 2 ? once[q] : acc[i];
+    if (v) atomicAdd(reinterpret_cast<unsigned long long *>(out + i), (unsigned long long)v);
+  }
+}
+
 }  // namespace
 
 extern "C" int tem_u8_zshift_tiles(const uint8_t *src, int32_t D, int32_t H, int32_t W, int32_t c0, int32_t c1,
@@ -250,6 +398,47 @@ extern "C" int tem_u8_zshift_tiles(const uint8_t *src, int32_t D, int32_t H, int
                      (int64_t)H, (int64_t)W, c0, (int64_t)r0, (int64_t)r1, (int64_t)y_org, (int64_t)Y, (int64_t)th,
                      (int64_t)tw, (int64_t)gy, (int64_t)gx, ti0, (uint32_t)nty, (uint32_t)ntx, (uint32_t)nrc,
                      (uint32_t)ncc, (int32_t)prows, radius, sums);
+  TEM_CHECK_LAUNCH();
+  return TEM_OK;
+}
+
+extern "C" int tem_u8_zshift_tiles_at(const uint8_t *src, int32_t D, int32_t H, int32_t W, int32_t c0, int32_t c1,
+                                      int32_t r0, int32_t r1, int32_t y_org, int32_t Y, int32_t th, int32_t tw,
+                                      int32_t gy, int32_t gx, int32_t radius, const int32_t *centers, int32_t cy_lo,
+                                      int32_t cy_hi, int32_t cx_max, uint64_t *sums, tem_stream_t stream) {
+  TEM_CLEAR_ERR();
+  if (!src || !sums || ((uintptr_t)sums & 7) || D < 1 || H < 1 || W < 1 || Y < 1 || th < 1 || th > ZS_MAX_TILE ||
+      tw < 1 || tw > ZS_MAX_TILE || gy < 1 || gx < 1 || radius < 1 || radius > ZS_MAX_R || y_org < 0 ||
+      (int64_t)y_org + H > Y || Y > (int64_t)gy * th || W > (int64_t)gx * tw || c0 < 0 || c0 > c1 || c1 > D || r0 < 0 ||
+      r0 > r1 || r1 > H)
+    return TEM_EINVAL;
+  if (!centers || ((uintptr_t)centers & 3) || cy_lo > 0 || cy_lo < -ZS_MAX_CENTER || cy_hi < 0 ||
+      cy_hi > ZS_MAX_CENTER || cx_max < 0 || cx_max > ZS_MAX_CENTER)
+    return TEM_EINVAL;
+  if (r0 < r1) {                                                         // every partner row that the volume has
+    const int64_t below = (int64_t)r0 - radius + cy_lo, above = (int64_t)r1 + radius + cy_hi;
+    const int64_t lo = below > -(int64_t)y_org ? below : -(int64_t)y_org;
+    const int64_t hi = above < (int64_t)Y - y_org ? above : (int64_t)Y - y_org;
+    if (lo < 0 || hi > H) return TEM_EINVAL;
+  }
+  int64_t ncore = c1 - c0;
+  if (c1 == D) --ncore;                                                  // the block's last plane has no partner plane
+  if (ncore <= 0 || r0 == r1) return TEM_OK;
+  const int64_t ti0 = ((int64_t)y_org + r0) / th, nty = ((int64_t)y_org + r1 - 1) / th - ti0 + 1;
+  const int64_t ntx = ((int64_t)W + tw - 1) / tw;
+  const int64_t rows = th < r1 - r0 ? th : r1 - r0, width = tw < W ? tw : W;    // of a tile's part in the core, at most
+  const int64_t cols = width < ZS_MAX_COLS ? width : ZS_MAX_COLS;
+  const int64_t ncc = (width + ZS_MAX_COLS - 1) / ZS_MAX_COLS;
+  int64_t prows = ZS_MAX_WORDS / ((cols + 3) / 4);                       // >= 32
+  prows = prows > ZS_MAX_ROWS ? ZS_MAX_ROWS : prows;
+  prows = prows > rows ? rows : prows;
+  const int64_t nrc = (rows + prows - 1) / prows;
+  const int64_t units = nty * ntx * nrc * ncc;                           // < 2^31 * 2^31 * 2^11 * 2^4
+  if (units > 0x7fffffff || units * ncore > 0x7fffffff) return TEM_EUNSUPPORTED;
+  hipLaunchKernelGGL(u8_zshift_tiles_at_k, dim3((unsigned)(units * ncore)), dim3(ZS_THREADS), 0, (hipStream_t)stream,
+                     src, (int64_t)H, (int64_t)W, c0, (int64_t)r0, (int64_t)r1, (int64_t)y_org, (int64_t)Y, (int64_t)th,
+                     (int64_t)tw, (int64_t)gy, (int64_t)gx, ti0, (uint32_t)nty, (uint32_t)ntx, (uint32_t)nrc,
+                     (uint32_t)ncc, (int32_t)prows, radius, centers, cy_lo, cy_hi, cx_max, sums);
   TEM_CHECK_LAUNCH();
   return TEM_OK;
 }

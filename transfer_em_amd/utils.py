@@ -54,6 +54,11 @@ radius (tem_u8_zshift_tiles); `shift_counts` and `shift_scores` turn the sums in
 the displacement of every section against the one below it, `shift_positions` into a position per section, and
 `volume_shift` moves the sections (or a mask) there on the host; `zshift_chunks` is the slab plan.
 
+`section_shifts_coarse_to_fine` measures displacements far beyond a radius: the same search on a pyramid of 2 x reduced
+sections (`volume_rescale`), every finer level centred per pair and tile on the coarser level's answer
+(tem_u8_zshift_tiles_at).  `shift_centers`, `zshift_chunks_at`, `shift_counts_at`, `section_shift_sums_at`,
+`shift_scores_at`, `section_shifts_at` and `shift_subpixel_at` are the centred forms of the functions above.
+
 `shift_subpixel` refines the same tile offsets below a pixel, `fit_section_maps` fits one affine map (or translation)
 per pair of sections to them, `section_maps` composes the pair maps into one map per section, `quantize_maps` brings
 them to the 2^-16 fixed point of the device, and `volume_warp` resamples every section through its map out of core
@@ -1827,6 +1832,8 @@ def defects_repair(d, tile, vol_shape, mask_out=None, max_gap=8):
 
 
 SHIFT_MAX_RADIUS = 8             # offsets of section_shift_sums: [-r, r]^2, r in 1...8
+SHIFT_MAX_CENTER = 1024          # tem_u8_zshift_tiles_at: |cy|, |cx| of a search window's centre, at most
+SHIFT_MAX_LEVELS = 6             # section_shifts_coarse_to_fine: the centres stay below (8 - 1) (2^7 - 2) = 882
 
 
 def _shift_radius(radius):
@@ -1846,6 +1853,12 @@ def zshift_chunks(vol_shape, radius, chunk_bytes=None, rank=0, world_size=1):
     fit next to the one above them, or, where two sections are larger than the budget, one section's rows, as many as
     fit twice next to their 2 radius rows of halo (one row at the least).  Slabs are in (z, y) order and go round-robin
     to the ranks.  Pure host function; ValueError as zcorr_chunks, and for a radius outside 1...8."""
+    return _zshift_chunks(vol_shape, radius, 0, 0, chunk_bytes, rank, world_size)
+
+
+def _zshift_chunks(vol_shape, radius, lo, hi, chunk_bytes, rank, world_size):
+    """zshift_chunks' list for windows centred within [lo, hi] rows of zero, lo <= 0 <= hi: a read slab is its core plus
+    radius - lo rows below and radius + hi rows above it."""
     r = _shift_radius(radius)
     budget = HIST_CHUNK_BYTES if chunk_bytes is None else int(chunk_bytes)
     if budget < 1:
@@ -1860,10 +1873,10 @@ def zshift_chunks(vol_shape, radius, chunk_bytes=None, rank=0, world_size=1):
         kz = budget // (ny * nx) - halo
         cores = [((z, min(z + kz, Z)), (0, ny)) for z in range(0, Z, kz)]
     else:
-        ky = max(1, budget // ((1 + halo) * nx) - 2 * r)
+        ky = max(1, budget // ((1 + halo) * nx) - (2 * r + hi - lo))
         cores = [((z, z + 1), (y, min(y + ky, ny))) for z in range(Z) for y in range(0, ny, ky)]
-    slabs = [((cz, cy, (0, nx)), ((cz[0], min(cz[1] + 1, Z)), (max(cy[0] - r, 0), min(cy[1] + r, ny)), (0, nx)))
-             for cz, cy in cores]
+    slabs = [((cz, cy, (0, nx)), ((cz[0], min(cz[1] + 1, Z)), (max(cy[0] - r + lo, 0), min(cy[1] + r + hi, ny)),
+                                  (0, nx))) for cz, cy in cores]
     return slabs[rank::world_size]
 
 
@@ -1874,14 +1887,23 @@ def shift_counts(vol_shape, tile, radius):
     columns, each the length of the tile's interval cut to [-d, extent - d).  Pure host function."""
     r = _shift_radius(radius)
     th, tw = _clahe_tile(tile)
-    _, (_, Y), (_, X) = hist_box(vol_shape)
     gy, gx = clahe_grid(vol_shape, (th, tw))
-    d = np.arange(-r, r + 1, dtype=np.int64)[None]
+    return _shift_counts(vol_shape, (th, tw), r, np.zeros((1, gy, gx, 2), np.int64))[0]
 
-    def along(t, g, n):
-        lo = (np.arange(g, dtype=np.int64) * t)[:, None]
+
+def _shift_counts(vol_shape, tile, r, C):
+    """shift_counts for every pair z and tile (i, j) at the total offsets C[z, i, j] + (dy, dx): int64[P, gy, gx, R, R]
+    from centres C int64[P, gy, gx, 2]."""
+    th, tw = tile
+    _, (_, Y), (_, X) = hist_box(vol_shape)
+    gy, gx = C.shape[1:3]
+    local = np.arange(-r, r + 1, dtype=np.int64)
+
+    def along(t, g, n, c, axis):
+        lo = (np.arange(g, dtype=np.int64) * t).reshape((1, g, 1, 1) if axis == 1 else (1, 1, g, 1))
+        d = c[..., None] + local
         return np.maximum(np.minimum(np.minimum(lo + t, n), n - d) - np.maximum(lo, -d), 0)
-    return along(th, gy, Y)[:, None, :, None] * along(tw, gx, X)[None, :, None, :]
+    return along(th, gy, Y, C[..., 0], 1)[..., :, None] * along(tw, gx, X, C[..., 1], 2)[..., None, :]
 
 
 def section_shift_sums(volume, tile=128, radius=4, chunk_bytes=None, rank=0, world_size=1, device=None, stats=None):
@@ -1901,12 +1923,24 @@ def section_shift_sums(volume, tile=128, radius=4, chunk_bytes=None, rank=0, wor
     most CLAHE_ACC_BYTES; else it holds one slab's core sections and is read back, and added on the host, per slab.
     Ranks take slabs round-robin and their results add up to the whole.  `stats` receives `read_s` and `chunks`.
     ValueError, before any GPU work: a non-uint8 volume, a bad tile, radius, shape, chunk_bytes or rank."""
+    return _shift_sums_pass(volume, None, tile, radius, chunk_bytes, rank, world_size, device, stats)
+
+
+def _shift_sums_pass(volume, centers, tile, radius, chunk_bytes, rank, world_size, device, stats):
+    """section_shift_sums (centers None: tem_u8_zshift_tiles) and section_shift_sums_at (tem_u8_zshift_tiles_at with the
+    table of shift_centers) are this one pass."""
     _check_u8(volume)
     th, tw = _clahe_tile(tile)
     r = _shift_radius(radius)
     gy, gx = clahe_grid(volume.shape, (th, tw))
     box = hist_box(volume.shape)
-    chunks = zshift_chunks(volume.shape, r, chunk_bytes, rank, world_size)
+    lo = hi = cx_max = 0
+    if centers is not None:
+        C = shift_centers(centers, volume.shape, (th, tw))
+        if C.size:
+            lo, hi = min(int(C[..., 0].min()), 0), max(int(C[..., 0].max()), 0)
+            cx_max = int(np.abs(C[..., 1]).max())
+    chunks = _zshift_chunks(volume.shape, r, lo, hi, chunk_bytes, rank, world_size)
     p = _SlabPass([volume], [box], chunk_bytes, rank, world_size, device, slabs=[s for _, s in chunks])
     lib = H.require_gpu()
     R = 2 * r + 1
@@ -1917,13 +1951,22 @@ def section_shift_sums(volume, tile=128, radius=4, chunk_bytes=None, rank=0, wor
     with p.streaming():
         most = max((c[0][1] - c[0][0] for c, _ in chunks), default=1)
         acc = torch.zeros((Z if whole else most, sec), dtype=torch.int64, device=p.dev)
+        if centers is not None:                                  # uploaded once; the last section's row is never read
+            table = torch.zeros((Z, gy * gx * 2), dtype=torch.int32, device=p.dev)
+            if C.size:
+                table[:Z - 1] = torch.from_numpy(C.astype(np.int32).reshape(Z - 1, -1)).to(p.dev)
         for k, ((s0, _), (y0, _), _), d, (src,) in p:
             (z0, z1), (c0, c1), _ = chunks[k][0]
             if not whole:
                 acc[:z1 - z0].zero_()
-            _lib.check(lib.tem_u8_zshift_tiles(src.data_ptr(), *d, z0 - s0, z1 - s0, c0 - y0, c1 - y0, y0, Y, th, tw,
-                                               gy, gx, r, acc.data_ptr() + 8 * sec * (z0 if whole else 0),
-                                               p.compute.cuda_stream), "tem_u8_zshift_tiles")
+            where = acc.data_ptr() + 8 * sec * (z0 if whole else 0)
+            if centers is None:
+                _lib.check(lib.tem_u8_zshift_tiles(src.data_ptr(), *d, z0 - s0, z1 - s0, c0 - y0, c1 - y0, y0, Y, th, tw,
+                                                   gy, gx, r, where, p.compute.cuda_stream), "tem_u8_zshift_tiles")
+            else:
+                _lib.check(lib.tem_u8_zshift_tiles_at(src.data_ptr(), *d, z0 - s0, z1 - s0, c0 - y0, c1 - y0, y0, Y, th,
+                                                      tw, gy, gx, r, table.data_ptr() + 8 * gy * gx * z0, lo, hi, cx_max,
+                                                      where, p.compute.cuda_stream), "tem_u8_zshift_tiles_at")
             if not whole:                                        # this slab's core sections, added on the host
                 out[z0:z1] += acc[:z1 - z0].cpu().numpy().reshape((z1 - z0,) + shape)
         if whole:
@@ -1939,7 +1982,11 @@ def _check_shift_sums(q, n, who):
             q.shape[3] % 2 != 1 or not 3 <= q.shape[3] <= 2 * SHIFT_MAX_RADIUS + 1:
         raise ValueError(f"{who}: q must be section_shift_sums' integer array [Z, gy, gx, R, R, 5], got {q.dtype} "
                          f"{q.shape}")
-    if n.shape != q.shape[1:5] or n.dtype.kind not in "iu":
+    if who.endswith("_at"):                                      # the counts carry the pair axis
+        if n.shape != (max(q.shape[0] - 1, 0),) + q.shape[1:5] or n.dtype.kind not in "iu":
+            raise ValueError(f"{who}: n must be shift_counts_at's integer array "
+                             f"{(max(q.shape[0] - 1, 0),) + q.shape[1:5]}, got {n.dtype} {n.shape}")
+    elif n.shape != q.shape[1:5] or n.dtype.kind not in "iu":
         raise ValueError(f"{who}: n must be shift_counts' integer array {q.shape[1:5]}, got {n.dtype} {n.shape}")
     return q.astype(np.int64, copy=False), n.astype(np.int64, copy=False)
 
@@ -1951,7 +1998,11 @@ def shift_scores(q, n):
       A = n S2 - S1^2,   B = n T2 - T1^2,   N = n P - S1 T1
     -- exact in int64: a tile holds at most 2^22 voxels of at most 255, so every term stays below 2^61 -- and
     c = N / (sqrt(A) sqrt(B)) where A > 0 and B > 0, else 0.0: a constant tile correlates with nothing."""
-    q, n = _check_shift_sums(q, n, "shift_scores")
+    return _shift_scores(*_check_shift_sums(q, n, "shift_scores"))
+
+
+def _shift_scores(q, n):
+    """shift_scores' formula; `n` is per tile and offset [gy, gx, R, R], or carries the pair axis in front."""
     Z = q.shape[0]
     c = np.zeros((max(Z - 1, 0),) + q.shape[1:5], np.float64)
     if Z < 2:
@@ -1990,25 +2041,35 @@ def section_shifts(q, n, min_corr=0.1):
     volume_shift moves the sections there."""
     q, n = _check_shift_sums(q, n, "section_shifts")
     min_corr = _unit(min_corr, "min_corr", False)
-    c = shift_scores(q, n)
-    R = q.shape[3]
+    return _section_shifts(_shift_scores(q, n), None, min_corr)[0]
+
+
+def _section_shifts(c, C, min_corr):
+    """section_shifts' rules on the scores `c` of searches centred on C int64[Z - 1, gy, gx, 2] (None: zero): the order
+    of the search, the rim and the tie-break are those of the LOCAL offset; `tiles` and `pairs` are TOTAL offsets,
+    centre + local; a pair without a decided tile gets the per-axis lower median of its tiles' centres.  Returns the
+    Shifts and the local offsets of `tiles`."""
+    R = c.shape[3]
     r = R // 2
     order = sorted(((dy, dx) for dy in range(-r, r + 1) for dx in range(-r, r + 1)),
                    key=lambda o: (o[0] * o[0] + o[1] * o[1], o[0], o[1]))
     offs = np.array(order, np.int64)                                             # [R R, 2]
     flat = c.reshape(c.shape[:3] + (R * R,))[..., (offs[:, 0] + r) * R + offs[:, 1] + r]
     best = flat.argmax(axis=-1)                                                  # the first of equal maxima
-    tiles = offs[best]
+    local = offs[best]
     peak = np.take_along_axis(flat, best[..., None], axis=-1)[..., 0]
-    decided = (peak > min_corr) & (np.abs(tiles) < r).all(axis=-1)
+    decided = (peak > min_corr) & (np.abs(local) < r).all(axis=-1)
+    tiles = local if C is None else C + local
     pairs, unresolved = np.zeros((c.shape[0], 2), np.int64), []
     for z in range(c.shape[0]):
         k = int(decided[z].sum())
         if k == 0:
             unresolved.append(z)
+            if C is not None:                                                    # the guess stands
+                pairs[z] = np.sort(C[z].reshape(-1, 2), axis=0)[(C[z].size // 2 - 1) // 2]
             continue
         pairs[z] = np.sort(tiles[z][decided[z]], axis=0)[(k - 1) // 2]
-    return Shifts(pairs, tiles, peak, decided, unresolved)
+    return Shifts(pairs, tiles, peak, decided, unresolved), local
 
 
 def shift_positions(pairs, window=None):
@@ -2096,12 +2157,19 @@ def shift_subpixel(q, n, min_corr=0.1):
       delta = (m - p) / (2 (m - 2 c0 + p)),   clipped to [-1/2, 1/2],
     is added where the denominator is below 0 (a true maximum).  Undecided tiles keep their integer offset and stay
     undecided.  fit_section_maps turns the offsets into one map per pair."""
-    s = section_shifts(q, n, min_corr)
-    c = shift_scores(q, n)
+    q, n = _check_shift_sums(q, n, "section_shifts")
+    min_corr = _unit(min_corr, "min_corr", False)
+    return _shift_subpixel(_shift_scores(q, n), None, min_corr)
+
+
+def _shift_subpixel(c, C, min_corr):
+    """shift_subpixel on the scores `c` of searches centred on C (None: zero): the parabola on the local table, added to
+    the total offset."""
+    s, local = _section_shifts(c, C, min_corr)
     r = c.shape[-1] // 2
     offsets = s.tiles.astype(np.float64)
     for z, i, j in zip(*np.nonzero(s.decided)):
-        dy, dx = (int(v) for v in s.tiles[z, i, j])
+        dy, dx = (int(v) for v in local[z, i, j])
         c0 = c[z, i, j, dy + r, dx + r]
         for axis, (m, p) in enumerate(((c[z, i, j, dy + r - 1, dx + r], c[z, i, j, dy + r + 1, dx + r]),
                                        (c[z, i, j, dy + r, dx + r - 1], c[z, i, j, dy + r, dx + r + 1]))):
@@ -2109,6 +2177,219 @@ def shift_subpixel(q, n, min_corr=0.1):
             if den < 0:
                 offsets[z, i, j, axis] += min(max((m - p) / (2.0 * den), -0.5), 0.5)
     return SubShifts(offsets, s.decided, s.peak)
+
+
+def shift_centers(centers, vol_shape, tile):
+    """The centres of the `_at` family's search windows, validated and expanded: np.int64 C[Z - 1, gy, gx, 2] = (cy, cx)
+    per pair of sections z (section z against z + 1) and tile (i, j) of clahe_grid's tiles of `tile` pixels over a
+    volume of shape `vol_shape`.  `centers` is integers of shape [Z - 1, 2] (one centre per pair, for every tile) or
+    [Z - 1, gy, gx, 2]; one image [y, x] has no pairs (Z - 1 = 0).  A centre goes per TILE because a rotation of a
+    fraction of a degree already displaces the corners of a large section by tens of pixels against its middle.
+    Pure host function; ValueError for another shape, a dtype that is not integer, and a component beyond
+    SHIFT_MAX_CENTER = 1024 (the message names the pair and the tile)."""
+    th, tw = _clahe_tile(tile)
+    gy, gx = clahe_grid(vol_shape, (th, tw))
+    P = hist_box(vol_shape)[0][1] - 1
+    C = np.asarray(centers)
+    if C.dtype.kind not in "iu" or C.shape not in ((P, 2), (P, gy, gx, 2)):
+        raise ValueError(f"centers must be integers of shape {(P, 2)} or {(P, gy, gx, 2)}, got {C.dtype} {C.shape}")
+    C = C.astype(np.int64)
+    if C.ndim == 2:
+        C = np.broadcast_to(C[:, None, None, :], (P, gy, gx, 2)).copy()
+    far = np.argwhere(np.abs(C) > SHIFT_MAX_CENTER)
+    if far.size:
+        z, i, j, _ = (int(v) for v in far[0])
+        raise ValueError(f"centers: pair {z}, tile ({i}, {j}) is centred on {tuple(int(v) for v in C[z, i, j])}, beyond "
+                         f"+-{SHIFT_MAX_CENTER}")
+    return C
+
+
+def _shift_reach(reach):
+    try:
+        lo, hi = reach
+        lo, hi = _index(lo, "reach"), _index(hi, "reach")
+    except TypeError:
+        raise ValueError(f"reach must be a pair of integers (lo, hi), got {reach!r}")
+    if not -SHIFT_MAX_CENTER <= lo <= 0 <= hi <= SHIFT_MAX_CENTER:
+        raise ValueError(f"reach (lo, hi) needs -{SHIFT_MAX_CENTER} <= lo <= 0 <= hi <= {SHIFT_MAX_CENTER}, got {reach!r}")
+    return lo, hi
+
+
+def zshift_chunks_at(vol_shape, radius, reach, chunk_bytes=None, rank=0, world_size=1):
+    """zshift_chunks for section_shift_sums_at: `reach` = (lo, hi), lo <= 0 <= hi, are the least and the largest row
+    centre cy of the pass (and 0).  The cores are cut as zshift_chunks cuts them; a read slab is its core plus the rows
+    [lo - radius, hi + radius] around it, clipped to the volume, and the same rows of the next section -- every partner
+    row of the core at every centre within the reach; where rows are cut, as many as fit twice next to their
+    2 radius + hi - lo rows of halo (one row at the least).  reach (0, 0) gives zshift_chunks' list.  Pure host
+    function; ValueError as zshift_chunks, and for a reach that is no such pair of integers within SHIFT_MAX_CENTER."""
+    lo, hi = _shift_reach(reach)
+    return _zshift_chunks(vol_shape, radius, lo, hi, chunk_bytes, rank, world_size)
+
+
+def shift_counts_at(vol_shape, tile, radius, centers):
+    """np.int64 n[Z - 1, gy, gx, R, R]: shift_counts for searches centred on `centers` (shift_centers): the number of
+    voxels (y, x) of tile (i, j) whose partner (y + cy + dy, x + cx + dx) lies inside the section, (cy, cx) the centre
+    of pair z and tile (i, j) -- the number of terms of section_shift_sums_at's q[z, i, j, dy + radius, dx + radius].
+    The same closed form with the total offset; 0 where the window has left the section.  Pure host function."""
+    r = _shift_radius(radius)
+    th, tw = _clahe_tile(tile)
+    return _shift_counts(vol_shape, (th, tw), r, shift_centers(centers, vol_shape, (th, tw)))
+
+
+def section_shift_sums_at(volume, centers, tile=128, radius=4, chunk_bytes=None, rank=0, world_size=1, device=None,
+                          stats=None):
+    """section_shift_sums with the search of every pair of sections and tile centred on an offset of its own:
+    np.int64 q[Z, gy, gx, R, R, 5] over the WHOLE uint8 `volume`, where for the centre (cy, cx) = C[z, i, j] of
+    `centers` (shift_centers: [Z - 1, 2] or [Z - 1, gy, gx, 2] integers within SHIFT_MAX_CENTER) and the local offset
+    (dy, dx) in [-radius, radius]^2 the sums run over the voxels (y, x) of tile (i, j) whose partner
+    (y + cy + dy, x + cx + dx) lies inside the section, v = volume[z, y, x], w = volume[z + 1, y + cy + dy, x + cx + dx]:
+      q[z, i, j, dy + radius, dx + radius] = (sum v, sum v v, sum w, sum w w, sum v w);   the last section's are 0.
+    The number of terms is shift_counts_at's.  Exact integers that numpy reproduces bit for bit; zero centres give
+    section_shift_sums' array.
+
+    The pass is section_shift_sums', over zshift_chunks_at with reach = the least and the largest cy over all centres
+    (and 0): the table goes to the device once, as int32; one tem_u8_zshift_tiles_at launch per slab, given the table's
+    rows of the slab's first core section; the same accumulator and read-back rule (CLAHE_ACC_BYTES); ranks' results
+    add.  `stats` receives `read_s` and `chunks`.  ValueError, before any GPU work: as section_shift_sums, and
+    shift_centers' for the centres."""
+    if centers is None:
+        raise ValueError("centers must be integers of shape [Z - 1, 2] or [Z - 1, gy, gx, 2], got None")
+    return _shift_sums_pass(volume, centers, tile, radius, chunk_bytes, rank, world_size, device, stats)
+
+
+def shift_scores_at(q, n):
+    """shift_scores for section_shift_sums_at's `q` and shift_counts_at's `n`, which carries the pair axis:
+    float64 c[Z - 1, gy, gx, R, R] indexed by the LOCAL offset.  Host only."""
+    return _shift_scores(*_check_shift_sums(q, n, "shift_scores_at"))
+
+
+def _check_centers_for(q, centers, who):
+    C = np.asarray(centers)
+    P = max(q.shape[0] - 1, 0)
+    if C.dtype.kind not in "iu" or C.shape not in ((P, 2), (P,) + q.shape[1:3] + (2,)):
+        raise ValueError(f"{who}: centers must be integers of shape {(P, 2)} or {(P,) + q.shape[1:3] + (2,)}, got "
+                         f"{C.dtype} {C.shape}")
+    C = C.astype(np.int64)
+    return np.broadcast_to(C[:, None, None, :], (P,) + q.shape[1:3] + (2,)) if C.ndim == 2 else C
+
+
+def section_shifts_at(q, n, centers, min_corr=0.1):
+    """section_shifts for searches centred on `centers` ([Z - 1, 2] or [Z - 1, gy, gx, 2] integers), from
+    section_shift_sums_at's `q` and shift_counts_at's `n`.  Host only.  The rules are section_shifts' on the LOCAL
+    offsets -- the search order (dy^2 + dx^2, dy, dx), ties to the smaller local displacement, the rim |dy| = r or
+    |dx| = r not trusted --; `tiles` and `pairs` of the Shifts are TOTAL offsets, centre + local.  A pair without a
+    decided tile is listed in `unresolved` and gets the per-axis lower median of its tiles' centres: the guess stands.
+    Zero centres reproduce section_shifts."""
+    q, n = _check_shift_sums(q, n, "section_shifts_at")
+    C = _check_centers_for(q, centers, "section_shifts_at")
+    min_corr = _unit(min_corr, "min_corr", False)
+    return _section_shifts(_shift_scores(q, n), C, min_corr)[0]
+
+
+def shift_subpixel_at(q, n, centers, min_corr=0.1):
+    """shift_subpixel for searches centred on `centers`: SubShifts whose offsets are section_shifts_at's total tile
+    offsets plus the vertex of the same parabola on the local table.  fit_section_maps takes it unchanged."""
+    q, n = _check_shift_sums(q, n, "section_shifts_at")
+    C = _check_centers_for(q, centers, "section_shifts_at")
+    min_corr = _unit(min_corr, "min_corr", False)
+    return _shift_subpixel(_shift_scores(q, n), C, min_corr)
+
+
+class CoarseShifts(NamedTuple):
+    """section_shifts_coarse_to_fine's verdict, all of the finest level (the volume itself): `shifts` the Shifts in total
+    offsets, `q` and `n` the sums and counts of the last search and `centers` int64[Z - 1, gy, gx, 2] where it was
+    centred -- what shift_subpixel_at takes."""
+    shifts: Shifts
+    q: np.ndarray
+    n: np.ndarray
+    centers: np.ndarray
+
+
+def section_shifts_coarse_to_fine(volume, tile=128, radius=4, levels=3, min_corr=0.1, min_decided=0.5, coarse=None,
+                                  chunk_bytes=None, device=None, stats=None):
+    """How far consecutive sections of the uint8 `volume` [z, y, x] sit apart where that is far more than a search
+    radius: section_shifts on a pyramid.  V_0 = volume, V_(l+1) = volume_rescale(V_l, (2, 2, 1)) for l < `levels`
+    (1...6; sections halved in y and x on the device, z kept).  The coarsest level is searched around zero; every finer
+    level l is searched around the doubled answer of level l + 1 (section_shift_sums_at -> section_shifts_at): the
+    centre of tile (i, j) of pair z is 2 tiles_(l+1)[z, i // 2, j // 2] where that coarse tile is decided, else
+    2 pairs_(l+1)[z].  `tile` and `radius` are the same at every level, in that level's pixels, so one pixel of the
+    coarsest search is 2^levels pixels of the volume and a displacement of up to (radius - 1) 2^levels is found there.
+
+    Returns CoarseShifts(shifts, q, n, centers) of level 0.  There a pair with fewer than `min_decided` (a number in
+    [0, 1]) of its tiles decided, and every pair section_shifts_at could not resolve, is listed in `unresolved` and gets
+    (0, 0): a section is not moved on a guess.  That is also how a displacement beyond the reach of the coarsest level
+    shows: its finer searches are centred off the truth and few of their tiles are decided -- chance peaks just above
+    `min_corr` can decide some, which is why the fraction, not the peaks, is the test.
+
+    `coarse`: None, or `levels` writable uint8 array-likes for V_1, V_2, ... of rescale_shape's shapes (np.memmap, h5py,
+    zarr) where the pyramid does not fit in memory; ndarrays are allocated otherwise.  `chunk_bytes` and `device` go to
+    every pass; `stats` receives `read_s` and `chunks` summed over all passes.  ValueError, before any GPU work: a volume
+    that is not a uint8 [z, y, x], a bad tile, radius, min_corr, min_decided or chunk_bytes, levels outside 1...6 or so
+    many that the coarsest section's shorter side min(Y, X) >> levels falls below 4 radius, a `coarse` of another
+    length, shape or dtype."""
+    _check_u8(volume)
+    vshape = tuple(int(v) for v in volume.shape)
+    if len(vshape) != 3 or min(vshape) < 1:
+        raise ValueError(f"section_shifts_coarse_to_fine needs a non-empty volume [z, y, x], got shape {vshape}")
+    th, tw = _clahe_tile(tile)
+    r = _shift_radius(radius)
+    L = _index(levels, "levels")
+    # a decided offset is at most r - 1 and is doubled on the way down: the centres of level l are at most
+    # (r - 1) (2^(L - l + 1) - 2), so the largest, at level 0, is (r - 1) (2^(L + 1) - 2) <= 7 x 126 = 882 < SHIFT_MAX_CENTER
+    if not 1 <= L <= SHIFT_MAX_LEVELS:
+        raise ValueError(f"levels must lie in 1...{SHIFT_MAX_LEVELS}, got {L}")
+    assert (SHIFT_MAX_RADIUS - 1) * (2 ** (SHIFT_MAX_LEVELS + 1) - 2) <= SHIFT_MAX_CENTER
+    if min(vshape[1:]) >> L < 4 * r:
+        raise ValueError(f"levels={L} leaves sections of {vshape[1] >> L} x {vshape[2] >> L} pixels at the coarsest level: "
+                         f"the shorter side must be at least 4 radius = {4 * r}")
+    min_corr = _unit(min_corr, "min_corr", False)
+    try:
+        if isinstance(min_decided, (bool, np.bool_, str, bytes)):
+            raise TypeError
+        min_decided = float(min_decided)
+        if not 0 <= min_decided <= 1:
+            raise TypeError
+    except (TypeError, ValueError):
+        raise ValueError(f"min_decided must be a number in [0, 1], got {min_decided!r}")
+    if chunk_bytes is not None and int(chunk_bytes) < 1:
+        raise ValueError(f"chunk_bytes must be positive, got {chunk_bytes}")
+    shapes = [vshape]
+    for _ in range(L):
+        shapes.append(rescale_shape(shapes[-1], (2, 2, 1)))
+    if coarse is None:
+        coarse = [None] * L
+    elif len(coarse) != L or any(tuple(c.shape) != s or getattr(c, "dtype", None) != np.uint8
+                                 for c, s in zip(coarse, shapes[1:])):
+        raise ValueError(f"coarse must be {L} uint8 array-likes of shapes {shapes[1:]}")
+    total = {"read_s": 0.0, "chunks": 0}
+
+    def counted(st):
+        total["read_s"] += st.get("read_s", 0.0)
+        total["chunks"] += st.get("chunks", 0)
+    V = [volume]
+    for l in range(L):
+        st = {}
+        V.append(volume_rescale(V[l], (2, 2, 1), out=coarse[l], chunk_bytes=chunk_bytes, device=device, stats=st))
+        counted(st)
+    s = None
+    for l in range(L, -1, -1):
+        gy, gx = clahe_grid(shapes[l], (th, tw))
+        C = np.zeros((vshape[0] - 1, gy, gx, 2), np.int64)
+        if s is not None:                                        # ceil(ceil(Y / 2) / th) = ceil(gy / 2): i // 2 exists
+            i, j = np.arange(gy)[:, None] // 2, np.arange(gx)[None, :] // 2
+            C[...] = 2 * np.where(s.decided[:, i, j, None], s.tiles[:, i, j], s.pairs[:, None, None, :])
+        st = {}
+        q = section_shift_sums_at(V[l], C, (th, tw), r, chunk_bytes=chunk_bytes, device=device, stats=st)
+        counted(st)
+        n = shift_counts_at(shapes[l], (th, tw), r, C)
+        s = section_shifts_at(q, n, C, min_corr)
+    few = s.decided.sum(axis=(1, 2)) < min_decided * s.decided.shape[1] * s.decided.shape[2]
+    unresolved = sorted(set(s.unresolved) | set(int(z) for z in np.nonzero(few)[0]))
+    pairs = s.pairs.copy()
+    pairs[np.array(unresolved, np.int64)] = 0
+    if stats is not None:
+        stats.update(total)
+    return CoarseShifts(Shifts(pairs, s.tiles, s.peak, s.decided, unresolved), q, n, C)
 
 
 class SectionFits(NamedTuple):
