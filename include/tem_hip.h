@@ -631,6 +631,31 @@ int tem_u8_zshift_tiles_at(const uint8_t *src, int32_t D, int32_t H, int32_t W, 
                            int32_t radius, const int32_t *centers, int32_t cy_lo, int32_t cy_hi, int32_t cx_max,
                            uint64_t *sums, tem_stream_t stream);
 
+/* tem_u8_zshift_tiles_at over an explicit list of section pairs instead of every core plane and the one above it
+ * (utils.section_shift_sums_pairs, the device leg of utils.section_shifts_bridged: a damaged section is skipped and
+ * its good neighbours are measured against each other, lag 2 and more; or a few pairs are measured again).
+ * src[D][H][W] is a dense block of whole rows as above whose plane 0 is VOLUME section z_org.  `pairs` is a device
+ * table of int32 (4-byte aligned) laid out [npairs][2] = (a, b), volume sections with a < b; `centers` is
+ * [npairs][gy][gx][2] and sums [npairs][gy][gx][R][R][5]: a row per PAIR.  For pair k = (a, b), a tile (i, j) with
+ * centre (cy, cx) and a local offset (dy, dx) in [-r, r]^2, over the tile's voxels (y, x) in the core rows [r0, r1)
+ * whose partner (y + cy + dy, x + cx + dx) lies inside the section, with v = src[a - z_org][y][x] and
+ * w = src[b - z_org][y + cy + dy][x + cx + dx]:
+ *   sums[((((k * gy + i) * gx + j) * R + dy + r) * R + dx + r) * 5 + 0..4] += (sum v, sum v v, sum w, sum w w, sum v w)
+ * The five terms, the layout within a row, the 64-bit atomic adds, the overflow bounds, the promised centre bounds
+ * (within +-1024) and the partner rows the block must hold are exactly tem_u8_zshift_tiles_at's; a table of
+ * (z_org + d, z_org + d + 1) for d = c0 ... c1 - 1 with the same centres gives its sums bit for bit.  The caller
+ * promises z_org <= a < b < z_org + D (utils keeps b - a <= SHIFT_MAX_LAG = 8, which bounds the block, not the
+ * kernel).  The workgroup reads its pair once and clamps both planes to [0, D - 1], and every centre to the promised
+ * bounds: a table that disagrees with the block or the promise gives other sums (those of the clamped table), never
+ * a read outside the block.  The same pair may be given in several calls whose core rows or blocks differ: they add.
+ * TEM_EINVAL as tem_u8_zshift_tiles_at (all but its core planes), and: a null pairs or one off 4-byte alignment,
+ * npairs < 0.  TEM_EUNSUPPORTED: more than 2^31 - 1 workgroups (one per pair, tile and part of it).  npairs == 0 or
+ * an empty core launches nothing. */
+int tem_u8_zshift_tiles_pairs(const uint8_t *src, int32_t D, int32_t H, int32_t W, int32_t z_org, int32_t npairs,
+                              const int32_t *pairs, int32_t r0, int32_t r1, int32_t y_org, int32_t Y, int32_t th,
+                              int32_t tw, int32_t gy, int32_t gx, int32_t radius, const int32_t *centers,
+                              int32_t cy_lo, int32_t cy_hi, int32_t cx_max, uint64_t *sums, tem_stream_t stream);
+
 /* Every section of a uint8 volume V[Z][Y][X] resampled through its own affine map (utils.volume_warp: sections aligned
  * by the maps that utils.fit_section_maps fits to the tile offsets of tem_u8_zshift_tiles).  The definition, once: a
  * section's map is six int64 in units of 2^-16, (a_yy, a_yx, b_y, a_xy, a_xx, b_x).  For the output voxel (y, x) of the

@@ -158,6 +158,8 @@ _SIGS = {
     "tem_u8_zcorr_tiles": [C.c_void_p] + [C.c_int32] * 11 + [C.c_void_p, C.c_void_p],
     "tem_u8_zshift_tiles": [C.c_void_p] + [C.c_int32] * 14 + [C.c_void_p, C.c_void_p],
     "tem_u8_zshift_tiles_at": [C.c_void_p] + [C.c_int32] * 14 + [C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p, C.c_void_p],
+    "tem_u8_zshift_tiles_pairs": [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p] + [C.c_int32] * 9 + [C.c_void_p] +
+                                 [C.c_int32] * 3 + [C.c_void_p, C.c_void_p],
     "tem_u8_warp_affine": [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_void_p,
                            C.c_int32, C.c_int32, C.c_void_p],
     "tem_u8_warp_field": [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p] * 4 +

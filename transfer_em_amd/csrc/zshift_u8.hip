@@ -5,7 +5,11 @@
 //                         section (no sums at all for the block's last plane)
 //   tem_u8_zshift_tiles_at  the same with the offsets of every plane and tile centred on (cy, cx) of a device table:
 //                         the partner is w = (d + 1, y + cy + dy, x + cx + dx) (utils.section_shift_sums_at, the
-//                         device leg of section_shifts_coarse_to_fine); see u8_zshift_tiles_at_k
+//                         device leg of section_shifts_coarse_to_fine); see zs_tiles_at
+//   tem_u8_zshift_tiles_pairs  the centred sums of an explicit device list of section pairs (a, b), a < b, with a row
+//                         of centres and of sums per pair: v = (a, y, x), w = (b, y + cy + dy, x + cx + dx)
+//                         (utils.section_shift_sums_pairs, the device leg of section_shifts_bridged: bad sections are
+//                         skipped and their good neighbours measured against each other); the same body, zs_tiles_at
 // The tile grid is tem_u8_hist_tiles': anchored at (0, 0) of the caller's VOLUME; the block holds whole rows, its row 0
 // at volume row y_org.  Everything is integers and the adds are atomic, so the sums do not depend on how the volume
 // was cut into blocks or the block into workgroups.
@@ -234,13 +238,20 @@ __global__ __launch_bounds__(ZS_THREADS) void u8_zshift_tiles_k(const uint8_t *s
 //     still one run at the row's left end (dx_total < 0) or right end (dx_total > 0), but the run is now up to the
 //     WHOLE width of the part -- |dx_total| reaches 1032, a part has 128 columns at most --, so its words k0 ... k1
 //     run over up to all pw words of the row, not over the one to three that r <= 8 columns took.
-__global__ __launch_bounds__(ZS_THREADS) void u8_zshift_tiles_at_k(const uint8_t *src, int64_t H, int64_t W, int32_t c0,
-                                                                   int64_t r0, int64_t r1, int64_t y_org, int64_t Y,
-                                                                   int64_t th, int64_t tw, int64_t gy, int64_t gx,
-                                                                   int64_t ti0, uint32_t nty, uint32_t ntx,
-                                                                   uint32_t nrc, uint32_t ncc, int32_t prows, int32_t r,
-                                                                   const int32_t *centers, int32_t cy_lo, int32_t cy_hi,
-                                                                   int32_t cx_max, uint64_t *sums) {
+// The body is written once for two kernels.  `plane`, the slowest part of the block index, is the row of `centers`
+// and of `sums`; what it says about the two planes of the block differs:
+//   PAIRS false (u8_zshift_tiles_at_k)     v is plane c0 + plane, w the plane above it
+//   PAIRS true  (u8_zshift_tiles_pairs_k)  `plane` is the index k of a pair (a, b) of VOLUME sections in the device
+//     table `pairs` ([npairs][2]); the block's plane 0 is section c0 (z_org), so v is plane a - c0 and w plane b - c0.
+//     The workgroup reads the two numbers once, uniformly, and clamps both planes to [0, D - 1]: a table that names a
+//     section outside the block gives the sums of the clamped planes, never a read outside the block.
+template <bool PAIRS>
+__device__ __forceinline__ void zs_tiles_at(const uint8_t *src, int64_t H, int64_t W, int32_t c0, const int32_t *pairs,
+                                            int32_t D, int64_t r0, int64_t r1, int64_t y_org, int64_t Y, int64_t th,
+                                            int64_t tw, int64_t gy, int64_t gx, int64_t ti0, uint32_t nty, uint32_t ntx,
+                                            uint32_t nrc, uint32_t ncc, int32_t prows, int32_t r,
+                                            const int32_t *centers, int32_t cy_lo, int32_t cy_hi, int32_t cx_max,
+                                            uint64_t *sums) {
   __shared__ uint32_t vl[ZS_MAX_WORDS + ZS_MAX_ROWS];
   __shared__ uint32_t wl[ZS_WIN_WORDS];
   __shared__ uint32_t acc[ZS_MAX_OFFS * 5];
@@ -272,14 +283,19 @@ __global__ __launch_bounds__(ZS_THREADS) void u8_zshift_tiles_at_k(const uint8_t
   const int nw = pw + (2 * r >> 2) + 1;                                  // words per row of the window that are read
   int stride = nw;                                                       // 5, 13, 19 or 27 modulo 32
   while ((stride & 31) != 5 && (stride & 31) != 13 && (stride & 31) != 19 && (stride & 31) != 27) ++stride;
-  const int64_t d = (int64_t)c0 + plane;
+  int64_t d = (int64_t)c0 + plane, dw = d + 1;                           // the planes of v and of w in the block
+  if constexpr (PAIRS) {
+    const int32_t *ab = pairs + 2 * (int64_t)plane;                      // the same for the whole workgroup
+    d = min(max((int64_t)__builtin_amdgcn_readfirstlane(ab[0]) - c0, (int64_t)0), (int64_t)D - 1);
+    dw = min(max((int64_t)__builtin_amdgcn_readfirstlane(ab[1]) - c0, (int64_t)0), (int64_t)D - 1);
+  }
   // a part whose every voxel has every partner: the whole window lies in the section
   const bool inner = wy0 >= 0 && wy1 <= Y && wx0 >= 0 && wx1 <= W;
 
   for (uint32_t i = threadIdx.x; i < (uint32_t)noffs * 5; i += ZS_THREADS) acc[i] = 0;
   if (threadIdx.x < 2) once[threadIdx.x] = 0;
   zs_stage(vl, rows, pw, pv, src, d, H, W, ya, xa, ya, yb, xa, xb);
-  zs_stage(wl, rows + 2 * r, nw, stride, src, d + 1, H, W, ya - r + cy, xa - r + cx, max((int64_t)0, -y_org),
+  zs_stage(wl, rows + 2 * r, nw, stride, src, dw, H, W, ya - r + cy, xa - r + cx, max((int64_t)0, -y_org),
            min(H, Y - y_org), 0, W);
   __syncthreads();
 
@@ -364,6 +380,31 @@ __global__ __launch_bounds__(ZS_THREADS) void u8_zshift_tiles_at_k(const uint8_t
   }
 }
 
+__global__ __launch_bounds__(ZS_THREADS) void u8_zshift_tiles_at_k(const uint8_t *src, int64_t H, int64_t W, int32_t c0,
+                                                                   int64_t r0, int64_t r1, int64_t y_org, int64_t Y,
+                                                                   int64_t th, int64_t tw, int64_t gy, int64_t gx,
+                                                                   int64_t ti0, uint32_t nty, uint32_t ntx,
+                                                                   uint32_t nrc, uint32_t ncc, int32_t prows, int32_t r,
+                                                                   const int32_t *centers, int32_t cy_lo, int32_t cy_hi,
+                                                                   int32_t cx_max, uint64_t *sums) {
+  zs_tiles_at<false>(src, H, W, c0, nullptr, 0, r0, r1, y_org, Y, th, tw, gy, gx, ti0, nty, ntx, nrc, ncc, prows, r,
+                     centers, cy_lo, cy_hi, cx_max, sums);
+}
+
+// Block b = (((pair * nty + ti) * ntx + tj) * nrc + rc) * ncc + cc: the sibling's index with the pair k of `pairs` in
+// the place of the core plane; centers and sums are [npairs][gy][gx]... tables with a row per pair.
+__global__ __launch_bounds__(ZS_THREADS) void u8_zshift_tiles_pairs_k(const uint8_t *src, int32_t D, int64_t H, int64_t W,
+                                                                      int32_t z_org, const int32_t *pairs, int64_t r0,
+                                                                      int64_t r1, int64_t y_org, int64_t Y, int64_t th,
+                                                                      int64_t tw, int64_t gy, int64_t gx, int64_t ti0,
+                                                                      uint32_t nty, uint32_t ntx, uint32_t nrc,
+                                                                      uint32_t ncc, int32_t prows, int32_t r,
+                                                                      const int32_t *centers, int32_t cy_lo,
+                                                                      int32_t cy_hi, int32_t cx_max, uint64_t *sums) {
+  zs_tiles_at<true>(src, H, W, z_org, pairs, D, r0, r1, y_org, Y, th, tw, gy, gx, ti0, nty, ntx, nrc, ncc, prows, r,
+                    centers, cy_lo, cy_hi, cx_max, sums);
+}
+
 }  // namespace
 
 extern "C" int tem_u8_zshift_tiles(const uint8_t *src, int32_t D, int32_t H, int32_t W, int32_t c0, int32_t c1,
@@ -402,15 +443,21 @@ extern "C" int tem_u8_zshift_tiles(const uint8_t *src, int32_t D, int32_t H, int
   return TEM_OK;
 }
 
-extern "C" int tem_u8_zshift_tiles_at(const uint8_t *src, int32_t D, int32_t H, int32_t W, int32_t c0, int32_t c1,
-                                      int32_t r0, int32_t r1, int32_t y_org, int32_t Y, int32_t th, int32_t tw,
-                                      int32_t gy, int32_t gx, int32_t radius, const int32_t *centers, int32_t cy_lo,
-                                      int32_t cy_hi, int32_t cx_max, uint64_t *sums, tem_stream_t stream) {
-  TEM_CLEAR_ERR();
+
+namespace {
+
+struct zs_grid {
+  int64_t ti0, nty, ntx, nrc, ncc, prows, units;                         // units: workgroups per core plane or pair
+};
+
+// What tem_u8_zshift_tiles_at and tem_u8_zshift_tiles_pairs share: every check that does not speak of core planes or
+// pairs, and the workgroups of one plane's core rows [r0, r1).
+int zs_at_grid(const uint8_t *src, int32_t D, int32_t H, int32_t W, int32_t r0, int32_t r1, int32_t y_org, int32_t Y,
+               int32_t th, int32_t tw, int32_t gy, int32_t gx, int32_t radius, const int32_t *centers, int32_t cy_lo,
+               int32_t cy_hi, int32_t cx_max, const uint64_t *sums, zs_grid *g) {
   if (!src || !sums || ((uintptr_t)sums & 7) || D < 1 || H < 1 || W < 1 || Y < 1 || th < 1 || th > ZS_MAX_TILE ||
       tw < 1 || tw > ZS_MAX_TILE || gy < 1 || gx < 1 || radius < 1 || radius > ZS_MAX_R || y_org < 0 ||
-      (int64_t)y_org + H > Y || Y > (int64_t)gy * th || W > (int64_t)gx * tw || c0 < 0 || c0 > c1 || c1 > D || r0 < 0 ||
-      r0 > r1 || r1 > H)
+      (int64_t)y_org + H > Y || Y > (int64_t)gy * th || W > (int64_t)gx * tw || r0 < 0 || r0 > r1 || r1 > H)
     return TEM_EINVAL;
   if (!centers || ((uintptr_t)centers & 3) || cy_lo > 0 || cy_lo < -ZS_MAX_CENTER || cy_hi < 0 ||
       cy_hi > ZS_MAX_CENTER || cx_max < 0 || cx_max > ZS_MAX_CENTER)
@@ -421,24 +468,61 @@ extern "C" int tem_u8_zshift_tiles_at(const uint8_t *src, int32_t D, int32_t H, 
     const int64_t hi = above < (int64_t)Y - y_org ? above : (int64_t)Y - y_org;
     if (lo < 0 || hi > H) return TEM_EINVAL;
   }
-  int64_t ncore = c1 - c0;
-  if (c1 == D) --ncore;                                                  // the block's last plane has no partner plane
-  if (ncore <= 0 || r0 == r1) return TEM_OK;
-  const int64_t ti0 = ((int64_t)y_org + r0) / th, nty = ((int64_t)y_org + r1 - 1) / th - ti0 + 1;
-  const int64_t ntx = ((int64_t)W + tw - 1) / tw;
+  g->units = 0;
+  if (r0 == r1) return TEM_OK;
+  g->ti0 = ((int64_t)y_org + r0) / th, g->nty = ((int64_t)y_org + r1 - 1) / th - g->ti0 + 1;
+  g->ntx = ((int64_t)W + tw - 1) / tw;
   const int64_t rows = th < r1 - r0 ? th : r1 - r0, width = tw < W ? tw : W;    // of a tile's part in the core, at most
   const int64_t cols = width < ZS_MAX_COLS ? width : ZS_MAX_COLS;
-  const int64_t ncc = (width + ZS_MAX_COLS - 1) / ZS_MAX_COLS;
+  g->ncc = (width + ZS_MAX_COLS - 1) / ZS_MAX_COLS;
   int64_t prows = ZS_MAX_WORDS / ((cols + 3) / 4);                       // >= 32
   prows = prows > ZS_MAX_ROWS ? ZS_MAX_ROWS : prows;
-  prows = prows > rows ? rows : prows;
-  const int64_t nrc = (rows + prows - 1) / prows;
-  const int64_t units = nty * ntx * nrc * ncc;                           // < 2^31 * 2^31 * 2^11 * 2^4
-  if (units > 0x7fffffff || units * ncore > 0x7fffffff) return TEM_EUNSUPPORTED;
-  hipLaunchKernelGGL(u8_zshift_tiles_at_k, dim3((unsigned)(units * ncore)), dim3(ZS_THREADS), 0, (hipStream_t)stream,
+  g->prows = prows > rows ? rows : prows;
+  g->nrc = (rows + g->prows - 1) / g->prows;
+  g->units = g->nty * g->ntx * g->nrc * g->ncc;                          // < 2^31 * 2^31 * 2^11 * 2^4
+  return TEM_OK;
+}
+
+}  // namespace
+
+extern "C" int tem_u8_zshift_tiles_at(const uint8_t *src, int32_t D, int32_t H, int32_t W, int32_t c0, int32_t c1,
+                                      int32_t r0, int32_t r1, int32_t y_org, int32_t Y, int32_t th, int32_t tw,
+                                      int32_t gy, int32_t gx, int32_t radius, const int32_t *centers, int32_t cy_lo,
+                                      int32_t cy_hi, int32_t cx_max, uint64_t *sums, tem_stream_t stream) {
+  TEM_CLEAR_ERR();
+  zs_grid g;
+  if (zs_at_grid(src, D, H, W, r0, r1, y_org, Y, th, tw, gy, gx, radius, centers, cy_lo, cy_hi, cx_max, sums, &g) !=
+          TEM_OK || c0 < 0 || c0 > c1 || c1 > D)
+    return TEM_EINVAL;
+  int64_t ncore = c1 - c0;
+  if (c1 == D) --ncore;                                                  // the block's last plane has no partner plane
+  if (ncore <= 0 || g.units == 0) return TEM_OK;
+  if (g.units > 0x7fffffff || g.units * ncore > 0x7fffffff) return TEM_EUNSUPPORTED;
+  hipLaunchKernelGGL(u8_zshift_tiles_at_k, dim3((unsigned)(g.units * ncore)), dim3(ZS_THREADS), 0, (hipStream_t)stream,
                      src, (int64_t)H, (int64_t)W, c0, (int64_t)r0, (int64_t)r1, (int64_t)y_org, (int64_t)Y, (int64_t)th,
-                     (int64_t)tw, (int64_t)gy, (int64_t)gx, ti0, (uint32_t)nty, (uint32_t)ntx, (uint32_t)nrc,
-                     (uint32_t)ncc, (int32_t)prows, radius, centers, cy_lo, cy_hi, cx_max, sums);
+                     (int64_t)tw, (int64_t)gy, (int64_t)gx, g.ti0, (uint32_t)g.nty, (uint32_t)g.ntx, (uint32_t)g.nrc,
+                     (uint32_t)g.ncc, (int32_t)g.prows, radius, centers, cy_lo, cy_hi, cx_max, sums);
+  TEM_CHECK_LAUNCH();
+  return TEM_OK;
+}
+
+extern "C" int tem_u8_zshift_tiles_pairs(const uint8_t *src, int32_t D, int32_t H, int32_t W, int32_t z_org,
+                                         int32_t npairs, const int32_t *pairs, int32_t r0, int32_t r1, int32_t y_org,
+                                         int32_t Y, int32_t th, int32_t tw, int32_t gy, int32_t gx, int32_t radius,
+                                         const int32_t *centers, int32_t cy_lo, int32_t cy_hi, int32_t cx_max,
+                                         uint64_t *sums, tem_stream_t stream) {
+  TEM_CLEAR_ERR();
+  zs_grid g;
+  if (zs_at_grid(src, D, H, W, r0, r1, y_org, Y, th, tw, gy, gx, radius, centers, cy_lo, cy_hi, cx_max, sums, &g) !=
+          TEM_OK || !pairs || ((uintptr_t)pairs & 3) || npairs < 0)
+    return TEM_EINVAL;
+  if (npairs == 0 || g.units == 0) return TEM_OK;
+  if (g.units > 0x7fffffff || g.units * npairs > 0x7fffffff) return TEM_EUNSUPPORTED;
+  hipLaunchKernelGGL(u8_zshift_tiles_pairs_k, dim3((unsigned)(g.units * npairs)), dim3(ZS_THREADS), 0,
+                     (hipStream_t)stream, src, D, (int64_t)H, (int64_t)W, z_org, pairs, (int64_t)r0, (int64_t)r1,
+                     (int64_t)y_org, (int64_t)Y, (int64_t)th, (int64_t)tw, (int64_t)gy, (int64_t)gx, g.ti0,
+                     (uint32_t)g.nty, (uint32_t)g.ntx, (uint32_t)g.nrc, (uint32_t)g.ncc, (int32_t)g.prows, radius,
+                     centers, cy_lo, cy_hi, cx_max, sums);
   TEM_CHECK_LAUNCH();
   return TEM_OK;
 }

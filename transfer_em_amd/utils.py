@@ -59,6 +59,12 @@ sections (`volume_rescale`), every finer level centred per pair and tile on the 
 (tem_u8_zshift_tiles_at).  `shift_centers`, `zshift_chunks_at`, `shift_counts_at`, `section_shift_sums_at`,
 `shift_scores_at`, `section_shifts_at` and `shift_subpixel_at` are the centred forms of the functions above.
 
+`section_shifts_bridged` is the same pyramid over an explicit list of section pairs (a, b), so that the good sections
+on either side of a bad one are measured against each other (tem_u8_zshift_tiles_pairs): `section_pairs` and
+`suspect_sections` make the list, `zshift_chunks_pairs`, `shift_counts_pairs`, `section_shift_sums_pairs`,
+`shift_scores_pairs`, `section_shifts_pairs` and `shift_subpixel_pairs` are the per-pair forms, and `chain_pairs` puts
+per-pair shifts, maps or fields back onto the stack's consecutive pairs.
+
 `shift_subpixel` refines the same tile offsets below a pixel, `fit_section_maps` fits one affine map (or translation)
 per pair of sections to them, `section_maps` composes the pair maps into one map per section, `quantize_maps` brings
 them to the 2^-16 fixed point of the device, and `volume_warp` resamples every section through its map out of core
@@ -1982,7 +1988,10 @@ def _check_shift_sums(q, n, who):
             q.shape[3] % 2 != 1 or not 3 <= q.shape[3] <= 2 * SHIFT_MAX_RADIUS + 1:
         raise ValueError(f"{who}: q must be section_shift_sums' integer array [Z, gy, gx, R, R, 5], got {q.dtype} "
                          f"{q.shape}")
-    if who.endswith("_at"):                                      # the counts carry the pair axis
+    if who.endswith("_pairs"):                                   # a row of sums and of counts per pair
+        if n.shape != q.shape[:5] or n.dtype.kind not in "iu":
+            raise ValueError(f"{who}: n must be shift_counts_pairs' integer array {q.shape[:5]}, got {n.dtype} {n.shape}")
+    elif who.endswith("_at"):                                    # the counts carry the pair axis
         if n.shape != (max(q.shape[0] - 1, 0),) + q.shape[1:5] or n.dtype.kind not in "iu":
             raise ValueError(f"{who}: n must be shift_counts_at's integer array "
                              f"{(max(q.shape[0] - 1, 0),) + q.shape[1:5]}, got {n.dtype} {n.shape}")
@@ -2003,11 +2012,15 @@ def shift_scores(q, n):
 
 def _shift_scores(q, n):
     """shift_scores' formula; `n` is per tile and offset [gy, gx, R, R], or carries the pair axis in front."""
-    Z = q.shape[0]
-    c = np.zeros((max(Z - 1, 0),) + q.shape[1:5], np.float64)
-    if Z < 2:
+    return _pair_scores(q[:-1], n)
+
+
+def _pair_scores(q, n):
+    """shift_scores' formula on one row of sums per PAIR, q[P, gy, gx, R, R, 5]: float64 c[P, gy, gx, R, R]."""
+    c = np.zeros(q.shape[:5], np.float64)
+    if not q.shape[0]:
         return c
-    S1, S2, T1, T2, P = (q[:-1, ..., k] for k in range(5))
+    S1, S2, T1, T2, P = (q[..., k] for k in range(5))
     A, B, N = n * S2 - S1 * S1, n * T2 - T1 * T1, n * P - S1 * T1
     ok = (A > 0) & (B > 0)
     c[ok] = N[ok] / (np.sqrt(A[ok].astype(np.float64)) * np.sqrt(B[ok].astype(np.float64)))
@@ -2189,7 +2202,11 @@ def shift_centers(centers, vol_shape, tile):
     SHIFT_MAX_CENTER = 1024 (the message names the pair and the tile)."""
     th, tw = _clahe_tile(tile)
     gy, gx = clahe_grid(vol_shape, (th, tw))
-    P = hist_box(vol_shape)[0][1] - 1
+    return _centers_table(centers, hist_box(vol_shape)[0][1] - 1, gy, gx)
+
+
+def _centers_table(centers, P, gy, gx):
+    """shift_centers for `P` pairs on a grid of gy x gx tiles."""
     C = np.asarray(centers)
     if C.dtype.kind not in "iu" or C.shape not in ((P, 2), (P, gy, gx, 2)):
         raise ValueError(f"centers must be integers of shape {(P, 2)} or {(P, gy, gx, 2)}, got {C.dtype} {C.shape}")
@@ -2265,7 +2282,7 @@ def shift_scores_at(q, n):
 
 def _check_centers_for(q, centers, who):
     C = np.asarray(centers)
-    P = max(q.shape[0] - 1, 0)
+    P = q.shape[0] if who.endswith("_pairs") else max(q.shape[0] - 1, 0)
     if C.dtype.kind not in "iu" or C.shape not in ((P, 2), (P,) + q.shape[1:3] + (2,)):
         raise ValueError(f"{who}: centers must be integers of shape {(P, 2)} or {(P,) + q.shape[1:3] + (2,)}, got "
                          f"{C.dtype} {C.shape}")
@@ -2327,10 +2344,23 @@ def section_shifts_coarse_to_fine(volume, tile=128, radius=4, levels=3, min_corr
     that is not a uint8 [z, y, x], a bad tile, radius, min_corr, min_decided or chunk_bytes, levels outside 1...6 or so
     many that the coarsest section's shorter side min(Y, X) >> levels falls below 4 radius, a `coarse` of another
     length, shape or dtype."""
+    def measure(v, C, tile, r, st):                              # looked up at the call: the tests' stand-ins apply
+        return section_shift_sums_at(v, C, tile, r, chunk_bytes=chunk_bytes, device=device, stats=st)
+    s, q, n, C = _shifts_pyramid(volume, None, measure, tile, radius, levels, min_corr, min_decided, coarse, chunk_bytes,
+                                 device, stats, "section_shifts_coarse_to_fine")
+    return CoarseShifts(s, q, n, C)
+
+
+def _shifts_pyramid(volume, pairs, measure, tile, radius, levels, min_corr, min_decided, coarse, chunk_bytes, device,
+                    stats, who):
+    """The one coarse-to-fine driver: section_shifts_coarse_to_fine (`pairs` None: section z against z + 1 for every z)
+    and section_shifts_bridged (`pairs` int64[P, 2], checked).  `measure(V_l, C, tile, r, st)` returns level l's sums
+    with a row per pair in front (further rows are ignored).  The pyramid holds the sections that a pair spans, run by
+    run; all of them for the chain of every z.  Returns (Shifts, q, n, C) of level 0."""
     _check_u8(volume)
     vshape = tuple(int(v) for v in volume.shape)
     if len(vshape) != 3 or min(vshape) < 1:
-        raise ValueError(f"section_shifts_coarse_to_fine needs a non-empty volume [z, y, x], got shape {vshape}")
+        raise ValueError(f"{who} needs a non-empty volume [z, y, x], got shape {vshape}")
     th, tw = _clahe_tile(tile)
     r = _shift_radius(radius)
     L = _index(levels, "levels")
@@ -2361,6 +2391,8 @@ def section_shifts_coarse_to_fine(volume, tile=128, radius=4, levels=3, min_corr
     elif len(coarse) != L or any(tuple(c.shape) != s or getattr(c, "dtype", None) != np.uint8
                                  for c, s in zip(coarse, shapes[1:])):
         raise ValueError(f"coarse must be {L} uint8 array-likes of shapes {shapes[1:]}")
+    P = vshape[0] - 1 if pairs is None else pairs.shape[0]
+    runs = [(0, vshape[0])] if pairs is None else _pair_runs(pairs)  # the sections the searches read, as z runs
     total = {"read_s": 0.0, "chunks": 0}
 
     def counted(st):
@@ -2368,28 +2400,330 @@ def section_shifts_coarse_to_fine(volume, tile=128, radius=4, levels=3, min_corr
         total["chunks"] += st.get("chunks", 0)
     V = [volume]
     for l in range(L):
-        st = {}
-        V.append(volume_rescale(V[l], (2, 2, 1), out=coarse[l], chunk_bytes=chunk_bytes, device=device, stats=st))
-        counted(st)
+        if runs == [(0, vshape[0])]:
+            st = {}
+            V.append(volume_rescale(V[l], (2, 2, 1), out=coarse[l], chunk_bytes=chunk_bytes, device=device, stats=st))
+            counted(st)
+            continue
+        V.append(np.zeros(shapes[l + 1], np.uint8) if coarse[l] is None else coarse[l])
+        for z0, z1 in runs:                                      # z is kept: output section z is source section z
+            st = {}
+            V[l + 1][z0:z1] = volume_rescale(V[l], (2, 2, 1), start=(0, 0, z0), size=shapes[l + 1][:0:-1] + (z1 - z0,),
+                                             chunk_bytes=chunk_bytes, device=device, stats=st)
+            counted(st)
     s = None
     for l in range(L, -1, -1):
         gy, gx = clahe_grid(shapes[l], (th, tw))
-        C = np.zeros((vshape[0] - 1, gy, gx, 2), np.int64)
+        C = np.zeros((P, gy, gx, 2), np.int64)
         if s is not None:                                        # ceil(ceil(Y / 2) / th) = ceil(gy / 2): i // 2 exists
             i, j = np.arange(gy)[:, None] // 2, np.arange(gx)[None, :] // 2
             C[...] = 2 * np.where(s.decided[:, i, j, None], s.tiles[:, i, j], s.pairs[:, None, None, :])
         st = {}
-        q = section_shift_sums_at(V[l], C, (th, tw), r, chunk_bytes=chunk_bytes, device=device, stats=st)
+        q = measure(V[l], C, (th, tw), r, st)
         counted(st)
-        n = shift_counts_at(shapes[l], (th, tw), r, C)
-        s = section_shifts_at(q, n, C, min_corr)
+        n = _shift_counts(shapes[l], (th, tw), r, C)
+        s = _section_shifts(_pair_scores(q[:P], n), C, min_corr)[0]
     few = s.decided.sum(axis=(1, 2)) < min_decided * s.decided.shape[1] * s.decided.shape[2]
     unresolved = sorted(set(s.unresolved) | set(int(z) for z in np.nonzero(few)[0]))
-    pairs = s.pairs.copy()
-    pairs[np.array(unresolved, np.int64)] = 0
+    found = s.pairs.copy()
+    found[np.array(unresolved, np.int64)] = 0
     if stats is not None:
         stats.update(total)
-    return CoarseShifts(Shifts(pairs, s.tiles, s.peak, s.decided, unresolved), q, n, C)
+    return Shifts(found, s.tiles, s.peak, s.decided, unresolved), q, n, C
+
+
+SHIFT_MAX_LAG = 8                # b - a of a pair of section_shift_sums_pairs, at most: bounds a chunk's dense read slab
+
+
+class SectionPairs(NamedTuple):
+    """section_pairs' plan: `pairs` int64[P, 2] the pairs (a, b) of good sections to measure, ascending, `broken` the list
+    of the gaps (a, b) between consecutive good sections that are longer than max_lag and stay unmeasured."""
+    pairs: np.ndarray
+    broken: list
+
+
+def section_pairs(Z, skip=(), max_lag=4):
+    """Which sections of a stack of `Z` to measure against each other when the sections `skip` are bad (black, charged,
+    folded, foreign: suspect_sections, find_defects or the user's own list): consecutive GOOD sections (g_k, g_(k+1)),
+    so a bad section is bridged by its neighbours, lag 2 and more, instead of breaking the chain twice.  Gaps longer
+    than `max_lag` (1...SHIFT_MAX_LAG) are listed in `broken` and not measured: sections too far apart in z share too
+    little.  No `skip` gives (z, z + 1) for every z.  Host only; ValueError for a Z or an entry of skip that is no
+    integer, an entry outside [0, Z), max_lag outside 1...8."""
+    Z = _index(Z, "Z")
+    if Z < 0:
+        raise ValueError(f"Z must not be negative, got {Z}")
+    lag = _index(max_lag, "max_lag")
+    if not 1 <= lag <= SHIFT_MAX_LAG:
+        raise ValueError(f"max_lag must lie in 1...{SHIFT_MAX_LAG}, got {lag}")
+    try:
+        bad = {_index(z, "a skipped section") for z in skip}
+    except TypeError:
+        raise ValueError(f"skip must be a list of sections, got {skip!r}")
+    if any(not 0 <= z < Z for z in bad):
+        raise ValueError(f"skip names sections outside [0, {Z}): {sorted(z for z in bad if not 0 <= z < Z)}")
+    good = [z for z in range(Z) if z not in bad]
+    steps = list(zip(good[:-1], good[1:]))
+    pairs = np.array([p for p in steps if p[1] - p[0] <= lag], np.int64).reshape(-1, 2)
+    return SectionPairs(pairs, [p for p in steps if p[1] - p[0] > lag])
+
+
+def _check_pairs(pairs, Z):
+    """int64[P, 2] of `pairs`: integers (a, b) with 0 <= a < b < Z and b - a <= SHIFT_MAX_LAG, sorted lexicographically,
+    none twice.  ValueError otherwise."""
+    p = np.asarray(pairs)
+    if p.ndim != 2 or p.shape[1] != 2 or p.dtype.kind not in "iu":
+        raise ValueError(f"pairs must be integers of shape [P, 2], got {p.dtype} {p.shape}")
+    p = p.astype(np.int64)
+    bad = np.nonzero((p[:, 0] < 0) | (p[:, 0] >= p[:, 1]) | (p[:, 1] >= Z) | (p[:, 1] - p[:, 0] > SHIFT_MAX_LAG))[0]
+    if bad.size:
+        k = int(bad[0])
+        raise ValueError(f"pairs[{k}] = {tuple(int(v) for v in p[k])} is not 0 <= a < b < {Z} with b - a <= {SHIFT_MAX_LAG}")
+    d = np.diff(p, axis=0)
+    bad = np.nonzero((d[:, 0] < 0) | ((d[:, 0] == 0) & (d[:, 1] <= 0)))[0]
+    if bad.size:
+        k = int(bad[0]) + 1
+        raise ValueError(f"pairs must be sorted by (a, b) without duplicates: pairs[{k}] = {tuple(int(v) for v in p[k])} "
+                         f"follows {tuple(int(v) for v in p[k - 1])}")
+    return p
+
+
+def _pair_runs(pairs):
+    """The sections that the sorted `pairs` span, as the list of maximal z runs (z0, z1) of the union of [a, b]."""
+    runs = []
+    for a, b in pairs.tolist():
+        if runs and a <= runs[-1][1] - 1:
+            runs[-1][1] = max(runs[-1][1], b + 1)
+        else:
+            runs.append([a, b + 1])
+    return [tuple(r) for r in runs]
+
+
+def zshift_chunks_pairs(vol_shape, pairs, radius, reach=(0, 0), chunk_bytes=None, rank=0, world_size=1):
+    """Cut the list `pairs` (_check_pairs' rules: section_pairs' list, or any part of it) over a volume of shape
+    `vol_shape` [z, y, x] into chunks for section_shift_sums_pairs.  Returns this rank's list of
+    ((k0, k1), (y0, y1), read slab): the list entries [k0, k1), their core rows, and the (z, y, x) (lo, hi) box to read.
+    A chunk is a run of consecutive entries, each of which starts inside the sections the run already spans (a <= the
+    largest b so far: a chain; a gap in z ends the run, so nothing between two distant bridges is read); its read slab
+    is the DENSE box of the sections [a_k0, largest b], all rows -- skipped sections inside it are read and ignored,
+    which SHIFT_MAX_LAG bounds -- and holds at most `chunk_bytes` bytes (HIST_CHUNK_BYTES when None): as many entries
+    as fit.  Where even one pair's b - a + 1 sections exceed the budget, the pair alone is cut into runs of core rows:
+    its b - a + 1 sections of as many rows as fit next to their halo, radius - lo rows below and radius + hi above for
+    `reach` = (lo, hi) (zshift_chunks_at's), one core row at the least.  Chunks are in list order and go round-robin to
+    the ranks.  With section_pairs(Z).pairs the read slabs are zshift_chunks_at's, less its last one where that holds
+    the last section alone.  Pure host function; ValueError as zshift_chunks_at, and _check_pairs'."""
+    r = _shift_radius(radius)
+    lo, hi = _shift_reach(reach)
+    budget = HIST_CHUNK_BYTES if chunk_bytes is None else int(chunk_bytes)
+    if budget < 1:
+        raise ValueError(f"chunk_bytes must be positive, got {chunk_bytes}")
+    if not 0 <= rank < world_size:
+        raise ValueError(f"rank {rank} is outside [0, {world_size})")
+    (_, Z), (_, ny), (_, nx) = hist_box(vol_shape)
+    p = _check_pairs(pairs, Z).tolist()
+    chunks, k = [], 0
+    while k < len(p):
+        a, top = p[k]
+        if (top - a + 1) * ny * nx > budget:                     # one pair in runs of rows
+            ky = max(1, budget // ((top - a + 1) * nx) - (2 * r + hi - lo))
+            chunks += [((k, k + 1), (y, min(y + ky, ny)), ((a, top + 1), (max(y - r + lo, 0), min(y + ky + r + hi, ny)),
+                                                           (0, nx))) for y in range(0, ny, ky)]
+            k += 1
+            continue
+        k1 = k + 1
+        while k1 < len(p) and p[k1][0] <= top and (max(top, p[k1][1]) - a + 1) * ny * nx <= budget:
+            top = max(top, p[k1][1])
+            k1 += 1
+        chunks.append(((k, k1), (0, ny), ((a, top + 1), (0, ny), (0, nx))))
+        k = k1
+    return chunks[rank::world_size]
+
+
+def shift_counts_pairs(vol_shape, tile, radius, centers):
+    """np.int64 n[P, gy, gx, R, R]: shift_counts_at for a list of P pairs: the number of terms of
+    section_shift_sums_pairs' q[k, i, j, dy + radius, dx + radius] with `centers` integers [P, 2] or [P, gy, gx, 2]
+    within SHIFT_MAX_CENTER -- geometry only, so which sections a pair names does not enter.  Pure host function."""
+    r = _shift_radius(radius)
+    th, tw = _clahe_tile(tile)
+    C = np.asarray(centers)
+    return _shift_counts(vol_shape, (th, tw), r, _centers_table(C, C.shape[0] if C.ndim else 0,
+                                                                *clahe_grid(vol_shape, (th, tw))))
+
+
+def section_shift_sums_pairs(volume, pairs, centers=None, tile=128, radius=4, chunk_bytes=None, rank=0, world_size=1,
+                             device=None, stats=None):
+    """section_shift_sums_at over an explicit list of section pairs: np.int64 q[P, gy, gx, R, R, 5] -- a row per PAIR,
+    none for "the last section" -- of the uint8 `volume` [z, y, x], where for pair k = (a, b) of `pairs`, the centre
+    (cy, cx) = C[k, i, j] and the local offset (dy, dx) in [-radius, radius]^2 the sums run over the voxels (y, x) of
+    tile (i, j) whose partner (y + cy + dy, x + cx + dx) lies inside the section, v = volume[a, y, x],
+    w = volume[b, y + cy + dy, x + cx + dx]:
+      q[k, i, j, dy + radius, dx + radius] = (sum v, sum v v, sum w, sum w w, sum v w)
+    `pairs` is integers [P, 2], sorted by (a, b), none twice, 0 <= a < b < Z and b - a <= SHIFT_MAX_LAG = 8:
+    section_pairs' bridges over bad sections, or a few pairs to measure again; only the sections they span are read.
+    `centers` is None (zero) or integers [P, 2] or [P, gy, gx, 2] within SHIFT_MAX_CENTER.  The number of terms is
+    shift_counts_pairs'.  Exact integers that numpy reproduces bit for bit; the pairs (z, z + 1) give
+    section_shift_sums_at's rows.
+
+    The pass is section_shift_sums_at's, over zshift_chunks_pairs with reach = the least and the largest cy (and 0):
+    both tables go to the device once, as int32; one tem_u8_zshift_tiles_pairs launch per chunk, given the tables'
+    rows of the chunk's first pair; the accumulator holds all P rows and is read back once where P*gy*gx*R*R*40 bytes
+    are at most CLAHE_ACC_BYTES, else one chunk's rows, read back and added on the host per chunk; ranks' results add.
+    `stats` receives `read_s` and `chunks`.  ValueError, before any GPU work: as section_shift_sums, a volume that is
+    not [z, y, x], _check_pairs' and shift_centers' rules."""
+    _check_u8(volume)
+    th, tw = _clahe_tile(tile)
+    r = _shift_radius(radius)
+    if len(volume.shape) != 3:
+        raise ValueError(f"section_shift_sums_pairs needs a volume [z, y, x], got shape {tuple(volume.shape)}")
+    gy, gx = clahe_grid(volume.shape, (th, tw))
+    (_, Z), (_, Y), _ = hist_box(volume.shape)
+    pr = _check_pairs(pairs, Z)
+    P = pr.shape[0]
+    C = _centers_table(np.zeros((P, 2), np.int64) if centers is None else centers, P, gy, gx)
+    lo = hi = cx_max = 0
+    if C.size:
+        lo, hi = min(int(C[..., 0].min()), 0), max(int(C[..., 0].max()), 0)
+        cx_max = int(np.abs(C[..., 1]).max())
+    chunks = zshift_chunks_pairs(volume.shape, pr, r, (lo, hi), chunk_bytes, rank, world_size)
+    p = _SlabPass([volume], [hist_box(volume.shape)], chunk_bytes, rank, world_size, device, slabs=[s for _, _, s in chunks])
+    R = 2 * r + 1
+    sec, shape = gy * gx * R * R * 5, (gy, gx, R, R, 5)
+    out = np.zeros((P,) + shape, np.int64)
+    if not chunks:
+        if stats is not None:
+            stats.update(p.st)
+        return out
+    lib = H.require_gpu()
+    whole = P * sec * 8 <= CLAHE_ACC_BYTES
+    with p.streaming():
+        most = max(k1 - k0 for (k0, k1), _, _ in chunks)
+        acc = torch.zeros((P if whole else most, sec), dtype=torch.int64, device=p.dev)
+        table = torch.from_numpy(pr.astype(np.int32)).to(p.dev)                  # both uploaded once
+        ctable = torch.from_numpy(C.astype(np.int32).reshape(P, -1)).to(p.dev)
+        for k, ((s0, _), (y0, _), _), d, (src,) in p:
+            (k0, k1), (c0, c1), _ = chunks[k]
+            if not whole:
+                acc[:k1 - k0].zero_()
+            where = acc.data_ptr() + 8 * sec * (k0 if whole else 0)
+            _lib.check(lib.tem_u8_zshift_tiles_pairs(src.data_ptr(), *d, s0, k1 - k0, table.data_ptr() + 8 * k0, c0 - y0,
+                                                     c1 - y0, y0, Y, th, tw, gy, gx, r,
+                                                     ctable.data_ptr() + 8 * gy * gx * k0, lo, hi, cx_max, where,
+                                                     p.compute.cuda_stream), "tem_u8_zshift_tiles_pairs")
+            if not whole:                                        # this chunk's pairs, added on the host
+                out[k0:k1] += acc[:k1 - k0].cpu().numpy().reshape((k1 - k0,) + shape)
+        if whole:
+            out = acc.cpu().numpy().reshape((P,) + shape)        # the one read-back
+    if stats is not None:
+        stats.update(p.st)
+    return out
+
+
+def shift_scores_pairs(q, n):
+    """shift_scores for section_shift_sums_pairs' `q` and shift_counts_pairs' `n`, both with a row per pair:
+    float64 c[P, gy, gx, R, R] indexed by the LOCAL offset.  Host only."""
+    return _pair_scores(*_check_shift_sums(q, n, "shift_scores_pairs"))
+
+
+def section_shifts_pairs(q, n, centers, min_corr=0.1):
+    """section_shifts_at for a list of P pairs, from section_shift_sums_pairs' `q`, shift_counts_pairs' `n` and the
+    `centers` ([P, 2] or [P, gy, gx, 2] integers) of that search.  Host only, and the same rules: row k of the Shifts
+    speaks of pair k -- `pairs[k]` is the (dy, dx) by which section b shows what section a shows at (y, x) --, and
+    `unresolved` lists indices k into the pair list."""
+    q, n = _check_shift_sums(q, n, "section_shifts_pairs")
+    C = _check_centers_for(q, centers, "section_shifts_pairs")
+    min_corr = _unit(min_corr, "min_corr", False)
+    return _section_shifts(_pair_scores(q, n), C, min_corr)[0]
+
+
+def shift_subpixel_pairs(q, n, centers, min_corr=0.1):
+    """shift_subpixel_at for a list of P pairs: SubShifts with a row per pair.  fit_section_maps takes it unchanged,
+    chain_pairs puts the fitted maps back onto the stack."""
+    q, n = _check_shift_sums(q, n, "section_shifts_pairs")
+    C = _check_centers_for(q, centers, "section_shifts_pairs")
+    min_corr = _unit(min_corr, "min_corr", False)
+    return _shift_subpixel(_pair_scores(q, n), C, min_corr)
+
+
+class BridgedShifts(NamedTuple):
+    """section_shifts_bridged's verdict, all of the finest level and with a row per pair of `pairs` int64[P, 2]:
+    `shifts` the Shifts in total offsets (`unresolved` holds indices into `pairs`), `q` and `n` the sums and counts of
+    the last search and `centers` int64[P, gy, gx, 2] where it was centred -- what shift_subpixel_pairs takes."""
+    pairs: np.ndarray
+    shifts: Shifts
+    q: np.ndarray
+    n: np.ndarray
+    centers: np.ndarray
+
+
+def section_shifts_bridged(volume, pairs, tile=128, radius=4, levels=3, min_corr=0.1, min_decided=0.5, coarse=None,
+                           chunk_bytes=None, device=None, stats=None):
+    """section_shifts_coarse_to_fine over a list of section pairs (section_pairs: the good sections on either side of a
+    bad one are measured against each other): the same pyramid and rescales, the same centre rule per pair and tile --
+    2 tiles_(l+1)[k, i // 2, j // 2] where that coarse tile is decided, else 2 pairs_(l+1)[k] --, the same
+    `min_decided` verdict, with section_shift_sums_pairs as the device pass.  `pairs` follows its rules.  Returns
+    BridgedShifts(pairs, shifts, q, n, centers); for section_pairs(Z).pairs these are section_shifts_coarse_to_fine's
+    shifts, q[:-1], n and centers exactly.  chain_pairs spreads `shifts.pairs` (or maps or fields fitted per pair) back
+    onto the Z - 1 consecutive pairs for shift_positions and its siblings.
+
+    The list may hold only the bridges, to mend an alignment that exists: then only the sections that these pairs span
+    are read, rescaled and searched, run by run; every other section of the pyramid, and of `coarse`, is left as it
+    is.  `coarse`, `chunk_bytes`, `device`, `stats` and every ValueError are section_shifts_coarse_to_fine's, plus
+    section_shift_sums_pairs' rules for the pairs, before any GPU work."""
+    _check_u8(volume)
+    vshape = tuple(int(v) for v in volume.shape)
+    if len(vshape) != 3 or min(vshape) < 1:
+        raise ValueError(f"section_shifts_bridged needs a non-empty volume [z, y, x], got shape {vshape}")
+    pr = _check_pairs(pairs, vshape[0])
+
+    def measure(v, C, tile, r, st):                              # looked up at the call, as its sibling
+        return section_shift_sums_pairs(v, pr, C, tile, r, chunk_bytes=chunk_bytes, device=device, stats=st)
+    s, q, n, C = _shifts_pyramid(volume, pr, measure, tile, radius, levels, min_corr, min_decided, coarse, chunk_bytes,
+                                 device, stats, "section_shifts_bridged")
+    return BridgedShifts(pr, s, q, n, C)
+
+
+def suspect_sections(unresolved, Z):
+    """The sections of a stack of `Z` that no neighbour resembles, from the `unresolved` pairs z (section z against
+    z + 1) of section_shifts_coarse_to_fine or section_shifts: those both of whose adjoining pairs, z - 1 and z, are
+    unresolved; for sections 0 and Z - 1 their one pair decides.  A sorted list: the `skip` of section_pairs where
+    nobody supplies one.  Host only; ValueError for entries that are no integers in [0, Z - 1)."""
+    Z = _index(Z, "Z")
+    u = {_index(z, "an unresolved pair") for z in unresolved}
+    if any(not 0 <= z < Z - 1 for z in u):
+        raise ValueError(f"unresolved names pairs outside [0, {max(Z - 1, 0)}): {sorted(z for z in u if not 0 <= z < Z - 1)}")
+    return [z for z in range(Z) if Z > 1 and (z == 0 or z - 1 in u) and (z == Z - 1 or z in u)]
+
+
+def chain_pairs(pairs, values, Z, base=None):
+    """Per-pair values of a pair list spread back onto the Z - 1 consecutive pairs (z, z + 1) of the stack, for
+    shift_positions, section_maps, section_fields and what follows them, which are used unchanged.  `values` has a row
+    per pair of `pairs` ([P, 2], _check_pairs' rules): integer shifts [P, 2], maps [P, 2, 3] or fields [P, ny, nx, 2].
+    One rule for all three: start from `base` ([Z - 1, ...]; None: the identity -- zero shifts and fields, the map
+    [[1, 0, 0], [0, 1, 0]]); pair (a, b) writes its value at index a and the identity at a + 1 ... b - 1.  So a skipped
+    section takes the position of the good section above it, and the sections above a bridge sit where the bridge
+    says.  What no pair covers -- section_pairs' `broken` gaps -- keeps the base; to leave an unresolved pair at the
+    identity, drop its row or give the identity for it.  Returns a new array of the values' dtype.  Host only;
+    ValueError for values of another shape, a base of another shape or dtype."""
+    Z = _index(Z, "Z")
+    pr = _check_pairs(pairs, Z)
+    v = np.asarray(values)
+    is_map = v.ndim == 3 and v.shape[1:] == (2, 3)
+    if v.shape[:1] != (pr.shape[0],) or v.dtype.kind not in "iuf" or \
+            not (is_map or (v.ndim == 2 and v.shape[1] == 2) or (v.ndim == 4 and v.shape[3] == 2)):
+        raise ValueError(f"values must be numbers of shape [{pr.shape[0]}, 2], [{pr.shape[0]}, 2, 3] or "
+                         f"[{pr.shape[0]}, ny, nx, 2], got {v.dtype} {v.shape}")
+    ident = np.zeros(v.shape[1:], v.dtype)
+    if is_map:
+        ident[0, 0] = ident[1, 1] = 1
+    shape = (max(Z - 1, 0),) + v.shape[1:]
+    if base is None:
+        out = np.broadcast_to(ident, shape).copy()
+    else:
+        out = np.array(base)
+        if out.shape != shape or out.dtype != v.dtype:
+            raise ValueError(f"base must be {v.dtype} of shape {shape}, got {out.dtype} {out.shape}")
+    for (a, b), val in zip(pr.tolist(), v):
+        out[a], out[a + 1:b] = val, ident
+    return out
 
 
 class SectionFits(NamedTuple):
