@@ -742,6 +742,31 @@ int tem_u8_warp_field_direct(const uint8_t *src, int32_t D, int32_t H, int32_t W
                              const int64_t *maps_dev, const int32_t *field_host, const int32_t *field_dev, int32_t ny,
                              int32_t nx, int32_t ky, int32_t kx, int32_t fill, int32_t nearest, tem_stream_t stream);
 
+/* tem_u8_warp_affine and tem_u8_warp_field from a source block that is cut in x as well (utils.predict_volume's and
+ * predict_cube's warp= keyword: a prediction chunk's footprint is a box inside sections many times its width, and whole
+ * rows would read X / BW times its bytes).  No second definition: the two above are the only ones.  src[D][BH][BW] is
+ * the dense box of rows [sy0, sy0 + BH) and columns [sx0, sx0 + BW) of D sections of VY x VX; dst, the output box,
+ * maps_host / maps_dev, fill, nearest and stream are tem_u8_warp_affine's.  field_host == field_dev == null: no field
+ * (ny, nx, ky, kx are ignored) and the bytes are tem_u8_warp_affine's; otherwise the field pointers and the lattice are
+ * tem_u8_warp_field's, and so are the bytes.  With sx0 = 0 and BW = VX the call is the one above, bit for bit.
+ * The kernels are the same two with the hull of a tile's taps clamped to the box on all four sides and the row stride
+ * BW (a row's shift in LDS is (a0 + r (BW & 3)) & 3): a load touches only naturally aligned 4-byte words that hold at
+ * least one byte of the box -- the word before its first byte and the word after its last are such words --, every
+ * coefficient, node and tap is clamped as before, and a device table that disagrees with the host's gives wrong bytes,
+ * never a read outside the box or LDS.  Any alignment of src, dst, BW, sx0 and OW.
+ * TEM_EINVAL, without a launch: everything the entry of the same form refuses (one null field pointer of the two
+ * included), a box that leaves the section (sy0 + BH > VY, sx0 + BW > VX, a negative origin), and an output block one
+ * of whose taps of weight above 0 lies outside the box in y or in x.  The row rule is the one above; the column rule is
+ * its mirror image: the extremes of the affine sx at the block's four corners, plus the least and the largest U[..][1]
+ * over the nodes of the cells the block meets, fx cut to [0, 256 (VX - 1)], the columns fx_min >> 8 ... (fx_max >> 8) +
+ * (fx_max & 255 ? 1 : 0), for nearest (fx + 128) >> 8.  A plane wholly outside the section in y or in x needs nothing.
+ * utils.warp_source_box states the same rule on the host, so a box it planned is never refused. */
+int tem_u8_warp_box(const uint8_t *src, int32_t D, int32_t BH, int32_t BW, int32_t sy0, int32_t sx0, int32_t VY,
+                    int32_t VX, uint8_t *dst, int32_t OD, int32_t OH, int32_t OW, int32_t oy0, int32_t ox0,
+                    const int64_t *maps_host, const int64_t *maps_dev, const int32_t *field_host,
+                    const int32_t *field_dev, int32_t ny, int32_t nx, int32_t ky, int32_t kx, int32_t fill,
+                    int32_t nearest, tem_stream_t stream);
+
 /* Random augmentation of one cached sample (datasets.py:123-155) with host-drawn parameters:
  *   dst = reverse(transpose(src, perm = (p0,p1,p2)), dims with f_k != 0) * scale + shift
  * src is a dense single-channel (D,H,W) volume (2-D: D == 1, p0 must be 0); dst has extents

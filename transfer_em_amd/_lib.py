@@ -166,6 +166,8 @@ _SIGS = {
                          [C.c_int32] * 6 + [C.c_void_p],
     "tem_u8_warp_field_direct": [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p] * 4 +
                                 [C.c_int32] * 6 + [C.c_void_p],
+    "tem_u8_warp_box": [C.c_void_p] + [C.c_int32] * 7 + [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p] * 4 +
+                       [C.c_int32] * 6 + [C.c_void_p],
     "tem_u8_clahe": [C.c_void_p] + [C.c_int32] * 6 + [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p],
     "tem_augment_f32": [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                         C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p],

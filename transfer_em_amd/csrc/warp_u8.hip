@@ -19,6 +19,11 @@
 // coefficient to the limits, the hull to the source block and to the LDS array, and every tap to the staged hull: a
 // device table that disagrees with the host's gives wrong bytes, never a load outside the block or LDS.  With a table
 // that agrees every clamp is the identity.
+//
+// Box.  tem_u8_warp_box runs the same kernels with BOX = true: the source is a block cut in x as well, the columns
+// [sx0, sx0 + BW) of the section, with the row stride BW.  The hull is then clamped to the block on all four sides, a row
+// is BW bytes from the one above it (the shift (a0 + r (BW & 3)) & 3), and nothing else changes: the section's width
+// still decides what is inside.  With BOX = false both are compiled out and the block is whole rows of the section.
 #include <algorithm>
 
 #include "tem_common.h"
@@ -42,6 +47,8 @@ struct warp_args {
   int tiles_x, tiles;                                  // tiles along x, tiles per plane
   const long long *maps;                               // device: [D][6] = a_yy, a_yx, b_y, a_xy, a_xx, b_x in 2^-16
   int fill;
+  int64_t BW;                                          // BOX kernels: the block's columns [sx0, sx0 + BW), its row stride
+  int sx0;
 };
 
 __host__ __device__ inline int64_t wp_min(int64_t a, int64_t b) { return a < b ? a : b; }
@@ -55,7 +62,7 @@ __host__ __device__ inline void warp_range(int64_t ay, int64_t ax, int64_t b, in
   lo = s + wp_min(ey, 0) + wp_min(ex, 0), hi = s + wp_max(ey, 0) + wp_max(ex, 0);
 }
 
-template <bool NEAREST>
+template <bool NEAREST, bool BOX>
 __global__ __launch_bounds__(WARP_THREADS) void u8_warp_affine_k(warp_args g) {
   __shared__ uint32_t hull[WARP_HY * WARP_HDW];
   const uint8_t *hb = (const uint8_t *)hull;
@@ -79,19 +86,21 @@ __global__ __launch_bounds__(WARP_THREADS) void u8_warp_affine_k(warp_args g) {
   const int64_t FY = 256 * ((int64_t)g.VY - 1), FX = 256 * (g.W - 1);
   const bool any = ((syhi + 128) >> 8) >= 0 && ((sylo + 128) >> 8) <= FY && ((sxhi + 128) >> 8) >= 0 && ((sxlo + 128) >> 8) <= FX;
   const int64_t top = g.sy0 + g.H - 1;
+  const int64_t sx0 = BOX ? g.sx0 : 0, BW = BOX ? g.BW : g.W;                     // the block's first column, its row stride
   const int64_t hy0 = wp_clamp(wp_clamp((sylo + 128) >> 16, 0, g.VY - 1), g.sy0, top);
   const int64_t hy1 = wp_clamp(wp_clamp(((syhi + 128) >> 16) + 1, 0, g.VY - 1), hy0, top);
-  const int64_t hx0 = wp_clamp((sxlo + 128) >> 16, 0, g.W - 1);
-  const int64_t hx1 = wp_clamp(((sxhi + 128) >> 16) + 1, hx0, g.W - 1);
+  int64_t hx0 = wp_clamp((sxlo + 128) >> 16, 0, g.W - 1);
+  int64_t hx1 = wp_clamp(((sxhi + 128) >> 16) + 1, hx0, g.W - 1);
+  if (BOX) hx0 = wp_clamp(hx0, sx0, sx0 + BW - 1), hx1 = wp_clamp(hx1, hx0, sx0 + BW - 1);
   const int nr = (int)wp_min(hy1 - hy0 + 1, WARP_HY), nc = (int)wp_min(hx1 - hx0 + 1, WARP_HX);
 
-  const uint8_t *row0 = g.src + ((int64_t)d * g.H + (hy0 - g.sy0)) * g.W + hx0;   // the hull's first byte
-  const int a0 = (int)((uintptr_t)row0 & 3), w3 = (int)(g.W & 3);                // a row's shift: (a0 + r w3) & 3
+  const uint8_t *row0 = g.src + ((int64_t)d * g.H + (hy0 - g.sy0)) * BW + (hx0 - sx0);   // the hull's first byte
+  const int a0 = (int)((uintptr_t)row0 & 3), w3 = (int)(BW & 3);                 // a row's shift: (a0 + r w3) & 3
   if (any) {
     const int k = tid & 31;
     for (int r = tid >> 5; r < nr; r += WARP_THREADS / 32) {
       const int sh = (a0 + r * w3) & 3;
-      if (4 * k < sh + nc) hull[r * WARP_HDW + k] = *(const uint32_t *)(row0 + (int64_t)r * g.W - sh + 4 * k);
+      if (4 * k < sh + nc) hull[r * WARP_HDW + k] = *(const uint32_t *)(row0 + (int64_t)r * BW - sh + 4 * k);
     }
     __syncthreads();
   }
@@ -139,47 +148,6 @@ __global__ __launch_bounds__(WARP_THREADS) void u8_warp_affine_k(warp_args g) {
 }
 
 }  // namespace
-
-extern "C" int tem_u8_warp_affine(const uint8_t *src, int32_t D, int32_t H, int32_t W, int32_t sy0, int32_t VY, uint8_t *dst,
-                                  int32_t OD, int32_t OH, int32_t OW, int32_t oy0, int32_t ox0, const int64_t *maps_host,
-                                  const int64_t *maps_dev, int32_t fill, int32_t nearest, tem_stream_t stream) {
-  TEM_CLEAR_ERR();
-  if (!src || !dst || !maps_host || !maps_dev || D < 1 || H < 1 || W < 1 || VY < 1 || OD != D || OH < 1 || OW < 1 || sy0 < 0 ||
-      oy0 < 0 || ox0 < 0 || fill < 0 || fill > 255 || (nearest != 0 && nearest != 1))
-    return TEM_EINVAL;
-  if ((int64_t)sy0 + H > VY || (int64_t)oy0 + OH > VY || (int64_t)ox0 + OW > W) return TEM_EINVAL;
-  const int64_t tiles_x = ((int64_t)OW + WARP_TX - 1) / WARP_TX, tiles_y = ((int64_t)OH + WARP_TY - 1) / WARP_TY;
-  if (tiles_x * tiles_y > WARP_MAX_WGS || tiles_x * tiles_y * D > WARP_MAX_WGS) return TEM_EINVAL;
-  const int64_t FY = 256 * ((int64_t)VY - 1), FX = 256 * ((int64_t)W - 1);
-  for (int64_t d = 0; d < D; ++d) {
-    const int64_t *m = maps_host + 6 * d;
-    if (m[0] < WARP_ONE - WARP_DEV || m[0] > WARP_ONE + WARP_DEV || m[4] < WARP_ONE - WARP_DEV || m[4] > WARP_ONE + WARP_DEV ||
-        m[1] < -WARP_DEV || m[1] > WARP_DEV || m[3] < -WARP_DEV || m[3] > WARP_DEV || m[2] < -WARP_MAX_B || m[2] > WARP_MAX_B ||
-        m[5] < -WARP_MAX_B || m[5] > WARP_MAX_B)
-      return TEM_EINVAL;
-    // the rows that the block's inside voxels read with a weight above 0, bounded from its corners
-    int64_t sylo, syhi, sxlo, sxhi;
-    warp_range(m[0], m[1], m[2], oy0, OH, ox0, OW, sylo, syhi);
-    warp_range(m[3], m[4], m[5], oy0, OH, ox0, OW, sxlo, sxhi);
-    const int64_t fylo = wp_max((sylo + 128) >> 8, 0), fyhi = wp_min((syhi + 128) >> 8, FY);
-    if (fylo > fyhi || wp_max((sxlo + 128) >> 8, 0) > wp_min((sxhi + 128) >> 8, FX)) continue;    // every voxel is outside
-    const int64_t lo = nearest ? (fylo + 128) >> 8 : fylo >> 8;
-    const int64_t hi = nearest ? (fyhi + 128) >> 8 : (fyhi >> 8) + ((fyhi & 255) ? 1 : 0);
-    if (lo < sy0 || hi >= (int64_t)sy0 + H) return TEM_EINVAL;
-  }
-  warp_args g;
-  g.src = src, g.H = H, g.W = W, g.sy0 = sy0, g.VY = VY;
-  g.dst = dst, g.OH = OH, g.OW = OW, g.oy0 = oy0, g.ox0 = ox0;
-  g.tiles_x = (int)tiles_x, g.tiles = (int)(tiles_x * tiles_y);
-  g.maps = (const long long *)maps_dev, g.fill = fill;
-  const unsigned wgs = (unsigned)(g.tiles * (int64_t)D);
-  if (nearest)
-    hipLaunchKernelGGL(u8_warp_affine_k<true>, dim3(wgs), dim3(WARP_THREADS), 0, (hipStream_t)stream, g);
-  else
-    hipLaunchKernelGGL(u8_warp_affine_k<false>, dim3(wgs), dim3(WARP_THREADS), 0, (hipStream_t)stream, g);
-  TEM_CHECK_LAUNCH();
-  return TEM_OK;
-}
 
 // ------------------------------------------------------------------------------------------------ tem_u8_warp_field
 // tem_u8_warp_field: the affine map plus a displacement field on a lattice of 2^ky x 2^kx pixels (include/tem_hip.h has
@@ -271,7 +239,7 @@ __device__ inline void fld_store(const warp_args &g, const fld_plane &p, int ly,
   }
 }
 
-template <bool NEAREST>
+template <bool NEAREST, bool BOX>
 __global__ __launch_bounds__(WARP_THREADS) void u8_warp_field_k(field_args f) {
   __shared__ uint32_t hull[FLD_HY * FLD_HDW];
   __shared__ int nodes[FLD_NR * FLD_NC * 2];
@@ -292,14 +260,16 @@ __global__ __launch_bounds__(WARP_THREADS) void u8_warp_field_k(field_args f) {
   const int64_t FY = 256 * ((int64_t)g.VY - 1), FX = 256 * (g.W - 1);
   const bool any = ((syhi + 128) >> 8) >= 0 && ((sylo + 128) >> 8) <= FY && ((sxhi + 128) >> 8) >= 0 && ((sxlo + 128) >> 8) <= FX;
   const int64_t top = g.sy0 + g.H - 1;
+  const int64_t sx0 = BOX ? g.sx0 : 0, BW = BOX ? g.BW : g.W;                       // the block's first column, its row stride
   const int64_t hy0 = wp_clamp(wp_clamp((sylo + 128) >> 16, 0, g.VY - 1), g.sy0, top);
   const int64_t hy1 = wp_clamp(wp_clamp(((syhi + 128) >> 16) + 1, 0, g.VY - 1), hy0, top);
-  const int64_t hx0 = wp_clamp((sxlo + 128) >> 16, 0, g.W - 1);
-  const int64_t hx1 = wp_clamp(((sxhi + 128) >> 16) + 1, hx0, g.W - 1);
+  int64_t hx0 = wp_clamp((sxlo + 128) >> 16, 0, g.W - 1);
+  int64_t hx1 = wp_clamp(((sxhi + 128) >> 16) + 1, hx0, g.W - 1);
+  if (BOX) hx0 = wp_clamp(hx0, sx0, sx0 + BW - 1), hx1 = wp_clamp(hx1, hx0, sx0 + BW - 1);
   const int nr = (int)wp_min(hy1 - hy0 + 1, FLD_HY), nc = (int)wp_min(hx1 - hx0 + 1, FLD_HX);
 
-  const uint8_t *row0 = g.src + ((int64_t)p.d * g.H + (hy0 - g.sy0)) * g.W + hx0;  // the hull's first byte
-  const int a0 = (int)((uintptr_t)row0 & 3), w3 = (int)(g.W & 3);                  // a row's shift: (a0 + r w3) & 3
+  const uint8_t *row0 = g.src + ((int64_t)p.d * g.H + (hy0 - g.sy0)) * BW + (hx0 - sx0);   // the hull's first byte
+  const int a0 = (int)((uintptr_t)row0 & 3), w3 = (int)(BW & 3);                   // a row's shift: (a0 + r w3) & 3
   if (any) {
     if (tid < FLD_NR * FLD_NC * 2) {                                               // the nodes of the cells the tile meets
       const int r = tid / (FLD_NC * 2), c = (tid >> 1) % FLD_NC;
@@ -309,7 +279,7 @@ __global__ __launch_bounds__(WARP_THREADS) void u8_warp_field_k(field_args f) {
     const int k = tid & 31;
     for (int r = tid >> 5; r < nr; r += WARP_THREADS / 32) {
       const int sh = (a0 + r * w3) & 3;
-      if (4 * k < sh + nc) hull[r * FLD_HDW + k] = *(const uint32_t *)(row0 + (int64_t)r * g.W - sh + 4 * k);
+      if (4 * k < sh + nc) hull[r * FLD_HDW + k] = *(const uint32_t *)(row0 + (int64_t)r * BW - sh + 4 * k);
     }
     __syncthreads();
   }
@@ -411,66 +381,98 @@ __global__ __launch_bounds__(WARP_THREADS) void u8_warp_field_direct_k(field_arg
   fld_store(g, p, ly, lx, packed);
 }
 
-// the checks of tem_u8_warp_field, and its launch arguments
-int fld_check(const uint8_t *src, int32_t D, int32_t H, int32_t W, int32_t sy0, int32_t VY, uint8_t *dst, int32_t OD, int32_t OH,
-              int32_t OW, int32_t oy0, int32_t ox0, const int64_t *maps_host, const int64_t *maps_dev, const int32_t *field_host,
-              const int32_t *field_dev, int32_t ny, int32_t nx, int32_t ky, int32_t kx, int32_t fill, int32_t nearest,
-              field_args &f) {
-  if (!src || !dst || !maps_host || !maps_dev || !field_host || !field_dev || D < 1 || H < 1 || W < 1 || VY < 1 || OD != D ||
-      OH < 1 || OW < 1 || sy0 < 0 || oy0 < 0 || ox0 < 0 || fill < 0 || fill > 255 || (nearest != 0 && nearest != 1))
+// The checks of every entry, and the launch arguments.  The source block is the rows [sy0, sy0 + BH) and the columns
+// [sx0, sx0 + BW) of D sections of VY x VX; the entries that take whole rows give sx0 = 0 and BW = VX, for which the
+// column rule below holds by itself (fx is cut to the section).  `field`: the map plus a displacement field, else
+// field_host, field_dev, ny, nx, ky and kx are not looked at.
+int warp_check(const uint8_t *src, int32_t D, int32_t BH, int32_t BW, int32_t sy0, int32_t sx0, int32_t VY, int32_t VX,
+               uint8_t *dst, int32_t OD, int32_t OH, int32_t OW, int32_t oy0, int32_t ox0, const int64_t *maps_host,
+               const int64_t *maps_dev, bool field, const int32_t *field_host, const int32_t *field_dev, int32_t ny, int32_t nx,
+               int32_t ky, int32_t kx, int32_t fill, int32_t nearest, field_args &f) {
+  if (!src || !dst || !maps_host || !maps_dev || D < 1 || BH < 1 || BW < 1 || VY < 1 || VX < 1 || OD != D || OH < 1 || OW < 1 ||
+      sy0 < 0 || sx0 < 0 || oy0 < 0 || ox0 < 0 || fill < 0 || fill > 255 || (nearest != 0 && nearest != 1))
     return TEM_EINVAL;
-  if ((int64_t)sy0 + H > VY || (int64_t)oy0 + OH > VY || (int64_t)ox0 + OW > W) return TEM_EINVAL;
-  if (ky < FLD_KMIN || ky > FLD_KMAX || kx < FLD_KMIN || kx > FLD_KMAX) return TEM_EINVAL;
-  if (ny != ((VY - 1) >> ky) + 2 || nx != ((W - 1) >> kx) + 2) return TEM_EINVAL;
+  if ((int64_t)sy0 + BH > VY || (int64_t)sx0 + BW > VX || (int64_t)oy0 + OH > VY || (int64_t)ox0 + OW > VX) return TEM_EINVAL;
+  if (field) {
+    if (!field_host || !field_dev) return TEM_EINVAL;
+    if (ky < FLD_KMIN || ky > FLD_KMAX || kx < FLD_KMIN || kx > FLD_KMAX) return TEM_EINVAL;
+    if (ny != ((VY - 1) >> ky) + 2 || nx != ((VX - 1) >> kx) + 2) return TEM_EINVAL;
+  }
   const int64_t tiles_x = ((int64_t)OW + WARP_TX - 1) / WARP_TX, tiles_y = ((int64_t)OH + WARP_TY - 1) / WARP_TY;
   if (tiles_x * tiles_y > WARP_MAX_WGS || tiles_x * tiles_y * D > WARP_MAX_WGS) return TEM_EINVAL;
-  const int64_t FY = 256 * ((int64_t)VY - 1), FX = 256 * ((int64_t)W - 1);
-  const int64_t dymax = (int64_t)WARP_DEV << ky, dxmax = (int64_t)WARP_DEV << kx;
-  const int ia = oy0 >> ky, ib = ((oy0 + OH - 1) >> ky) + 1, ja = ox0 >> kx, jb = ((ox0 + OW - 1) >> kx) + 1;
+  const int64_t FY = 256 * ((int64_t)VY - 1), FX = 256 * ((int64_t)VX - 1);
   for (int64_t d = 0; d < D; ++d) {
     const int64_t *m = maps_host + 6 * d;
     if (m[0] < WARP_ONE - WARP_DEV || m[0] > WARP_ONE + WARP_DEV || m[4] < WARP_ONE - WARP_DEV || m[4] > WARP_ONE + WARP_DEV ||
         m[1] < -WARP_DEV || m[1] > WARP_DEV || m[3] < -WARP_DEV || m[3] > WARP_DEV || m[2] < -WARP_MAX_B || m[2] > WARP_MAX_B ||
         m[5] < -WARP_MAX_B || m[5] > WARP_MAX_B)
       return TEM_EINVAL;
-    const int32_t *U = field_host + d * ny * nx * 2;
-    for (int i = 0; i < ny; ++i)
-      for (int j = 0; j < nx; ++j)
-        for (int e = 0; e < 2; ++e) {
-          const int64_t u = U[((int64_t)i * nx + j) * 2 + e];
-          if (u < -FLD_MAX || u > FLD_MAX) return TEM_EINVAL;
-          if (i + 1 < ny && std::llabs((int64_t)U[((int64_t)(i + 1) * nx + j) * 2 + e] - u) > dymax) return TEM_EINVAL;
-          if (j + 1 < nx && std::llabs((int64_t)U[((int64_t)i * nx + j + 1) * 2 + e] - u) > dxmax) return TEM_EINVAL;
-        }
-    // the rows that the block's inside voxels can read: the affine extremes at its corners plus the least and largest
-    // node of the cells it meets (the interpolated value lies between them; every shift is monotone)
-    int64_t ulo[2] = {FLD_MAX, FLD_MAX}, uhi[2] = {-FLD_MAX, -FLD_MAX};
-    for (int i = ia; i <= ib; ++i)
-      for (int j = ja; j <= jb; ++j)
-        for (int e = 0; e < 2; ++e) {
-          const int64_t u = U[((int64_t)i * nx + j) * 2 + e];
-          ulo[e] = wp_min(ulo[e], u), uhi[e] = wp_max(uhi[e], u);
-        }
+    int64_t ulo[2] = {0, 0}, uhi[2] = {0, 0};
+    if (field) {
+      const int64_t dymax = (int64_t)WARP_DEV << ky, dxmax = (int64_t)WARP_DEV << kx;
+      const int32_t *U = field_host + d * ny * nx * 2;
+      for (int i = 0; i < ny; ++i)
+        for (int j = 0; j < nx; ++j)
+          for (int e = 0; e < 2; ++e) {
+            const int64_t u = U[((int64_t)i * nx + j) * 2 + e];
+            if (u < -FLD_MAX || u > FLD_MAX) return TEM_EINVAL;
+            if (i + 1 < ny && std::llabs((int64_t)U[((int64_t)(i + 1) * nx + j) * 2 + e] - u) > dymax) return TEM_EINVAL;
+            if (j + 1 < nx && std::llabs((int64_t)U[((int64_t)i * nx + j + 1) * 2 + e] - u) > dxmax) return TEM_EINVAL;
+          }
+      // the least and largest node of the cells the block meets (the interpolated value lies between them; every shift
+      // is monotone)
+      const int ia = oy0 >> ky, ib = ((oy0 + OH - 1) >> ky) + 1, ja = ox0 >> kx, jb = ((ox0 + OW - 1) >> kx) + 1;
+      ulo[0] = ulo[1] = FLD_MAX, uhi[0] = uhi[1] = -FLD_MAX;
+      for (int i = ia; i <= ib; ++i)
+        for (int j = ja; j <= jb; ++j)
+          for (int e = 0; e < 2; ++e) {
+            const int64_t u = U[((int64_t)i * nx + j) * 2 + e];
+            ulo[e] = wp_min(ulo[e], u), uhi[e] = wp_max(uhi[e], u);
+          }
+    }
+    // the rows and columns that the block's inside voxels can read with a weight above 0: the affine extremes at its
+    // corners plus the field's range, cut to the section
     int64_t sylo, syhi, sxlo, sxhi;
     warp_range(m[0], m[1], m[2], oy0, OH, ox0, OW, sylo, syhi);
     warp_range(m[3], m[4], m[5], oy0, OH, ox0, OW, sxlo, sxhi);
     sylo += ulo[0], syhi += uhi[0], sxlo += ulo[1], sxhi += uhi[1];
     const int64_t fylo = wp_max((sylo + 128) >> 8, 0), fyhi = wp_min((syhi + 128) >> 8, FY);
-    if (fylo > fyhi || wp_max((sxlo + 128) >> 8, 0) > wp_min((sxhi + 128) >> 8, FX)) continue;    // every voxel is outside
+    const int64_t fxlo = wp_max((sxlo + 128) >> 8, 0), fxhi = wp_min((sxhi + 128) >> 8, FX);
+    if (fylo > fyhi || fxlo > fxhi) continue;                                                     // every voxel is outside
     const int64_t lo = nearest ? (fylo + 128) >> 8 : fylo >> 8;
     const int64_t hi = nearest ? (fyhi + 128) >> 8 : (fyhi >> 8) + ((fyhi & 255) ? 1 : 0);
-    if (lo < sy0 || hi >= (int64_t)sy0 + H) return TEM_EINVAL;
+    if (lo < sy0 || hi >= (int64_t)sy0 + BH) return TEM_EINVAL;
+    const int64_t cl = nearest ? (fxlo + 128) >> 8 : fxlo >> 8;
+    const int64_t ch = nearest ? (fxhi + 128) >> 8 : (fxhi >> 8) + ((fxhi & 255) ? 1 : 0);
+    if (cl < sx0 || ch >= (int64_t)sx0 + BW) return TEM_EINVAL;
   }
   warp_args &g = f.w;
-  g.src = src, g.H = H, g.W = W, g.sy0 = sy0, g.VY = VY;
+  g.src = src, g.H = BH, g.W = VX, g.sy0 = sy0, g.VY = VY, g.BW = BW, g.sx0 = sx0;
   g.dst = dst, g.OH = OH, g.OW = OW, g.oy0 = oy0, g.ox0 = ox0;
   g.tiles_x = (int)tiles_x, g.tiles = (int)(tiles_x * tiles_y);
   g.maps = (const long long *)maps_dev, g.fill = fill;
-  f.field = field_dev, f.ny = ny, f.nx = nx, f.ky = ky, f.kx = kx;
+  f.field = field ? field_dev : nullptr, f.ny = ny, f.nx = nx, f.ky = ky, f.kx = kx;
   return TEM_OK;
 }
 
 }  // namespace
+
+extern "C" int tem_u8_warp_affine(const uint8_t *src, int32_t D, int32_t H, int32_t W, int32_t sy0, int32_t VY, uint8_t *dst,
+                                  int32_t OD, int32_t OH, int32_t OW, int32_t oy0, int32_t ox0, const int64_t *maps_host,
+                                  const int64_t *maps_dev, int32_t fill, int32_t nearest, tem_stream_t stream) {
+  TEM_CLEAR_ERR();
+  field_args f;
+  const int rc = warp_check(src, D, H, W, sy0, 0, VY, W, dst, OD, OH, OW, oy0, ox0, maps_host, maps_dev, false, nullptr, nullptr,
+                            0, 0, 0, 0, fill, nearest, f);
+  if (rc != TEM_OK) return rc;
+  const unsigned wgs = (unsigned)(f.w.tiles * (int64_t)D);
+  if (nearest)
+    hipLaunchKernelGGL((u8_warp_affine_k<true, false>), dim3(wgs), dim3(WARP_THREADS), 0, (hipStream_t)stream, f.w);
+  else
+    hipLaunchKernelGGL((u8_warp_affine_k<false, false>), dim3(wgs), dim3(WARP_THREADS), 0, (hipStream_t)stream, f.w);
+  TEM_CHECK_LAUNCH();
+  return TEM_OK;
+}
 
 extern "C" int tem_u8_warp_field(const uint8_t *src, int32_t D, int32_t H, int32_t W, int32_t sy0, int32_t VY, uint8_t *dst,
                                  int32_t OD, int32_t OH, int32_t OW, int32_t oy0, int32_t ox0, const int64_t *maps_host,
@@ -478,14 +480,14 @@ extern "C" int tem_u8_warp_field(const uint8_t *src, int32_t D, int32_t H, int32
                                  int32_t nx, int32_t ky, int32_t kx, int32_t fill, int32_t nearest, tem_stream_t stream) {
   TEM_CLEAR_ERR();
   field_args f;
-  const int rc = fld_check(src, D, H, W, sy0, VY, dst, OD, OH, OW, oy0, ox0, maps_host, maps_dev, field_host, field_dev, ny, nx,
-                           ky, kx, fill, nearest, f);
+  const int rc = warp_check(src, D, H, W, sy0, 0, VY, W, dst, OD, OH, OW, oy0, ox0, maps_host, maps_dev, true, field_host,
+                            field_dev, ny, nx, ky, kx, fill, nearest, f);
   if (rc != TEM_OK) return rc;
   const unsigned wgs = (unsigned)(f.w.tiles * (int64_t)D);
   if (nearest)
-    hipLaunchKernelGGL(u8_warp_field_k<true>, dim3(wgs), dim3(WARP_THREADS), 0, (hipStream_t)stream, f);
+    hipLaunchKernelGGL((u8_warp_field_k<true, false>), dim3(wgs), dim3(WARP_THREADS), 0, (hipStream_t)stream, f);
   else
-    hipLaunchKernelGGL(u8_warp_field_k<false>, dim3(wgs), dim3(WARP_THREADS), 0, (hipStream_t)stream, f);
+    hipLaunchKernelGGL((u8_warp_field_k<false, false>), dim3(wgs), dim3(WARP_THREADS), 0, (hipStream_t)stream, f);
   TEM_CHECK_LAUNCH();
   return TEM_OK;
 }
@@ -497,14 +499,38 @@ extern "C" int tem_u8_warp_field_direct(const uint8_t *src, int32_t D, int32_t H
                                         int32_t nearest, tem_stream_t stream) {
   TEM_CLEAR_ERR();
   field_args f;
-  const int rc = fld_check(src, D, H, W, sy0, VY, dst, OD, OH, OW, oy0, ox0, maps_host, maps_dev, field_host, field_dev, ny, nx,
-                           ky, kx, fill, nearest, f);
+  const int rc = warp_check(src, D, H, W, sy0, 0, VY, W, dst, OD, OH, OW, oy0, ox0, maps_host, maps_dev, true, field_host,
+                            field_dev, ny, nx, ky, kx, fill, nearest, f);
   if (rc != TEM_OK) return rc;
   const unsigned wgs = (unsigned)(f.w.tiles * (int64_t)D);
   if (nearest)
     hipLaunchKernelGGL(u8_warp_field_direct_k<true>, dim3(wgs), dim3(WARP_THREADS), 0, (hipStream_t)stream, f);
   else
     hipLaunchKernelGGL(u8_warp_field_direct_k<false>, dim3(wgs), dim3(WARP_THREADS), 0, (hipStream_t)stream, f);
+  TEM_CHECK_LAUNCH();
+  return TEM_OK;
+}
+
+extern "C" int tem_u8_warp_box(const uint8_t *src, int32_t D, int32_t BH, int32_t BW, int32_t sy0, int32_t sx0, int32_t VY,
+                               int32_t VX, uint8_t *dst, int32_t OD, int32_t OH, int32_t OW, int32_t oy0, int32_t ox0,
+                               const int64_t *maps_host, const int64_t *maps_dev, const int32_t *field_host,
+                               const int32_t *field_dev, int32_t ny, int32_t nx, int32_t ky, int32_t kx, int32_t fill,
+                               int32_t nearest, tem_stream_t stream) {
+  TEM_CLEAR_ERR();
+  const bool field = field_host || field_dev;                  // both null: the affine definition; one null is refused
+  field_args f;
+  const int rc = warp_check(src, D, BH, BW, sy0, sx0, VY, VX, dst, OD, OH, OW, oy0, ox0, maps_host, maps_dev, field, field_host,
+                            field_dev, ny, nx, ky, kx, fill, nearest, f);
+  if (rc != TEM_OK) return rc;
+  const dim3 wgs((unsigned)(f.w.tiles * (int64_t)D)), threads(WARP_THREADS);
+  if (field && nearest)
+    hipLaunchKernelGGL((u8_warp_field_k<true, true>), wgs, threads, 0, (hipStream_t)stream, f);
+  else if (field)
+    hipLaunchKernelGGL((u8_warp_field_k<false, true>), wgs, threads, 0, (hipStream_t)stream, f);
+  else if (nearest)
+    hipLaunchKernelGGL((u8_warp_affine_k<true, true>), wgs, threads, 0, (hipStream_t)stream, f.w);
+  else
+    hipLaunchKernelGGL((u8_warp_affine_k<false, true>), wgs, threads, 0, (hipStream_t)stream, f.w);
   TEM_CHECK_LAUNCH();
   return TEM_OK;
 }

@@ -2993,8 +2993,8 @@ def volume_warp(volume, maps, out=None, start=None, size=None, fill=0, nearest=F
     `read_s`, `write_s` and `chunks`.
 
     Elastic warps -- the map plus a smooth displacement field -- are volume_warp_field's.  Out of scope: resampling
-    along z, a warp= keyword on predict_cube / predict_volume (warp, then predict), and majority resampling of labels
-    (nearest is what masks get).
+    along z, and majority resampling of labels (nearest is what masks get).  predict_cube / predict_volume take the
+    same maps as warp=Warp(maps) and align on the way in, without the aligned copy.
 
     ValueError, before any GPU work: a volume that is not uint8 or not [z, y, x] (or one image), maps of a wrong shape
     or dtype or outside the limits, an ROI outside the volume, an `out` of another shape or dtype, a fill outside
@@ -3346,8 +3346,9 @@ def volume_warp_field(volume, maps, fields, spacing, out=None, start=None, size=
     their taps (field_chunks); host thread -> pinned -> H2D -> one tem_u8_warp_field launch per slab -> D2H -> host
     write, on double buffers, in the order write(k), read(k + 2) on the one host thread; both tables are uploaded once.
 
-    Out of scope: resampling along z, a warp= keyword on predict_cube / predict_volume (warp, then predict), majority
-    resampling of labels (nearest is what masks get), and fields finer than 16 px.
+    Out of scope: resampling along z, majority resampling of labels (nearest is what masks get), and fields finer than
+    16 px.  predict_cube / predict_volume take the same maps and fields as warp=Warp(maps, fields, spacing) and align
+    on the way in, without the aligned copy.
 
     ValueError, before any GPU work: everything volume_warp refuses, a bad spacing, fields of a wrong shape or dtype
     or outside the limits."""
@@ -3401,6 +3402,151 @@ def volume_warp_field(volume, maps, fields, spacing, out=None, start=None, size=
     if stats is not None:
         stats.update(p.st)
     return out
+
+
+WARP_MAX_WGS = (1 << 24) - 1     # workgroups of one warp launch: 16 x 64 outputs of one plane each
+
+
+class Warp(NamedTuple):
+    """What the `warp=` keyword of predict_cube / predict_volume takes: how every section of a uint8 volume [z, y, x] is
+    aligned ahead of the prediction.  `maps` are volume_warp's -- float [Z, 2, 3] (section_maps') or quantize_maps' int64
+    [Z, 6], one image also takes one map --; `fields` with `spacing` are volume_warp_field's -- float or quantize_field's
+    int32 [Z, ny, nx, 2] on the lattice of `spacing` (field_grid) --, both None for the maps alone; `fill` (0...255) is
+    what a voxel reads whose position lies outside its section.  The prediction is that of the same call on
+    volume_warp_field(volume, maps, fields, spacing, fill=fill) (volume_warp without a field), which is never made."""
+    maps: object
+    fields: object = None
+    spacing: object = None
+    fill: int = 0
+
+
+class _WarpSpec(NamedTuple):
+    """_check_warp's result: `M` np.int64[Z, 6], `U` np.int32[Z, ny, nx, 2] or None, the lattice (ny, nx, ky, kx), all 0
+    without a field, and `fill`."""
+    M: np.ndarray
+    U: object
+    ny: int
+    nx: int
+    ky: int
+    kx: int
+    fill: int
+
+
+def _check_warp(warp, vol_shape):
+    """None, or the _WarpSpec of `warp` (a Warp, or any (maps, fields, spacing, fill) tuple) for a volume of shape
+    `vol_shape` [z, y, x] or one image [y, x]: the tables that volume_warp / volume_warp_field compute with, through
+    _warp_table and _field_table, with their limits and messages.  ValueError also for fields without a spacing or a
+    spacing without fields, and a fill outside 0...255."""
+    if warp is None or isinstance(warp, _WarpSpec):
+        return warp
+    try:
+        maps, fields, spacing, fill = warp
+    except (TypeError, ValueError):
+        raise ValueError(f"warp must be None or a Warp (maps, fields, spacing, fill), got {type(warp).__name__}")
+    shape = tuple(int(v) for v in vol_shape)
+    if len(shape) not in (2, 3) or min(shape) < 1:
+        raise ValueError(f"warp needs a non-empty volume [z, y, x] or one image [y, x], got shape {shape}")
+    one = len(shape) == 2
+    Z = 1 if one else shape[0]
+    M = _warp_table(maps, Z, one)
+    if (fields is None) != (spacing is None):
+        raise ValueError("warp: fields and spacing go together, give both or neither")
+    U, ny, nx, ky, kx = None, 0, 0, 0, 0
+    if fields is not None:
+        ky, kx = _field_spacing(spacing)
+        ny, nx = field_grid(shape, spacing)
+        U = np.ascontiguousarray(_field_table(fields, (Z, ny, nx, 2), ky, kx, one))
+    fill = _index(fill, "fill")
+    if not 0 <= fill <= 255:
+        raise ValueError(f"fill must lie in 0...255, got {fill}")
+    return _WarpSpec(np.ascontiguousarray(M), U, ny, nx, ky, kx, fill)
+
+
+def _warp_span(w, c, z0, z1, y0, y1, x0, x1, n, nearest):
+    """tem_u8_warp_box's rule along one axis, per section of [z0, z1), for the outputs [y0, y1) x [x0, x1): c = 0 the
+    rows (sy, U[..][0]) of a section of n rows, c = 1 the columns (sx, U[..][1]) of one of n columns.  The extremes of
+    the affine position at the box's corners plus the least and largest node of the cells the box meets, the position
+    in 1/256 px cut to [0, 256 (n - 1)].  Returns (some, first, last): whether that interval is not empty, and the
+    first and last row (column) a tap of weight above 0 can lie in."""
+    a, b, t = (w.M[z0:z1, 3 * c + i] for i in range(3))
+    s, ey, ex = a * y0 + b * x0 + t, a * (y1 - 1 - y0), b * (x1 - 1 - x0)
+    lo, hi = s + np.minimum(ey, 0) + np.minimum(ex, 0), s + np.maximum(ey, 0) + np.maximum(ex, 0)
+    if w.U is not None:
+        u = w.U[z0:z1, y0 >> w.ky:((y1 - 1) >> w.ky) + 2, x0 >> w.kx:((x1 - 1) >> w.kx) + 2, c]
+        u = u.reshape(z1 - z0, -1).astype(np.int64)
+        lo, hi = lo + u.min(axis=1), hi + u.max(axis=1)
+    flo, fhi = np.maximum((lo + 128) >> 8, 0), np.minimum((hi + 128) >> 8, 256 * (n - 1))
+    if nearest:
+        return flo <= fhi, (flo + 128) >> 8, (fhi + 128) >> 8
+    return flo <= fhi, flo >> 8, (fhi >> 8) + ((fhi & 255) != 0)
+
+
+def warp_source_box(box, warp, vol_shape, nearest=False):
+    """((y0, y1), (x0, x1)): the rows and columns of the raw volume of shape `vol_shape` [z, y, x] that hold every tap
+    of the (z, y, x) (lo, hi) `box` of the volume aligned by `warp` (a Warp) -- what predict_volume(..., warp=) reads
+    for a chunk whose footprint is `box`, in place of the footprint itself.  It is the union over the box's sections of
+    exactly the rows and columns that tem_u8_warp_box demands of its source block (include/tem_hip.h: per section the
+    extremes of the affine position at the box's corners plus the least and largest node of the cells the box meets,
+    cut to the section; `nearest`: the rule for masks), so a launch on a planned box is never refused; a section that
+    is wholly outside by the same bounds demands nothing, and None is returned where every section is.  With identity
+    maps and a zero field the result is the box's own rows and columns, exactly.  Pure host function; ValueError for a
+    box that is empty or leaves the volume, and _check_warp's."""
+    vol_shape = tuple(int(v) for v in vol_shape)
+    if len(vol_shape) != 3 or min(vol_shape) < 1:
+        raise ValueError(f"warp_source_box takes a non-empty volume shape [z, y, x], got {vol_shape}")
+    w = _check_warp(warp, vol_shape)
+    if w is None:
+        raise ValueError("warp_source_box needs a Warp")
+    (z0, z1), (y0, y1), (x0, x1) = ((int(lo), int(hi)) for lo, hi in box)
+    if any(lo < 0 or hi > n or hi <= lo for (lo, hi), n in zip(((z0, z1), (y0, y1), (x0, x1)), vol_shape)):
+        raise ValueError(f"the box {tuple(box)} is empty or reaches outside the volume of shape {vol_shape}")
+    ys, ya, yb = _warp_span(w, 0, z0, z1, y0, y1, x0, x1, vol_shape[1], nearest)
+    xs, xa, xb = _warp_span(w, 1, z0, z1, y0, y1, x0, x1, vol_shape[2], nearest)
+    need = ys & xs
+    if not need.any():
+        return None
+    return ((int(ya[need].min()), int(yb[need].max()) + 1), (int(xa[need].min()), int(xb[need].max()) + 1))
+
+
+def _warp_footprints(chunks, max_gap, wp, vol_shape, with_mask):
+    """predict_volume's reads under `warp` (wp: _check_warp's spec), per chunk of `chunks` (chunk_plan's): (foot, sbox,
+    mbox).  foot[k] is the (z, y, x) (lo, hi) box of the aligned volume that chunk k's device block holds -- its
+    footprint `read`, with `max_gap` (repair's; 0 without) more sections on each side of z, clipped to the volume -- or
+    None for a chunk wholly outside the volume; sbox[k] = warp_source_box(foot[k]) the rows and columns of the raw
+    volume's same sections that are read for it (None: nothing is read, the block is `fill`); mbox[k] the same for a
+    Repair's mask, which is moved with nearest (None without a mask)."""
+    foot = [((max(c.read[0][0] - max_gap, 0), min(c.read[0][1] + max_gap, vol_shape[0])),) + tuple(c.read[1:])
+            if min(c.block) > 0 else None for c in chunks]
+    sbox = [None if f is None else warp_source_box(f, wp, vol_shape) for f in foot]
+    mbox = [None if f is None or not with_mask else warp_source_box(f, wp, vol_shape, nearest=True) for f in foot]
+    return foot, sbox, mbox
+
+
+class _Warper:
+    """The device leg of the `warp=` keyword, made once per call: the tables of `spec` (_check_warp's) are uploaded here,
+    once, and box() resamples sections of a dense source box into a dense output box on `stream` (tem_u8_warp_box)."""
+
+    def __init__(self, lib, spec, dev, stream, vol_shape):
+        self.lib, self.w, self.stream, self.vol = lib, spec, stream, tuple(vol_shape)
+        self.M_dev = torch.from_numpy(spec.M).to(dev)
+        self.U_dev = None if spec.U is None else torch.from_numpy(spec.U).to(dev)
+        self.per = spec.ny * spec.nx * 8                                     # bytes of one section's field
+
+    def box(self, src, dst, zs, source, out, nearest=False, fill=None):
+        """Sections [zs[0], zs[1]) of the volume: the dense block at `src` holds their rows and columns `source` =
+        ((y0, y1), (x0, x1)), the dense block at `dst` receives the aligned sections' box `out` of the same form.  One
+        launch per run of sections that stays within a launch's workgroups.  `fill` defaults to the spec's."""
+        (z0, z1), ((sy0, sy1), (sx0, sx1)), ((oy0, oy1), (ox0, ox1)) = zs, source, out
+        BH, BW, OH, OW, w = sy1 - sy0, sx1 - sx0, oy1 - oy0, ox1 - ox0, self.w
+        run = max(WARP_MAX_WGS // (-(-OH // 16) * -(-OW // 64)), 1)
+        for z in range(z0, z1, run):
+            n, field = min(run, z1 - z), w.U is not None
+            _lib.check(self.lib.tem_u8_warp_box(
+                src + (z - z0) * BH * BW, n, BH, BW, sy0, sx0, self.vol[1], self.vol[2], dst + (z - z0) * OH * OW, n, OH, OW,
+                oy0, ox0, w.M.ctypes.data + 48 * z, self.M_dev.data_ptr() + 48 * z,
+                w.U.ctypes.data + self.per * z if field else None, self.U_dev.data_ptr() + self.per * z if field else None,
+                w.ny, w.nx, w.ky, w.kx, w.fill if fill is None else fill, int(bool(nearest)), self.stream),
+                "tem_u8_warp_box")
 
 
 def _check_compare(compare, vol_shape, stats):
@@ -3742,7 +3888,8 @@ def clahe_volume(volume, clahe, out=None, start=None, size=None, chunk_bytes=Non
 
 def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=False, outdimsize=None, buffer=None,
                  rank=0, world_size=1, tile_batch=None, boundary="zeros", ensemble=None, mips=None, lut=None,
-                 histogram=False, stats=None, clahe=None, compare=None, repair=None, spread=None, spread_gain=8.0):
+                 histogram=False, stats=None, clahe=None, warp=None, compare=None, repair=None, spread=None,
+                 spread_gain=8.0):
     """Predict the subvolume [start, start+size) (x,y,z order as in the reference) of a uint8
     array `volume` indexed [z, y, x].  Voxels outside the array read as 0 (the reference fetches
     them from the store) or, with boundary="reflect" / "edge", the voxel that `fold` names on every axis: the result
@@ -3843,7 +3990,23 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
     gives an all-zero map.  When `stats` is a dict, stats["spread_histogram"] receives the map's np.int64[256]
     histogram over the ROI's voxels, counted on the device as `histogram` counts the prediction.  `spread` without
     `ensemble`, another shape or dtype, a read-only array and a `spread_gain` that is not a finite number above 0 raise
-    ValueError before any GPU work."""
+    ValueError before any GPU work.
+
+    warp=None reads the volume as it is and runs the launches above.  warp = a Warp (per-section maps, optionally
+    displacement fields on a lattice, a fill) aligns the sections first: the uploaded volume is resampled once into a
+    second device buffer of its shape (tem_u8_warp_box over whole sections, in runs of sections that stay within a
+    launch's workgroups; the raw buffer is then dropped), ahead of `repair`, `clahe` and `lut`, and the result is, bit
+    for bit, that of the same call on A = volume_warp_field(volume, maps, fields, spacing, fill=fill) (volume_warp
+    without fields), for 3-D and 2-D models, one image, and every boundary, ensemble, mips, lut, clahe, compare, repair,
+    spread, tile_batch and rank split.  A has the volume's shape, so `start`, `size` and the boundary's folding are
+    unchanged.  Frames, one rule: what has the volume's shape and is an input -- `volume`, and a Repair's `mask` --
+    lives in the raw frame and goes through the warp (the mask with nearest=True and fill 0, as volume_warp_field(mask,
+    ..., nearest=True) moves it); what is indexed by section or belongs to the result -- Repair.sections, the rows of
+    a [Z, 256] `lut`, ClaheTables, `compare`'s ground truth, `spread` and the return values -- lives in the aligned
+    frame.  Order on the device: warp, repair, clahe, lut, gather.  fetch_input returns what the network saw.
+    _check_warp's ValueErrors (maps or fields of a wrong shape or dtype or outside volume_warp's and
+    volume_warp_field's limits, fields without a spacing, a fill outside 0...255, a volume that is not uint8) come
+    before any GPU work."""
     gen = getattr(model, "generator_g", None)
     is3d = getattr(gen, "is3d", True)
     syms = _check_ensemble(ensemble, is3d)
@@ -3855,6 +4018,9 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
     if repair is not None:
         _check_u8(volume)
     rp = _check_repair(repair, np.shape(volume))
+    if warp is not None:
+        _check_u8(volume)
+    wp = _check_warp(warp, np.shape(volume))
     histogram = _check_histogram(histogram, stats)
     compare = _check_compare(compare, np.shape(volume), stats)
     if outdimsize is None:
@@ -3869,7 +4035,7 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
                            world_size=world_size, tile_batch=tile_batch, boundary=boundary, ensemble=ensemble,
                            mips=mips, lut=lut, histogram=histogram, stats=stats, clahe=clahe,
                            compare=None if compare is None else np.asarray(compare)[None], repair=repair,
-                           spread=None if spread is None else spread[None], spread_gain=spread_gain)
+                           spread=None if spread is None else spread[None], spread_gain=spread_gain, warp=wp)
         one = lambda r: [v[0] for v in r] if isinstance(r, list) else r[0]
         return tuple(one(r) for r in res) if fetch_input else one(res)
     outdimsize, buffer, tpad, rois, index = _tile_plan(start, size, outdimsize, buffer, is3d)
@@ -3882,9 +4048,19 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
     vol = torch.from_numpy(vol_host).to(dev, non_blocking=True)          # ONE upload of the whole volume
     Z, Y, X = vol_host.shape
     stream = H.current_stream()
+    whole = ((0, Y), (0, X))
+    if wp is not None:                                                   # first of all: the aligned volume, A, once
+        warper = _Warper(lib, wp, dev, stream, (Z, Y, X))
+        raw, vol = vol, torch.empty_like(vol)
+        warper.box(raw.data_ptr(), vol.data_ptr(), (0, Z), whole, whole)
+        del raw
     prepare = _Prepare(lib, cl, lut, dev, stream, repair=rp)
-    if rp is not None:                                                   # first: one launch, the core is the whole volume
+    if rp is not None:                                                   # then: one launch, the core is the whole volume
         mask_dev = None if rp.mask is None else torch.from_numpy(np.ascontiguousarray(rp.mask, dtype=np.uint8)).to(dev)
+        if wp is not None and mask_dev is not None:                      # the mask lives in the raw frame: nearest, fill 0
+            raw, mask_dev = mask_dev, torch.empty_like(mask_dev)
+            warper.box(raw.data_ptr(), mask_dev.data_ptr(), (0, Z), whole, whole, nearest=True, fill=0)
+            del raw
         prepare.repair_block(vol.data_ptr(), (Z, Y, X), 0, 0, Z, None if mask_dev is None else mask_dev.data_ptr())
     prepare.apply(vol.data_ptr(), (Z, Y, X), (0, 0, 0))                  # in place, once, behind the upload
     out_buffer = torch.zeros((rnd(z) if is3d else z, rnd(y), rnd(x)), dtype=torch.uint8, device=dev)
@@ -3933,7 +4109,7 @@ def predict_cube(volume, start, size, model, meanstd_x, meanstd_y, fetch_input=F
         # the reference returns the RAW uint8 block here after a detour (utils.py:122-125: the standardized float
         # tile is un-standardized, rescaled and truncated into a uint8 buffer -- the original bytes up to float
         # rounding); the bytes themselves are returned instead
-        if cl is not None or rp is not None:     # ... as the network saw them: the bytes the kernels left
+        if cl is not None or rp is not None or wp is not None:     # ... as the network saw them: the bytes the kernels left
             vol_host = vol.cpu().numpy()
         elif lut is not None:                    # ... remapped
             vol_host = _lut_host(vol_host, lut)
@@ -4083,8 +4259,8 @@ def chunk_plan(start, size, outdimsize, buffer, vol_shape, chunk_tiles, rank=0, 
 
 def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, chunk_tiles=None, tile_batch=None,
                    outdimsize=None, buffer=None, rank=0, world_size=1, stats=None, boundary="zeros", ensemble=None,
-                   mips=None, lut=None, histogram=False, clahe=None, compare=None, repair=None, spread=None,
-                   spread_gain=8.0):
+                   mips=None, lut=None, histogram=False, clahe=None, warp=None, compare=None, repair=None,
+                   spread=None, spread_gain=8.0):
     """Out-of-core predict_cube: the subvolume [start, start+size) (x,y,z order) of a uint8 array-like `volume`
     indexed [z, y, x] (ndarray, np.memmap, h5py / zarr dataset: `.shape` and basic slicing are all it needs) is
     predicted chunk by chunk (chunk_plan) into `out`, a writable uint8 array-like of shape (size[2], size[1], size[0])
@@ -4168,7 +4344,22 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
     thread writes the chunk's `out_box` of S with the chunk's `out`.  stats["spread_histogram"] receives the map's
     np.int64[256] histogram: one more tem_u8_hist launch per chunk into one device accumulator, read back once; each rank
     reports its own chunks and the ranks' histograms add up.  One read thread, one output stream and no collective, as
-    before."""
+    before.
+
+    `warp` is predict_cube's (a Warp of the whole volume; its tables are uploaded once per call): the chunk plan and its
+    footprints stay as they are, but a footprint is no longer read, it is produced on the device.  Per chunk the host
+    thread reads the raw volume's box volume[rz0:rz1, sy0:sy1, sx0:sx1] -- the footprint's sections (with `repair`:
+    and its max_gap sections on each side of z) over warp_source_box of the footprint, the rows and columns that hold
+    every tap, cut in y and in x -- into the pinned double buffers; behind its H2D one tem_u8_warp_box launch on the
+    compute stream writes the aligned footprint into one device buffer that is reused in stream order, and the upload
+    buffer is released behind that launch.  A Repair's mask, which lives in the raw frame, is read likewise (the
+    planner's box for nearest) through the second input stream and moved by a second launch with nearest = 1 and fill
+    0.  repair_block, clahe, lut and every gather then get the footprint exactly as they get the uploaded one without
+    `warp`.  A footprint none of whose sections has a source (warp_source_box: None) is filled with `fill` without
+    reading the volume.  A voxel of A depends on its section's map and field alone, so the result does not depend on
+    the chunk: it equals predict_cube(warp=...)'s, i.e. that of the same call on the aligned volume, which is never
+    made.  `stats` gains `warp_read_voxels`, the voxels of the volume that were read, and `footprint_voxels`, the
+    voxels of the footprints they produced: their ratio is the read amplification."""
     gen = model.generator_g
     is3d = getattr(gen, "is3d", True)
     syms = _check_ensemble(ensemble, is3d)
@@ -4183,6 +4374,9 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
     if repair is not None:
         _check_u8(volume)
     rp = _check_repair(repair, tuple(volume.shape))
+    if warp is not None:
+        _check_u8(volume)
+    wp = _check_warp(warp, tuple(volume.shape))
     histogram = _check_histogram(histogram, stats)
     compare = _check_compare(compare, tuple(volume.shape), stats)
     lib = H.require_gpu()
@@ -4199,7 +4393,7 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
                        tile_batch=tile_batch, outdimsize=outdimsize, buffer=buffer, rank=rank, world_size=world_size,
                        stats=stats, boundary=boundary, ensemble=ensemble, mips=mips, lut=lut, histogram=histogram,
                        clahe=clahe, compare=None if compare is None else _OneSection(compare), repair=repair,
-                       spread=None if spread is None else _OneSection(spread), spread_gain=spread_gain)
+                       spread=None if spread is None else _OneSection(spread), spread_gain=spread_gain, warp=wp)
         return out
     vol_shape = tuple(int(v) for v in volume.shape)
     if len(vol_shape) != 3:
@@ -4216,6 +4410,8 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
     elif tuple(out.shape) != (size[2], size[1], size[0]):
         raise ValueError(f"out has shape {tuple(out.shape)}, expected {(size[2], size[1], size[0])}")
     st = {"read_s": 0.0, "write_s": 0.0, "chunks": len(chunks), "mips": L}
+    if wp is not None:
+        st["warp_read_voxels"] = st["footprint_voxels"] = 0
     if histogram:
         st["histogram"] = np.zeros(256, np.int64)
     if compare is not None:
@@ -4236,6 +4432,18 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
     rz = [(max(c.read[0][0] - R, 0), min(c.read[0][1] + R, vol_shape[0])) if min(c.block) > 0 else (0, 1) for c in chunks]
     rdims = [(z1 - z0,) + tuple(g[1:]) for (z0, z1), g in zip(rz, gdims)]
     in_bytes = [int(np.prod(g)) for g in rdims]
+    with_mask = rp is not None and rp.mask is not None
+    if wp is not None:
+        # with `warp` the block that is read is not the footprint (with its halo along z) but the box of the raw volume
+        # that holds its taps: sbox[k], the rows and columns of the same sections, or None where no section has any
+        foot, sbox, mbox = _warp_footprints(chunks, R, wp, vol_shape, with_mask)
+        sbytes = lambda boxes: [1 if b is None else (z1 - z0) * (b[0][1] - b[0][0]) * (b[1][1] - b[1][0])
+                                for b, (z0, z1) in zip(boxes, rz)]
+        foot_bytes, in_bytes, mask_bytes = in_bytes, sbytes(sbox), sbytes(mbox)
+        st["warp_read_voxels"] = sum(n for n, b in zip(in_bytes, sbox) if b is not None)
+        st["footprint_voxels"] = sum(n for n, f in zip(foot_bytes, foot) if f is not None)
+        if stats is not None:
+            stats.update(st)
     # a chunk's output block on the device and in pinned memory: its L + 1 levels back to back, level l at
     # lvl_off[k][l] with the dense dims lvl_dims[k][l] = c.dims divided by 2^l on the pooled axes (exact: dims are
     # whole tiles and outdimsize % 2^L == 0)
@@ -4276,8 +4484,26 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
                 dst[...] = 0
         return read_into
 
-    read_into = read_box(volume)
-    with_mask = rp is not None and rp.mask is not None
+    def read_source(src, boxes):        # host thread, with `warp`: the raw box that holds the footprint's taps
+        def read_into(k, flat):
+            if boxes[k] is not None:
+                (z0, z1), ((y0, y1), (x0, x1)) = rz[k], boxes[k]
+                flat.reshape(z1 - z0, y1 - y0, x1 - x0)[...] = src[z0:z1, y0:y1, x0:x1]
+        return read_into
+
+    read_into = read_box(volume) if wp is None else read_source(volume, sbox)
+    if wp is not None:                  # the aligned footprints, on the device: one buffer each, reused in stream order
+        warper = _Warper(lib, wp, dev, compute.cuda_stream, vol_shape)
+        foot_dev = torch.zeros(max(foot_bytes), dtype=torch.uint8, device=dev)
+        mask_foot = torch.zeros(max(foot_bytes), dtype=torch.uint8, device=dev) if with_mask else None
+
+    def align(k, buf, into, boxes, nearest, fill):      # compute stream: the footprint of chunk k from its raw box
+        if foot[k] is None:             # the stand-in zero byte of a chunk wholly outside the volume
+            into[:1].zero_()
+        elif boxes[k] is None:          # no section has a source: `fill`, nothing was read
+            into[:foot_bytes[k]].fill_(fill)
+        else:
+            warper.box(buf.data_ptr(), into.data_ptr(), rz[k], boxes[k], foot[k][1:], nearest, fill)
 
     def write_from(k, buf):             # host thread: the chunk's box of `out` (and of `spread`)
         c = chunks[k]
@@ -4296,27 +4522,37 @@ def predict_volume(volume, start, size, model, meanstd_x, meanstd_y, out=None, c
     outp = _OutputStream(out_bytes, write_from, dev, pool, st, own_buffers=True)
     with _InputStream(in_bytes, read_into, dev, pool, st) as inp, \
             (contextlib.nullcontext() if compare is None else _InputStream(gt_bytes, read_gt, dev, pool, st)) as gt_inp, \
-            (_InputStream(in_bytes, read_box(rp.mask), dev, pool, st) if with_mask else
-             contextlib.nullcontext()) as mask_inp, \
+            (contextlib.nullcontext() if not with_mask else
+             _InputStream(in_bytes, read_box(rp.mask), dev, pool, st) if wp is None else
+             _InputStream(mask_bytes, read_source(rp.mask, mbox), dev, pool, st)) as mask_inp, \
             outp:
         for k, c in enumerate(chunks):
-            src, dst = inp.get(k).data_ptr(), outp.device(k).data_ptr()
-            lo = tuple(r[0] for r in c.read)
+            in_buf, dst = inp.get(k), outp.device(k).data_ptr()
+            src, lo = in_buf.data_ptr(), tuple(r[0] for r in c.read)
             if with_mask:
                 mask_buf = mask_inp.get(k)
+            last_gather = lambda: inp.release(k, compute.record_event())
+            if wp is not None:                               # first of all: the aligned footprint, from the raw box
+                align(k, in_buf, foot_dev, sbox, False, wp.fill)
+                inp.release(k, compute.record_event())
+                src, last_gather = foot_dev.data_ptr(), None
+                if with_mask:
+                    align(k, mask_buf, mask_foot, mbox, True, 0)
+                    mask_inp.release(k, compute.record_event())
+                    mask_buf = mask_foot
             if rp is not None and min(c.block) > 0:          # first: the footprint is the core of the block that was read
                 c0 = lo[0] - rz[k][0]
                 prepare.repair_block(src, (rdims[k][0],) + tuple(c.block[1:]), rz[k][0], c0, c0 + c.block[0],
                                      mask_buf.data_ptr() if with_mask else None)
                 src += c0 * c.block[1] * c.block[2]          # ... and what everything behind it sees
-            if with_mask:
+            if with_mask and wp is None:
                 mask_inp.release(k, compute.record_event())
             prepare.apply(src, c.block, lo)                  # the footprint; never the stand-in zero byte
             t = 12 * int(first[k])
             # the staging buffer is free for the next upload once the chunk's last gather is enqueued
             sdst = None if gain is None else dst + int(lvl_off[k][-1])
             runner.run(src, gdims[k], lo, org.data_ptr() + t, idx.data_ptr() + t, len(c.tiles), nb, dst, c.dims,
-                       lambda: inp.release(k, compute.record_event()), sdst)
+                       last_gather, sdst)
             valid = tuple(hi - lo_ for lo_, hi in c.out_box)     # the chunk's part of the result
             if L:                                            # its pyramid, level by level behind its scatters
                 _pool_levels(lib, dst, c.dims, valid, L, is3d, [dst + int(o) for o in lvl_off[k][1:L + 1]],
@@ -4385,7 +4621,7 @@ def predict_ng_cube(location, start, size, model, meanstd_x, meanstd_y, cloudrun
     instead of a cloud path; `cloudrun` is accepted and ignored.  The signature is the reference's, so voxels outside
     the array always read 0 here: predict_cube(..., boundary="reflect" | "edge") mirrors or clamps at the faces.
     It takes no `mips` either: predict_cube(..., mips=L) returns the mip pyramid of the prediction; nor `lut`, `clahe`,
-    `compare`, `repair` or `spread`."""
+    `compare`, `repair`, `spread` or `warp`."""
     return predict_cube(_local_volume(location), start, size, model, meanstd_x, meanstd_y, fetch_input=fetch_input,
                         outdimsize=outdimsize, buffer=buffer)
 
@@ -4415,7 +4651,8 @@ def predict_volume_from_saved_model(volume, start, size, model_dir, out=None, **
     joint histogram of (ground truth, result), see compare_from_joint), repair (None, or a Repair: the volume's bad
     sections and voxels are filled along z on the device, ahead of clahe and lut) and spread / spread_gain (None, or a
     writable uint8 array-like of the result's shape that receives the map of the ensemble members' disagreement, see
-    predict_cube).
+    predict_cube) and warp (None, or a Warp: the sections are aligned on the device, chunk by chunk from the raw box
+    that holds a footprint's taps, ahead of repair, clahe and lut).
     The reference's signatures, predict_ng_cube and predict_cube_from_saved_model, take none of these keywords; they
     run unensembled and return the full-resolution array alone."""
     model = _load_saved(model_dir)
