@@ -574,6 +574,48 @@ int tem_u8_zcorr_tiles(const uint8_t *src, int32_t D, int32_t H, int32_t W, int3
                        int32_t x_org, int32_t th, int32_t tw, int32_t gy, int32_t gx, uint64_t *sums,
                        tem_stream_t stream);
 
+/* tem_u8_zcorr_tiles with nlag partners instead of one (utils.section_lag_sums -> lag_scores -> section_spacing: how
+ * fast the correlation of a section with those above it decays with the lag is how far the sections sit apart along
+ * z).  The tile grid, the block src[D][H][W] at (y_org, x_org), the core [c0, c1), the alignments, the loads, the adds,
+ * the argument that no partial overflows and the refusals are tem_u8_zcorr_tiles'; nlag lies in 1...8.  For every core
+ * plane d and every voxel of value v in tile (i, j), with v+k the voxel at (d + k, y, x):
+ *   q = sums + (((d - c0) * gy + i) * gx + j) * (3 + nlag)
+ *   q[0] += v     q[1] += v v     q[2] += 1     q[2 + k] += v v+k  (k = 1...nlag, only if d + k < D)
+ * The caller lets the block reach nlag planes past the core, or to the volume's last section.  With nlag = 1 the four
+ * quantities are tem_u8_zcorr_tiles', in another column order.  A thread sums at most 64 voxels of a plane and a
+ * workgroup is given at most 16384 (nlag <= 4) or 8192 (above) voxels of a plane.
+ * TEM_EINVAL, without a launch: what tem_u8_zcorr_tiles refuses, and nlag outside 1...8.  TEM_EUNSUPPORTED: 2^24
+ * workgroups or more (one per tile of the block, run of rows of about 1024 or 512 16-byte pieces, and run of up to
+ * 24 + 8 nlag core planes; their 256 threads then stay below 2^32 per launch).  An empty core launches nothing. */
+int tem_u8_zcorr_lags(const uint8_t *src, int32_t D, int32_t H, int32_t W, int32_t c0, int32_t c1, int32_t y_org,
+                      int32_t x_org, int32_t th, int32_t tw, int32_t gy, int32_t gx, int32_t nlag, uint64_t *sums,
+                      tem_stream_t stream);
+
+/* A uint8 volume resampled along z through a table of taps (utils.volume_resample_z: sections whose measured
+ * positions are uneven, brought onto an even grid).  The definition, once: V[VZ][H][W] is the volume, the output has NZ
+ * sections, and taps[NZ][2] = (z0, w) per output section, int32, 0 <= z0 <= VZ - 1 and 0 <= w <= 255 (utils.
+ * resample_z_taps).  With a = V[z0][y][x] and b = V[min(z0 + 1, VZ - 1)][y][x]:
+ *   out = ((256 - w) a + w b + 128) >> 8            (at most 255 x 256 + 128 < 2^16; w = 0 gives a)
+ *   nearest = 1 (masks):  out = w < 128 ? a : b
+ * A tap of weight 0 -- b where w = 0 -- is no tap: it is not read and need not lie in the block.
+ * src[D][H][W] holds sections sz0 ... sz0 + D - 1 of the volume, dst[OD][H][W] output sections oz0 ... oz0 + OD - 1.
+ * taps_host points at the whole table on the host, whose rows oz0 ... oz0 + OD - 1 are validated without a launch;
+ * taps_dev at the same table on the device, which the kernel reads.  The kernel clamps every z0 it reads into the
+ * block and every w to 0...255, so a device table that disagrees with the host's gives wrong bytes, never a fault.
+ * Every byte of dst is written exactly once and nothing else is written; no source byte outside the taps' planes is
+ * read, and a load touches only naturally aligned words (up to 16 bytes) that hold at least one byte of the block.
+ * Any alignment of src, dst and H W, src and dst independently; every byte offset is 64 bits.  A voxel depends on its
+ * tap alone, not on how the volume was cut.
+ * TEM_EINVAL, without a launch: a null pointer, a dimension below 1, a block outside the volume (sz0 < 0, sz0 + D > VZ)
+ * or outside the output (oz0 < 0, oz0 + OD > NZ), nearest outside {0, 1}, a row of the block's with z0 or w out of
+ * range, and one whose plane z0, or whose plane min(z0 + 1, VZ - 1) where w > 0, lies outside the source block.
+ * TEM_EUNSUPPORTED: 2^24 workgroups or more (one per 4096 bytes of a plane and run of up to 32 output planes; their 256
+ * threads then stay below 2^32 per launch).  A block of fewer than 2^34 voxels with planes of 4096 bytes or more
+ * always passes. */
+int tem_u8_resample_z(const uint8_t *src, int32_t D, int32_t H, int32_t W, int32_t sz0, int32_t VZ, uint8_t *dst,
+                      int32_t OD, int32_t oz0, int32_t NZ, const int32_t *taps_host, const int32_t *taps_dev,
+                      int32_t nearest, tem_stream_t stream);
+
 /* The sums behind the correlation of every tile of a section with the NEXT SECTION DISPLACED by every integer offset
  * within a radius (utils.section_shift_sums -> shift_scores -> section_shifts: how far consecutive sections sit apart
  * in y and x).  The definition: the volume is V[Z][Y][X], uint8; tiles of (th, tw) pixels on tem_u8_hist_tiles' grid,

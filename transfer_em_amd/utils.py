@@ -74,6 +74,12 @@ them to the 2^-16 fixed point of the device, and `volume_warp` resamples every s
 pair on a lattice (`field_grid`), `section_fields` composes the pairs into one map and one field per section,
 `quantize_field` brings the fields to the device's fixed point, and `volume_warp_field` resamples every section through
 "affine map + field" out of core (tem_u8_warp_field); `field_chunks` is the slab plan.
+
+`section_lag_sums` is `section_sums` at several lags (tem_u8_zcorr_lags); `lag_scores` turns the sums into correlations
+per lag and `section_spacing` into the sections' positions along z, from how fast the correlation decays with the lag;
+`quantize_positions` brings them to 2^-16 section, `resample_z_taps` to the table of taps, and `volume_resample_z`
+resamples the stack (or, nearest, a mask) onto the even grid out of core (tem_u8_resample_z); `zlag_chunks` and
+`resample_z_chunks` are the slab plans.
 """
 import contextlib
 import json
@@ -1642,6 +1648,11 @@ def zcorr_chunks(vol_shape, chunk_bytes=None, rank=0, world_size=1):
     allows it: as many whole sections per core as fit next to the one above them, or, where two sections are larger
     than the budget, one section's rows, as many as fit twice (one row at the least).  Slabs are in (z, y) order and go
     round-robin to the ranks.  Pure host function; ValueError as hist_box and hist_chunks."""
+    return _zhalo_chunks(vol_shape, 1, chunk_bytes, rank, world_size)
+
+
+def _zhalo_chunks(vol_shape, reach, chunk_bytes, rank, world_size):
+    """zcorr_chunks' cuts with read slabs that reach `reach` sections past their core, where the volume has them."""
     budget = HIST_CHUNK_BYTES if chunk_bytes is None else int(chunk_bytes)
     if budget < 1:
         raise ValueError(f"chunk_bytes must be positive, got {chunk_bytes}")
@@ -1650,14 +1661,14 @@ def zcorr_chunks(vol_shape, chunk_bytes=None, rank=0, world_size=1):
     (_, Z), (_, ny), (_, nx) = hist_box(vol_shape)
     if Z <= 0 or ny <= 0 or nx <= 0:
         return []
-    halo = 1 if Z > 1 else 0
+    halo = min(reach, Z - 1)
     if (1 + halo) * ny * nx <= budget:
         kz = budget // (ny * nx) - halo
         cores = [((z, min(z + kz, Z)), (0, ny)) for z in range(0, Z, kz)]
     else:
         ky = max(1, budget // ((1 + halo) * nx))
         cores = [((z, z + 1), (y, min(y + ky, ny))) for z in range(Z) for y in range(0, ny, ky)]
-    slabs = [((cz, cy, (0, nx)), ((cz[0], min(cz[1] + 1, Z)), cy, (0, nx))) for cz, cy in cores]
+    slabs = [((cz, cy, (0, nx)), ((cz[0], min(cz[1] + halo, Z)), cy, (0, nx))) for cz, cy in cores]
     return slabs[rank::world_size]
 
 
@@ -1835,6 +1846,421 @@ def defects_repair(d, tile, vol_shape, mask_out=None, max_gap=8):
         raise ValueError(f"defects_repair needs find_defects' Defects, got {type(d).__name__}")
     mask = defect_mask(tiles, tile, vol_shape, mask_out) if tiles.any() else None
     return Repair(sections, mask, None, R)
+
+
+ZLAG_MAX = 8                     # tem_u8_zcorr_lags: 1 <= nlag <= 8
+ZSPACE_MIN, ZSPACE_MAX = Fraction(1, 8), 8       # a section's spacing along z, in sections: volume_rescale's step limits
+ZSPACE_UNIT = 1 << 16            # quantize_positions: positions along z in 2^-16 section
+
+
+def _max_lag(max_lag):
+    L = _index(max_lag, "max_lag")
+    if not 1 <= L <= ZLAG_MAX:
+        raise ValueError(f"max_lag must lie in 1...{ZLAG_MAX}, got {L}")
+    return L
+
+
+def zlag_chunks(vol_shape, max_lag=4, chunk_bytes=None, rank=0, world_size=1):
+    """zcorr_chunks for section_lag_sums: the same cores, and read slabs that reach min(max_lag, Z - 1) sections past
+    their core where the volume has them -- the planes a core plane is correlated with.  The budget counts a core next to
+    that halo.  With max_lag = 1 it is zcorr_chunks.  Pure host function; ValueError as zcorr_chunks and for max_lag
+    outside 1...ZLAG_MAX."""
+    return _zhalo_chunks(vol_shape, _max_lag(max_lag), chunk_bytes, rank, world_size)
+
+
+def section_lag_sums(volume, tile=128, max_lag=4, chunk_bytes=None, rank=0, world_size=1, device=None, stats=None):
+    """section_sums with L = `max_lag` (1...8) partners instead of one: np.int64 [Z, gy, gx, 3 + L] over the WHOLE uint8
+    `volume` [z, y, x] on clahe_grid's tiles of `tile` pixels.  With v the voxels of tile (i, j) of section z and v+k
+    those k sections up:
+      s[z, i, j] = (sum v, sum v v, the number of voxels, sum v v+1, ..., sum v v+L);   sum v v+k is 0 where z + k >= Z.
+    Exact integers that numpy reproduces bit for bit, whatever the slabs, ranks and launches.  lag_scores turns them into
+    correlations per lag, section_spacing into the sections' positions along z.
+
+    Out of core exactly as section_sums, over read slabs that reach L sections past their core (zlag_chunks): one
+    tem_u8_zcorr_lags launch per slab into a device accumulator, which holds the whole volume's sums and is read back
+    once where they are at most CLAHE_ACC_BYTES, else one slab's.  Ranks take slabs round-robin and their results add up
+    to the whole.  `stats` receives `read_s` and `chunks`.  ValueError, before any GPU work, as section_sums and for
+    max_lag outside 1...8."""
+    _check_u8(volume)
+    L = _max_lag(max_lag)
+    th, tw = _clahe_tile(tile)
+    gy, gx = clahe_grid(volume.shape, (th, tw))
+    box = hist_box(volume.shape)
+    chunks = zlag_chunks(volume.shape, L, chunk_bytes, rank, world_size)
+    p = _SlabPass([volume], [box], chunk_bytes, rank, world_size, device, slabs=[r for _, r in chunks])
+    lib = H.require_gpu()
+    Z, sec = box[0][1], gy * gx * (3 + L)
+    whole = Z * sec * 8 <= CLAHE_ACC_BYTES
+    out = None if whole else np.zeros((Z, gy, gx, 3 + L), np.int64)
+    with p.streaming():
+        most = max((c[0][1] - c[0][0] for c, _ in chunks), default=1)
+        acc = torch.zeros((Z if whole else most, sec), dtype=torch.int64, device=p.dev)
+        for k, ((r0, _), (y0, _), (x0, _)), d, (src,) in p:
+            z0, z1 = chunks[k][0][0]
+            if not whole:
+                acc[:z1 - z0].zero_()
+            _lib.check(lib.tem_u8_zcorr_lags(src.data_ptr(), *d, z0 - r0, z1 - r0, y0, x0, th, tw, gy, gx, L,
+                                             acc.data_ptr() + 8 * sec * (z0 if whole else 0), p.compute.cuda_stream),
+                       "tem_u8_zcorr_lags")
+            if not whole:                                        # this slab's core sections, added on the host
+                out[z0:z1] += acc[:z1 - z0].cpu().numpy().reshape(z1 - z0, gy, gx, 3 + L)
+        if whole:
+            out = acc.cpu().numpy().reshape(Z, gy, gx, 3 + L)    # the one read-back
+    if stats is not None:
+        stats.update(p.st)
+    return out
+
+
+def _check_lag_sums(s, who):
+    s = np.asarray(s)
+    if s.ndim != 4 or not 4 <= s.shape[3] <= 3 + ZLAG_MAX or s.dtype.kind not in "iu":
+        raise ValueError(f"{who}: s must be section_lag_sums' integer array [Z, gy, gx, 3 + L], got {s.dtype} {s.shape}")
+    return s.astype(np.int64, copy=False)
+
+
+def lag_scores(s):
+    """float64 c[Z, gy, gx, L]: the Pearson correlation of every tile of section z with the same tile of section
+    z + k, k = 1...L in c[..., k - 1], from section_lag_sums' `s`.  Host only.  section_scores' formula per lag, with
+    n = s[..., 2], S1 = s[..., 0], S2 = s[..., 1], Pk = s[..., 2 + k]:
+      A = n S2[z] - S1[z]^2,   B = the same at z + k,   N = n Pk[z] - S1[z] S1[z + k]
+    exact in int64, and c = N / (sqrt(A) sqrt(B)) where A > 0 and B > 0, else 0.0 -- as past the last section."""
+    s = _check_lag_sums(s, "lag_scores")
+    Z, L = s.shape[0], s.shape[3] - 3
+    c = np.zeros(s.shape[:3] + (L,), np.float64)
+    n, S1, S2 = s[..., 2], s[..., 0], s[..., 1]
+    var = n * S2 - S1 * S1
+    for k in range(1, min(L, Z - 1) + 1):
+        A, B = var[:-k], var[k:]
+        N = n[:-k] * s[:-k, :, :, 2 + k] - S1[:-k] * S1[k:]
+        ok = (A > 0) & (B > 0)
+        c[:-k, :, :, k - 1][ok] = N[ok] / (np.sqrt(A[ok].astype(np.float64)) * np.sqrt(B[ok].astype(np.float64)))
+    return c
+
+
+class Spacing(NamedTuple):
+    """section_spacing's estimate: `positions` float64[Z] of the sections along z, in sections, from 0 to Z - 1;
+    `curve` float64[L + 1] the correlation at a distance of 0...L sections; `used` bool[Z, L] the pairs (z, z + k) that
+    were measured; `clipped` the list of (a, b), consecutive good sections whose spacing was cut to the limits;
+    `unresolved` the list of (a, b), consecutive good sections between which nominal spacing was assumed."""
+    positions: np.ndarray
+    curve: np.ndarray
+    used: np.ndarray
+    clipped: list
+    unresolved: list
+
+
+def _lower_median(v, axis):
+    """The element at index (n - 1) // 2 of the sorted values along `axis`, NaNs last and not counted; NaN for none."""
+    v = np.sort(v, axis=axis)                                            # NaNs sort to the end
+    n = np.sum(~np.isnan(v), axis=axis, keepdims=True)
+    got = np.take_along_axis(v, np.maximum(n - 1, 0) // 2, axis=axis)
+    return np.where(n > 0, got, np.nan).squeeze(axis)
+
+
+def _solve_banded(U, rhs):
+    """x of the symmetric positive definite band system whose upper band is U[i, t] = A[i, i + t]: elimination without
+    pivoting, O(n L^2), in place."""
+    n, B = U.shape
+    for i in range(n):
+        for t in range(1, min(B, n - i)):
+            if U[i, t] != 0.0:
+                f = U[i, t] / U[i, 0]
+                U[i + t, :B - t] -= f * U[i, t:]
+                rhs[i + t] -= f * rhs[i]
+    x = np.zeros(n, np.float64)
+    for i in range(n - 1, -1, -1):
+        m = min(B, n - i)
+        x[i] = (rhs[i] - np.dot(U[i, 1:m], x[i + 1:i + m])) / U[i, 0]
+    return x
+
+
+def section_spacing(s, skip=(), min_corr=0.1):
+    """Where the sections of a stack sit along z, from how fast their correlation decays with the lag (Hanslovsky et
+    al. 2017): Spacing(positions, curve, used, clipped, unresolved) from section_lag_sums' `s` [Z, gy, gx, 3 + L].  Host
+    only and deterministic.  Run it after in-plane alignment: misaligned sections read as "far apart".  `skip` lists
+    the bad sections (find_defects, suspect_sections, flat_sections); the others are good.  The rule:
+      1. a tile column is decided where its median lag-1 score over the pairs of good sections is above `min_corr`;
+      2. c[z, k] is the lower median over the decided columns of the score of (z, z + k), both sections good;
+      3. curve[k] is the median over z of c[z, k], curve[0] = 1: the correlation at a distance of k sections of median
+         spacing.  ValueError where the curve is not strictly decreasing (no decided column, too few sections);
+      4. a pair is used where c[z, k] > curve[L]; its distance d is the piecewise-linear inverse of the curve at
+         min(c, 1), between 0 and L;
+      5. the positions p of the good sections are the weighted least squares of p[z + k] - p[z] = d over the used
+         pairs, weight 1 / k, the first section of each connected group at 0: a band system, solved in O(Z L^2);
+      6. a group of good sections that no used pair joins to the sections before it starts at nominal spacing -- 1 per
+         section spanned -- behind the good section before it, and that pair is listed in `unresolved`;
+      7. the spacing of two consecutive good sections is cut to [ZSPACE_MIN, ZSPACE_MAX] x (sections spanned), and the
+         pair is listed in `clipped`;
+      8. a skipped section is placed linearly between its good neighbours (at spacing 1 before the first good section
+         and behind the last);
+      9. the positions are normalised to P[0] = 0 and P[Z - 1] = Z - 1.
+    ValueError for sums of another shape, a bad skip or min_corr (in (0, 1)), a stack without two good sections."""
+    s = _check_lag_sums(s, "section_spacing")
+    Z, L = s.shape[0], s.shape[3] - 3
+    try:
+        bad = {_index(z, "a skipped section") for z in skip}
+    except TypeError:
+        raise ValueError(f"skip must be a list of sections, got {skip!r}")
+    if any(not 0 <= z < Z for z in bad):
+        raise ValueError(f"skip names sections outside [0, {Z}): {sorted(z for z in bad if not 0 <= z < Z)}")
+    m = _unit(min_corr, "min_corr", closed=False)
+    good = np.array([z not in bad for z in range(Z)], bool)
+    gidx = np.flatnonzero(good)
+    if gidx.size < 2:
+        raise ValueError(f"section_spacing needs two good sections at least, got {gidx.size} of {Z}")
+    c = lag_scores(s)                                                    # [Z, gy, gx, L]
+    both = np.zeros((Z, L), bool)                                        # (z, z + k): both sections good
+    for k in range(1, min(L, Z - 1) + 1):
+        both[:-k, k - 1] = good[:-k] & good[k:]
+    c = np.where(both[:, None, None, :], c, np.nan)
+    # 1. the decided columns
+    pairs1 = (~np.isnan(c[..., 0])).sum(axis=0)                          # [gy, gx]
+    decided = (pairs1 > 0) & (np.nanmedian(np.where(pairs1 > 0, c[..., 0], 0.0), axis=0) > m)
+    # 2. the lower median over the decided columns
+    cz = _lower_median(c[:, decided, :], axis=1) if decided.any() else np.full((Z, L), np.nan)
+    # 3. the curve
+    curve = np.ones(L + 1, np.float64)
+    for k in range(L):
+        v = cz[:, k][~np.isnan(cz[:, k])]
+        curve[k + 1] = np.median(v) if v.size else np.nan
+    if not np.all(np.diff(curve) < 0):                                   # a NaN fails too
+        raise ValueError(f"section_spacing: the correlation does not decrease strictly with the lag: {curve.tolist()}")
+    # 4. the used pairs and their distances
+    used = ~np.isnan(cz) & (np.nan_to_num(cz, nan=-2.0) > curve[L])
+    dist = np.interp(np.minimum(np.nan_to_num(cz, nan=1.0), 1.0), curve[::-1], np.arange(L, -1, -1.0))
+    # 5. the band system over the good sections, in their order
+    rank_of = np.cumsum(good) - 1
+    n = gidx.size
+    U, rhs = np.zeros((n, L + 1), np.float64), np.zeros(n, np.float64)
+    group = np.arange(n)                                                 # union-find: the connected groups
+
+    def root(a):
+        while group[a] != a:
+            group[a] = group[group[a]]
+            a = group[a]
+        return a
+
+    for z, k in np.argwhere(used).tolist():
+        a, b, w, d = int(rank_of[z]), int(rank_of[z + k + 1]), 1.0 / (k + 1), dist[z, k]
+        U[a, 0] += w
+        U[b, 0] += w
+        U[a, b - a] -= w
+        rhs[a] -= w * d
+        rhs[b] += w * d
+        ra, rb = root(a), root(b)
+        if ra != rb:
+            group[max(ra, rb)] = min(ra, rb)                             # a group's root is its first section
+    roots = np.array([root(a) for a in range(n)])
+    for f in np.flatnonzero(roots == np.arange(n)).tolist():             # p[first of a group] = 0: its row and column go
+        for t in range(1, min(L + 1, n - f)):
+            U[f, t] = 0.0
+        for t in range(1, min(L + 1, f + 1)):
+            U[f - t, t] = 0.0
+        U[f, 0], rhs[f] = 1.0, 0.0
+    p = _solve_banded(U, rhs)
+    # 6. the groups, in the order of their first sections
+    unresolved, shift = [], np.zeros(n, np.float64)
+    for a in range(1, n):
+        if roots[a] == a:
+            shift[a] = p[a - 1] + shift[roots[a - 1]] + float(gidx[a] - gidx[a - 1])
+            unresolved.append((int(gidx[a - 1]), int(gidx[a])))
+    p = p + shift[roots]
+    # 7. the limits
+    span = np.diff(gidx).astype(np.float64)
+    raw = np.diff(p)
+    step = np.clip(raw, float(ZSPACE_MIN) * span, float(ZSPACE_MAX) * span)
+    clipped = [(int(gidx[a]), int(gidx[a + 1])) for a in np.flatnonzero(step != raw).tolist()]
+    p = np.concatenate([[0.0], np.cumsum(step)])
+    # 8. the skipped sections
+    P = np.interp(np.arange(Z), gidx, p)
+    P[:gidx[0]] = p[0] - (gidx[0] - np.arange(gidx[0]))
+    P[gidx[-1] + 1:] = p[-1] + (np.arange(gidx[-1] + 1, Z) - gidx[-1])
+    # 9. the scale
+    P = (P - P[0]) * ((Z - 1) / (P[-1] - P[0]))
+    P[0], P[-1] = 0.0, float(Z - 1)
+    return Spacing(P, curve, used, clipped, unresolved)
+
+
+def quantize_positions(P):
+    """np.int64[Z]: the positions `P` of a stack's sections along z (section_spacing's, or any float or integer
+    sequence; integers are taken as quantised already) in units of 2^-16 section, rounded to nearest.  ValueError,
+    naming the section: a first position that is not 0, positions that do not increase strictly, a spacing outside
+    [ZSPACE_MIN, ZSPACE_MAX] sections."""
+    a = np.asarray(P)
+    if a.ndim != 1 or a.size < 1 or a.dtype.kind not in "iuf":
+        raise ValueError(f"positions must be one number per section, got {a.dtype} {a.shape}")
+    if a.dtype.kind == "f":
+        if not np.all(np.isfinite(a)) or np.abs(a).max() >= 2.0 ** 40:
+            raise ValueError("positions must be finite and below 2^40")
+        Q = np.rint(a * ZSPACE_UNIT).astype(np.int64)
+    else:
+        Q = a.astype(np.int64)
+    if Q[0] != 0:
+        raise ValueError(f"section 0 must sit at position 0, got {P[0]!r}")
+    d = np.diff(Q)
+    lo, hi = int(ZSPACE_MIN * ZSPACE_UNIT), int(ZSPACE_MAX * ZSPACE_UNIT)
+    for z in np.flatnonzero((d <= 0) | (d < lo) | (d > hi)).tolist():
+        if d[z] <= 0:
+            raise ValueError(f"positions must increase strictly: section {z + 1} at {Q[z + 1] / ZSPACE_UNIT} does not "
+                             f"lie above section {z} at {Q[z] / ZSPACE_UNIT}")
+        raise ValueError(f"the spacing of sections {z} and {z + 1}, {d[z] / ZSPACE_UNIT}, is outside "
+                         f"[{ZSPACE_MIN}, {ZSPACE_MAX}] sections")
+    return Q
+
+
+def resample_z_taps(Q, nz=None):
+    """The one host copy of tem_u8_resample_z's table: np.int32[NZ, 2] = (z0, w) per section j of an even grid of
+    spacing 1 over sections at the quantised positions `Q` (quantize_positions), in exact integers.  With t = j 2^16:
+      z0 is the largest z with Q[z] <= t, held to Z - 1;   den = Q[z0 + 1] - Q[z0];
+      w = (512 (t - Q[z0]) + den) // (2 den), the weight of section z0 + 1 in 1/256, rounded half up;
+      w == 256 becomes (z0 + 1, 0), and the last section has w = 0: a tap of weight 0 is no tap.
+    `nz` defaults to Q[Z - 1] // 2^16 + 1, the sections up to the last position; a larger one repeats the last
+    section.  ValueError for what quantize_positions refuses and nz below 1."""
+    Q = quantize_positions(np.asarray(Q))
+    Z = Q.size
+    NZ = int(Q[-1]) // ZSPACE_UNIT + 1 if nz is None else _index(nz, "nz")
+    if NZ < 1:
+        raise ValueError(f"nz must be positive, got {NZ}")
+    t = np.arange(NZ, dtype=np.int64) * ZSPACE_UNIT
+    z0 = np.minimum(np.searchsorted(Q, t, side="right") - 1, Z - 1)
+    z1 = np.minimum(z0 + 1, Z - 1)
+    den = np.where(z1 > z0, Q[z1] - Q[z0], 1)
+    w = np.where(z1 > z0, (512 * (t - Q[z0]) + den) // (2 * den), 0)
+    w = np.where(z1 > z0, np.minimum(w, 256), 0)                         # past the last position: the last section
+    carry = w == 256
+    return np.stack([np.where(carry, z0 + 1, z0), np.where(carry, 0, w)], axis=1).astype(np.int32)
+
+
+def _check_taps(taps, Z):
+    t = np.asarray(taps)
+    if t.ndim != 2 or t.shape[1] != 2 or t.shape[0] < 1 or t.dtype.kind not in "iu":
+        raise ValueError(f"taps must be resample_z_taps' integers [NZ, 2], got {t.dtype} {t.shape}")
+    t = t.astype(np.int64)
+    bad = np.flatnonzero((t[:, 0] < 0) | (t[:, 0] > Z - 1) | (t[:, 1] < 0) | (t[:, 1] > 255))
+    if bad.size:
+        j = int(bad[0])
+        raise ValueError(f"taps[{j}] = {tuple(int(v) for v in t[j])} is not 0 <= z0 <= {Z - 1}, 0 <= w <= 255")
+    return t
+
+
+def resample_z_chunks(out_box, vol_shape, taps, chunk_bytes=None, rank=0, world_size=1):
+    """Cut the (z, y, x) (lo, hi) box `out_box` of the output [NZ, Y, X] of a volume of shape `vol_shape` [Z, Y, X]
+    resampled through `taps` (resample_z_taps) into slabs for volume_resample_z.  Returns this rank's list of (output
+    slab, read slab), (z, y, x) (lo, hi) boxes of the output and of the volume with the same y and x: the output slabs
+    are disjoint and their union is the box -- runs of whole sections of the box, or runs of whole rows of one section
+    --; a read slab is the dense hull along z of its output sections' taps of weight above 0.  The two together hold at
+    most `chunk_bytes` bytes (HIST_CHUNK_BYTES when None) wherever one row allows it.  Slabs are in (z, y) order and go
+    round-robin to the ranks.  Pure host function; ValueError as hist_chunks, for bad taps and a box outside the
+    output."""
+    budget = HIST_CHUNK_BYTES if chunk_bytes is None else int(chunk_bytes)
+    if budget < 1:
+        raise ValueError(f"chunk_bytes must be positive, got {chunk_bytes}")
+    if not 0 <= rank < world_size:
+        raise ValueError(f"rank {rank} is outside [0, {world_size})")
+    vol_shape = tuple(int(v) for v in vol_shape)
+    if len(vol_shape) != 3 or min(vol_shape) < 1:
+        raise ValueError(f"resample_z_chunks takes a non-empty volume shape [z, y, x], got {vol_shape}")
+    VZ = vol_shape[0]
+    t = _check_taps(taps, VZ)
+    grid = (t.shape[0],) + vol_shape[1:]
+    (z0, z1), (y0, y1), (x0, x1) = out_box
+    if any(lo < 0 or hi > n for (lo, hi), n in zip(out_box, grid)):
+        raise ValueError(f"the box {tuple(out_box)} reaches outside the output of shape {grid}")
+    ny, nx = y1 - y0, x1 - x0
+    if z1 <= z0 or ny <= 0 or nx <= 0:
+        return []
+    first = t[:, 0]
+    last = np.where(t[:, 1] > 0, np.minimum(t[:, 0] + 1, VZ - 1), t[:, 0])
+
+    def hull(a, b):                     # the source sections of output sections [a, b)
+        return int(first[a:b].min()), int(last[a:b].max()) + 1
+
+    slabs, z = [], z0
+    while z < z1:
+        lo, hi = hull(z, z + 1)
+        if (1 + hi - lo) * ny * nx <= budget:
+            k = 1
+            while z + k < z1:
+                more = hull(z, z + k + 1)
+                if (k + 1 + more[1] - more[0]) * ny * nx > budget:
+                    break
+                k, (lo, hi) = k + 1, more
+            slabs.append((((z, z + k), (y0, y1), (x0, x1)), ((lo, hi), (y0, y1), (x0, x1))))
+            z += k
+            continue
+        ky = max(1, budget // ((1 + hi - lo) * nx))
+        slabs += [(((z, z + 1), (y, min(y + ky, y1)), (x0, x1)), ((lo, hi), (y, min(y + ky, y1)), (x0, x1)))
+                  for y in range(y0, y1, ky)]
+        z += 1
+    return slabs[rank::world_size]
+
+
+def volume_resample_z(volume, positions, out=None, start=None, size=None, nz=None, nearest=False, chunk_bytes=None,
+                      rank=0, world_size=1, device=None, stats=None):
+    """A uint8 array-like `volume` [z, y, x] (ndarray, np.memmap, h5py / zarr dataset) whose sections sit at
+    `positions` along z (section_spacing's floats, or quantize_positions' integers), resampled onto the even grid of
+    spacing 1: output section j is the linear blend of the two sections around position j, weights in 1/256, rounded
+    once, half up (resample_z_taps has the table, include/tem_hip.h the voxel's rule; numpy reproduces it bit for
+    bit).  `nearest=True` takes the nearer of the two instead: that moves a mask.  The output has `nz` sections
+    (default: up to the last position; with section_spacing's positions that is Z).  Where sections are denser than
+    the output, the nearest two are blended and the others are not averaged in.
+
+    `start` / `size` are an ROI of the OUTPUT in (x, y, z) order (default: all of it); `out` is a writable uint8
+    array-like of the ROI's shape (allocated when None) and is returned.  volume_rescale's pass: the ROI is cut into
+    output slabs and the read slabs that hold their taps (resample_z_chunks), together at most `chunk_bytes`; host
+    thread -> pinned -> H2D -> one tem_u8_resample_z launch per slab -> D2H -> host write, on double buffers.  Ranks
+    take slabs round-robin and write disjoint boxes of a shared `out`.  `stats` receives `read_s`, `write_s` and
+    `chunks`.
+
+    There is no resample_z= keyword on predict_cube / predict_volume: the output's shape changes, as with rescale.
+
+    ValueError, before any GPU work: a volume that is not uint8 [z, y, x], positions that quantize_positions refuses or
+    that are not one per section, an ROI outside the output, an `out` of another shape or dtype."""
+    _check_u8(volume)
+    vshape = tuple(int(v) for v in volume.shape)
+    if len(vshape) != 3 or min(vshape) < 1:
+        raise ValueError(f"volume_resample_z takes a non-empty volume [z, y, x], got shape {vshape}")
+    Q = quantize_positions(positions)
+    if Q.size != vshape[0]:
+        raise ValueError(f"positions must hold one position per section: {vshape[0]}, got {Q.size}")
+    taps = np.ascontiguousarray(resample_z_taps(Q, nz))
+    grid = (taps.shape[0],) + vshape[1:]
+    try:
+        box = hist_box(grid, start, size)
+    except ValueError as e:
+        raise ValueError(f"volume_resample_z: start / size are an ROI of the output of shape {grid}: {e}")
+    shape = tuple(hi - lo for lo, hi in box)
+    if out is None:
+        out = np.zeros(shape, np.uint8)
+    elif tuple(out.shape) != shape or getattr(out, "dtype", None) != np.uint8:
+        raise ValueError(f"out must be uint8 of the ROI's shape {shape}, got {getattr(out, 'dtype', None)} "
+                         f"{tuple(out.shape)}")
+    chunks = resample_z_chunks(box, vshape, taps, chunk_bytes, rank, world_size)
+    p = _SlabPass([volume], [hist_box(vshape)], chunk_bytes, rank, world_size, device, slabs=[r for _, r in chunks])
+    lib = H.require_gpu()
+    oslabs = [o for o, _ in chunks]
+    odims = [tuple(hi - lo for lo, hi in o) for o in oslabs]
+    (oz, _), (oy, _), (ox, _) = box
+    p.st["write_s"] = 0.0
+
+    def write_from(k, flat):            # host thread: the slab's box of `out`
+        (z0, z1), (y0, y1), (x0, x1) = oslabs[k]
+        out[z0 - oz:z1 - oz, y0 - oy:y1 - oy, x0 - ox:x1 - ox] = flat.reshape(odims[k])
+
+    with p.streaming():
+        taps_dev = torch.from_numpy(taps).to(p.dev)
+        with _OutputStream([int(np.prod(d)) for d in odims], write_from, p.dev, p.pool, p.st,
+                           own_buffers=True) as outp:                    # the reader's thread: write(k), read(k + 2)
+            for k, slab, d, (src,) in p:
+                _lib.check(lib.tem_u8_resample_z(src.data_ptr(), *d, slab[0][0], vshape[0], outp.device(k).data_ptr(),
+                                                 odims[k][0], oslabs[k][0][0], grid[0], taps.ctypes.data,
+                                                 taps_dev.data_ptr(), int(bool(nearest)), p.compute.cuda_stream),
+                           "tem_u8_resample_z")
+                p.release_on = p.compute.record_event()                  # behind the kernel: the input is free too
+                outp.put(k, p.release_on)
+    if stats is not None:
+        stats.update(p.st)
+    return out
 
 
 SHIFT_MAX_RADIUS = 8             # offsets of section_shift_sums: [-r, r]^2, r in 1...8
