@@ -616,6 +616,67 @@ int tem_u8_resample_z(const uint8_t *src, int32_t D, int32_t H, int32_t W, int32
                       int32_t OD, int32_t oz0, int32_t NZ, const int32_t *taps_host, const int32_t *taps_dev,
                       int32_t nearest, tem_stream_t stream);
 
+/* Damaged voxels below the tile: how far a voxel lies outside the range of the voxels below and above it in the nearest
+ * good sections (utils.section_outlier_sums -> outlier_thresholds -> volume_outliers -> find_debris: dust, precipitate
+ * and knife debris sit on one section).  The definition, once.  V[Z][Y][X] is the uint8 volume; tiles of (th, tw) pixels
+ * on tem_u8_hist_tiles' grid, gy x gx of them anchored at the volume's (0, 0).
+ *   Neighbours   nbr[Z][2] = (lo, hi) per section, int32 (utils.section_neighbours): either (-1, -1), no verdict, or
+ *                lo < z < hi, both in [0, Z), z - lo <= 8 and hi - z <= 8: the nearest good sections below and above.
+ *   Deviation    with a = V[lo][y][x], v = V[z][y][x], b = V[hi][y][x]:  e = |v - median(a, v, b)|, that is 0 where
+ *                min(a, b) <= v <= max(a, b), else min(|v - a|, |v - b|); e = 0 where the section has no verdict.
+ *                0 <= e <= 255.
+ *   Tile sums    t[z][i][j] = (sum e, n) over the voxels of tile (i, j) of section z, int64; n is the tile's voxel count
+ *                where the section has a verdict, else 0.
+ *   Mask         for a radius r in 1...7, Ws(z, y, x) is the sum of e over [y - r, y + r] x [x - r, x + r] cut to the
+ *                section and c the number of voxels of the cut window.  With thr[gy][gx], int32 in [1, 65280], in 1/256
+ *                grey level, and (i, j) the tile of (y, x):  mask = 1 iff 256 Ws > thr[i][j] c, or where an optional
+ *                table tiles[Z][gy][gx] of uint8 is non-zero at [z][i][j]; else 0.  Equality does not flag.
+ *                Ws <= 225 x 255 = 57,375; 256 Ws and thr c stay below 2^24: everything fits 32 bits.
+ * Both entries take the whole table nbr twice: nbr_host on the host, whose rows for the core planes are validated
+ * without a launch, and nbr_dev (4-byte aligned) with the same contents on the device, which the kernel reads.  The
+ * block's plane 0 is section sz0 of the stack of Z.  On the device a row with a negative entry is no verdict, and lo
+ * and hi of any other row are clamped into the block, as tem_u8_resample_z does with its taps: a device table that
+ * disagrees with the host's gives other results, never a read outside the block.
+ *
+ * tem_u8_zdev_tiles follows tem_u8_zcorr_tiles' contract: the block src[D][H][W] at (y_org, x_org), the core planes
+ * [c0, c1), any alignment of src, W and the origins, loads of naturally aligned words that hold a byte of the block,
+ * 64-bit sums (8-byte aligned, pointing at the rows of plane c0) that it ADDS to with one 64-bit global atomic add (an
+ * ordinary vector atomic) per workgroup, plane and quantity:
+ *   q = sums + (((d - c0) * gy + i) * gx + j) * 2        q[0] += e     q[1] += 1    (nothing for a plane without a verdict)
+ * so blocks that cut a tile along y, x or z between them accumulate into it.  lo and hi of every core plane with a
+ * verdict must lie in the block.  A thread sums at most 64 voxels of a plane (< 2^14), a wave 64 such partials, a
+ * workgroup at most 16384 voxels (< 2^22).
+ * TEM_EINVAL, without a launch: what tem_u8_zcorr_tiles refuses, a null table, nbr_dev off 4-byte alignment, Z < 1, a
+ * block outside the stack (sz0 < 0, sz0 + D > Z), a core row of nbr_host that breaks the rules above or names a
+ * section outside the block.  TEM_EUNSUPPORTED: 2^24 workgroups or more (tem_u8_zcorr_tiles' parts and runs of up to 16
+ * core planes).  An empty core launches nothing.
+ *
+ * tem_u8_zdev_mask: src[D][H][W] is a dense block of WHOLE rows (W == X, as tem_u8_zshift_tiles) whose row 0 sits at
+ * volume row y_org of a section of Y rows.  It writes dst[c1 - c0][r1 - r0][x1 - x0], dense, for the core planes
+ * [c0, c1), core rows [r0, r1) and core columns [x0, x1) of the block: every byte of dst, 0 or 1, and nothing else but
+ * count.  The block must hold every row under a core window that the section has -- [0, H) contains
+ * [r0 - radius, r1 + radius) cut to [-y_org, Y - y_org) -- and lo and hi of every core plane with a verdict.
+ * thr_host[gy][gx] is validated (1...65280); thr_dev (4-byte aligned) is the same table on the device, clamped to that
+ * range as it is read.  tiles_dev may be null; it points at the rows of section sz0 + c0: tiles_dev[((d - c0) * gy + i)
+ * * gx + j].  count may be null; it is 8-byte aligned, and the number of ones written is ADDED to it with one 64-bit
+ * global atomic add (an ordinary vector atomic) per workgroup.  Any alignment of src, dst and W.  A voxel's verdict
+ * depends on its window and its section's row alone, not on how the volume was cut.
+ * TEM_EINVAL, without a launch: a null src, dst or table, a table or count off its alignment, a dimension, Y, Z, gy or
+ * gx below 1, th or tw outside [1, 2048], a radius outside [1, 7], a negative y_org, a block that reaches past the
+ * section or the stack, a section past the grid (Y > gy th, W > gx tw), a core that is not 0 <= c0 <= c1 <= D,
+ * 0 <= r0 <= r1 <= H, 0 <= x0 <= x1 <= W, an entry of thr_host out of range, a core row of nbr_host that breaks the
+ * rules or names a section outside the block, a block without a row that a core window needs.  TEM_EUNSUPPORTED: 2^24
+ * workgroups or more (one per core plane and run of up to 64 tiles of 8 x 32 outputs; the run is as long as leaves
+ * about 8192 workgroups).  An empty core launches nothing. */
+int tem_u8_zdev_tiles(const uint8_t *src, int32_t D, int32_t H, int32_t W, int32_t sz0, int32_t Z, int32_t c0,
+                      int32_t c1, int32_t y_org, int32_t x_org, int32_t th, int32_t tw, int32_t gy, int32_t gx,
+                      const int32_t *nbr_host, const int32_t *nbr_dev, uint64_t *sums, tem_stream_t stream);
+int tem_u8_zdev_mask(const uint8_t *src, int32_t D, int32_t H, int32_t W, int32_t sz0, int32_t Z, int32_t Y,
+                     int32_t y_org, int32_t c0, int32_t c1, int32_t r0, int32_t r1, int32_t x0, int32_t x1, int32_t th,
+                     int32_t tw, int32_t gy, int32_t gx, int32_t radius, const int32_t *nbr_host,
+                     const int32_t *nbr_dev, const int32_t *thr_host, const int32_t *thr_dev,
+                     const uint8_t *tiles_dev, uint8_t *dst, uint64_t *count, tem_stream_t stream);
+
 /* The sums behind the correlation of every tile of a section with the NEXT SECTION DISPLACED by every integer offset
  * within a radius (utils.section_shift_sums -> shift_scores -> section_shifts: how far consecutive sections sit apart
  * in y and x).  The definition: the volume is V[Z][Y][X], uint8; tiles of (th, tw) pixels on tem_u8_hist_tiles' grid,

@@ -1616,7 +1616,8 @@ def flat_sections(h, fraction=Fraction(1, 2)):
     (np integer [Z, 256]: volume_histogram(..., per_section=True)) whose most frequent grey level holds at least
     `fraction` (an int, a Fraction or a (num, den) pair in (0, 1]) of their pixels, decided in integers:
     max(h[z]) den >= num sum(h[z]).  An empty section is not flagged.  Blank and saturated sections are what this
-    finds -- the list is what Repair takes as `sections` --; find_defects finds what is subtler."""
+    finds -- the list is what Repair takes as `sections` --; find_defects finds the sections and tile-sized regions that
+    resemble neither neighbour, find_debris the particles far smaller than a tile."""
     h = np.asarray(h)
     if h.ndim != 2 or h.shape[1] != 256 or h.dtype.kind not in "iu":
         raise ValueError(f"flat_sections: h must be integer counts of shape [Z, 256], got {h.dtype} {h.shape}")
@@ -1845,6 +1846,355 @@ def defects_repair(d, tile, vol_shape, mask_out=None, max_gap=8):
     except (AttributeError, TypeError):
         raise ValueError(f"defects_repair needs find_defects' Defects, got {type(d).__name__}")
     mask = defect_mask(tiles, tile, vol_shape, mask_out) if tiles.any() else None
+    return Repair(sections, mask, None, R)
+
+
+OUTLIER_MAX_RADIUS = 7           # tem_u8_zdev_mask: windows of 3...15 pixels
+OUTLIER_MAX_THR = 255 * 256      # a threshold, in 1/256 grey level
+
+
+def section_neighbours(Z, skip=(), max_lag=4):
+    """The nearest good sections below and above every section of a stack of `Z` when the sections `skip` are bad:
+    np.int32 nbr[Z, 2] = (lo, hi), the table that tem_u8_zdev_tiles and tem_u8_zdev_mask judge a section against
+    (include/tem_hip.h has the definition).  A row is (-1, -1), no verdict, for a skipped section, for the first and the
+    last good section, and for a good section whose nearest good neighbour on either side is further than `max_lag`
+    (1...SHIFT_MAX_LAG) away; every other row is lo < z < hi.  No `skip` gives (z - 1, z + 1) for 0 < z < Z - 1.  Host
+    only; section_pairs' ValueErrors."""
+    try:
+        skip = list(skip)
+    except TypeError:
+        raise ValueError(f"skip must be a list of sections, got {skip!r}")
+    section_pairs(Z, skip, max_lag)                              # the checks, and their messages
+    Z, lag = _index(Z, "Z"), _index(max_lag, "max_lag")
+    bad = {_index(z, "a skipped section") for z in skip}
+    good = [z for z in range(Z) if z not in bad]
+    nbr = np.full((Z, 2), -1, np.int32)
+    for lo, z, hi in zip(good[:-2], good[1:-1], good[2:]):
+        if z - lo <= lag and hi - z <= lag:
+            nbr[z] = (lo, hi)
+    return nbr
+
+
+def _check_neighbours(nbr, Z):
+    """int32[Z, 2] of `nbr`: rows (-1, -1) or lo < z < hi in [0, Z) at most SHIFT_MAX_LAG away.  ValueError otherwise."""
+    t = np.asarray(nbr)
+    if t.shape != (Z, 2) or t.dtype.kind not in "iu":
+        raise ValueError(f"nbr must be section_neighbours' integers [{Z}, 2], got {t.dtype} {t.shape}")
+    t = t.astype(np.int64)
+    z = np.arange(Z)
+    lo, hi = t[:, 0], t[:, 1]
+    ok = ((lo == -1) & (hi == -1)) | ((lo >= 0) & (lo < z) & (hi > z) & (hi < Z) & (z - lo <= SHIFT_MAX_LAG) &
+                                      (hi - z <= SHIFT_MAX_LAG))
+    if not ok.all():
+        k = int(np.flatnonzero(~ok)[0])
+        raise ValueError(f"nbr[{k}] = {tuple(int(v) for v in t[k])} is neither (-1, -1) nor lo < {k} < hi inside [0, {Z}) "
+                         f"at most {SHIFT_MAX_LAG} sections away")
+    return np.ascontiguousarray(t.astype(np.int32))
+
+
+def _outlier_radius(radius, least):
+    r = _index(radius, "radius")
+    if not least <= r <= OUTLIER_MAX_RADIUS:
+        raise ValueError(f"radius must lie in {least}...{OUTLIER_MAX_RADIUS}, got {r}")
+    return r
+
+
+def _outlier_window(window):
+    """The radius of an odd `window` in 3...15."""
+    win = _index(window, "window")
+    if not 3 <= win <= 2 * OUTLIER_MAX_RADIUS + 1 or not win & 1:
+        raise ValueError(f"window must be odd and lie in 3...{2 * OUTLIER_MAX_RADIUS + 1}, got {win}")
+    return win // 2
+
+
+def _outlier_params(ratio, min_dev):
+    try:
+        if any(isinstance(v, (bool, np.bool_, str, bytes)) for v in (ratio, min_dev)):
+            raise TypeError
+        ratio, min_dev = float(ratio), float(min_dev)
+    except (TypeError, ValueError):
+        raise ValueError(f"ratio and min_dev must be numbers, got {ratio!r}, {min_dev!r}")
+    if not ratio > 0 or not np.isfinite(ratio):
+        raise ValueError(f"ratio must be positive, got {ratio!r}")
+    if not 0 < min_dev <= 255:
+        raise ValueError(f"min_dev must lie in (0, 255], got {min_dev!r}")
+    return ratio, min_dev
+
+
+def outlier_chunks(box, vol_shape, nbr, radius, chunk_bytes=None, rank=0, world_size=1):
+    """Cut the (z, y, x) (lo, hi) `box` of a volume of shape `vol_shape` [z, y, x] into slabs for volume_outliers and, with
+    radius = 0 and the whole volume as the box, for section_outlier_sums.  Returns this rank's list of (core slab, read
+    slab), both (z, y, x) (lo, hi) boxes of the volume: the cores are disjoint and their union is the box (hist_chunks'
+    kinds of cut: runs of whole sections of the box, or runs of whole rows of one section; x is never cut); a read slab
+    is the dense hull along z of its core's sections and their (lo, hi) of `nbr` (section_neighbours' table; a section
+    without a verdict asks for itself alone), the core's rows and `radius` (0...7) more on each side, cut to the volume,
+    and the volume's whole x extent.  A read slab holds at most `chunk_bytes` bytes (HIST_CHUNK_BYTES when None) wherever
+    one row allows it: as many whole sections per core as fit with their hull, or, where one section's hull is larger
+    than the budget, that section's rows, as many as fit next to their 2 radius (one row at the least).  Slabs are in
+    (z, y) order and go round-robin to the ranks.  Pure host function; ValueError as hist_chunks, for a bad table or
+    radius and a box outside the volume."""
+    budget = HIST_CHUNK_BYTES if chunk_bytes is None else int(chunk_bytes)
+    if budget < 1:
+        raise ValueError(f"chunk_bytes must be positive, got {chunk_bytes}")
+    if not 0 <= rank < world_size:
+        raise ValueError(f"rank {rank} is outside [0, {world_size})")
+    vol_shape = tuple(int(v) for v in vol_shape)
+    if len(vol_shape) != 3 or min(vol_shape) < 1:
+        raise ValueError(f"outlier_chunks takes a non-empty volume shape [z, y, x], got {vol_shape}")
+    Z, Y, X = vol_shape
+    t = _check_neighbours(nbr, Z)
+    r = _outlier_radius(radius, 0)
+    (z0, z1), (y0, y1), (x0, x1) = box
+    if any(lo < 0 or hi > n for (lo, hi), n in zip(box, vol_shape)):
+        raise ValueError(f"the box {tuple(box)} reaches outside the volume of shape {vol_shape}")
+    if z1 <= z0 or y1 <= y0 or x1 <= x0:
+        return []
+    first = np.where(t[:, 0] < 0, np.arange(Z), t[:, 0])
+    last = np.where(t[:, 0] < 0, np.arange(Z), t[:, 1])
+    ra, rb = max(y0 - r, 0), min(y1 + r, Y)                      # the rows read for a core of whole sections
+    slabs, z = [], z0
+    while z < z1:
+        lo, hi = int(first[z]), int(last[z]) + 1
+        if (hi - lo) * (rb - ra) * X <= budget:
+            k = 1
+            while z + k < z1:
+                more = min(lo, int(first[z + k])), max(hi, int(last[z + k]) + 1)
+                if (more[1] - more[0]) * (rb - ra) * X > budget:
+                    break
+                k, (lo, hi) = k + 1, more
+            slabs.append((((z, z + k), (y0, y1), (x0, x1)), ((lo, hi), (ra, rb), (0, X))))
+            z += k
+            continue
+        ky = max(1, budget // ((hi - lo) * X) - 2 * r)
+        slabs += [(((z, z + 1), (y, min(y + ky, y1)), (x0, x1)),
+                   ((lo, hi), (max(y - r, 0), min(min(y + ky, y1) + r, Y)), (0, X))) for y in range(y0, y1, ky)]
+        z += 1
+    return slabs[rank::world_size]
+
+
+def section_outlier_sums(volume, tile=128, skip=(), max_lag=4, chunk_bytes=None, rank=0, world_size=1, device=None,
+                         stats=None):
+    """How far the voxels of every tile of a section lie outside the range of the voxels below and above them:
+    np.int64 [Z, gy, gx, 2] over the WHOLE uint8 `volume` [z, y, x] (ndarray, np.memmap, h5py / zarr dataset; one image
+    [y, x]: Z = 1, all zero) on clahe_grid's tiles of `tile` pixels (an int or (th, tw) in [1, 2048]).  With
+    (lo, hi) = section_neighbours(Z, skip, max_lag)[z], the nearest good sections around z, and per voxel
+    a = volume[lo, y, x], v = volume[z, y, x], b = volume[hi, y, x]:
+      e = |v - median(a, v, b)|: 0 where v lies between a and b, else its distance to the nearer one
+      s[z, i, j] = (sum e, the number of voxels) over tile (i, j);   (0, 0) for a section without a verdict
+    -- the voxel's form of find_defects' rule "resembles NEITHER neighbour", and the three-tap temporal median of film
+    restoration.  Exact integers that numpy reproduces bit for bit, whatever the slabs, ranks and launches.
+    outlier_thresholds turns them into what is ordinary for each column of tiles, volume_outliers into a mask; find_debris
+    runs all three.  The stack must be ALIGNED first (section_shifts ... volume_warp): misaligned sections read as
+    outliers everywhere.
+
+    section_sums' pass over outlier_chunks' read slabs (radius 0): one host thread -> pinned -> H2D -> one
+    tem_u8_zdev_tiles launch per slab, adding into a device accumulator that holds the whole volume's Z*gy*gx*16 bytes
+    and is read back once where that is at most CLAHE_ACC_BYTES, else one slab's core sections, read back and added on
+    the host per slab.  The table goes to the device once.  Ranks take slabs round-robin and their results add up to
+    the whole.  `stats` receives `read_s` and `chunks`.  ValueError, before any GPU work: as section_sums, and
+    section_pairs' for skip and max_lag."""
+    _check_u8(volume)
+    th, tw = _clahe_tile(tile)
+    gy, gx = clahe_grid(volume.shape, (th, tw))
+    box = hist_box(volume.shape)
+    Z = box[0][1]
+    nbr = section_neighbours(Z, skip, max_lag)
+    chunks = outlier_chunks(box, tuple(hi for _, hi in box), nbr, 0, chunk_bytes, rank, world_size)
+    p = _SlabPass([volume], [box], chunk_bytes, rank, world_size, device, slabs=[r for _, r in chunks])
+    lib = H.require_gpu()
+    sec = gy * gx * 2
+    whole = Z * sec * 8 <= CLAHE_ACC_BYTES
+    out = None if whole else np.zeros((Z, gy, gx, 2), np.int64)
+    with p.streaming():
+        most = max((c[0][1] - c[0][0] for c, _ in chunks), default=1)
+        acc = torch.zeros((Z if whole else most, sec), dtype=torch.int64, device=p.dev)
+        nbr_dev = torch.from_numpy(nbr).to(p.dev)                # uploaded once
+        for k, ((s0, _), (y0, _), (x0, _)), d, (src,) in p:
+            z0, z1 = chunks[k][0][0]
+            if not whole:
+                acc[:z1 - z0].zero_()
+            _lib.check(lib.tem_u8_zdev_tiles(src.data_ptr(), *d, s0, Z, z0 - s0, z1 - s0, y0, x0, th, tw, gy, gx,
+                                             nbr.ctypes.data, nbr_dev.data_ptr(),
+                                             acc.data_ptr() + 8 * sec * (z0 if whole else 0), p.compute.cuda_stream),
+                       "tem_u8_zdev_tiles")
+            if not whole:                                        # this slab's core sections, added on the host
+                out[z0:z1] += acc[:z1 - z0].cpu().numpy().reshape(z1 - z0, gy, gx, 2)
+        if whole:
+            out = acc.cpu().numpy().reshape(Z, gy, gx, 2)        # the one read-back
+    if stats is not None:
+        stats.update(p.st)
+    return out
+
+
+class OutlierThresholds(NamedTuple):
+    """outlier_thresholds' result: `thr` int32[gy, gx], what volume_outliers compares a window's mean deviation with, in
+    1/256 grey level; `scale` float64[gy, gx], the ordinary mean deviation of each column of tiles, in grey levels."""
+    thr: np.ndarray
+    scale: np.ndarray
+
+
+def outlier_thresholds(s, ratio=12.0, min_dev=16.0):
+    """What is ordinary for each column of tiles, from section_outlier_sums' `s`.  Host only.
+      scale[i, j] = np.median over the sections with n > 0 of sum e / n: the ordinary mean deviation of a voxel of the
+                    column from its neighbours' range, in grey levels; 0.0 for a column with no such section
+      thr[i, j]   = min(ceil(256 max(ratio scale, min_dev)), 65280)
+    A window is flagged where its mean deviation exceeds thr / 256 grey levels: `ratio` (> 0) times the ordinary one, and
+    at least `min_dev` (in (0, 255]), a floor in grey levels that keeps resin and constant columns from flagging their
+    noise.  ValueError for an `s` of another kind and parameters out of range."""
+    s = np.asarray(s)
+    if s.ndim != 4 or s.shape[3] != 2 or s.dtype.kind not in "iu":
+        raise ValueError(f"outlier_thresholds: s must be section_outlier_sums' integer array [Z, gy, gx, 2], got "
+                         f"{s.dtype} {s.shape}")
+    ratio, min_dev = _outlier_params(ratio, min_dev)
+    grid = s.shape[1:3]
+    scale = np.zeros(grid, np.float64)
+    for i in range(grid[0]):
+        for j in range(grid[1]):
+            n = s[:, i, j, 1]
+            if (n > 0).any():
+                scale[i, j] = np.median(s[n > 0, i, j, 0] / n[n > 0])
+    thr = np.minimum(np.ceil(256.0 * np.maximum(ratio * scale, min_dev)), OUTLIER_MAX_THR).astype(np.int32)
+    return OutlierThresholds(thr, scale)
+
+
+def volume_outliers(volume, thr, tile=128, window=9, skip=(), max_lag=4, tiles=None, out=None, start=None, size=None,
+                    chunk_bytes=None, stats=None, rank=0, world_size=1, device=None):
+    """The uint8 mask, 1 or 0, of the voxels of the ROI [start, start + size) ((x, y, z) order; default: the whole
+    volume) of a uint8 array-like `volume` [z, y, x] (ndarray, np.memmap, h5py / zarr dataset) that stand out from the
+    nearest good sections below and above them -- dust, precipitate, knife debris: damage far smaller than a tile --,
+    written into `out`: a writable uint8 array-like of the ROI's shape (ndarray, memmap, h5py, zarr; allocated when
+    None), which is returned; Repair takes it as `mask` where the ROI is the whole volume.  With e the deviation of
+    section_outlier_sums (neighbours by `skip` and `max_lag`), r = (window - 1) / 2 for an odd `window` in 3...15, Ws the
+    sum of e over the window of `window` x `window` pixels around the voxel, cut to the section, and c the number of
+    voxels of the cut window:
+      mask = 1 iff 256 Ws > thr[i, j] c, (i, j) the voxel's tile of `tile` pixels     (equality does not flag)
+    -- the window's mean deviation exceeds thr / 256 grey levels -- with `thr` outlier_thresholds' result or its int
+    table [gy, gx] in [1, 65280]; also 1 throughout the tiles named by `tiles` (find_defects' bool [Z, gy, gx]) where
+    given.  Summed over the window, a particle stands apart from the ordinary change between sections; the mask reaches
+    up to r pixels past it.  A section without a verdict, and one image [y, x], give zeros.  Everything is integers and
+    numpy reproduces every byte; a voxel depends on its window and two other sections alone, so the result of an ROI is
+    the ROI of the whole result, however it is cut.  The stack must be aligned first, and damage two or more sections
+    thick at the same place resembles a neighbour and is NOT flagged: find_defects or a `skip` list is the tool for that.
+
+    volume_repair's pass over outlier_chunks' read slabs: one host thread reads each -- the core, the sections its
+    neighbours name, r rows more on each side -- into double-buffered pinned memory -> H2D -> one tem_u8_zdev_mask
+    launch per slab -> D2H through the output stream -> host write, in the order write(k), read(k + 2) on the one host
+    thread.  The tables are uploaded once.  Ranks take slabs round-robin and write disjoint boxes of a shared `out`.
+    `stats` receives `read_s`, `write_s`, `chunks` and `flagged`: the ones written by this rank.
+    ValueError, before any GPU work: a non-uint8 volume, an ROI outside it, a bad tile, window, skip or max_lag, a `thr`
+    or `tiles` of another shape, dtype or range, an `out` of another shape or dtype."""
+    _check_u8(volume)
+    th, tw = _clahe_tile(tile)
+    gy, gx = clahe_grid(volume.shape, (th, tw))
+    box = hist_box(volume.shape, start, size)
+    whole = hist_box(volume.shape)
+    Z, Y, X = (hi for _, hi in whole)
+    r = _outlier_window(window)
+    nbr = section_neighbours(Z, skip, max_lag)
+    t = np.asarray(thr.thr if isinstance(thr, OutlierThresholds) else thr)
+    if t.shape != (gy, gx) or t.dtype.kind not in "iu":
+        raise ValueError(f"thr must be outlier_thresholds' integers of the tile grid's shape {(gy, gx)}, got {t.dtype} "
+                         f"{t.shape}")
+    if int(t.min()) < 1 or int(t.max()) > OUTLIER_MAX_THR:
+        raise ValueError(f"thr must lie in [1, {OUTLIER_MAX_THR}], got {int(t.min())}...{int(t.max())}")
+    t = np.ascontiguousarray(t.astype(np.int32))
+    if tiles is not None:
+        tiles = np.asarray(tiles)
+        if tiles.shape != (Z, gy, gx) or tiles.dtype.kind not in "biu":
+            raise ValueError(f"tiles must be bool or integers of the shape {(Z, gy, gx)} of the volume's tile grid, got "
+                             f"{tiles.dtype} {tiles.shape}")
+        tiles = np.ascontiguousarray((tiles != 0).astype(np.uint8))
+    one = len(volume.shape) == 2
+    shape = tuple(hi - lo for lo, hi in box)
+    if out is None:
+        out = np.zeros(shape[1:] if one else shape, np.uint8)
+    elif tuple(out.shape) != (shape[1:] if one else shape) or getattr(out, "dtype", None) != np.uint8:
+        raise ValueError(f"out must be uint8 of the ROI's shape {shape[1:] if one else shape}, got "
+                         f"{getattr(out, 'dtype', None)} {tuple(out.shape)}")
+    chunks = outlier_chunks(box, (Z, Y, X), nbr, r, chunk_bytes, rank, world_size)
+    p = _SlabPass([volume], [whole], chunk_bytes, rank, world_size, device, slabs=[rd for _, rd in chunks])
+    lib = H.require_gpu()
+    cores = [c for c, _ in chunks]
+    cdims = [tuple(hi - lo for lo, hi in c) for c in cores]
+    (oz, _), (oy, _), (ox, _) = box
+    dst_vol = _OneSection(out) if one else out
+    p.st["write_s"] = 0.0
+
+    def write_from(k, flat):            # host thread: the core's box of `out`
+        (z0, z1), (y0, y1), (x0, x1) = cores[k]
+        dst_vol[z0 - oz:z1 - oz, y0 - oy:y1 - oy, x0 - ox:x1 - ox] = flat.reshape(cdims[k])
+
+    with p.streaming():
+        nbr_dev, thr_dev = torch.from_numpy(nbr).to(p.dev), torch.from_numpy(t).to(p.dev)   # the tables, once
+        tiles_dev = None if tiles is None else torch.from_numpy(tiles).to(p.dev)
+        count = torch.zeros(1, dtype=torch.int64, device=p.dev)
+        with _OutputStream([int(np.prod(d)) for d in cdims], write_from, p.dev, p.pool, p.st,
+                           own_buffers=True) as outp:                    # the reader's thread: write(k), read(k + 2)
+            for k, ((s0, _), (ry, _), _), d, (src,) in p:
+                (cz0, cz1), (cy0, cy1), (cx0, cx1) = cores[k]
+                _lib.check(lib.tem_u8_zdev_mask(src.data_ptr(), *d, s0, Z, Y, ry, cz0 - s0, cz1 - s0, cy0 - ry, cy1 - ry,
+                                                cx0, cx1, th, tw, gy, gx, r, nbr.ctypes.data, nbr_dev.data_ptr(),
+                                                t.ctypes.data, thr_dev.data_ptr(),
+                                                None if tiles is None else tiles_dev.data_ptr() + cz0 * gy * gx,
+                                                outp.device(k).data_ptr(), count.data_ptr(), p.compute.cuda_stream),
+                           "tem_u8_zdev_mask")
+                p.release_on = p.compute.record_event()                  # behind the kernel: the input is free too
+                outp.put(k, p.release_on)
+        p.st["flagged"] = int(count.cpu().numpy()[0])                    # the one read-back
+    if stats is not None:
+        stats.update(p.st)
+    return out
+
+
+def find_debris(volume, tile=128, window=9, ratio=12.0, min_dev=16.0, skip=(), max_lag=4, defects=None, mask_out=None,
+                max_gap=8, **pass_kw):
+    """Find the small damage of a uint8 `volume` [z, y, x] -- dust, precipitate, knife debris: particles on ONE section,
+    far below what find_defects' tile correlations can see -- and return the Repair that fills it:
+    section_outlier_sums -> outlier_thresholds(ratio, min_dev) -> volume_outliers(window) over the whole volume, the
+    mask written into `mask_out` where given (a uint8 array-like of the volume's shape; np.memmap for a volume that does
+    not fit).  The sections `skip` (black, lost, foreign) are judged by nobody and no section is judged against them:
+    their neighbours are bridged up to `max_lag`.  With `defects` (find_defects' Defects) its sections join `skip` and
+    its bad tiles are set in the mask whole.  Returns Repair(sorted skipped sections, mask, None, max_gap), which
+    volume_repair and predict_*(repair=...) take unchanged.  `pass_kw` (chunk_bytes, device, stats) goes to both passes;
+    `stats` is the mask pass's.  For several ranks run the passes themselves: their sums must be added in between.
+
+    The stack must be aligned first: misaligned sections read as outliers everywhere.  The limit of the rule: damage two
+    or more sections thick at the same place resembles a neighbour and is not flagged; find_defects or a `skip` list is
+    the tool for that."""
+    R = _index(max_gap, "max_gap")
+    if not 1 <= R <= REPAIR_MAX_GAP:
+        raise ValueError(f"max_gap must lie in 1...{REPAIR_MAX_GAP}, got {R}")
+    extra = set(pass_kw) - {"chunk_bytes", "device", "stats"}
+    if extra:
+        raise ValueError(f"find_debris passes chunk_bytes, device and stats on, got {sorted(extra)}")
+    if len(volume.shape) != 3:
+        raise ValueError(f"find_debris needs a volume [z, y, x], got shape {tuple(volume.shape)}")
+    try:
+        bad = {_index(z, "a skipped section") for z in skip}
+    except TypeError:
+        raise ValueError(f"skip must be a list of sections, got {skip!r}")
+    tiles = None
+    if defects is not None:
+        try:
+            bad |= {_index(z, "a section") for z in defects.sections}
+            tiles = np.asarray(defects.tiles)
+        except (AttributeError, TypeError):
+            raise ValueError(f"defects must be find_defects' Defects, got {type(defects).__name__}")
+    sections = sorted(bad)
+    _check_u8(volume)                                            # every ValueError ahead of the first pass
+    tile = _clahe_tile(tile)
+    _outlier_window(window), _outlier_params(ratio, min_dev)
+    vshape = tuple(int(v) for v in volume.shape)
+    if mask_out is not None and (tuple(mask_out.shape) != vshape or getattr(mask_out, "dtype", None) != np.uint8):
+        raise ValueError(f"mask_out must be uint8 of the volume's shape {vshape}, got {getattr(mask_out, 'dtype', None)} "
+                         f"{tuple(mask_out.shape)}")
+    if tiles is not None and tiles.shape != (vshape[0],) + clahe_grid(vshape, tile):
+        raise ValueError(f"defects.tiles must have the shape {(vshape[0],) + clahe_grid(vshape, tile)} of the volume's "
+                         f"tile grid, got {tiles.shape}")
+    sums_kw = {k: v for k, v in pass_kw.items() if k != "stats"}
+    s = section_outlier_sums(volume, tile, sections, max_lag, **sums_kw)
+    t = outlier_thresholds(s, ratio, min_dev)
+    mask = volume_outliers(volume, t, tile, window, sections, max_lag, tiles=tiles, out=mask_out, **pass_kw)
     return Repair(sections, mask, None, R)
 
 
