@@ -710,6 +710,42 @@ int tem_u8_zshift_tiles(const uint8_t *src, int32_t D, int32_t H, int32_t W, int
                         int32_t r1, int32_t y_org, int32_t Y, int32_t th, int32_t tw, int32_t gy, int32_t gx,
                         int32_t radius, uint64_t *sums, tem_stream_t stream);
 
+/* The sums behind the correlation of every tile of a section with ITSELF displaced by 1...nlag pixels along y and along
+ * x (utils.section_plane_sums -> plane_scores -> section_sharpness -> find_blurred: sections and regions that are out of
+ * focus; plane_curve -> z_pitch: how many pixels thick a section is).  The definition, once: the volume is V[Z][Y][X],
+ * uint8; tiles of (th, tw) pixels on tem_u8_hist_tiles' grid, gy x gx of them anchored at the volume's (0, 0); L = nlag
+ * lies in 1...8.  For a section z and a tile (i, j), over the tile's voxels (y, x): the partner of the y lag k is
+ * (y + k, x), that of the x lag k is (y, x + k); a pair counts where the partner lies inside the section -- y + k < Y,
+ * x + k < X; it may lie outside the tile: tem_u8_zshift_tiles' rule.  With v the voxel and w its partner:
+ *   q = sums + ((z * gy + i) * gx + j) * (3 + 2 L)
+ *   q[0] += v      q[1] += v v      q[2] += 1
+ *   q[2 + k]     += (v - w)^2   for the y lag k = 1...L
+ *   q[2 + L + k] += (v - w)^2   for the x lag k = 1...L
+ * int64 and exact.  The number of terms per lag is geometry only (utils.plane_lag_counts); the kernel does not count
+ * them.  Squared differences, not products: the variogram needs no mean, whose error on a small tile swamps the
+ * decay from one pixel to the next.  A full 2048 x 2048 tile of 255s next to 0s stays below 2^38 per entry.
+ *
+ * tem_u8_zplane_lags follows tem_u8_zshift_tiles' block contract: src[D][H][W] is a dense block of WHOLE rows (W == X)
+ * whose row 0 sits at volume row y_org of a section of Y rows.  The voxels counted as v are the core planes [c0, c1) and
+ * core rows [r0, r1); the block must hold every partner row of the core that the section has -- [0, H) contains
+ * [r0, r1 + nlag) cut to Y - y_org.  No partner plane is needed: every plane of the block may be core.  sums (8-byte
+ * aligned) points at the rows of plane c0:
+ *   sums[(((d - c0) * gy + i) * gx + j) * (3 + 2 nlag) + 0 .. 2 + 2 nlag] += the sums above
+ * The kernel ADDS (64-bit global atomic adds, ordinary vector atomics: one per workgroup, plane and quantity): the
+ * caller clears sums once, and blocks that cut a tile along y or z between them accumulate into it.  Nothing but sums
+ * is written.  A load touches only naturally aligned words (up to 16 bytes) that hold at least one byte of the block.
+ * Any alignment of src and W.  No partial can overflow at (v - w)^2 <= 65025 per term: a thread sums at most 16 rows of
+ * 16 bytes, 256 terms, in 32 bits (256 x 65025 < 2^24), a wave 64 such partials (< 2^30); a workgroup is four waves, one
+ * plane each, and every wave's sum is widened to 64 bits for its global add; the 64-bit counter takes a whole
+ * 2048 x 2048 tile per plane (2^22 x 65025 < 2^38) 2^25 times over.
+ * TEM_EINVAL, without a launch: what tem_u8_zshift_tiles refuses (with nlag outside 1...8 in the place of its radius),
+ * and a block without a partner row that the section has.  TEM_EUNSUPPORTED: 2^24 workgroups or more (one per four core
+ * planes, tile, run of up to 16 x 64 / ceil(columns / 16) rows and 1024 columns of it; their 256 threads then stay
+ * below 2^32 per launch).  An empty core launches nothing. */
+int tem_u8_zplane_lags(const uint8_t *src, int32_t D, int32_t H, int32_t W, int32_t c0, int32_t c1, int32_t r0,
+                       int32_t r1, int32_t y_org, int32_t Y, int32_t th, int32_t tw, int32_t gy, int32_t gx,
+                       int32_t nlag, uint64_t *sums, tem_stream_t stream);
+
 /* tem_u8_zshift_tiles with the search window of every section and tile CENTRED on an offset of its own instead of on
  * zero (utils.section_shift_sums_at, the device leg of utils.section_shifts_coarse_to_fine: a coarse level's answer,
  * doubled, is the centre of the next finer level's search, so displacements far past the radius are measured).

@@ -162,6 +162,7 @@ _SIGS = {
     "tem_u8_zdev_tiles": [C.c_void_p] + [C.c_int32] * 13 + [C.c_void_p] * 4,
     "tem_u8_zdev_mask": [C.c_void_p] + [C.c_int32] * 18 + [C.c_void_p] * 8,
     "tem_u8_zshift_tiles": [C.c_void_p] + [C.c_int32] * 14 + [C.c_void_p, C.c_void_p],
+    "tem_u8_zplane_lags": [C.c_void_p] + [C.c_int32] * 14 + [C.c_void_p, C.c_void_p],
     "tem_u8_zshift_tiles_at": [C.c_void_p] + [C.c_int32] * 14 + [C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p, C.c_void_p],
     "tem_u8_zshift_tiles_pairs": [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p] + [C.c_int32] * 9 + [C.c_void_p] +
                                  [C.c_int32] * 3 + [C.c_void_p, C.c_void_p],

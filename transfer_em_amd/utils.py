@@ -80,6 +80,12 @@ per lag and `section_spacing` into the sections' positions along z, from how fas
 `quantize_positions` brings them to 2^-16 section, `resample_z_taps` to the table of taps, and `volume_resample_z`
 resamples the stack (or, nearest, a mask) onto the even grid out of core (tem_u8_resample_z); `zlag_chunks` and
 `resample_z_chunks` are the slab plans.
+
+`section_plane_sums` looks INSIDE a section: the sums behind the correlation of every tile with itself displaced by a few
+pixels along y and x (tem_u8_zplane_lags; `plane_lag_chunks` is the slab plan, `plane_lag_counts` the number of pairs).
+`plane_scores` turns them into correlations, `section_sharpness` and `find_blurred` into the sections and regions that
+are out of focus (a Defects; `join_defects` joins it with find_defects'), `plane_curve` and `z_pitch` into the sections'
+distance in pixels, and `pitch_step` into the `volume_rescale` step that makes the stack isotropic.
 """
 import contextlib
 import json
@@ -2611,6 +2617,323 @@ def volume_resample_z(volume, positions, out=None, start=None, size=None, nz=Non
     if stats is not None:
         stats.update(p.st)
     return out
+
+
+PLANE_LAG_MAX = 8                # tem_u8_zplane_lags: 1 <= nlag <= 8
+
+
+def _plane_lag(max_lag):
+    L = _index(max_lag, "max_lag")
+    if not 1 <= L <= PLANE_LAG_MAX:
+        raise ValueError(f"max_lag must lie in 1...{PLANE_LAG_MAX}, got {L}")
+    return L
+
+
+def plane_lag_chunks(vol_shape, max_lag=8, chunk_bytes=None, rank=0, world_size=1):
+    """Cut a volume of shape `vol_shape` [z, y, x] (one image [y, x]: one section) into slabs for section_plane_sums.
+    Returns this rank's list of (core slab, read slab), both (z, y, x) (lo, hi) boxes: the cores are disjoint and their
+    union is the volume (hist_chunks' cuts: runs of whole sections, or runs of whole rows of one section; x is never
+    cut).  Nothing is looked at along z, so a run of whole sections is its own read slab; where a section is cut into
+    rows, the read slab reaches `max_lag` rows past the core, clipped to the section -- where the y partners of its
+    last rows lie.  A read slab holds at most `chunk_bytes` bytes (HIST_CHUNK_BYTES when None) wherever one core row
+    allows it: as many whole sections as fit, or, where one section is larger than the budget, as many rows as fit next
+    to their max_lag rows of halo (one row at the least).  Slabs are in (z, y) order and go round-robin to the ranks.
+    Pure host function; ValueError as hist_box and hist_chunks, and for max_lag outside 1...PLANE_LAG_MAX."""
+    L = _plane_lag(max_lag)
+    budget = HIST_CHUNK_BYTES if chunk_bytes is None else int(chunk_bytes)
+    if budget < 1:
+        raise ValueError(f"chunk_bytes must be positive, got {chunk_bytes}")
+    if not 0 <= rank < world_size:
+        raise ValueError(f"rank {rank} is outside [0, {world_size})")
+    (_, Z), (_, ny), (_, nx) = hist_box(vol_shape)
+    if Z <= 0 or ny <= 0 or nx <= 0:
+        return []
+    if ny * nx <= budget:
+        kz = budget // (ny * nx)
+        slabs = [(((z, min(z + kz, Z)), (0, ny), (0, nx)),) * 2 for z in range(0, Z, kz)]
+    else:
+        ky = max(1, budget // nx - L)
+        slabs = [(((z, z + 1), (y, min(y + ky, ny)), (0, nx)), ((z, z + 1), (y, min(y + ky + L, ny)), (0, nx)))
+                 for z in range(Z) for y in range(0, ny, ky)]
+    return slabs[rank::world_size]
+
+
+def plane_lag_counts(vol_shape, tile, max_lag=8):
+    """np.int64 n[gy, gx, 2, L]: the number of voxels (y, x) of tile (i, j) of a section of a volume of shape
+    `vol_shape` ([z, y, x] or [y, x]) whose partner lies inside the section -- n[i, j, 0, k - 1] for the partner
+    (y + k, x), n[i, j, 1, k - 1] for (y, x + k): the number of terms of section_plane_sums' s[z, i, j, 2 + k] and
+    s[z, i, j, 2 + L + k].  Geometry only, in closed form: rows times columns, the tile's rows (columns) cut to
+    [0, extent - k).  Pure host function."""
+    L = _plane_lag(max_lag)
+    th, tw = _clahe_tile(tile)
+    gy, gx = clahe_grid(vol_shape, (th, tw))
+    _, (_, Y), (_, X) = hist_box(vol_shape)
+    k = np.arange(1, L + 1, dtype=np.int64)
+
+    def along(t, g, n):                                                  # [g, 1 + L]: the whole interval, then cut by k
+        lo = (np.arange(g, dtype=np.int64) * t)[:, None]
+        cut = np.concatenate([[0], k])[None, :]
+        return np.maximum(np.minimum(lo + t, n - cut) - lo, 0)
+    ry, rx = along(th, gy, Y), along(tw, gx, X)
+    n = np.zeros((gy, gx, 2, L), np.int64)
+    n[:, :, 0, :] = ry[:, None, 1:] * rx[None, :, :1]
+    n[:, :, 1, :] = ry[:, None, :1] * rx[None, :, 1:]
+    return n
+
+
+def section_plane_sums(volume, tile=128, max_lag=8, chunk_bytes=None, rank=0, world_size=1, device=None, stats=None):
+    """The sums behind the correlation of every tile of a section with ITSELF displaced by 1...L = `max_lag` (1...8)
+    pixels along y and along x: np.int64 s[Z, gy, gx, 3 + 2 L] over the WHOLE uint8 `volume` [z, y, x] (ndarray,
+    np.memmap, h5py / zarr dataset; one image [y, x]: Z = 1) on clahe_grid's tiles of `tile` pixels (an int or (th, tw)
+    in [1, 2048]).  Over the voxels v = volume[z, y, x] of tile (i, j), with the partner w = volume[z, y + k, x] for
+    the y lag k and w = volume[z, y, x + k] for the x lag k, where it lies inside the section -- it may lie outside the
+    tile:
+      s[z, i, j] = (sum v, sum v v, the number of voxels, sum (v - w)^2 for y lag 1...L, sum (v - w)^2 for x lag 1...L)
+    The number of terms per lag is plane_lag_counts'.  Exact integers that numpy reproduces bit for bit, whatever the
+    slabs, ranks and launches.  plane_scores turns them into correlations, section_sharpness and find_blurred into the
+    sections and regions that are out of focus, plane_curve and z_pitch into the sections' thickness in pixels.
+
+    Out of core exactly as section_lag_sums, over plane_lag_chunks' read slabs (a core of rows reaches L rows further):
+    one host thread -> pinned -> H2D -> one tem_u8_zplane_lags launch per slab, adding into a device accumulator.  The
+    accumulator holds the whole volume's sums and is read back once where they are at most CLAHE_ACC_BYTES; else it
+    holds one slab's core sections and is read back, and added on the host, per slab.  Ranks take slabs round-robin and
+    their results add up to the whole.  `stats` receives `read_s` and `chunks`.  ValueError, before any GPU work: a
+    non-uint8 volume, a bad tile, max_lag, shape, chunk_bytes or rank."""
+    _check_u8(volume)
+    L = _plane_lag(max_lag)
+    th, tw = _clahe_tile(tile)
+    gy, gx = clahe_grid(volume.shape, (th, tw))
+    box = hist_box(volume.shape)
+    chunks = plane_lag_chunks(volume.shape, L, chunk_bytes, rank, world_size)
+    p = _SlabPass([volume], [box], chunk_bytes, rank, world_size, device, slabs=[r for _, r in chunks])
+    lib = H.require_gpu()
+    Z, Y, sec = box[0][1], box[1][1], gy * gx * (3 + 2 * L)
+    whole = Z * sec * 8 <= CLAHE_ACC_BYTES
+    out = None if whole else np.zeros((Z, gy, gx, 3 + 2 * L), np.int64)
+    with p.streaming():
+        most = max((c[0][1] - c[0][0] for c, _ in chunks), default=1)
+        acc = torch.zeros((Z if whole else most, sec), dtype=torch.int64, device=p.dev)
+        for k, ((s0, _), (y0, _), _), d, (src,) in p:
+            (z0, z1), (c0, c1), _ = chunks[k][0]
+            if not whole:
+                acc[:z1 - z0].zero_()
+            _lib.check(lib.tem_u8_zplane_lags(src.data_ptr(), *d, z0 - s0, z1 - s0, c0 - y0, c1 - y0, y0, Y, th, tw, gy,
+                                              gx, L, acc.data_ptr() + 8 * sec * (z0 if whole else 0),
+                                              p.compute.cuda_stream), "tem_u8_zplane_lags")
+            if not whole:                                        # this slab's core sections, added on the host
+                out[z0:z1] += acc[:z1 - z0].cpu().numpy().reshape(z1 - z0, gy, gx, 3 + 2 * L)
+        if whole:
+            out = acc.cpu().numpy().reshape(Z, gy, gx, 3 + 2 * L)        # the one read-back
+    if stats is not None:
+        stats.update(p.st)
+    return out
+
+
+def _check_plane_sums(s, n, who):
+    s, n = np.asarray(s), np.asarray(n)
+    if s.ndim != 4 or s.shape[3] < 5 or (s.shape[3] - 3) % 2 or s.shape[3] > 3 + 2 * PLANE_LAG_MAX or \
+            s.dtype.kind not in "iu":
+        raise ValueError(f"{who}: s must be section_plane_sums' integer array [Z, gy, gx, 3 + 2 L], got {s.dtype} "
+                         f"{s.shape}")
+    L = (s.shape[3] - 3) // 2
+    if n.shape != s.shape[1:3] + (2, L) or n.dtype.kind not in "iu":
+        raise ValueError(f"{who}: n must be plane_lag_counts' integer array {s.shape[1:3] + (2, L)}, got {n.dtype} "
+                         f"{n.shape}")
+    return s.astype(np.int64, copy=False), n.astype(np.int64, copy=False), L
+
+
+def plane_scores(s, n):
+    """float64 r[Z, gy, gx, 2, L]: the correlation of every tile of a section with itself displaced by k = 1...L pixels
+    along y (r[..., 0, k - 1]) and along x (r[..., 1, k - 1]), from section_plane_sums' `s` and plane_lag_counts' `n`.
+    Host only.  It is the variogram's form, r = 1 - (D / n) / (2 var): with N = s[..., 2], S1 = s[..., 0],
+    S2 = s[..., 1] and D the lag's sum of squared differences,
+      A = N S2 - S1^2          exact in int64: the tile's variance is A / N^2
+      r = 1.0 - (float(D) * float(N * N)) / ((2.0 * float(n)) * float(A))      in this order, in float64
+    and 0.0 where A <= 0 (a constant tile correlates with nothing) or n = 0 (no pair)."""
+    s, n, L = _check_plane_sums(s, n, "plane_scores")
+    N, S1, S2 = s[..., 2], s[..., 0], s[..., 1]
+    A = (N * S2 - S1 * S1)[..., None, None]
+    D = s[..., 3:].reshape(s.shape[:3] + (2, L))
+    ok = (A > 0) & (n[None] > 0)
+    r = np.zeros(D.shape, np.float64)
+    num = D.astype(np.float64) * (N * N).astype(np.float64)[..., None, None]
+    den = (2.0 * n.astype(np.float64))[None] * A.astype(np.float64)
+    np.divide(num, den, out=r, where=ok)
+    return np.where(ok, 1.0 - r, 0.0)
+
+
+def _plane_mean_scores(s, n, who, least):
+    r = plane_scores(s, n)
+    if r.shape[4] < least:
+        raise ValueError(f"{who} needs sums of {least} lags at least, got {r.shape[4]}")
+    return (r[..., 0, :] + r[..., 1, :]) * 0.5                          # [Z, gy, gx, L]
+
+
+def section_sharpness(s, n):
+    """float64 g[Z, gy, gx]: how fast every tile's correlation with itself decays from a displacement of one pixel to
+    two -- with r_k the mean of plane_scores' y and x score at lag k ((r_y + r_x) * 0.5), g = 1 - r_2 / r_1 where
+    r_1 > 0, else 0.0.  Host only; needs L >= 2 (ValueError).  A section that is out of focus has lost its fine detail:
+    its correlation decays slowly, g is small.  The decay, not 1 - r_1: white detector noise lowers every r_k, k >= 1,
+    by the same factor, so the ratio does not see it."""
+    m = _plane_mean_scores(s, n, "section_sharpness", 2)
+    r1, r2 = m[..., 0], m[..., 1]
+    g = np.zeros(r1.shape, np.float64)
+    np.divide(r2, r1, out=g, where=r1 > 0)
+    return np.where(r1 > 0, 1.0 - g, 0.0)
+
+
+def find_blurred(s, n, ratio=0.65, min_corr=0.1, section_fraction=0.5):
+    """The sections and regions of a volume that are softer than the same place in the other sections -- focus drift, a
+    section that lifted off the grid, a frame taken while the beam re-tuned -- from section_plane_sums' `s` and
+    plane_lag_counts' `n`: a Defects, as find_defects', which passes them all (a soft section still resembles both
+    neighbours).  Host only.  With r_1 the mean lag-1 score of plane_scores and g = section_sharpness(s, n):
+      undecided  np.median(r_1[:, i, j]) <= min_corr, or np.median(g[:, i, j]) is not positive: resin, no texture
+                 -- no verdict for this column of tiles
+      bad        decided and g < ratio x the column's median of g
+      sections   the sorted list of sections whose bad tiles are at least `section_fraction` of the decided tiles
+      tiles      bool[Z, gy, gx]: the bad tiles of the other sections
+      scores     g
+    One image (Z = 1) is judged against nothing: every column is undecided.  `ratio` and `section_fraction` lie in
+    (0, 1], `min_corr` in (0, 1): ValueError otherwise, as for fewer than two lags.  The limits of the rule: a run of
+    soft sections longer than half the stack moves the median, and then the SHARP sections are what differs; a column
+    that is soft throughout the stack is not flagged.  join_defects and defects_repair turn the verdict, with
+    find_defects', into one Repair."""
+    m = _plane_mean_scores(s, n, "find_blurred", 2)
+    ratio, frac = _unit(ratio, "ratio", True), _unit(section_fraction, "section_fraction", True)
+    min_corr = _unit(min_corr, "min_corr", False)
+    g = section_sharpness(s, n)
+    Z, grid = g.shape[0], g.shape[1:]
+    if Z < 2:
+        return Defects([], np.zeros((Z,) + grid, bool), np.ones(grid, bool), g)
+    med = np.median(g, axis=0)
+    undecided = (np.median(m[..., 0], axis=0) <= min_corr) | ~(med > 0)
+    bad = ~undecided[None] & (g < ratio * med[None])
+    decided = int((~undecided).sum())
+    nbad = bad.reshape(Z, -1).sum(axis=1)
+    sections = [z for z in range(Z) if nbad[z] > 0 and nbad[z] >= frac * decided]
+    tiles = bad.copy()
+    tiles[sections] = False
+    return Defects(sections, tiles, undecided, g)
+
+
+def join_defects(*d):
+    """One Defects from several verdicts on the same stack and tile grid (find_defects', find_blurred's): `sections`
+    the union, `tiles` the OR with the tiles of bad sections cleared, `undecided` the AND -- a column is without a
+    verdict only where no rule had one --, `scores` the first verdict's (scores of different rules do not combine).
+    defects_repair(join_defects(...), ...) is then one Repair.  ValueError for no verdict, for something that is not a
+    Defects, and for verdicts of different shapes."""
+    if not d:
+        raise ValueError("join_defects needs one verdict at least")
+    try:
+        sections = sorted({_index(z, "a section") for v in d for z in v.sections})
+        tiles = [np.asarray(v.tiles) != 0 for v in d]
+        undecided = [np.asarray(v.undecided) != 0 for v in d]
+        scores = d[0].scores
+    except (AttributeError, TypeError):
+        raise ValueError(f"join_defects needs Defects, got {[type(v).__name__ for v in d]}")
+    if any(t.ndim != 3 or t.shape != tiles[0].shape or u.shape != t.shape[1:] for t, u in zip(tiles, undecided)):
+        raise ValueError(f"join_defects: the verdicts' shapes differ: {[t.shape for t in tiles]}, "
+                         f"{[u.shape for u in undecided]}")
+    if any(not 0 <= z < tiles[0].shape[0] for z in sections):
+        raise ValueError(f"join_defects: sections outside [0, {tiles[0].shape[0]}): {sections}")
+    t = np.logical_or.reduce(tiles)
+    t[sections] = False
+    return Defects(sections, t, np.logical_and.reduce(undecided), scores)
+
+
+def plane_curve(s, n, skip=(), min_corr=0.1):
+    """float64 curve[K + 1]: the correlation of the stack's texture with itself at an in-plane distance of 0...K
+    pixels, K <= L -- the ruler, in pixels, for section_spacing's curve along z (z_pitch).  From section_plane_sums' `s`
+    and plane_lag_counts' `n`; host only.  `skip` lists the bad sections (find_defects, find_blurred); the others are
+    good.  With r_k the mean of plane_scores' y and x score at lag k:
+      1. a tile column is decided where the median of r_1 over the good sections is above `min_corr`;
+      2. c[z, k] is the lower median over the decided columns of r_k of section z;
+      3. curve[0] = 1 and curve[k] is the median of c[z, k] over the good sections;
+      4. the curve is cut behind the last lag up to which it decreases strictly: K.
+    ValueError if K < 1 (no good section, no decided column, a flat stack), and for a bad skip or min_corr."""
+    m = _plane_mean_scores(s, n, "plane_curve", 1)
+    Z, L = m.shape[0], m.shape[3]
+    try:
+        bad = {_index(z, "a skipped section") for z in skip}
+    except TypeError:
+        raise ValueError(f"skip must be a list of sections, got {skip!r}")
+    if any(not 0 <= z < Z for z in bad):
+        raise ValueError(f"skip names sections outside [0, {Z}): {sorted(z for z in bad if not 0 <= z < Z)}")
+    mc = _unit(min_corr, "min_corr", closed=False)
+    good = [z for z in range(Z) if z not in bad]
+    curve = [1.0]
+    if good:
+        m = m[good]
+        decided = np.median(m[..., 0], axis=0) > mc
+        if decided.any():
+            c = _lower_median(m[:, decided, :], axis=1)                  # [good, L]
+            for k in range(L):
+                v = float(np.median(c[:, k]))
+                if not v < curve[-1]:
+                    break
+                curve.append(v)
+    if len(curve) < 2:
+        raise ValueError(f"plane_curve: the correlation does not decrease with the distance ({len(good)} good sections)")
+    return np.array(curve, np.float64)
+
+
+class ZPitch(NamedTuple):
+    """z_pitch's estimate: `pixels` the distance of two consecutive sections in in-plane pixels (the median of
+    `per_lag`'s used entries), `per_lag` float64[Lz] the estimate of z lag k in [k - 1], NaN where the lag is out of
+    reach, `used` bool[Lz]."""
+    pixels: float
+    per_lag: np.ndarray
+    used: np.ndarray
+
+
+def _check_curve(c, what):
+    c = np.asarray(c, np.float64)
+    if c.ndim != 1 or c.size < 2 or not np.isfinite(c).all() or c[0] != 1.0 or not np.all(np.diff(c) < 0):
+        raise ValueError(f"{what} must be a curve that decreases strictly from 1.0, two values at least, got {c!r}")
+    return c
+
+
+def z_pitch(z_curve, p_curve):
+    """How far two consecutive sections lie apart, in in-plane pixels: ZPitch(pixels, per_lag, used) from `z_curve`,
+    the correlation at 0...Lz sections (section_spacing's Spacing.curve), and `p_curve`, the correlation at 0...K
+    pixels (plane_curve).  Host only.  For every z lag k with p_curve[K] < z_curve[k] < 1, the in-plane distance at
+    which the texture is as correlated as across k sections is the piecewise-linear inverse of p_curve at z_curve[k]
+    (section_spacing's step 4); divided by k it is that lag's estimate, and `pixels` is the median of the estimates.
+    pitch_step turns it into volume_rescale's step.  The assumption: the tissue's statistics and the imaging blur are
+    isotropic -- a section is thick and the beam's spot is not, so a real stack's pitch comes out a little large.
+    ValueError for curves that do not decrease strictly from 1.0, and where no lag is within reach."""
+    zc, pc = _check_curve(z_curve, "z_curve"), _check_curve(p_curve, "p_curve")
+    K = pc.size - 1
+    per_lag = np.full(zc.size - 1, np.nan)
+    used = (zc[1:] > pc[K]) & (zc[1:] < 1.0)
+    if not used.any():
+        raise ValueError(f"z_pitch: no z lag lies within reach of the in-plane curve: z {zc.tolist()}, plane {pc.tolist()}")
+    dist = np.interp(zc[1:], pc[::-1], np.arange(K, -1, -1.0))
+    per_lag[used] = dist[used] / np.arange(1, zc.size)[used]
+    return ZPitch(float(np.median(per_lag[used])), per_lag, used)
+
+
+def pitch_step(pixels):
+    """volume_rescale's step (1, 1, Fraction) in (x, y, z) order that makes a stack isotropic whose sections lie
+    `pixels` in-plane pixels apart (z_pitch): along z an output voxel is 1 / pixels sections, brought to the nearest
+    p / q with 1 <= p, q <= RESCALE_MAX_PQ (the smallest q on a tie).  ValueError for a pitch that is not a positive
+    finite number, and where 1 / pixels lies outside [1 / RESCALE_MAX_STEP, RESCALE_MAX_STEP]."""
+    try:
+        if isinstance(pixels, (bool, np.bool_, str, bytes)):
+            raise TypeError
+        x = float(pixels)
+    except (TypeError, ValueError):
+        raise ValueError(f"pixels must be a number, got {pixels!r}")
+    if not (np.isfinite(x) and x > 0) or not 1 / RESCALE_MAX_STEP <= 1 / x <= RESCALE_MAX_STEP:
+        raise ValueError(f"a pitch must be positive and 1 / pixels within [1/{RESCALE_MAX_STEP}, {RESCALE_MAX_STEP}], "
+                         f"got {pixels!r}")
+    best = None
+    for q in range(1, RESCALE_MAX_PQ + 1):
+        p = min(max(int(np.floor(q / x + 0.5)), 1), RESCALE_MAX_PQ)
+        f = Fraction(p, q)
+        if RESCALE_MAX_STEP * f >= 1 and f <= RESCALE_MAX_STEP and (best is None or abs(f - 1 / Fraction(x)) < best[0]):
+            best = (abs(f - 1 / Fraction(x)), f)
+    return (Fraction(1), Fraction(1), best[1])
 
 
 SHIFT_MAX_RADIUS = 8             # offsets of section_shift_sums: [-r, r]^2, r in 1...8
