@@ -7,16 +7,9 @@ import numpy as np
 import pytest
 import torch
 
-from util import activation_stats, hip_gates, rel_err, scaled_params
+from util import _inputs, _pole_margin, activation_stats, hip_gates, rel_err, scaled_params
 
 pytestmark = pytest.mark.gpu
-
-
-def _inputs(shape, seed):
-    rng = np.random.default_rng(seed)
-    u = rng.integers(0, 256, shape[:-1], dtype=np.uint8)
-    x = (u.astype(np.float32) / np.float32(127.5) - np.float32(1.0))[..., None]
-    return ((x - x.mean()) / x.std()).astype(np.float32)
 
 
 def _load(model, st):
@@ -34,17 +27,6 @@ def _state(graph, is3d, scaled):
         st["g"], st["f"] = scaled_params(gs, 10), scaled_params(gs, 11)
         st["dx"], st["dy"] = scaled_params(ds, 12), scaled_params(ds, 13)
     return st
-
-
-def _pole_margin(aux, rx, ry, b, crop_by):
-    """Smallest 1 - |a - b| / 2 over the pixels of the four cycle / identity terms, from the oracle's own outputs: the
-    loss -log(1 - |a - b| / 2) has a pole there, and its gradient moves by delta / (2 margin) of itself when an output
-    moves by delta (conditioning note)."""
-    worst = np.inf
-    for key, real in (("same_x", rx), ("same_y", ry), ("cyc_x", rx), ("cyc_y", ry)):
-        a, o = (crop_by(real, 2 * b), crop_by(aux[key], b)) if key.startswith("cyc") else (crop_by(real, b), aux[key])
-        worst = min(worst, float((1.0 - np.abs(a.astype(np.float64) - o) / 2).min()))
-    return worst
 
 
 def _step_matches_oracle(tmp_path, n, batch, is3d, scaled, amplitude=1.0, gtol_net=None):

@@ -216,6 +216,75 @@ def activation_stats(cs, saved, is3d=True, tol=None):
     return n, total, worst, where
 
 
+def gate_masks(cs):
+    """The LeakyReLU branches of the HIP forward, off the device: {call: {saved key: (act > 0, region or None)}} for every
+    saved layer of the ten call sites of the compiled step `cs` (cgan._CompiledStep).  region = (lo, hi) of fwd.regions for
+    a generator's layer -- the cycle-path call sites hold only that window of each tensor -- and None for a discriminator's."""
+    out = {}
+    for call, fwd in cs.fwd.items():
+        gen = call[0] in "gf"
+        out[call] = {key: (fwd.act[layer].float().cpu().numpy() > 0, tuple(fwd.regions[layer]) if gen else None)
+                     for layer, key in (_GEN_SAVED if gen else _DISC_SAVED).items() if layer in fwd.act}
+    return out
+
+
+def pack_masks(masks, prefix="gate"):
+    """gate_masks() as flat arrays for np.savez: per mask its packed bits, its shape and its region (-1, -1: none)."""
+    out = {}
+    for call, g in masks.items():
+        for key, (pos, region) in g.items():
+            out[f"{prefix}.{call}.{key}.bits"] = np.packbits(pos)
+            out[f"{prefix}.{call}.{key}.shape"] = np.asarray(pos.shape, np.int64)
+            out[f"{prefix}.{call}.{key}.region"] = np.asarray(region if region is not None else (-1, -1), np.int64)
+    return out
+
+
+def unpack_masks(rec, prefix="gate"):
+    """Inverse of pack_masks over a loaded .npz (or any mapping with its keys)."""
+    out = {}
+    for name in rec.keys() if hasattr(rec, "keys") else rec.files:
+        if not (name.startswith(prefix + ".") and name.endswith(".bits")):
+            continue
+        call, key = name[len(prefix) + 1:-len(".bits")].split(".")
+        shape = tuple(int(v) for v in rec[f"{prefix}.{call}.{key}.shape"])
+        lo, hi = (int(v) for v in rec[f"{prefix}.{call}.{key}.region"])
+        pos = np.unpackbits(rec[name], count=int(np.prod(shape))).reshape(shape).astype(bool)
+        out.setdefault(call, {})[key] = (pos, None if lo < 0 else (lo, hi))
+    return out
+
+
+def gates_from_masks(masks, is3d=True):
+    """`gates` argument of oracle.graph.train_step(_grads) from gate_masks(): a callable that takes the oracle's `saved`.
+
+    Inside a generator layer's region the mask replaces the oracle's own sign pattern; outside it the oracle's signs stay
+    (every gradient is exactly zero there).  The callable's `.flips` is filled per call site with (positions where the mask
+    differs from the oracle's own sign inside the region, positions compared): pre-activations within rounding of 0."""
+    def build(saved):
+        out = {}
+        for call, sv in saved.items():
+            g, n, total = {}, 0, 0
+            for key, (got, region) in masks[call].items():
+                if key not in sv:
+                    continue
+                pos = np.asarray(sv[key]) > 0
+                if region is not None:
+                    lo, hi = region
+                    win = pos[:, lo:hi, lo:hi, lo:hi, :] if is3d else pos[:, :, lo:hi, lo:hi, :]
+                    assert win.shape == got.shape, (call, key, win.shape, got.shape)
+                    n, total = n + int(np.count_nonzero(win != got)), total + got.size
+                    win[...] = got
+                else:
+                    assert pos.shape == got.shape, (call, key, pos.shape, got.shape)
+                    n, total = n + int(np.count_nonzero(pos != got)), total + got.size
+                    pos = got
+                g[key] = pos
+            out[call] = g
+            build.flips[call] = (n, total)
+        return out
+    build.flips = {}
+    return build
+
+
 def hip_gates(cs, is3d=True):
     """`gates` argument of oracle.graph.train_step(_grads): the LeakyReLU branches of the HIP forward.
 
@@ -224,31 +293,71 @@ def hip_gates(cs, is3d=True):
     (models/generator.needed_regions) -- outside it the oracle's own signs stay (every gradient is exactly
     zero there).  With this the oracle differentiates the very branch the HIP backward gates on, and the
     step-level gradient comparison needs no widened tolerance; gate_flips() stays a printed diagnostic."""
-    def build(saved):
-        out = {}
-        for call, sv in saved.items():
-            fwd = cs.fwd[call]
-            gen = call[0] in "gf"
-            table = _GEN_SAVED if gen else _DISC_SAVED
-            g = {}
-            for layer, key in table.items():
-                if key not in sv or layer not in fwd.act:
-                    continue
-                pos = np.asarray(sv[key]) > 0
-                got = fwd.act[layer].float().cpu().numpy() > 0
-                if gen:
-                    lo, hi = fwd.regions[layer]
-                    if is3d:
-                        pos[:, lo:hi, lo:hi, lo:hi, :] = got
-                    else:
-                        pos[:, :, lo:hi, lo:hi, :] = got
-                else:
-                    assert pos.shape == got.shape
-                    pos = got
-                g[key] = pos
-            out[call] = g
-        return out
-    return build
+    return gates_from_masks(gate_masks(cs), is3d)
+
+
+def _inputs(shape, seed):
+    """A standardized uint8 volume (B, D, H, W, 1) as the data pipeline delivers it: zero mean, unit deviation."""
+    rng = np.random.default_rng(seed)
+    u = rng.integers(0, 256, shape[:-1], dtype=np.uint8)
+    x = (u.astype(np.float32) / np.float32(127.5) - np.float32(1.0))[..., None]
+    return ((x - x.mean()) / x.std()).astype(np.float32)
+
+
+DP_AMPLITUDE = 0.5      # of the two-replica tests' inputs; see dp_inputs
+DP_OUTPUTS = (("fake_y", "g1"), ("cyc_x", "f2"), ("fake_x", "f1"), ("cyc_y", "g2"), ("same_x", "f3"), ("same_y", "g3"))
+
+
+def dp_inputs(rank, is3d, n=74):
+    """(real_x, real_y) of one replica of the two-replica tests (tests/tools/dp_rank.py and the oracle side of
+    test_gpu_dp.py): standardized uint8 volumes, seeds 1000 + rank / 2000 + rank, at half amplitude.  At amplitude 1 the
+    inputs reach +-1.73 and the test weights' outputs +-0.3 .. 0.8, so the oracle's own 1 - |a - b| / 2 of the cycle /
+    identity terms runs through the pole for EVERY seed (60 seed pairs scanned in 2-D: -0.25 .. -0.02; 6 in 3-D: -0.07 ..
+    -0.02); at 0.5 it is 0.37 .. 0.49 (2-D) and 0.48 (3-D), as for the 132^2 / 260^2 instances of test_gpu_step.py."""
+    shape = (1, n if is3d else 1, n, n, 1)
+    return np.float32(DP_AMPLITUDE) * _inputs(shape, 1000 + rank), np.float32(DP_AMPLITUDE) * _inputs(shape, 2000 + rank)
+
+
+def _pole_margin(aux, rx, ry, b, crop_by):
+    """Smallest 1 - |a - b| / 2 over the pixels of the four cycle / identity terms, from the oracle's own outputs: the
+    loss -log(1 - |a - b| / 2) has a pole there, and its gradient moves by delta / (2 margin) of itself when an output
+    moves by delta (conditioning note)."""
+    worst = np.inf
+    for key, real in (("same_x", rx), ("same_y", ry), ("cyc_x", rx), ("cyc_y", ry)):
+        a, o = (crop_by(real, 2 * b), crop_by(aux[key], b)) if key.startswith("cyc") else (crop_by(real, b), aux[key])
+        worst = min(worst, float((1.0 - np.abs(a.astype(np.float64) - o) / 2).min()))
+    return worst
+
+
+def linearise(lists, priority):
+    """One serial order of a stream-list set (cgan._CompiledStep.lists / lists_fused) under a priority order over the
+    lists: the launches and ("allreduce", key) items, in the order a host loop like EM2EM._run_streams's would issue them
+    if list priority[0] always went first.  Each turn advances, by ONE item, the highest-priority list that is not
+    blocked on an event no list has recorded yet (a `record` marks its event; "inputs" is recorded up front), then starts
+    again from the top -- so a list overtakes every lower one the moment the event it waits for exists.
+
+    Every order the declared events allow is a legal execution of the schedule.  A dependency with no event between
+    list i and list j is broken by the order that ranks the consumer's list above the producer's: the consumer then runs
+    first.  The permutations of the lists give the extremal orders of that kind, not all orders."""
+    lists = [list(l) for l in lists]
+    assert sorted(priority) == list(range(len(lists))), priority
+    pos, recorded, out = [0] * len(lists), {"inputs"}, []
+    while any(p < len(l) for p, l in zip(pos, lists)):
+        for i in priority:
+            if pos[i] == len(lists[i]):
+                continue
+            item = lists[i][pos[i]]
+            if isinstance(item, tuple) and item[0] == "wait" and item[1] not in recorded:
+                continue
+            if isinstance(item, tuple) and item[0] == "record":
+                recorded.add(item[1])
+            elif not (isinstance(item, tuple) and item[0] == "wait"):
+                out.append(item)
+            pos[i] += 1
+            break
+        else:
+            raise AssertionError("stream schedule deadlocked")
+    return out
 
 
 def reference_tile(volume, roi, edge, meanstd_x):

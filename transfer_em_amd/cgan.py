@@ -201,7 +201,9 @@ class _CompiledStep:
         # that leave half the chip idle.  Each one waits for the input-gradient launch that produced its gradient; the chain
         # joins them in front of its slab reduction.  bf16 4.15 -> 4.03 ms/step, fp32 7.42 -> 7.35 (TEM_BWW_TAIL: 0 = in the
         # chain, 1 = the last sweep only: 4.07 / 7.42; on two MORE streams instead: 6.6 ms, six streams serialize).
-        tail_mode = int(os.environ.get("TEM_BWW_TAIL", "2")) if side_split else 0
+        # Under capture every wait hops to a fresh stream (_run_streams(hop=True)): the ~80 waits of the tails would make a
+        # graph of as many branches, so use_graph keeps the kernel gradients in the chains whatever TEM_SIDE_SPLIT says.
+        tail_mode = int(os.environ.get("TEM_BWW_TAIL", "2")) if side_split and not m.use_graph else 0
         tails = {}
         def sweep(plan, tag, mode=1):
             if tail_mode < mode:
@@ -452,11 +454,14 @@ class EM2EM(object):
         st.events["inputs"].record(cur)              # losses cleared + inputs copied
         streams = [cur] + list(st.extra_streams)
         used = [True] + [False] * (len(streams) - 1)
-        its = [iter(l) for l in (st.lists if lists is None else lists)]
+        lists = st.lists if lists is None else lists
+        its = [iter(l) for l in lists]
         pending = [None] * len(its)
         done = [False] * len(its)
         recorded = {"inputs"}
-        hops = iter(st.hop_streams(32)) if hop else None
+        # one hop per wait at the most, whatever the lists hold
+        nwait = sum(1 for l in lists for it in l if isinstance(it, tuple) and it[0] == "wait")
+        hops = iter(st.hop_streams(nwait)) if hop else None
 
         def wait(i, name):
             if hop and used[i]:
