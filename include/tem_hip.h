@@ -494,6 +494,55 @@ int tem_u8_rescale(const uint8_t *src, int32_t D, int32_t H, int32_t W, int32_t 
 int tem_u8_lut(uint8_t *buf, int32_t D, int32_t H, int32_t W, const uint8_t *lut, int32_t per_section, int32_t zsec0,
                tem_stream_t stream);
 
+/* 16-bit volumes, the first link of the preparation chain (utils.volume_histogram16, utils.volume_to_u8): counted in
+ * 65,536 bins and brought to uint8 by a table.  A voxel v of a native-endian 16-bit block has the INDEX
+ *   u = v             for uint16  (is_signed = 0)
+ *   u = v + 32768     for int16   (is_signed = 1):  on the bits v ^ 0x8000, so the order of the values is kept.
+ * Histograms and tables are indexed by u and always hold 65,536 entries.
+ *
+ * tem_u16_hist: src[D][H][W] is dense.  counts[u] += the number of voxels of the box [z0, z1) x [y0, y1) x [x0, x1)
+ * whose index is u: counts holds 65,536 entries, or with per_section = 1 (z1 - z0) rows of 65,536, row z - z0 counting
+ * section z.  The kernel ADDS (64-bit global atomic adds, one per non-zero bin, workgroup and flush): the caller clears
+ * counts once and any number of calls, from any number of streams, accumulate into it.  Exact for any data -- a
+ * constant block (every lane on one bin) and a block that fills all 65,536 bins included.  Voxels outside the box are
+ * never read and nothing but counts is written; a load touches only naturally aligned words (up to 16 bytes) that hold
+ * at least one voxel of the box.  src at any 2-byte alignment, any W (an odd W leaves rows 2-byte aligned only) and any
+ * box; counts must be 8-byte aligned.  An empty box (lo == hi on an axis) returns TEM_OK without a launch.
+ * TEM_EINVAL, without a launch: a null pointer, src off 2-byte or counts off 8-byte alignment, a dimension below 1, a
+ * box outside [0, dim] or with lo > hi, per_section or is_signed outside {0, 1}, and a box too large for the
+ * workgroups' 32-bit counters.  The table is split by the high bit of u, and each half's workgroups see every voxel of
+ * their run.  The box's rows form nsec stretches of nyd rows that are flushed apart -- the (z1 - z0) sections of
+ * (y1 - y0) rows with per_section, else the one box of (z1 - z0)(y1 - y0) rows -- and with S = (2 (x1 - x0) + 29) / 16
+ * segments per row a stretch is cut into pieces of
+ *   rpp = ceil(nyd / P),  P = min(max(1, 128 / nsec), max(1, ceil(nyd * S / 4096)))
+ * rows; a workgroup takes whole pieces and flushes wherever it leaves a stretch, and
+ *   rpp x max(x1 - x0, S)  must stay below 2^31
+ * (no counter can see more voxels than that between two flushes, and the 32-bit index of (row, segment) items, split
+ * exactly for every value below 2^31, stays in range).  Without per_section a box of fewer than 2^37 voxels always
+ * passes; with per_section every box whose sections hold fewer than 2^31 voxels each. */
+int tem_u16_hist(const uint16_t *src, int32_t D, int32_t H, int32_t W, int32_t z0, int32_t z1, int32_t y0, int32_t y1,
+                 int32_t x0, int32_t x1, uint64_t *counts, int32_t per_section, int32_t is_signed, tem_stream_t stream);
+
+/* tem_u16_lut_u8: src is a dense 16-bit block [D][H][W], dst a dense uint8 block [D][H][W]:
+ *   per_section = 0:  dst[z][y][x] = lut[u(src[z][y][x])]                            lut: 65,536 bytes
+ *   per_section = 1:  dst[z][y][x] = lut[(zsec0 + z) * 65536 + u(src[z][y][x])]      lut: at least zsec0 + D rows
+ * (zsec0: the section of the caller's volume that the block's section 0 is).  One table form serves linear windows,
+ * gamma, inversion and CDF matching (utils.window_lut16, utils.match_lut16): there is no second arithmetic definition
+ * on the device.  Every byte of dst is written exactly once and nothing else is written; no voxel outside src is read.
+ * src at any 2-byte alignment and dst at any alignment, independently (8 outputs leave as one 8-byte store where dst
+ * allows it, their 16 source bytes arrive as one load where src does too); every byte offset is 64 bits.  src and dst
+ * must not overlap.  A workgroup serves one section's table: tem_u16_lut_u8 stages its 64 KiB in LDS once and looks up
+ * there, tem_u16_lut_u8_direct looks up in global memory (the baseline the staged form is measured against; the same
+ * bytes for the same arguments).
+ * TEM_EINVAL, without a launch: a null pointer, src off 2-byte alignment, a dimension below 1, a negative zsec0,
+ * per_section or is_signed outside {0, 1}, and a block of more workgroups than one launch holds: a section (the whole
+ * block without per_section) of n voxels goes to min(ceil(512 / nsec), ceil(ceil((n + 14) / 8) / 16384)) workgroups
+ * and their total must stay below 2^31 -- which it does for every D an int32_t holds, so no block is refused for it. */
+int tem_u16_lut_u8(const uint16_t *src, int32_t D, int32_t H, int32_t W, uint8_t *dst, const uint8_t *lut,
+                   int32_t per_section, int32_t zsec0, int32_t is_signed, tem_stream_t stream);
+int tem_u16_lut_u8_direct(const uint16_t *src, int32_t D, int32_t H, int32_t W, uint8_t *dst, const uint8_t *lut,
+                          int32_t per_section, int32_t zsec0, int32_t is_signed, tem_stream_t stream);
+
 /* Repair of damaged sections and voxels of a dense uint8 block along z, in place (tiled inference and
  * utils.volume_repair: the uploaded bytes, ahead of everything else).  buf[D][H][W] holds the sections zsec0 ...
  * zsec0 + D - 1 of the caller's volume.  A voxel (d, y, x) is BAD if any source that is given says so:

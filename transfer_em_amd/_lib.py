@@ -152,6 +152,9 @@ _SIGS = {
     "tem_u8_ssim": ([C.c_void_p] + [C.c_int32] * 6) * 2 + [C.c_int32] * 5 + [C.c_void_p, C.c_void_p, C.c_void_p],
     "tem_u8_rescale": [C.c_void_p] + [C.c_int32] * 15 + [C.c_void_p] + [C.c_int32] * 6 + [C.c_void_p],
     "tem_u8_lut": [C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p],
+    "tem_u16_hist": [C.c_void_p] + [C.c_int32] * 9 + [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p],
+    "tem_u16_lut_u8": [C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p, C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p],
+    "tem_u16_lut_u8_direct": [C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p, C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p],
     "tem_u8_repair_z": [C.c_void_p] + [C.c_int32] * 6 + [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                         C.c_void_p],
     "tem_u8_hist_tiles":[C.c_void_p] + [C.c_int32] * 9 + [C.c_void_p, C.c_void_p],

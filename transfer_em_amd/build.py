@@ -15,7 +15,7 @@ SOURCES = ["conv_direct.hip", "conv_bww.hip", "bww_lds.hip", "conv_lds.hip", "el
            "conv2d_bf16.hip", "convT2d_bf16.hip", "bww2d_bf16.hip", "tiles_sym.hip", "pool_u8.hip", "hist_u8.hip",
            "clahe_u8.hip", "hist2_u8.hip", "ssim_u8.hip", "rescale_u8.hip", "repair_u8.hip",
            "zcorr_u8.hip", "zshift_u8.hip", "warp_u8.hip", "zlags_u8.hip", "resamplez_u8.hip",
-           "zdev_u8.hip", "zplane_u8.hip"]
+           "zdev_u8.hip", "zplane_u8.hip", "u16.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-Wno-pass-failed"] + os.environ.get("TEM_BUILD_FLAGS", "").split()
 # TEM_BUILD_FLAGS=-DTEM_DEBUG_KNOBS: the environment knobs of csrc/tem_common.h (microbenchmarks only; off in the shipped build)

@@ -706,19 +706,22 @@ def hist_box(vol_shape, start=None, size=None):
     return box if nd == 3 else ((0, 1),) + box
 
 
-def hist_chunks(box, chunk_bytes=None, rank=0, world_size=1):
+def hist_chunks(box, chunk_bytes=None, rank=0, world_size=1, itemsize=1):
     """Cut the (z, y, x) (lo, hi) `box` into disjoint slabs of at most `chunk_bytes` bytes (HIST_CHUNK_BYTES when None)
     whose union is the box: runs of whole sections, or, where one section of the box is larger than the budget, runs of
     whole rows of one section (one row at the least: a budget below a row's bytes gives one-row slabs).  x is never
-    cut.  Slabs are in (z, y) order and go round-robin to the ranks; returns this rank's list of boxes.  Pure host
-    function."""
+    cut.  A voxel holds `itemsize` bytes (1, or 2 for the 16-bit passes: the budget is bytes, so such a slab holds half
+    the voxels).  Slabs are in (z, y) order and go round-robin to the ranks; returns this rank's list of boxes.  Pure
+    host function."""
     budget = HIST_CHUNK_BYTES if chunk_bytes is None else int(chunk_bytes)
     if budget < 1:
         raise ValueError(f"chunk_bytes must be positive, got {chunk_bytes}")
     if not 0 <= rank < world_size:
         raise ValueError(f"rank {rank} is outside [0, {world_size})")
+    if itemsize not in (1, 2):
+        raise ValueError(f"itemsize must be 1 or 2, got {itemsize!r}")
     (z0, z1), (y0, y1), (x0, x1) = box
-    ny, nx = y1 - y0, x1 - x0
+    ny, nx = y1 - y0, (x1 - x0) * itemsize                  # nx: a row's bytes
     if z1 <= z0 or ny <= 0 or nx <= 0:
         return []
     slabs = []                          # zcorr_chunks restates these cuts with one section of halo: keep the two in step
@@ -852,7 +855,9 @@ class _SlabPass:
     stack), slab by slab through the input side of predict_volume's pipeline.  Making it is host work and comes ahead
     of any GPU work: the dtype check (ValueError) and this rank's slabs of boxes[0] (hist_chunks, or the list `slabs`
     of boxes inside boxes[0] where the caller cuts them itself: overlapping read slabs, ssim_chunks); the slab of
-    volumes[i] is the same box shifted from boxes[0] to boxes[i].  `st` holds the read seconds `read_s` and the slab
+    volumes[i] is the same box shifted from boxes[0] to boxes[i].  itemsize=2 is the pass over native-endian uint16 /
+    int16 volumes: the budget and the buffers stay bytes (a slab holds half the voxels) and the reader writes through a
+    16-bit view.  `st` holds the read seconds `read_s` and the slab
     count `chunks`.
 
     `with p.streaming():` is the pass, on `device` (None: the current one) as the current device: one host thread
@@ -862,22 +867,24 @@ class _SlabPass:
     `p.release_on` where the caller has set an event for this slab, else on one recorded there -- and the slabs k + 2
     are prefetched."""
 
-    def __init__(self, volumes, boxes, chunk_bytes, rank, world_size, device, slabs=None):
+    def __init__(self, volumes, boxes, chunk_bytes, rank, world_size, device, slabs=None, itemsize=1):
+        check = _check_u8 if itemsize == 1 else _check_16
         for v in volumes:
-            _check_u8(v)
-        self.slabs = hist_chunks(boxes[0], chunk_bytes, rank, world_size) if slabs is None else list(slabs)
+            check(v)
+        self.slabs = hist_chunks(boxes[0], chunk_bytes, rank, world_size, itemsize) if slabs is None else list(slabs)
         self.dims = [tuple(hi - lo for lo, hi in s) for s in self.slabs]
-        self.nbytes = [int(np.prod(d)) for d in self.dims]
+        self.nbytes = [int(np.prod(d)) * itemsize for d in self.dims]
+        self.views = [np.dtype(np.uint8) if itemsize == 1 else np.dtype(v.dtype) for v in volumes]
         self.volumes = [_OneSection(v) if len(v.shape) == 2 else v for v in volumes]
         self.shifts = [tuple(b[0] - a[0] for a, b in zip(boxes[0], box)) for box in boxes]
         self.device, self.st = device, {"read_s": 0.0, "chunks": len(self.slabs)}
 
-    def _reader(self, vol, shift):
+    def _reader(self, vol, shift, view=np.dtype(np.uint8)):
         slabs, dims = self.slabs, self.dims         # not `self`: the streams, which the pass holds, must not hold it
 
-        def read_into(k, flat):
+        def read_into(k, flat):                     # the buffers are bytes; a 16-bit slab is written through a view
             (z0, z1), (y0, y1), (x0, x1) = (tuple(v + o for v in r) for r, o in zip(slabs[k], shift))
-            flat.reshape(dims[k])[...] = vol[z0:z1, y0:y1, x0:x1]
+            flat.view(view).reshape(dims[k])[...] = vol[z0:z1, y0:y1, x0:x1]
         return read_into
 
     @contextlib.contextmanager
@@ -887,8 +894,8 @@ class _SlabPass:
         self.pool = ThreadPoolExecutor(max_workers=1)            # one reader thread, however many volumes
         with torch.cuda.device(dev), contextlib.ExitStack() as stack:
             self.compute = torch.cuda.current_stream(dev)
-            self.inputs = [stack.enter_context(_InputStream(self.nbytes, self._reader(v, o), dev, self.pool, self.st))
-                           for v, o in zip(self.volumes, self.shifts)]
+            self.inputs = [stack.enter_context(_InputStream(self.nbytes, self._reader(v, o, w), dev, self.pool, self.st))
+                           for v, o, w in zip(self.volumes, self.shifts, self.views)]
             yield self
 
     def __iter__(self):
@@ -4979,6 +4986,238 @@ def clahe_volume(volume, clahe, out=None, start=None, size=None, chunk_bytes=Non
                 prepare.apply(buf.data_ptr(), d, tuple(lo for lo, _ in slab))
                 measure.add(buf.data_ptr(), d, d)
                 p.release_on = outp.put(k, p.compute.record_event(), buf)        # the input buffer: free once copied out
+        measure.report(p.st)
+    if stats is not None:
+        stats.update(p.st)
+    return out
+
+
+U16_BINS = 1 << 16               # bins of a 16-bit histogram and bytes of a 16-bit table: indexed by u = v (uint16), v + 32768 (int16)
+
+
+def _check_16(volume):
+    """True for int16, False for uint16 voxels; ValueError for any other dtype and for the other byte order."""
+    dt = getattr(volume, "dtype", None)
+    if dt is None or np.dtype(dt) not in (np.dtype(np.uint16), np.dtype(np.int16)) or not np.dtype(dt).isnative:
+        raise ValueError(f"volume must be native-endian uint16 or int16, got {dt}")
+    return np.dtype(dt).kind == "i"
+
+
+def volume_histogram16(volume, start=None, size=None, per_section=False, chunk_bytes=None, rank=0, world_size=1,
+                       device=None, stats=None):
+    """Intensity histogram of the ROI [start, start + size) ((x, y, z) order; default: the whole volume) of a
+    native-endian uint16 or int16 array-like `volume` indexed [z, y, x] (ndarray, np.memmap, h5py / zarr dataset), or
+    of one image [y, x] with 2-element start / size: volume_histogram's pass over 16-bit voxels.  A voxel v counts in
+    bin u = v (uint16) or u = v + 32768 (int16: the order is kept).  Returns np.int64[65536], or with per_section
+    np.int64[size_z, 65536] whose row i counts section start_z + i.  ValueError, before any GPU work: another dtype or
+    byte order, an ROI outside the volume.
+
+    Out of core: slabs of at most `chunk_bytes` BYTES (hist_chunks with itemsize=2); one host thread reads each slab
+    into double-buffered pinned memory -> H2D -> tem_u16_hist, adding into ONE device accumulator that is read back
+    once at the end -- a per-section table is 512 KiB per section; past CLAHE_ACC_BYTES the accumulator holds one
+    slab's sections and is read back, and added on the host, per slab.  `stats` receives `read_s` and `chunks`.  Ranks
+    take slabs round-robin and their results add up to the whole."""
+    box = hist_box(volume.shape, start, size)
+    p = _SlabPass([volume], [box], chunk_bytes, rank, world_size, device, itemsize=2)
+    signed = int(_check_16(volume))
+    lib = H.require_gpu()
+    oz, nz = box[0][0], box[0][1] - box[0][0]
+    rows = nz if per_section else 1
+    whole = rows * U16_BINS * 8 <= CLAHE_ACC_BYTES
+    out = None if whole else np.zeros((rows, U16_BINS), np.int64)
+    with p.streaming():
+        acc = torch.zeros((rows if whole else max((d[0] for d in p.dims), default=1), U16_BINS), dtype=torch.int64,
+                          device=p.dev)
+        for k, slab, d, (src,) in p:
+            row = (slab[0][0] - oz) if per_section else 0
+            if not whole:
+                acc[:d[0]].zero_()
+            _lib.check(lib.tem_u16_hist(src.data_ptr(), *d, 0, d[0], 0, d[1], 0, d[2],
+                                        acc.data_ptr() + 8 * U16_BINS * (row if whole else 0), int(bool(per_section)),
+                                        signed, p.compute.cuda_stream), "tem_u16_hist")
+            if not whole:                                        # this slab's sections, added on the host
+                out[row:row + d[0]] += acc[:d[0]].cpu().numpy()
+        if whole:
+            out = acc.cpu().numpy()                              # the one read-back
+    if stats is not None:
+        stats.update(p.st)
+    return out if per_section else out[0]
+
+
+def _check_hist16(h, who, bins=U16_BINS):
+    h = np.asarray(h)
+    if h.ndim not in (1, 2) or h.shape[-1] != bins or h.dtype.kind not in "iu":
+        raise ValueError(f"{who} must be integer counts of shape [{bins}] or [Z, {bins}], got {h.dtype} {h.shape}")
+    if h.size and int(h.min()) < 0:
+        raise ValueError(f"{who} has negative counts")
+    if h.dtype == np.uint64 and h.size and int(h.max()) >= 1 << 63:
+        raise ValueError(f"{who} has counts of 2^63 and more")
+    return h.astype(np.int64, copy=False)
+
+
+def _unit_fraction(v, what):
+    try:
+        f = Fraction(v)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what} must be a fraction in [0, 1], got {v!r}")
+    if not 0 <= f <= 1:
+        raise ValueError(f"{what} must be a fraction in [0, 1], got {v!r}")
+    return f
+
+
+def window16(h, low=Fraction(1, 1000), high=Fraction(999, 1000)):
+    """The quantile window (lo, hi), in index units, of a 16-bit histogram `h` (integer counts [65536]:
+    volume_histogram16's result): with C the inclusive cumulative counts and N their total, lo is the smallest u with
+    C[u] / N >= low and hi the smallest u with C[u] / N >= high, decided in exact integers (C[u] den >= num N for
+    low = num / den: pass Fractions; a float stands for its exact binary value).  Hot and dead pixels, a fraction below
+    `low` of the voxels, do not stretch it.  hi == lo is widened by one, hi = lo + 1 (lo = 65534 at lo == 65535), so
+    that window_lut16 always takes the pair; a histogram without voxels gives (0, 65535).  Row-wise for [Z, 65536]
+    (per-section histograms): two np.int64[Z].  ValueError unless 0 <= low <= high <= 1."""
+    lo_f, hi_f = _unit_fraction(low, "low"), _unit_fraction(high, "high")
+    if lo_f > hi_f:
+        raise ValueError(f"low {low!r} is above high {high!r}")
+    h = _check_hist16(h, "window16: h")
+    rows = h.reshape(-1, U16_BINS)
+    lo, hi = np.zeros(len(rows), np.int64), np.full(len(rows), U16_BINS - 1, np.int64)
+    for z, r in enumerate(rows):
+        c = np.cumsum(r)
+        n = int(c[-1])
+        if n == 0:
+            continue
+        if n >= 1 << 62:
+            raise ValueError("window16: more than 2^62 voxels")
+        for f, dst in ((lo_f, lo), (hi_f, hi)):             # C[u] den >= num N  <=>  C[u] >= ceil(num N / den)
+            dst[z] = np.searchsorted(c, -((-f.numerator * n) // f.denominator), side="left")
+        if hi[z] == lo[z]:
+            if lo[z] == U16_BINS - 1:
+                lo[z] -= 1
+            else:
+                hi[z] += 1
+    return (int(lo[0]), int(hi[0])) if h.ndim == 1 else (lo, hi)
+
+
+def window_lut16(lo, hi, invert=False):
+    """The linear window [lo, hi] -> [0, 255] as a 16-bit table np.uint8[65536]: 0 for u <= lo, 255 for u >= hi and
+    (2 * 255 (u - lo) + (hi - lo)) // (2 (hi - lo)) between, rounded half up in integers; invert=True gives 255 - t
+    (a detector of the other polarity).  Arrays lo, hi of Z entries (window16 of per-section histograms) give
+    [Z, 65536], the form volume_to_u8 takes per section.  ValueError unless 0 <= lo < hi <= 65535 (integers)."""
+    a, b = np.asarray(lo), np.asarray(hi)
+    if a.dtype.kind not in "iu" or b.dtype.kind not in "iu" or a.shape != b.shape or a.ndim > 1:
+        raise ValueError(f"window_lut16: lo and hi must be integers, or integer arrays of one length; got {lo!r}, {hi!r}")
+    a, b = a.astype(np.int64).reshape(-1, 1), b.astype(np.int64).reshape(-1, 1)
+    if a.size and not ((0 <= a) & (a < b) & (b <= U16_BINS - 1)).all():
+        raise ValueError(f"window_lut16: needs 0 <= lo < hi <= 65535, got {lo!r}, {hi!r}")
+    u = np.arange(U16_BINS, dtype=np.int64)[None]
+    w = b - a
+    t = np.clip((2 * 255 * (np.clip(u, a, b) - a) + w) // (2 * w), 0, 255)
+    if invert:
+        t = 255 - t
+    t = t.astype(np.uint8)
+    return t[0] if np.ndim(lo) == 0 else t
+
+
+def _match_row16(hs, hr):
+    cs, cr = np.cumsum(hs), np.cumsum(hr)
+    ns, nr = int(cs[-1]), int(cr[-1])
+    if nr == 0:
+        raise ValueError("match_lut16: the reference histogram is empty")
+    if ns == 0:
+        return np.arange(U16_BINS, dtype=np.int64) >> 8
+    if ns * nr < 1 << 63:                   # the smallest w with cr[w] ns >= cs[u] nr; cr[255] ns == cs[65535] nr ends it
+        return np.searchsorted(cr * ns, cs * nr, side="left")
+    lut, w, cr = np.empty(U16_BINS, np.int64), 0, [int(c) * ns for c in cr]
+    for u, c in enumerate(cs.tolist()):     # Python ints; cs is non-decreasing, so w only moves up
+        c *= nr
+        while cr[w] < c:
+            w += 1
+        lut[u] = w
+    return lut
+
+
+def match_lut16(h_src, h_ref):
+    """match_lut from 65,536 source bins: np.uint8[65536] with lut[u] = the smallest w in 0...255 whose reference CDF
+    reaches the source CDF of u, cr[w] N_src >= cs[u] N_ref, decided in exact integers (int64 where N_src N_ref < 2^63,
+    Python ints otherwise).  `h_src` is a 16-bit histogram [65536] (volume_histogram16), `h_ref` the 256-bin histogram
+    of the uint8 target domain (volume_histogram).  Taken from the 16-bit counts the match can split what an 8-bit
+    window has already merged.  The table is non-decreasing.  Row-wise for an h_src [Z, 65536] against one h_ref [256]
+    or [Z, 256]: returns [Z, 65536], the per-section form volume_to_u8 takes.  A source row without voxels gets the
+    identity coarsening u >> 8; an empty reference raises ValueError, as negative counts and other shapes do."""
+    hs, hr = _check_hist16(h_src, "match_lut16: h_src"), _check_hist16(h_ref, "match_lut16: h_ref", 256)
+    if hs.ndim == 1:
+        if hr.ndim != 1:
+            raise ValueError("match_lut16: a [Z, 256] h_ref needs a [Z, 65536] h_src")
+        return _match_row16(hs, hr).astype(np.uint8)
+    if hr.ndim == 2 and hr.shape[0] != hs.shape[0]:
+        raise ValueError(f"match_lut16: h_src has {hs.shape[0]} rows, h_ref {hr.shape[0]}")
+    out = np.empty(hs.shape, np.uint8)
+    for z in range(hs.shape[0]):
+        out[z] = _match_row16(hs[z], hr[z] if hr.ndim == 2 else hr)
+    return out
+
+
+def _check_lut16(lut, vol_shape):
+    """`lut` as a C-contiguous np.uint8 array: [65536], or [Z, 65536] with Z the section count of the volume of shape
+    `vol_shape` ([z, y, x]; one image [y, x] has one section).  ValueError for anything else."""
+    if not isinstance(lut, np.ndarray) or lut.dtype != np.uint8:
+        raise ValueError(f"lut must be a numpy uint8 array, got {getattr(lut, 'dtype', type(lut).__name__)}")
+    Z = int(vol_shape[0]) if len(vol_shape) == 3 else 1
+    if lut.shape != (U16_BINS,) and lut.shape != (Z, U16_BINS):
+        raise ValueError(f"lut must have shape ({U16_BINS},) or ({Z}, {U16_BINS}) -- one row per section of the volume "
+                         f"-- got {lut.shape}")
+    return np.ascontiguousarray(lut)
+
+
+def volume_to_u8(volume, lut, out=None, start=None, size=None, chunk_bytes=None, histogram=False, stats=None, rank=0,
+                 world_size=1, device=None):
+    """The ROI [start, start + size) ((x, y, z) order; default: the whole volume) of a native-endian uint16 or int16
+    array-like `volume` [z, y, x] (or one image [y, x] with 2-element start / size) brought to uint8 by the table
+    `lut`, written into `out`: a writable uint8 array-like of the ROI's shape (ndarray, memmap, h5py, zarr; allocated
+    when None), which is returned.  out[z, y, x] = lut[u] with u = v (uint16) or v + 32768 (int16); `lut` is
+    np.uint8[65536] (window_lut16, match_lut16, any table: gamma, inversion) or [Z, 65536] with one row per section of
+    the WHOLE volume, so that an ROI's bytes are the ROI of the whole result.  The first link of the preparation chain:
+    everything after it -- volume_rescale, find_defects, volume_repair, clahe_fit, predict_volume -- takes uint8.
+
+    Out of core, clahe_volume's pass: slabs of at most `chunk_bytes` source BYTES (hist_chunks with itemsize=2); host
+    thread -> pinned -> H2D -> one tem_u16_lut_u8 launch per slab into an output buffer -> D2H -> host write, on double
+    buffers, in the order write(k), read(k + 2).  The table is uploaded once.  histogram=True adds one tem_u8_hist
+    launch per converted slab and puts the 256 bins of the converted ROI (np.int64) into stats["histogram"], for a
+    match_lut or clahe_fit that follows.  Ranks take slabs round-robin and write disjoint boxes of a shared `out` (each
+    reports the histogram of its own slabs).  `stats` also receives `read_s`, `write_s` and `chunks`.
+    ValueError, before any GPU work: another dtype or byte order, a table of another dtype or shape, an `out` of
+    another shape or dtype, an ROI outside the volume."""
+    box = hist_box(volume.shape, start, size)
+    p = _SlabPass([volume], [box], chunk_bytes, rank, world_size, device, itemsize=2)
+    signed = int(_check_16(volume))
+    lut = _check_lut16(lut, tuple(volume.shape))
+    histogram = _check_histogram(histogram, stats)
+    one = len(volume.shape) == 2
+    shape = tuple(hi - lo for lo, hi in box)
+    if out is None:
+        out = np.zeros(shape[1:] if one else shape, np.uint8)
+    elif tuple(out.shape) != (shape[1:] if one else shape):
+        raise ValueError(f"out has shape {tuple(out.shape)}, expected {shape[1:] if one else shape}")
+    elif getattr(out, "dtype", np.dtype(np.uint8)) != np.uint8:
+        raise ValueError(f"out must be uint8, got {out.dtype}")
+    lib = H.require_gpu()
+    dst_vol = _OneSection(out) if one else out
+    p.st["write_s"] = 0.0
+    nvox = [n // 2 for n in p.nbytes]
+
+    def write_from(k, flat):            # host thread: the slab's box of `out`
+        (z0, z1), (y0, y1), (x0, x1) = p.slabs[k]
+        (oz, _), (oy, _), (ox, _) = box
+        dst_vol[z0 - oz:z1 - oz, y0 - oy:y1 - oy, x0 - ox:x1 - ox] = flat.reshape(p.dims[k])
+
+    with p.streaming():
+        lut_dev = torch.from_numpy(lut).to(p.dev)                                # the table(s), once
+        measure = _Measure(lib, histogram, False, p.dev, p.compute.cuda_stream)
+        with _OutputStream(nvox, write_from, p.dev, p.pool, p.st, own_buffers=True) as outp:
+            for k, slab, d, (src,) in p:                                         # the reader's thread: write(k), read(k + 2)
+                dst = outp.device(k)
+                _lib.check(lib.tem_u16_lut_u8(src.data_ptr(), *d, dst.data_ptr(), lut_dev.data_ptr(), int(lut.ndim == 2),
+                                              slab[0][0], signed, p.compute.cuda_stream), "tem_u16_lut_u8")
+                measure.add(dst.data_ptr(), d, d)
+                outp.put(k, p.compute.record_event())
         measure.report(p.st)
     if stats is not None:
         stats.update(p.st)
