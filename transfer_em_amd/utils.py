@@ -713,24 +713,44 @@ def hist_chunks(box, chunk_bytes=None, rank=0, world_size=1, itemsize=1):
     cut.  A voxel holds `itemsize` bytes (1, or 2 for the 16-bit passes: the budget is bytes, so such a slab holds half
     the voxels).  Slabs are in (z, y) order and go round-robin to the ranks; returns this rank's list of boxes.  Pure
     host function."""
+    budget = _budget(chunk_bytes, rank, world_size)
+    if itemsize not in (1, 2):
+        raise ValueError(f"itemsize must be 1 or 2, got {itemsize!r}")
+    return [core for core, _ in _cut_slabs(box, box[:2], budget, rank, world_size, itemsize=itemsize)]
+
+
+def _budget(chunk_bytes, rank, world_size):
+    """A cutter's budget in bytes: `chunk_bytes`, HIST_CHUNK_BYTES when None.  ValueError for a budget below 1 and for a
+    rank outside [0, world_size)."""
     budget = HIST_CHUNK_BYTES if chunk_bytes is None else int(chunk_bytes)
     if budget < 1:
         raise ValueError(f"chunk_bytes must be positive, got {chunk_bytes}")
     if not 0 <= rank < world_size:
         raise ValueError(f"rank {rank} is outside [0, {world_size})")
-    if itemsize not in (1, 2):
-        raise ValueError(f"itemsize must be 1 or 2, got {itemsize!r}")
+    return budget
+
+
+def _cut_slabs(box, limits, budget, rank, world_size, zreach=(0, 0), yreach=(0, 0), itemsize=1):
+    """The one rule behind hist_chunks, zcorr_chunks, zlag_chunks, repair_chunks, plane_lag_chunks and zshift_chunks*:
+    this rank's list of (core slab, read slab), (z, y, x) (lo, hi) boxes.  The cores are disjoint and their union is
+    `box`: runs of whole sections while a core next to its halo fits `budget` bytes, else runs of whole rows of one
+    section, one row at the least; x is never cut; (z, y) order, dealt round-robin to the ranks.  A read slab is its
+    core extended by `zreach` = (below, above) sections and `yreach` = (below, above) rows and clipped to `limits`, the
+    (lo, hi) of z and of y; the budget counts a core next to both reaches.  A voxel holds `itemsize` bytes."""
     (z0, z1), (y0, y1), (x0, x1) = box
+    (za, zb), (ya, yb) = zreach, yreach
     ny, nx = y1 - y0, (x1 - x0) * itemsize                  # nx: a row's bytes
     if z1 <= z0 or ny <= 0 or nx <= 0:
         return []
-    slabs = []                          # zcorr_chunks restates these cuts with one section of halo: keep the two in step
-    if ny * nx <= budget:
-        kz = budget // (ny * nx)
-        slabs = [((z, min(z + kz, z1)), (y0, y1), (x0, x1)) for z in range(z0, z1, kz)]
+    if (1 + za + zb) * ny * nx <= budget:
+        kz = budget // (ny * nx) - (za + zb)
+        cores = [((z, min(z + kz, z1)), (y0, y1)) for z in range(z0, z1, kz)]
     else:
-        ky = max(1, budget // nx)
-        slabs = [((z, z + 1), (y, min(y + ky, y1)), (x0, x1)) for z in range(z0, z1) for y in range(y0, y1, ky)]
+        ky = max(1, budget // ((1 + za + zb) * nx) - (ya + yb))
+        cores = [((z, z + 1), (y, min(y + ky, y1))) for z in range(z0, z1) for y in range(y0, y1, ky)]
+    (lz, hz), (ly, hy) = limits
+    slabs = [((cz, cy, (x0, x1)), ((max(cz[0] - za, lz), min(cz[1] + zb, hz)), (max(cy[0] - ya, ly), min(cy[1] + yb, hy)),
+                                   (x0, x1))) for cz, cy in cores]
     return slabs[rank::world_size]
 
 
@@ -800,7 +820,8 @@ class _OutputStream:
     without, put() is given the device tensor to copy out of.  Used as a context manager inside the _InputStream's
     (the same executor: one host thread, whose work the consumer queues in the order write(k), read(k + 2)): leaving
     the pass waits for the queued writes, and a failed one raises there; on an exception it does nothing, the
-    _InputStream around it owns the executor's end.
+    _InputStream around it owns the executor's end.  A slab pass makes it with _SlabPass.writing and feeds it with
+    _SlabPass.put; predict_volume drives one of its own.
 
     The consumer's loop over k: [`device(k)`,] its kernels on the compute stream (the current stream of `dev`),
     `put(k, event)` with the event behind the last of them.  Buffers k % 2 are reused in this order: the D2H of block
@@ -860,12 +881,17 @@ class _SlabPass:
     16-bit view.  `st` holds the read seconds `read_s` and the slab
     count `chunks`.
 
-    `with p.streaming():` is the pass, on `device` (None: the current one) as the current device: one host thread
+    `with p.streaming(stats):` is the pass, on `device` (None: the current one) as the current device: one host thread
     (`p.pool`) reads every volume's slab into an _InputStream of its own, which also ends the thread, on an exception
-    as it describes.  Inside, `for k, slab, dims, buffers in p:` gives slab k's box, its shape and one device buffer
-    per volume that holds it, for the caller's launches on `p.compute`; behind them the buffers are released -- on
-    `p.release_on` where the caller has set an event for this slab, else on one recorded there -- and the slabs k + 2
-    are prefetched."""
+    as it describes; a pass that ends cleanly leaves `st` in the dict `stats` where one is given.  Inside,
+    `for k, slab, dims, buffers in p:` gives slab k's box, its shape and one device buffer per volume that holds it,
+    for the caller's launches on `p.compute`; behind them the buffers are released -- on `p.release_on` where an event
+    has been set for this slab, else on one recorded there -- and the slabs k + 2 are prefetched.
+
+    `with p.writing(out, box) as outp:`, inside the pass, is its output side: an _OutputStream on the same host thread
+    that writes block k into slab k's box of `out`, the array-like of the ROI `box` (_roi_out).  The launches of slab k
+    write into `outp.device(k)`, or work in place on the input buffer; `p.put(k)`, or `p.put(k, src)`, behind them hands
+    the block over and sets `p.release_on`, so the host thread is given write(k) before read(k + 2)."""
 
     def __init__(self, volumes, boxes, chunk_bytes, rank, world_size, device, slabs=None, itemsize=1):
         check = _check_u8 if itemsize == 1 else _check_16
@@ -888,7 +914,7 @@ class _SlabPass:
         return read_into
 
     @contextlib.contextmanager
-    def streaming(self):
+    def streaming(self, stats=None):
         dev = self.dev = (torch.device("cuda", torch.cuda.current_device()) if self.device is None else
                           torch.device(self.device))
         self.pool = ThreadPoolExecutor(max_workers=1)            # one reader thread, however many volumes
@@ -897,6 +923,36 @@ class _SlabPass:
             self.inputs = [stack.enter_context(_InputStream(self.nbytes, self._reader(v, o, w), dev, self.pool, self.st))
                            for v, o, w in zip(self.volumes, self.shifts, self.views)]
             yield self
+        if stats is not None:                                    # a clean end: the thread is done with `st`
+            stats.update(self.st)
+
+    @contextlib.contextmanager
+    def writing(self, out, box, out_slabs=None, own_buffers=True):
+        """The output side: block k goes into the box out_slabs[k] (default: the pass's own slab k; else the cores or
+        output slabs, in the coordinates of `box`) of `out`, whose origin is the ROI `box`'s; one image [y, x] is
+        written as a one-section stack.  With `own_buffers` the stream holds the device buffers that the launches write
+        into; without, put() copies out of the input buffer.  `st` gains the write seconds `write_s`."""
+        slabs = self.slabs if out_slabs is None else list(out_slabs)
+        dims = [tuple(hi - lo for lo, hi in s) for s in slabs]
+        origin = tuple(lo for lo, _ in box)
+        dst = _OneSection(out) if len(out.shape) == 2 else out
+        self.st["write_s"] = 0.0
+
+        def write_from(k, flat):                    # host thread; like _reader's closure it does not hold `self`
+            (z0, z1), (y0, y1), (x0, x1) = (tuple(v - o for v in r) for r, o in zip(slabs[k], origin))
+            dst[z0:z1, y0:y1, x0:x1] = flat.reshape(dims[k])
+
+        with _OutputStream([int(np.prod(d)) for d in dims], write_from, self.dev, self.pool, self.st,
+                           own_buffers=own_buffers) as self.outp:        # the reader's thread: write(k), read(k + 2)
+            yield self.outp
+
+    def put(self, k, src=None):
+        """Behind slab k's launches: queue the D2H and the write of block k, and say when the input buffers are free.
+        Out of the stream's own buffer that is behind the kernel; out of `src`, a view of the input buffer that the
+        launches worked on in place, once the D2H has read it."""
+        ready = self.compute.record_event()
+        copied = self.outp.put(k, ready, src)
+        self.release_on = ready if src is None else copied
 
     def __iter__(self):
         for k, (slab, dims) in enumerate(zip(self.slabs, self.dims)):
@@ -907,6 +963,58 @@ class _SlabPass:
                 inp.release(k, done)
             for inp in self.inputs:
                 inp.prefetch(k + 2)
+
+
+class _RowAccumulator:
+    """The device accumulator of a pass that sums into `rows` rows of `shape` elements each -- a row per section, per
+    section of the ROI, per pair -- of `dtype`: np.int64, or np.uint32, which the kernels add into as int32.  Made inside
+    `p.streaming()`.  Where the whole table is at most CLAHE_ACC_BYTES (the module's value at that moment) it lives on
+    `dev` and is read back once; else the device holds `most` rows, the most that one slab touches, zeroed ahead of
+    every slab, read back behind it and added on the host.  Per slab, whose rows are [r0, r1): the launch adds at
+    `ptr(r0, r1)`, and `add(r0, r1)` follows it; `result()` is the table, np `dtype` [rows, *shape]."""
+
+    def __init__(self, dev, rows, shape, most, dtype=np.int64):
+        self.shape, self.dtype = tuple(shape), np.dtype(dtype)
+        self.row_bytes = int(np.prod(shape)) * self.dtype.itemsize
+        self.whole = rows * self.row_bytes <= CLAHE_ACC_BYTES
+        self.out = None if self.whole else np.zeros((rows,) + self.shape, self.dtype)
+        self.acc = torch.zeros((rows if self.whole else most, int(np.prod(shape))), device=dev,
+                               dtype=torch.int64 if self.dtype == np.int64 else torch.int32)
+
+    def _host(self, rows):
+        return rows.cpu().numpy().view(self.dtype).reshape((rows.shape[0],) + self.shape)
+
+    def ptr(self, r0, r1):
+        if self.whole:
+            return self.acc.data_ptr() + self.row_bytes * r0
+        self.acc[:r1 - r0].zero_()
+        return self.acc.data_ptr()
+
+    def add(self, r0, r1):
+        if not self.whole:                                       # this slab's rows, added on the host
+            self.out[r0:r1] += self._host(self.acc[:r1 - r0])
+
+    def result(self):
+        return self._host(self.acc) if self.whole else self.out  # the one read-back
+
+
+def _most_rows(spans):
+    """The `most` of a _RowAccumulator: the longest of the row ranges (r0, r1) of this rank's slabs, 1 without any."""
+    return max((r1 - r0 for r0, r1 in spans), default=1)
+
+
+def _roi_out(out, box, one, any_dtype=False):
+    """The `out` of a pass that writes the ROI `box`: a writable uint8 array-like of the box's shape -- [y, x] for `one`
+    image; with `any_dtype` the shape alone is checked --, allocated when None.  ValueError otherwise."""
+    shape = tuple(hi - lo for lo, hi in box)
+    want = shape[1:] if one else shape
+    if out is None:
+        return np.zeros(want, np.uint8)
+    dtype = getattr(out, "dtype", None)
+    if tuple(out.shape) != want or not (any_dtype or dtype == np.uint8):
+        raise ValueError(f"out must be {'' if any_dtype else 'uint8 '}of the ROI's shape {want}, got {dtype} "
+                         f"{tuple(out.shape)}")
+    return out
 
 
 def volume_histogram(volume, start=None, size=None, per_section=False, chunk_bytes=None, rank=0, world_size=1,
@@ -926,15 +1034,13 @@ def volume_histogram(volume, start=None, size=None, per_section=False, chunk_byt
     box = hist_box(volume.shape, start, size)
     p = _SlabPass([volume], [box], chunk_bytes, rank, world_size, device)
     lib = H.require_gpu()
-    with p.streaming():
+    with p.streaming(stats):
         acc = torch.zeros((box[0][1] - box[0][0] if per_section else 1, 256), dtype=torch.int64, device=p.dev)
         for k, slab, d, (src,) in p:
             row = (slab[0][0] - box[0][0]) if per_section else 0
             _lib.check(lib.tem_u8_hist(src.data_ptr(), *d, 0, d[0], 0, d[1], 0, d[2], acc.data_ptr() + 2048 * row,
                                        int(bool(per_section)), p.compute.cuda_stream), "tem_u8_hist")
         out = acc.cpu().numpy()                              # the one read-back
-    if stats is not None:
-        stats.update(p.st)
     return out if per_section else out[0]
 
 
@@ -960,14 +1066,12 @@ def volume_joint_histogram(a, b, start=None, size=None, b_start=None, chunk_byte
     box_b = hist_box(b.shape, tuple(lo for lo, _ in reversed(box))[:nd] if b_start is None else b_start, extent)
     p = _SlabPass([a, b], [box, box_b], chunk_bytes, rank, world_size, device)
     lib = H.require_gpu()
-    with p.streaming():
+    with p.streaming(stats):
         measure = _Measure(lib, False, True, p.dev, p.compute.cuda_stream)
         for k, slab, d, (pa, pb) in p:
             measure.add(pb.data_ptr(), d, d, gt=(pa.data_ptr(), d, (0, 0, 0)))
         res = {}
         measure.report(res)                                      # the one read-back
-    if stats is not None:
-        stats.update(p.st)
     return res["joint_histogram"]
 
 
@@ -1081,11 +1185,7 @@ def ssim_chunks(box, win=7, flat=False, chunk_bytes=None, rank=0, world_size=1):
     order and go round-robin to the ranks.  A box in which no window fits gives [].  Pure host function; ValueError as
     hist_chunks, and for a `win` that is not odd or outside 3...11."""
     wz, wy, wx = _ssim_window(win, flat)
-    budget = HIST_CHUNK_BYTES if chunk_bytes is None else int(chunk_bytes)
-    if budget < 1:
-        raise ValueError(f"chunk_bytes must be positive, got {chunk_bytes}")
-    if not 0 <= rank < world_size:
-        raise ValueError(f"rank {rank} is outside [0, {world_size})")
+    budget = _budget(chunk_bytes, rank, world_size)
     (z0, z1), (y0, y1), (x0, x1) = box
     ny, nx = y1 - y0, x1 - x0
     zw1, yw1, xw1 = z1 - wz + 1, y1 - wy + 1, x1 - wx + 1                # the window box's high ends
@@ -1151,33 +1251,18 @@ def volume_ssim(a, b, start=None, size=None, b_start=None, win=7, flat=False, ma
                              f"{getattr(map_out, 'dtype', None)} {tuple(map_out.shape)}")
     lib = H.require_gpu()
     wslabs = [w for w, _ in chunks]
-    wdims = [tuple(hi - lo for lo, hi in w) for w in wslabs]
-    map_vol = _OneSection(map_out) if one and map_out is not None else map_out
-    (oz, _), (oy, _), _ = box
-
-    def write_from(k, flat_bytes):      # host thread: the slab's box of `map_out`
-        (z0, z1), (y0, y1), _ = wslabs[k]
-        map_vol[z0 - oz:z1 - oz, y0 - oy:y1 - oy, 0:wshape[2]] = flat_bytes.reshape(wdims[k])
-
-    with p.streaming():
+    with p.streaming(stats):
         acc = torch.zeros((wshape[0], 3), dtype=torch.int64, device=p.dev)
         with contextlib.ExitStack() as stack:
-            outp = None
-            if map_out is not None:
-                p.st["write_s"] = 0.0
-                outp = stack.enter_context(_OutputStream([int(np.prod(d)) for d in wdims], write_from, p.dev, p.pool, p.st,
-                                                         own_buffers=True))  # the reader's thread: write(k), read(k + 2)
+            outp = None if map_out is None else stack.enter_context(p.writing(map_out, box, wslabs))
             for k, slab, d, (pa, pb) in p:
                 mp = outp.device(k).data_ptr() if outp is not None else None
                 _lib.check(lib.tem_u8_ssim(pa.data_ptr(), *d, 0, 0, 0, pb.data_ptr(), *d, 0, 0, 0, *d, wy, int(wz == 1),
-                                           acc.data_ptr() + 24 * (wslabs[k][0][0] - oz), mp, p.compute.cuda_stream),
-                           "tem_u8_ssim")
+                                           acc.data_ptr() + 24 * (wslabs[k][0][0] - box[0][0]), mp,
+                                           p.compute.cuda_stream), "tem_u8_ssim")
                 if outp is not None:
-                    p.release_on = p.compute.record_event()              # behind the kernel: the inputs are free too
-                    outp.put(k, p.release_on)
+                    p.put(k)
         sums = acc.cpu().numpy()                                         # the one read-back
-    if stats is not None:
-        stats.update(p.st)
     return SsimSums(sums, wshape[1] * wshape[2], (wz, wy, wx))
 
 
@@ -1315,11 +1400,7 @@ def rescale_chunks(out_box, vol_shape, step, chunk_bytes=None, rank=0, world_siz
     its hull is larger than the budget, runs of whole output rows of that plane (one row at the least).  Slabs are in
     (z, y) order and go round-robin to the ranks.  Pure host function; ValueError as hist_chunks, for a bad step and
     for a box outside the grid."""
-    budget = HIST_CHUNK_BYTES if chunk_bytes is None else int(chunk_bytes)
-    if budget < 1:
-        raise ValueError(f"chunk_bytes must be positive, got {chunk_bytes}")
-    if not 0 <= rank < world_size:
-        raise ValueError(f"rank {rank} is outside [0, {world_size})")
+    budget = _budget(chunk_bytes, rank, world_size)
     vol_shape = tuple(int(v) for v in vol_shape)
     if len(vol_shape) != 3:
         raise ValueError(f"rescale_chunks takes a volume shape [z, y, x], got {vol_shape}")
@@ -1403,39 +1484,19 @@ def volume_rescale(volume, step, out=None, start=None, size=None, chunk_bytes=No
         box = hist_box(grid, start, size)
     except ValueError as e:
         raise ValueError(f"volume_rescale: start / size are an ROI of the output grid of shape {grid}: {e}")
-    shape = tuple(hi - lo for lo, hi in box)
-    want = shape[1:] if one else shape
-    if out is None:
-        out = np.zeros(want, np.uint8)
-    elif tuple(out.shape) != want or getattr(out, "dtype", None) != np.uint8:
-        raise ValueError(f"out must be uint8 of the ROI's shape {want}, got {getattr(out, 'dtype', None)} "
-                         f"{tuple(out.shape)}")
+    out = _roi_out(out, box, one)
     vol3 = (1,) + vshape if one else vshape
     chunks = rescale_chunks(box, vol3, steps, chunk_bytes, rank, world_size)
     p = _SlabPass([volume], [hist_box(vshape)], chunk_bytes, rank, world_size, device, slabs=[r for _, r in chunks])
     lib = H.require_gpu()
     oslabs = [o for o, _ in chunks]
-    odims = [tuple(hi - lo for lo, hi in o) for o in oslabs]
     pq = [v for f in reversed(steps) for v in (f.numerator, f.denominator)]          # pz, qz, py, qy, px, qx
-    dst_vol = _OneSection(out) if one else out
-    (oz, _), (oy, _), (ox, _) = box
-    p.st["write_s"] = 0.0
-
-    def write_from(k, flat):            # host thread: the slab's box of `out`
-        (z0, z1), (y0, y1), (x0, x1) = oslabs[k]
-        dst_vol[z0 - oz:z1 - oz, y0 - oy:y1 - oy, x0 - ox:x1 - ox] = flat.reshape(odims[k])
-
-    with p.streaming():
-        with _OutputStream([int(np.prod(d)) for d in odims], write_from, p.dev, p.pool, p.st,
-                           own_buffers=True) as outp:                    # the reader's thread: write(k), read(k + 2)
-            for k, slab, d, (src,) in p:
-                _lib.check(lib.tem_u8_rescale(src.data_ptr(), *d, *(lo for lo, _ in slab), *vol3, *pq,
-                                              outp.device(k).data_ptr(), *odims[k], *(lo for lo, _ in oslabs[k]),
-                                              p.compute.cuda_stream), "tem_u8_rescale")
-                p.release_on = p.compute.record_event()                  # behind the kernel: the input is free too
-                outp.put(k, p.release_on)
-    if stats is not None:
-        stats.update(p.st)
+    with p.streaming(stats), p.writing(out, box, oslabs) as outp:
+        for k, slab, d, (src,) in p:
+            _lib.check(lib.tem_u8_rescale(src.data_ptr(), *d, *(lo for lo, _ in slab), *vol3, *pq,
+                                          outp.device(k).data_ptr(), *(hi - lo for lo, hi in oslabs[k]),
+                                          *(lo for lo, _ in oslabs[k]), p.compute.cuda_stream), "tem_u8_rescale")
+            p.put(k)
     return out
 
 
@@ -1538,27 +1599,11 @@ def repair_chunks(box, vol_shape, max_gap, chunk_bytes=None, rank=0, world_size=
     or, where 2 max_gap + 1 sections of the box are larger than the budget, one section's rows, as many as fit (one row
     at the least).  Slabs are in (z, y) order and go round-robin to the ranks.  Pure host function; ValueError as
     hist_chunks, and for a max_gap outside 1...32."""
-    budget = HIST_CHUNK_BYTES if chunk_bytes is None else int(chunk_bytes)
-    if budget < 1:
-        raise ValueError(f"chunk_bytes must be positive, got {chunk_bytes}")
-    if not 0 <= rank < world_size:
-        raise ValueError(f"rank {rank} is outside [0, {world_size})")
+    budget = _budget(chunk_bytes, rank, world_size)
     R = _index(max_gap, "max_gap")
     if not 1 <= R <= REPAIR_MAX_GAP:
         raise ValueError(f"max_gap must lie in 1...{REPAIR_MAX_GAP}, got {R}")
-    Z = int(vol_shape[0])
-    (z0, z1), (y0, y1), (x0, x1) = box
-    ny, nx = y1 - y0, x1 - x0
-    if z1 <= z0 or ny <= 0 or nx <= 0:
-        return []
-    if (2 * R + 1) * ny * nx <= budget:
-        kz = budget // (ny * nx) - 2 * R
-        cores = [((z, min(z + kz, z1)), (y0, y1)) for z in range(z0, z1, kz)]
-    else:
-        ky = max(1, budget // ((2 * R + 1) * nx))
-        cores = [((z, z + 1), (y, min(y + ky, y1))) for z in range(z0, z1) for y in range(y0, y1, ky)]
-    slabs = [((cz, cy, (x0, x1)), ((max(cz[0] - R, 0), min(cz[1] + R, Z)), cy, (x0, x1))) for cz, cy in cores]
-    return slabs[rank::world_size]
+    return _cut_slabs(box, ((0, int(vol_shape[0])), box[1]), budget, rank, world_size, zreach=(R, R))
 
 
 def volume_repair(volume, repair, out=None, start=None, size=None, chunk_bytes=None, stats=None, rank=0, world_size=1,
@@ -1588,39 +1633,23 @@ def volume_repair(volume, repair, out=None, start=None, size=None, chunk_bytes=N
     if rp is None:
         raise ValueError("volume_repair needs a Repair")
     box = hist_box(vshape, start, size)
-    shape = tuple(hi - lo for lo, hi in box)
-    if out is None:
-        out = np.zeros(shape, np.uint8)
-    elif tuple(out.shape) != shape or getattr(out, "dtype", None) != np.uint8:
-        raise ValueError(f"out must be uint8 of the ROI's shape {shape}, got {getattr(out, 'dtype', None)} "
-                         f"{tuple(out.shape)}")
+    out = _roi_out(out, box, False)
     chunks = repair_chunks(box, vshape, rp.max_gap, chunk_bytes, rank, world_size)
     whole = hist_box(vshape)
     vols = [volume] + ([rp.mask] if rp.mask is not None else [])
     p = _SlabPass(vols, [whole] * len(vols), chunk_bytes, rank, world_size, device, slabs=[r for _, r in chunks])
     lib = H.require_gpu()
     cores = [c for c, _ in chunks]
-    cdims = [tuple(hi - lo for lo, hi in c) for c in cores]
-    (oz, _), (oy, _), (ox, _) = box
-    p.st["write_s"] = 0.0
-
-    def write_from(k, flat):            # host thread: the core's box of `out`
-        (z0, z1), (y0, y1), (x0, x1) = cores[k]
-        out[z0 - oz:z1 - oz, y0 - oy:y1 - oy, x0 - ox:x1 - ox] = flat.reshape(cdims[k])
-
-    with p.streaming():
+    with p.streaming(stats):
         prepare = _Prepare(lib, None, None, p.dev, p.compute.cuda_stream, repair=rp)     # the section flags, once
         counts = torch.zeros(2, dtype=torch.int64, device=p.dev)
-        with _OutputStream([int(np.prod(d)) for d in cdims], write_from, p.dev, p.pool, p.st) as outp:
+        with p.writing(out, box, cores, own_buffers=False):
             for k, slab, d, bufs in p:
-                c0 = cores[k][0][0] - slab[0][0]
-                prepare.repair_block(bufs[0].data_ptr(), d, slab[0][0], c0, c0 + cdims[k][0],
+                c0, c1 = (v - slab[0][0] for v in cores[k][0])
+                prepare.repair_block(bufs[0].data_ptr(), d, slab[0][0], c0, c1,
                                      bufs[1].data_ptr() if rp.mask is not None else None, counts.data_ptr())
-                # the core planes: one contiguous range of the block; the inputs are free once it is copied out
-                p.release_on = outp.put(k, p.compute.record_event(), bufs[0][c0 * d[1] * d[2]:])
+                p.put(k, bufs[0][c0 * d[1] * d[2]:])     # the core planes: one contiguous range of the block
         p.st["repaired"], p.st["unrepaired"] = (int(v) for v in counts.cpu().numpy())    # the one read-back
-    if stats is not None:
-        stats.update(p.st)
     return out
 
 
@@ -1667,23 +1696,9 @@ def zcorr_chunks(vol_shape, chunk_bytes=None, rank=0, world_size=1):
 
 def _zhalo_chunks(vol_shape, reach, chunk_bytes, rank, world_size):
     """zcorr_chunks' cuts with read slabs that reach `reach` sections past their core, where the volume has them."""
-    budget = HIST_CHUNK_BYTES if chunk_bytes is None else int(chunk_bytes)
-    if budget < 1:
-        raise ValueError(f"chunk_bytes must be positive, got {chunk_bytes}")
-    if not 0 <= rank < world_size:
-        raise ValueError(f"rank {rank} is outside [0, {world_size})")
-    (_, Z), (_, ny), (_, nx) = hist_box(vol_shape)
-    if Z <= 0 or ny <= 0 or nx <= 0:
-        return []
-    halo = min(reach, Z - 1)
-    if (1 + halo) * ny * nx <= budget:
-        kz = budget // (ny * nx) - halo
-        cores = [((z, min(z + kz, Z)), (0, ny)) for z in range(0, Z, kz)]
-    else:
-        ky = max(1, budget // ((1 + halo) * nx))
-        cores = [((z, z + 1), (y, min(y + ky, ny))) for z in range(Z) for y in range(0, ny, ky)]
-    slabs = [((cz, cy, (0, nx)), ((cz[0], min(cz[1] + halo, Z)), cy, (0, nx))) for cz, cy in cores]
-    return slabs[rank::world_size]
+    budget = _budget(chunk_bytes, rank, world_size)
+    box = hist_box(vol_shape)
+    return _cut_slabs(box, box[:2], budget, rank, world_size, zreach=(0, min(reach, box[0][1] - 1)))
 
 
 def section_sums(volume, tile=128, chunk_bytes=None, rank=0, world_size=1, device=None, stats=None):
@@ -1708,26 +1723,14 @@ def section_sums(volume, tile=128, chunk_bytes=None, rank=0, world_size=1, devic
     chunks = zcorr_chunks(volume.shape, chunk_bytes, rank, world_size)
     p = _SlabPass([volume], [box], chunk_bytes, rank, world_size, device, slabs=[r for _, r in chunks])
     lib = H.require_gpu()
-    Z, sec = box[0][1], gy * gx * 4
-    whole = Z * sec * 8 <= CLAHE_ACC_BYTES
-    out = None if whole else np.zeros((Z, gy, gx, 4), np.int64)
-    with p.streaming():
-        most = max((c[0][1] - c[0][0] for c, _ in chunks), default=1)
-        acc = torch.zeros((Z if whole else most, sec), dtype=torch.int64, device=p.dev)
+    with p.streaming(stats):
+        acc = _RowAccumulator(p.dev, box[0][1], (gy, gx, 4), _most_rows(c[0] for c, _ in chunks))
         for k, ((r0, _), (y0, _), (x0, _)), d, (src,) in p:
             z0, z1 = chunks[k][0][0]
-            if not whole:
-                acc[:z1 - z0].zero_()
             _lib.check(lib.tem_u8_zcorr_tiles(src.data_ptr(), *d, z0 - r0, z1 - r0, y0, x0, th, tw, gy, gx,
-                                              acc.data_ptr() + 8 * sec * (z0 if whole else 0), p.compute.cuda_stream),
-                       "tem_u8_zcorr_tiles")
-            if not whole:                                        # this slab's core sections, added on the host
-                out[z0:z1] += acc[:z1 - z0].cpu().numpy().reshape(z1 - z0, gy, gx, 4)
-        if whole:
-            out = acc.cpu().numpy().reshape(Z, gy, gx, 4)        # the one read-back
-    if stats is not None:
-        stats.update(p.st)
-    return out
+                                              acc.ptr(z0, z1), p.compute.cuda_stream), "tem_u8_zcorr_tiles")
+            acc.add(z0, z1)
+        return acc.result()
 
 
 def _check_sums(s, who):
@@ -1946,11 +1949,7 @@ def outlier_chunks(box, vol_shape, nbr, radius, chunk_bytes=None, rank=0, world_
     than the budget, that section's rows, as many as fit next to their 2 radius (one row at the least).  Slabs are in
     (z, y) order and go round-robin to the ranks.  Pure host function; ValueError as hist_chunks, for a bad table or
     radius and a box outside the volume."""
-    budget = HIST_CHUNK_BYTES if chunk_bytes is None else int(chunk_bytes)
-    if budget < 1:
-        raise ValueError(f"chunk_bytes must be positive, got {chunk_bytes}")
-    if not 0 <= rank < world_size:
-        raise ValueError(f"rank {rank} is outside [0, {world_size})")
+    budget = _budget(chunk_bytes, rank, world_size)
     vol_shape = tuple(int(v) for v in vol_shape)
     if len(vol_shape) != 3 or min(vol_shape) < 1:
         raise ValueError(f"outlier_chunks takes a non-empty volume shape [z, y, x], got {vol_shape}")
@@ -2015,28 +2014,16 @@ def section_outlier_sums(volume, tile=128, skip=(), max_lag=4, chunk_bytes=None,
     chunks = outlier_chunks(box, tuple(hi for _, hi in box), nbr, 0, chunk_bytes, rank, world_size)
     p = _SlabPass([volume], [box], chunk_bytes, rank, world_size, device, slabs=[r for _, r in chunks])
     lib = H.require_gpu()
-    sec = gy * gx * 2
-    whole = Z * sec * 8 <= CLAHE_ACC_BYTES
-    out = None if whole else np.zeros((Z, gy, gx, 2), np.int64)
-    with p.streaming():
-        most = max((c[0][1] - c[0][0] for c, _ in chunks), default=1)
-        acc = torch.zeros((Z if whole else most, sec), dtype=torch.int64, device=p.dev)
+    with p.streaming(stats):
+        acc = _RowAccumulator(p.dev, Z, (gy, gx, 2), _most_rows(c[0] for c, _ in chunks))
         nbr_dev = torch.from_numpy(nbr).to(p.dev)                # uploaded once
         for k, ((s0, _), (y0, _), (x0, _)), d, (src,) in p:
             z0, z1 = chunks[k][0][0]
-            if not whole:
-                acc[:z1 - z0].zero_()
             _lib.check(lib.tem_u8_zdev_tiles(src.data_ptr(), *d, s0, Z, z0 - s0, z1 - s0, y0, x0, th, tw, gy, gx,
-                                             nbr.ctypes.data, nbr_dev.data_ptr(),
-                                             acc.data_ptr() + 8 * sec * (z0 if whole else 0), p.compute.cuda_stream),
-                       "tem_u8_zdev_tiles")
-            if not whole:                                        # this slab's core sections, added on the host
-                out[z0:z1] += acc[:z1 - z0].cpu().numpy().reshape(z1 - z0, gy, gx, 2)
-        if whole:
-            out = acc.cpu().numpy().reshape(Z, gy, gx, 2)        # the one read-back
-    if stats is not None:
-        stats.update(p.st)
-    return out
+                                             nbr.ctypes.data, nbr_dev.data_ptr(), acc.ptr(z0, z1),
+                                             p.compute.cuda_stream), "tem_u8_zdev_tiles")
+            acc.add(z0, z1)
+        return acc.result()
 
 
 class OutlierThresholds(NamedTuple):
@@ -2117,32 +2104,16 @@ def volume_outliers(volume, thr, tile=128, window=9, skip=(), max_lag=4, tiles=N
             raise ValueError(f"tiles must be bool or integers of the shape {(Z, gy, gx)} of the volume's tile grid, got "
                              f"{tiles.dtype} {tiles.shape}")
         tiles = np.ascontiguousarray((tiles != 0).astype(np.uint8))
-    one = len(volume.shape) == 2
-    shape = tuple(hi - lo for lo, hi in box)
-    if out is None:
-        out = np.zeros(shape[1:] if one else shape, np.uint8)
-    elif tuple(out.shape) != (shape[1:] if one else shape) or getattr(out, "dtype", None) != np.uint8:
-        raise ValueError(f"out must be uint8 of the ROI's shape {shape[1:] if one else shape}, got "
-                         f"{getattr(out, 'dtype', None)} {tuple(out.shape)}")
+    out = _roi_out(out, box, len(volume.shape) == 2)
     chunks = outlier_chunks(box, (Z, Y, X), nbr, r, chunk_bytes, rank, world_size)
     p = _SlabPass([volume], [whole], chunk_bytes, rank, world_size, device, slabs=[rd for _, rd in chunks])
     lib = H.require_gpu()
     cores = [c for c, _ in chunks]
-    cdims = [tuple(hi - lo for lo, hi in c) for c in cores]
-    (oz, _), (oy, _), (ox, _) = box
-    dst_vol = _OneSection(out) if one else out
-    p.st["write_s"] = 0.0
-
-    def write_from(k, flat):            # host thread: the core's box of `out`
-        (z0, z1), (y0, y1), (x0, x1) = cores[k]
-        dst_vol[z0 - oz:z1 - oz, y0 - oy:y1 - oy, x0 - ox:x1 - ox] = flat.reshape(cdims[k])
-
-    with p.streaming():
+    with p.streaming(stats):
         nbr_dev, thr_dev = torch.from_numpy(nbr).to(p.dev), torch.from_numpy(t).to(p.dev)   # the tables, once
         tiles_dev = None if tiles is None else torch.from_numpy(tiles).to(p.dev)
         count = torch.zeros(1, dtype=torch.int64, device=p.dev)
-        with _OutputStream([int(np.prod(d)) for d in cdims], write_from, p.dev, p.pool, p.st,
-                           own_buffers=True) as outp:                    # the reader's thread: write(k), read(k + 2)
+        with p.writing(out, box, cores) as outp:
             for k, ((s0, _), (ry, _), _), d, (src,) in p:
                 (cz0, cz1), (cy0, cy1), (cx0, cx1) = cores[k]
                 _lib.check(lib.tem_u8_zdev_mask(src.data_ptr(), *d, s0, Z, Y, ry, cz0 - s0, cz1 - s0, cy0 - ry, cy1 - ry,
@@ -2151,11 +2122,8 @@ def volume_outliers(volume, thr, tile=128, window=9, skip=(), max_lag=4, tiles=N
                                                 None if tiles is None else tiles_dev.data_ptr() + cz0 * gy * gx,
                                                 outp.device(k).data_ptr(), count.data_ptr(), p.compute.cuda_stream),
                            "tem_u8_zdev_mask")
-                p.release_on = p.compute.record_event()                  # behind the kernel: the input is free too
-                outp.put(k, p.release_on)
+                p.put(k)
         p.st["flagged"] = int(count.cpu().numpy()[0])                    # the one read-back
-    if stats is not None:
-        stats.update(p.st)
     return out
 
 
@@ -2252,26 +2220,14 @@ def section_lag_sums(volume, tile=128, max_lag=4, chunk_bytes=None, rank=0, worl
     chunks = zlag_chunks(volume.shape, L, chunk_bytes, rank, world_size)
     p = _SlabPass([volume], [box], chunk_bytes, rank, world_size, device, slabs=[r for _, r in chunks])
     lib = H.require_gpu()
-    Z, sec = box[0][1], gy * gx * (3 + L)
-    whole = Z * sec * 8 <= CLAHE_ACC_BYTES
-    out = None if whole else np.zeros((Z, gy, gx, 3 + L), np.int64)
-    with p.streaming():
-        most = max((c[0][1] - c[0][0] for c, _ in chunks), default=1)
-        acc = torch.zeros((Z if whole else most, sec), dtype=torch.int64, device=p.dev)
+    with p.streaming(stats):
+        acc = _RowAccumulator(p.dev, box[0][1], (gy, gx, 3 + L), _most_rows(c[0] for c, _ in chunks))
         for k, ((r0, _), (y0, _), (x0, _)), d, (src,) in p:
             z0, z1 = chunks[k][0][0]
-            if not whole:
-                acc[:z1 - z0].zero_()
             _lib.check(lib.tem_u8_zcorr_lags(src.data_ptr(), *d, z0 - r0, z1 - r0, y0, x0, th, tw, gy, gx, L,
-                                             acc.data_ptr() + 8 * sec * (z0 if whole else 0), p.compute.cuda_stream),
-                       "tem_u8_zcorr_lags")
-            if not whole:                                        # this slab's core sections, added on the host
-                out[z0:z1] += acc[:z1 - z0].cpu().numpy().reshape(z1 - z0, gy, gx, 3 + L)
-        if whole:
-            out = acc.cpu().numpy().reshape(Z, gy, gx, 3 + L)    # the one read-back
-    if stats is not None:
-        stats.update(p.st)
-    return out
+                                             acc.ptr(z0, z1), p.compute.cuda_stream), "tem_u8_zcorr_lags")
+            acc.add(z0, z1)
+        return acc.result()
 
 
 def _check_lag_sums(s, who):
@@ -2515,11 +2471,7 @@ def resample_z_chunks(out_box, vol_shape, taps, chunk_bytes=None, rank=0, world_
     most `chunk_bytes` bytes (HIST_CHUNK_BYTES when None) wherever one row allows it.  Slabs are in (z, y) order and go
     round-robin to the ranks.  Pure host function; ValueError as hist_chunks, for bad taps and a box outside the
     output."""
-    budget = HIST_CHUNK_BYTES if chunk_bytes is None else int(chunk_bytes)
-    if budget < 1:
-        raise ValueError(f"chunk_bytes must be positive, got {chunk_bytes}")
-    if not 0 <= rank < world_size:
-        raise ValueError(f"rank {rank} is outside [0, {world_size})")
+    budget = _budget(chunk_bytes, rank, world_size)
     vol_shape = tuple(int(v) for v in vol_shape)
     if len(vol_shape) != 3 or min(vol_shape) < 1:
         raise ValueError(f"resample_z_chunks takes a non-empty volume shape [z, y, x], got {vol_shape}")
@@ -2592,37 +2544,20 @@ def volume_resample_z(volume, positions, out=None, start=None, size=None, nz=Non
         box = hist_box(grid, start, size)
     except ValueError as e:
         raise ValueError(f"volume_resample_z: start / size are an ROI of the output of shape {grid}: {e}")
-    shape = tuple(hi - lo for lo, hi in box)
-    if out is None:
-        out = np.zeros(shape, np.uint8)
-    elif tuple(out.shape) != shape or getattr(out, "dtype", None) != np.uint8:
-        raise ValueError(f"out must be uint8 of the ROI's shape {shape}, got {getattr(out, 'dtype', None)} "
-                         f"{tuple(out.shape)}")
+    out = _roi_out(out, box, False)
     chunks = resample_z_chunks(box, vshape, taps, chunk_bytes, rank, world_size)
     p = _SlabPass([volume], [hist_box(vshape)], chunk_bytes, rank, world_size, device, slabs=[r for _, r in chunks])
     lib = H.require_gpu()
     oslabs = [o for o, _ in chunks]
-    odims = [tuple(hi - lo for lo, hi in o) for o in oslabs]
-    (oz, _), (oy, _), (ox, _) = box
-    p.st["write_s"] = 0.0
-
-    def write_from(k, flat):            # host thread: the slab's box of `out`
-        (z0, z1), (y0, y1), (x0, x1) = oslabs[k]
-        out[z0 - oz:z1 - oz, y0 - oy:y1 - oy, x0 - ox:x1 - ox] = flat.reshape(odims[k])
-
-    with p.streaming():
+    with p.streaming(stats):
         taps_dev = torch.from_numpy(taps).to(p.dev)
-        with _OutputStream([int(np.prod(d)) for d in odims], write_from, p.dev, p.pool, p.st,
-                           own_buffers=True) as outp:                    # the reader's thread: write(k), read(k + 2)
+        with p.writing(out, box, oslabs) as outp:
             for k, slab, d, (src,) in p:
+                oz0, oz1 = oslabs[k][0]
                 _lib.check(lib.tem_u8_resample_z(src.data_ptr(), *d, slab[0][0], vshape[0], outp.device(k).data_ptr(),
-                                                 odims[k][0], oslabs[k][0][0], grid[0], taps.ctypes.data,
-                                                 taps_dev.data_ptr(), int(bool(nearest)), p.compute.cuda_stream),
-                           "tem_u8_resample_z")
-                p.release_on = p.compute.record_event()                  # behind the kernel: the input is free too
-                outp.put(k, p.release_on)
-    if stats is not None:
-        stats.update(p.st)
+                                                 oz1 - oz0, oz0, grid[0], taps.ctypes.data, taps_dev.data_ptr(),
+                                                 int(bool(nearest)), p.compute.cuda_stream), "tem_u8_resample_z")
+                p.put(k)
     return out
 
 
@@ -2647,22 +2582,9 @@ def plane_lag_chunks(vol_shape, max_lag=8, chunk_bytes=None, rank=0, world_size=
     to their max_lag rows of halo (one row at the least).  Slabs are in (z, y) order and go round-robin to the ranks.
     Pure host function; ValueError as hist_box and hist_chunks, and for max_lag outside 1...PLANE_LAG_MAX."""
     L = _plane_lag(max_lag)
-    budget = HIST_CHUNK_BYTES if chunk_bytes is None else int(chunk_bytes)
-    if budget < 1:
-        raise ValueError(f"chunk_bytes must be positive, got {chunk_bytes}")
-    if not 0 <= rank < world_size:
-        raise ValueError(f"rank {rank} is outside [0, {world_size})")
-    (_, Z), (_, ny), (_, nx) = hist_box(vol_shape)
-    if Z <= 0 or ny <= 0 or nx <= 0:
-        return []
-    if ny * nx <= budget:
-        kz = budget // (ny * nx)
-        slabs = [(((z, min(z + kz, Z)), (0, ny), (0, nx)),) * 2 for z in range(0, Z, kz)]
-    else:
-        ky = max(1, budget // nx - L)
-        slabs = [(((z, z + 1), (y, min(y + ky, ny)), (0, nx)), ((z, z + 1), (y, min(y + ky + L, ny)), (0, nx)))
-                 for z in range(Z) for y in range(0, ny, ky)]
-    return slabs[rank::world_size]
+    budget = _budget(chunk_bytes, rank, world_size)
+    box = hist_box(vol_shape)
+    return _cut_slabs(box, box[:2], budget, rank, world_size, yreach=(0, L))
 
 
 def plane_lag_counts(vol_shape, tile, max_lag=8):
@@ -2714,26 +2636,15 @@ def section_plane_sums(volume, tile=128, max_lag=8, chunk_bytes=None, rank=0, wo
     chunks = plane_lag_chunks(volume.shape, L, chunk_bytes, rank, world_size)
     p = _SlabPass([volume], [box], chunk_bytes, rank, world_size, device, slabs=[r for _, r in chunks])
     lib = H.require_gpu()
-    Z, Y, sec = box[0][1], box[1][1], gy * gx * (3 + 2 * L)
-    whole = Z * sec * 8 <= CLAHE_ACC_BYTES
-    out = None if whole else np.zeros((Z, gy, gx, 3 + 2 * L), np.int64)
-    with p.streaming():
-        most = max((c[0][1] - c[0][0] for c, _ in chunks), default=1)
-        acc = torch.zeros((Z if whole else most, sec), dtype=torch.int64, device=p.dev)
+    Z, Y = box[0][1], box[1][1]
+    with p.streaming(stats):
+        acc = _RowAccumulator(p.dev, Z, (gy, gx, 3 + 2 * L), _most_rows(c[0] for c, _ in chunks))
         for k, ((s0, _), (y0, _), _), d, (src,) in p:
             (z0, z1), (c0, c1), _ = chunks[k][0]
-            if not whole:
-                acc[:z1 - z0].zero_()
             _lib.check(lib.tem_u8_zplane_lags(src.data_ptr(), *d, z0 - s0, z1 - s0, c0 - y0, c1 - y0, y0, Y, th, tw, gy,
-                                              gx, L, acc.data_ptr() + 8 * sec * (z0 if whole else 0),
-                                              p.compute.cuda_stream), "tem_u8_zplane_lags")
-            if not whole:                                        # this slab's core sections, added on the host
-                out[z0:z1] += acc[:z1 - z0].cpu().numpy().reshape(z1 - z0, gy, gx, 3 + 2 * L)
-        if whole:
-            out = acc.cpu().numpy().reshape(Z, gy, gx, 3 + 2 * L)        # the one read-back
-    if stats is not None:
-        stats.update(p.st)
-    return out
+                                              gx, L, acc.ptr(z0, z1), p.compute.cuda_stream), "tem_u8_zplane_lags")
+            acc.add(z0, z1)
+        return acc.result()
 
 
 def _check_plane_sums(s, n, who):
@@ -2972,24 +2883,9 @@ def _zshift_chunks(vol_shape, radius, lo, hi, chunk_bytes, rank, world_size):
     """zshift_chunks' list for windows centred within [lo, hi] rows of zero, lo <= 0 <= hi: a read slab is its core plus
     radius - lo rows below and radius + hi rows above it."""
     r = _shift_radius(radius)
-    budget = HIST_CHUNK_BYTES if chunk_bytes is None else int(chunk_bytes)
-    if budget < 1:
-        raise ValueError(f"chunk_bytes must be positive, got {chunk_bytes}")
-    if not 0 <= rank < world_size:
-        raise ValueError(f"rank {rank} is outside [0, {world_size})")
-    (_, Z), (_, ny), (_, nx) = hist_box(vol_shape)
-    if Z <= 0 or ny <= 0 or nx <= 0:
-        return []
-    halo = 1 if Z > 1 else 0
-    if (1 + halo) * ny * nx <= budget:
-        kz = budget // (ny * nx) - halo
-        cores = [((z, min(z + kz, Z)), (0, ny)) for z in range(0, Z, kz)]
-    else:
-        ky = max(1, budget // ((1 + halo) * nx) - (2 * r + hi - lo))
-        cores = [((z, z + 1), (y, min(y + ky, ny))) for z in range(Z) for y in range(0, ny, ky)]
-    slabs = [((cz, cy, (0, nx)), ((cz[0], min(cz[1] + 1, Z)), (max(cy[0] - r + lo, 0), min(cy[1] + r + hi, ny)),
-                                  (0, nx))) for cz, cy in cores]
-    return slabs[rank::world_size]
+    budget = _budget(chunk_bytes, rank, world_size)
+    box = hist_box(vol_shape)
+    return _cut_slabs(box, box[:2], budget, rank, world_size, zreach=(0, min(1, box[0][1] - 1)), yreach=(r - lo, r + hi))
 
 
 def shift_counts(vol_shape, tile, radius):
@@ -3056,22 +2952,16 @@ def _shift_sums_pass(volume, centers, tile, radius, chunk_bytes, rank, world_siz
     p = _SlabPass([volume], [box], chunk_bytes, rank, world_size, device, slabs=[s for _, s in chunks])
     lib = H.require_gpu()
     R = 2 * r + 1
-    Z, Y, sec = box[0][1], box[1][1], gy * gx * R * R * 5
-    shape = (gy, gx, R, R, 5)
-    whole = Z * sec * 8 <= CLAHE_ACC_BYTES
-    out = None if whole else np.zeros((Z,) + shape, np.int64)
-    with p.streaming():
-        most = max((c[0][1] - c[0][0] for c, _ in chunks), default=1)
-        acc = torch.zeros((Z if whole else most, sec), dtype=torch.int64, device=p.dev)
+    Z, Y = box[0][1], box[1][1]
+    with p.streaming(stats):
+        acc = _RowAccumulator(p.dev, Z, (gy, gx, R, R, 5), _most_rows(c[0] for c, _ in chunks))
         if centers is not None:                                  # uploaded once; the last section's row is never read
             table = torch.zeros((Z, gy * gx * 2), dtype=torch.int32, device=p.dev)
             if C.size:
                 table[:Z - 1] = torch.from_numpy(C.astype(np.int32).reshape(Z - 1, -1)).to(p.dev)
         for k, ((s0, _), (y0, _), _), d, (src,) in p:
             (z0, z1), (c0, c1), _ = chunks[k][0]
-            if not whole:
-                acc[:z1 - z0].zero_()
-            where = acc.data_ptr() + 8 * sec * (z0 if whole else 0)
+            where = acc.ptr(z0, z1)
             if centers is None:
                 _lib.check(lib.tem_u8_zshift_tiles(src.data_ptr(), *d, z0 - s0, z1 - s0, c0 - y0, c1 - y0, y0, Y, th, tw,
                                                    gy, gx, r, where, p.compute.cuda_stream), "tem_u8_zshift_tiles")
@@ -3079,13 +2969,8 @@ def _shift_sums_pass(volume, centers, tile, radius, chunk_bytes, rank, world_siz
                 _lib.check(lib.tem_u8_zshift_tiles_at(src.data_ptr(), *d, z0 - s0, z1 - s0, c0 - y0, c1 - y0, y0, Y, th,
                                                       tw, gy, gx, r, table.data_ptr() + 8 * gy * gx * z0, lo, hi, cx_max,
                                                       where, p.compute.cuda_stream), "tem_u8_zshift_tiles_at")
-            if not whole:                                        # this slab's core sections, added on the host
-                out[z0:z1] += acc[:z1 - z0].cpu().numpy().reshape((z1 - z0,) + shape)
-        if whole:
-            out = acc.cpu().numpy().reshape((Z,) + shape)        # the one read-back
-    if stats is not None:
-        stats.update(p.st)
-    return out
+            acc.add(z0, z1)
+        return acc.result()
 
 
 def _check_shift_sums(q, n, who):
@@ -3619,11 +3504,7 @@ def zshift_chunks_pairs(vol_shape, pairs, radius, reach=(0, 0), chunk_bytes=None
     the last section alone.  Pure host function; ValueError as zshift_chunks_at, and _check_pairs'."""
     r = _shift_radius(radius)
     lo, hi = _shift_reach(reach)
-    budget = HIST_CHUNK_BYTES if chunk_bytes is None else int(chunk_bytes)
-    if budget < 1:
-        raise ValueError(f"chunk_bytes must be positive, got {chunk_bytes}")
-    if not 0 <= rank < world_size:
-        raise ValueError(f"rank {rank} is outside [0, {world_size})")
+    budget = _budget(chunk_bytes, rank, world_size)
     (_, Z), (_, ny), (_, nx) = hist_box(vol_shape)
     p = _check_pairs(pairs, Z).tolist()
     chunks, k = [], 0
@@ -3692,35 +3573,24 @@ def section_shift_sums_pairs(volume, pairs, centers=None, tile=128, radius=4, ch
     chunks = zshift_chunks_pairs(volume.shape, pr, r, (lo, hi), chunk_bytes, rank, world_size)
     p = _SlabPass([volume], [hist_box(volume.shape)], chunk_bytes, rank, world_size, device, slabs=[s for _, _, s in chunks])
     R = 2 * r + 1
-    sec, shape = gy * gx * R * R * 5, (gy, gx, R, R, 5)
-    out = np.zeros((P,) + shape, np.int64)
-    if not chunks:
+    shape = (gy, gx, R, R, 5)
+    if not chunks:                                               # nothing to read: no GPU is needed
         if stats is not None:
             stats.update(p.st)
-        return out
+        return np.zeros((P,) + shape, np.int64)
     lib = H.require_gpu()
-    whole = P * sec * 8 <= CLAHE_ACC_BYTES
-    with p.streaming():
-        most = max(k1 - k0 for (k0, k1), _, _ in chunks)
-        acc = torch.zeros((P if whole else most, sec), dtype=torch.int64, device=p.dev)
+    with p.streaming(stats):
+        acc = _RowAccumulator(p.dev, P, shape, _most_rows(c[0] for c in chunks))
         table = torch.from_numpy(pr.astype(np.int32)).to(p.dev)                  # both uploaded once
         ctable = torch.from_numpy(C.astype(np.int32).reshape(P, -1)).to(p.dev)
         for k, ((s0, _), (y0, _), _), d, (src,) in p:
             (k0, k1), (c0, c1), _ = chunks[k]
-            if not whole:
-                acc[:k1 - k0].zero_()
-            where = acc.data_ptr() + 8 * sec * (k0 if whole else 0)
             _lib.check(lib.tem_u8_zshift_tiles_pairs(src.data_ptr(), *d, s0, k1 - k0, table.data_ptr() + 8 * k0, c0 - y0,
                                                      c1 - y0, y0, Y, th, tw, gy, gx, r,
-                                                     ctable.data_ptr() + 8 * gy * gx * k0, lo, hi, cx_max, where,
-                                                     p.compute.cuda_stream), "tem_u8_zshift_tiles_pairs")
-            if not whole:                                        # this chunk's pairs, added on the host
-                out[k0:k1] += acc[:k1 - k0].cpu().numpy().reshape((k1 - k0,) + shape)
-        if whole:
-            out = acc.cpu().numpy().reshape((P,) + shape)        # the one read-back
-    if stats is not None:
-        stats.update(p.st)
-    return out
+                                                     ctable.data_ptr() + 8 * gy * gx * k0, lo, hi, cx_max,
+                                                     acc.ptr(k0, k1), p.compute.cuda_stream), "tem_u8_zshift_tiles_pairs")
+            acc.add(k0, k1)
+        return acc.result()
 
 
 def shift_scores_pairs(q, n):
@@ -4012,11 +3882,7 @@ def warp_chunks(out_box, vol_shape, M, chunk_bytes=None, rank=0, world_size=1):
     is outside), over the volume's whole x extent: x is never cut.  Both slabs hold at most `chunk_bytes` bytes
     (HIST_CHUNK_BYTES when None).  Slabs are in (z, y) order and go round-robin to the ranks.  Pure host function;
     ValueError as rescale_chunks, and for maps of another shape or dtype or outside the limits."""
-    budget = HIST_CHUNK_BYTES if chunk_bytes is None else int(chunk_bytes)
-    if budget < 1:
-        raise ValueError(f"chunk_bytes must be positive, got {chunk_bytes}")
-    if not 0 <= rank < world_size:
-        raise ValueError(f"rank {rank} is outside [0, {world_size})")
+    budget = _budget(chunk_bytes, rank, world_size)
     vol_shape = tuple(int(v) for v in vol_shape)
     if len(vol_shape) != 3 or min(vol_shape) < 1:
         raise ValueError(f"warp_chunks takes a non-empty volume shape [z, y, x], got {vol_shape}")
@@ -4116,39 +3982,20 @@ def volume_warp(volume, maps, out=None, start=None, size=None, fill=0, nearest=F
     if not 0 <= fill <= 255:
         raise ValueError(f"fill must lie in 0...255, got {fill}")
     box = hist_box(vshape, start, size)
-    shape = tuple(hi - lo for lo, hi in box)
-    want = shape[1:] if one else shape
-    if out is None:
-        out = np.zeros(want, np.uint8)
-    elif tuple(out.shape) != want or getattr(out, "dtype", None) != np.uint8:
-        raise ValueError(f"out must be uint8 of the ROI's shape {want}, got {getattr(out, 'dtype', None)} "
-                         f"{tuple(out.shape)}")
+    out = _roi_out(out, box, one)
     chunks = warp_chunks(box, vol3, M, chunk_bytes, rank, world_size)
     p = _SlabPass([volume], [hist_box(vshape)], chunk_bytes, rank, world_size, device, slabs=[r for _, r in chunks])
     lib = H.require_gpu()
     oslabs = [o for o, _ in chunks]
-    odims = [tuple(hi - lo for lo, hi in o) for o in oslabs]
-    dst_vol = _OneSection(out) if one else out
-    (oz, _), (oy, _), (ox, _) = box
-    p.st["write_s"] = 0.0
-
-    def write_from(k, flat):            # host thread: the slab's box of `out`
-        (z0, z1), (y0, y1), (x0, x1) = oslabs[k]
-        dst_vol[z0 - oz:z1 - oz, y0 - oy:y1 - oy, x0 - ox:x1 - ox] = flat.reshape(odims[k])
-
-    with p.streaming():
+    with p.streaming(stats):
         table = torch.from_numpy(M).to(p.dev)                            # the whole table, once
-        with _OutputStream([int(np.prod(d)) for d in odims], write_from, p.dev, p.pool, p.st,
-                           own_buffers=True) as outp:                    # the reader's thread: write(k), read(k + 2)
+        with p.writing(out, box, oslabs) as outp:
             for k, ((z0, _), (y0, _), _), d, (src,) in p:
-                _lib.check(lib.tem_u8_warp_affine(src.data_ptr(), *d, y0, vol3[1], outp.device(k).data_ptr(), *odims[k],
-                                                  oslabs[k][1][0], oslabs[k][2][0], M.ctypes.data + 48 * z0,
-                                                  table.data_ptr() + 48 * z0, fill, int(bool(nearest)),
-                                                  p.compute.cuda_stream), "tem_u8_warp_affine")
-                p.release_on = p.compute.record_event()                  # behind the kernel: the input is free too
-                outp.put(k, p.release_on)
-    if stats is not None:
-        stats.update(p.st)
+                _lib.check(lib.tem_u8_warp_affine(src.data_ptr(), *d, y0, vol3[1], outp.device(k).data_ptr(),
+                                                  *(hi - lo for lo, hi in oslabs[k]), oslabs[k][1][0], oslabs[k][2][0],
+                                                  M.ctypes.data + 48 * z0, table.data_ptr() + 48 * z0, fill,
+                                                  int(bool(nearest)), p.compute.cuda_stream), "tem_u8_warp_affine")
+                p.put(k)
     return out
 
 
@@ -4405,11 +4252,7 @@ def field_chunks(out_box, vol_shape, M, U, spacing, chunk_bytes=None, rank=0, wo
     and the largest u_y over the nodes of the cells the slab meets, [min iy, max iy + 2), unioned over the slab's
     sections and clipped to the section (one row at the least).  With U = 0 it is warp_chunks.  Pure host function;
     ValueError as warp_chunks, and for a bad spacing or fields of another shape or dtype or outside the limits."""
-    budget = HIST_CHUNK_BYTES if chunk_bytes is None else int(chunk_bytes)
-    if budget < 1:
-        raise ValueError(f"chunk_bytes must be positive, got {chunk_bytes}")
-    if not 0 <= rank < world_size:
-        raise ValueError(f"rank {rank} is outside [0, {world_size})")
+    budget = _budget(chunk_bytes, rank, world_size)
     vol_shape = tuple(int(v) for v in vol_shape)
     if len(vol_shape) != 3 or min(vol_shape) < 1:
         raise ValueError(f"field_chunks takes a non-empty volume shape [z, y, x], got {vol_shape}")
@@ -4472,41 +4315,22 @@ def volume_warp_field(volume, maps, fields, spacing, out=None, start=None, size=
     if not 0 <= fill <= 255:
         raise ValueError(f"fill must lie in 0...255, got {fill}")
     box = hist_box(vshape, start, size)
-    shape = tuple(hi - lo for lo, hi in box)
-    want = shape[1:] if one else shape
-    if out is None:
-        out = np.zeros(want, np.uint8)
-    elif tuple(out.shape) != want or getattr(out, "dtype", None) != np.uint8:
-        raise ValueError(f"out must be uint8 of the ROI's shape {want}, got {getattr(out, 'dtype', None)} "
-                         f"{tuple(out.shape)}")
+    out = _roi_out(out, box, one)
     chunks = field_chunks(box, vol3, M, U, (1 << ky, 1 << kx), chunk_bytes, rank, world_size)
     p = _SlabPass([volume], [hist_box(vshape)], chunk_bytes, rank, world_size, device, slabs=[r for _, r in chunks])
     lib = H.require_gpu()
     oslabs = [o for o, _ in chunks]
-    odims = [tuple(hi - lo for lo, hi in o) for o in oslabs]
-    dst_vol = _OneSection(out) if one else out
-    (oz, _), (oy, _), (ox, _) = box
-    p.st["write_s"] = 0.0
     per = ny * nx * 8                                                       # bytes of one section's field
-
-    def write_from(k, flat):            # host thread: the slab's box of `out`
-        (z0, z1), (y0, y1), (x0, x1) = oslabs[k]
-        dst_vol[z0 - oz:z1 - oz, y0 - oy:y1 - oy, x0 - ox:x1 - ox] = flat.reshape(odims[k])
-
-    with p.streaming():
+    with p.streaming(stats):
         table, ftable = torch.from_numpy(M).to(p.dev), torch.from_numpy(U).to(p.dev)   # both tables, once
-        with _OutputStream([int(np.prod(d)) for d in odims], write_from, p.dev, p.pool, p.st,
-                           own_buffers=True) as outp:                    # the reader's thread: write(k), read(k + 2)
+        with p.writing(out, box, oslabs) as outp:
             for k, ((z0, _), (y0, _), _), d, (src,) in p:
-                _lib.check(lib.tem_u8_warp_field(src.data_ptr(), *d, y0, vol3[1], outp.device(k).data_ptr(), *odims[k],
-                                                 oslabs[k][1][0], oslabs[k][2][0], M.ctypes.data + 48 * z0,
-                                                 table.data_ptr() + 48 * z0, U.ctypes.data + per * z0,
-                                                 ftable.data_ptr() + per * z0, ny, nx, ky, kx, fill, int(bool(nearest)),
-                                                 p.compute.cuda_stream), "tem_u8_warp_field")
-                p.release_on = p.compute.record_event()                  # behind the kernel: the input is free too
-                outp.put(k, p.release_on)
-    if stats is not None:
-        stats.update(p.st)
+                _lib.check(lib.tem_u8_warp_field(src.data_ptr(), *d, y0, vol3[1], outp.device(k).data_ptr(),
+                                                 *(hi - lo for lo, hi in oslabs[k]), oslabs[k][1][0], oslabs[k][2][0],
+                                                 M.ctypes.data + 48 * z0, table.data_ptr() + 48 * z0,
+                                                 U.ctypes.data + per * z0, ftable.data_ptr() + per * z0, ny, nx, ky, kx,
+                                                 fill, int(bool(nearest)), p.compute.cuda_stream), "tem_u8_warp_field")
+                p.put(k)
     return out
 
 
@@ -4827,24 +4651,13 @@ def clahe_histograms(volume, tile=128, chunk_bytes=None, rank=0, world_size=1, d
     box = hist_box(volume.shape)
     p = _SlabPass([volume], [box], chunk_bytes, rank, world_size, device)
     lib = H.require_gpu()
-    Z, sec = box[0][1], gy * gx * 256
-    whole = Z * sec * 4 <= CLAHE_ACC_BYTES
-    out = None if whole else np.zeros((Z, gy, gx, 256), np.uint32)
-    with p.streaming():
-        acc = torch.zeros((Z if whole else max((d[0] for d in p.dims), default=1), sec), dtype=torch.int32, device=p.dev)
+    with p.streaming(stats):
+        acc = _RowAccumulator(p.dev, box[0][1], (gy, gx, 256), _most_rows(s[0] for s in p.slabs), np.uint32)
         for k, ((z0, z1), (y0, _), (x0, _)), d, (src,) in p:
-            if not whole:
-                acc[:d[0]].zero_()
-            _lib.check(lib.tem_u8_hist_tiles(src.data_ptr(), *d, y0, x0, th, tw, gy, gx,
-                                             acc.data_ptr() + 4 * sec * (z0 if whole else 0), p.compute.cuda_stream),
-                       "tem_u8_hist_tiles")
-            if not whole:                                        # this slab's sections, added on the host
-                out[z0:z1] += acc[:d[0]].cpu().numpy().view(np.uint32).reshape(d[0], gy, gx, 256)
-        if whole:
-            out = acc.cpu().numpy().view(np.uint32).reshape(Z, gy, gx, 256)        # the one read-back
-    if stats is not None:
-        stats.update(p.st)
-    return out
+            _lib.check(lib.tem_u8_hist_tiles(src.data_ptr(), *d, y0, x0, th, tw, gy, gx, acc.ptr(z0, z1),
+                                             p.compute.cuda_stream), "tem_u8_hist_tiles")
+            acc.add(z0, z1)
+        return acc.result()
 
 
 def _clahe_params(clip_limit, z_radius):
@@ -4963,32 +4776,17 @@ def clahe_volume(volume, clahe, out=None, start=None, size=None, chunk_bytes=Non
     p = _SlabPass([volume], [box], chunk_bytes, rank, world_size, device)
     cl = tuple(_check_clahe(clahe, tuple(volume.shape)))        # a TypeError for None: here the tables are no option
     histogram = _check_histogram(histogram, stats)
-    one = len(volume.shape) == 2
-    shape = tuple(hi - lo for lo, hi in box)
-    if out is None:
-        out = np.zeros(shape[1:] if one else shape, np.uint8)
-    elif tuple(out.shape) != (shape[1:] if one else shape):
-        raise ValueError(f"out has shape {tuple(out.shape)}, expected {shape[1:] if one else shape}")
+    out = _roi_out(out, box, len(volume.shape) == 2, any_dtype=True)
     lib = H.require_gpu()
-    dst_vol = _OneSection(out) if one else out
-    p.st["write_s"] = 0.0
-
-    def write_from(k, flat):            # host thread: the slab's box of `out`
-        (z0, z1), (y0, y1), (x0, x1) = p.slabs[k]
-        (oz, _), (oy, _), (ox, _) = box
-        dst_vol[z0 - oz:z1 - oz, y0 - oy:y1 - oy, x0 - ox:x1 - ox] = flat.reshape(p.dims[k])
-
-    with p.streaming():
+    with p.streaming(stats):
         prepare = _Prepare(lib, cl, None, p.dev, p.compute.cuda_stream)          # the tables, once
         measure = _Measure(lib, histogram, False, p.dev, p.compute.cuda_stream)
-        with _OutputStream(p.nbytes, write_from, p.dev, p.pool, p.st) as outp:   # the reader's thread: write(k), read(k + 2)
+        with p.writing(out, box, own_buffers=False):
             for k, slab, d, (buf,) in p:
                 prepare.apply(buf.data_ptr(), d, tuple(lo for lo, _ in slab))
                 measure.add(buf.data_ptr(), d, d)
-                p.release_on = outp.put(k, p.compute.record_event(), buf)        # the input buffer: free once copied out
+                p.put(k, buf)                                                    # remapped in place
         measure.report(p.st)
-    if stats is not None:
-        stats.update(p.st)
     return out
 
 
@@ -5022,25 +4820,14 @@ def volume_histogram16(volume, start=None, size=None, per_section=False, chunk_b
     signed = int(_check_16(volume))
     lib = H.require_gpu()
     oz, nz = box[0][0], box[0][1] - box[0][0]
-    rows = nz if per_section else 1
-    whole = rows * U16_BINS * 8 <= CLAHE_ACC_BYTES
-    out = None if whole else np.zeros((rows, U16_BINS), np.int64)
-    with p.streaming():
-        acc = torch.zeros((rows if whole else max((d[0] for d in p.dims), default=1), U16_BINS), dtype=torch.int64,
-                          device=p.dev)
+    spans = [(z0 - oz, z1 - oz) if per_section else (0, 1) for (z0, z1), _, _ in p.slabs]   # a slab's rows of the table
+    with p.streaming(stats):
+        acc = _RowAccumulator(p.dev, nz if per_section else 1, (U16_BINS,), _most_rows(spans))
         for k, slab, d, (src,) in p:
-            row = (slab[0][0] - oz) if per_section else 0
-            if not whole:
-                acc[:d[0]].zero_()
-            _lib.check(lib.tem_u16_hist(src.data_ptr(), *d, 0, d[0], 0, d[1], 0, d[2],
-                                        acc.data_ptr() + 8 * U16_BINS * (row if whole else 0), int(bool(per_section)),
-                                        signed, p.compute.cuda_stream), "tem_u16_hist")
-            if not whole:                                        # this slab's sections, added on the host
-                out[row:row + d[0]] += acc[:d[0]].cpu().numpy()
-        if whole:
-            out = acc.cpu().numpy()                              # the one read-back
-    if stats is not None:
-        stats.update(p.st)
+            _lib.check(lib.tem_u16_hist(src.data_ptr(), *d, 0, d[0], 0, d[1], 0, d[2], acc.ptr(*spans[k]),
+                                        int(bool(per_section)), signed, p.compute.cuda_stream), "tem_u16_hist")
+            acc.add(*spans[k])
+        out = acc.result()
     return out if per_section else out[0]
 
 
@@ -5190,37 +4977,19 @@ def volume_to_u8(volume, lut, out=None, start=None, size=None, chunk_bytes=None,
     signed = int(_check_16(volume))
     lut = _check_lut16(lut, tuple(volume.shape))
     histogram = _check_histogram(histogram, stats)
-    one = len(volume.shape) == 2
-    shape = tuple(hi - lo for lo, hi in box)
-    if out is None:
-        out = np.zeros(shape[1:] if one else shape, np.uint8)
-    elif tuple(out.shape) != (shape[1:] if one else shape):
-        raise ValueError(f"out has shape {tuple(out.shape)}, expected {shape[1:] if one else shape}")
-    elif getattr(out, "dtype", np.dtype(np.uint8)) != np.uint8:
-        raise ValueError(f"out must be uint8, got {out.dtype}")
+    out = _roi_out(out, box, len(volume.shape) == 2)
     lib = H.require_gpu()
-    dst_vol = _OneSection(out) if one else out
-    p.st["write_s"] = 0.0
-    nvox = [n // 2 for n in p.nbytes]
-
-    def write_from(k, flat):            # host thread: the slab's box of `out`
-        (z0, z1), (y0, y1), (x0, x1) = p.slabs[k]
-        (oz, _), (oy, _), (ox, _) = box
-        dst_vol[z0 - oz:z1 - oz, y0 - oy:y1 - oy, x0 - ox:x1 - ox] = flat.reshape(p.dims[k])
-
-    with p.streaming():
+    with p.streaming(stats):
         lut_dev = torch.from_numpy(lut).to(p.dev)                                # the table(s), once
         measure = _Measure(lib, histogram, False, p.dev, p.compute.cuda_stream)
-        with _OutputStream(nvox, write_from, p.dev, p.pool, p.st, own_buffers=True) as outp:
-            for k, slab, d, (src,) in p:                                         # the reader's thread: write(k), read(k + 2)
+        with p.writing(out, box) as outp:
+            for k, slab, d, (src,) in p:
                 dst = outp.device(k)
                 _lib.check(lib.tem_u16_lut_u8(src.data_ptr(), *d, dst.data_ptr(), lut_dev.data_ptr(), int(lut.ndim == 2),
                                               slab[0][0], signed, p.compute.cuda_stream), "tem_u16_lut_u8")
                 measure.add(dst.data_ptr(), d, d)
-                outp.put(k, p.compute.record_event())
+                p.put(k)
         measure.report(p.st)
-    if stats is not None:
-        stats.update(p.st)
     return out
 
 
